@@ -4,23 +4,32 @@
 Metric: RNN timesteps/sec (fwd+bwd) at B=64 T=128 hid=180 r=16 (UCI-HAR shape, MyVMLMFCell, fp32).
 A "step" is one pass of the hot path over one synthetic batch:
     zero_grad -> Net.forward (MyLSTM over T=128 + Linear) -> cross-entropy -> backward
-    (+ ONE flat RCCL all-reduce of the gradients when N > 1).  The optimizer is outside the timed region and
-reported separately (`adam_ms` stock, `fused_adam_ms` the package's, `train_step_ms` everything in one graph).  `other_configs` (single GPU, outside the metric, `--no-extra` skips it): BASELINE configs[2] in fp32 as the wavefront launches and as the chained per-layer kernels, and configs[4]'s two group layers on one GPU.  Inputs are resident in HBM before the timed region starts.
+    (+ ONE flat RCCL all-reduce of the gradients when N > 1).  Inputs are resident in HBM before the timed region starts.
 value = (N ranks x T timesteps per step) / step time: weak scaling, per-GPU batch fixed at 64
-(N = 8 is BASELINE config D: global batch 512).
+(N = 8 is BASELINE config D: global batch 512).  ms_per_step = the time of one of the K timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps (replayed from a hipGraph,
+or eager launches with --no-graph), the result line.  `--dump-outputs DIR` writes what the last timed step handed its caller
+(`loss.npy`, `grad.<parameter>.npy`, float32) from seeded inputs, so two builds can be compared output for output.
+`--full` adds everything outside the metric: the eager timed region with the roofline of its dominant kernel, the step with
+the other parameter-image mode, the other scaling mode (N > 1), the per-kernel breakdown pass, the all-reduce alone and the
+check that every rank holds the same reduced gradients (N > 1), the optimizers (`adam_ms` stock, `fused_adam_ms` the
+package's, `train_step_ms` everything in one graph), and at N = 1 the `harness` loops and `other_configs` (`--no-extra`
+skips both: BASELINE configs[2] in fp32 as the wavefront launches and as the chained per-layer kernels, and configs[4]'s two
+group layers on one GPU) and `cpu_baseline` (`--no-cpu-baseline` skips it).
 
 `--gpus N` (N > 1) without a torchrun environment starts the N ranks itself: the parent process - before it makes
 any GPU call - runs the torchrun line above as a child, relays rank 0's JSON line and exits with the child's code.
 `--global-batch G` is the strong-scaling mode (BASELINE configs[3]: G = 512 split contiguously, 512/N rows per GPU);
 `value` then counts 64-row batches: (G / 64) x T / step time, the same unit as the weak mode's N x T / step time.
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel, HIP events on the launch stream,
-inside the timed region) and, at N = 1, "cpu_baseline" (the oracle's op-for-op PyTorch-CPU port of the
-reference cell + time loop, timed on this box's host cores).
+Rank 0 prints ONE JSON line.  Extra objects under --full: "roofline" (dominant kernel, HIP events on the launch stream,
+inside the eager timed region) and, at N = 1, "cpu_baseline" (the oracle's op-for-op PyTorch-CPU port of the
+reference cell + time loop, timed on the host's cores).
 """
 import argparse
 import ctypes
@@ -356,8 +365,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the measurements outside the metric (other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything outside the headline figure (see the module docstring); "
+                         "a plain run only sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's loss and parameter gradients to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the harness loops and other_configs")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches only")
     ap.add_argument("--graph-collective", action="store_true", help="capture the gradient all-reduce inside the hipGraph too")
     ap.add_argument("--force-collective", action="store_true", help="run the RCCL gradient all-reduce even with one rank")
@@ -383,6 +397,10 @@ def main():
                          "only ever run in a group of one: no multi-GPU box was available to the builder), the C ABI in the "
                          "one-rank self-test of --force-collective")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config != "A":
+        ap.error("--dump-outputs writes the headline step's outputs (config A)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     # Only the JSON line may reach stdout: libraries print there too (RCCL's version banner at N > 1), so fd 1 is
@@ -502,33 +520,38 @@ def main():
         if rank == 0:
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
+    def time_eager():
+        """K eager steps between barriers: (seconds, loss of the last step)."""
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = step()
+        barrier()
+        return time.perf_counter() - t0, out.detach().clone()
+
     log(f"world={world} device={torch.cuda.get_device_name(dev)}")
     for _ in range(args.warmup):
         step()
     barrier()
     log("warm-up done")
 
-    # ---- timed region 1 (eager launches): HIP event pairs around the two serial recurrent kernels (rocprof
+    # ---- --full, timed region 1 (eager launches): HIP event pairs around the two serial recurrent kernels (rocprof
     # names them rec_fwd_kernel / rec_bwd_kernel), recorded on the stream they are launched on.  Eager PyTorch
     # is HOST-bound at this size (~0.4 ms of Python/dispatcher per step vs ~0.3 ms of GPU work), so this region
     # supplies the per-kernel durations for the roofline, and region 2 supplies `value`.
-    lib.vmlmf_profile_enable((1 << 2) | (1 << 3))
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    dt_eager = time.perf_counter() - t0
     usec = (ctypes.c_float * _lib.NKERNELS)()
     cnt = (ctypes.c_int32 * _lib.NKERNELS)()
-    lib.vmlmf_profile_read(usec, cnt, 1)
-    lib.vmlmf_profile_enable(0)
-    rec = {lib.vmlmf_kernel_name(k).decode(): usec[k] / max(cnt[k], 1) for k in (2, 3)}
-    log(f"eager timed region done: {dt_eager / args.steps * 1e3:.4f} ms/step")
+    if args.full:
+        lib.vmlmf_profile_enable((1 << 2) | (1 << 3))
+        dt_eager, _ = time_eager()
+        lib.vmlmf_profile_read(usec, cnt, 1)
+        lib.vmlmf_profile_enable(0)
+        rec = {lib.vmlmf_kernel_name(k).decode(): usec[k] / max(cnt[k], 1) for k in (2, 3)}
+        log(f"eager timed region done: {dt_eager / args.steps * 1e3:.4f} ms/step")
 
     # ---- timed region 2 (hipGraph): forward + loss + backward captured ONCE into a HIP graph and replayed;
     # the gradient all-reduce (N > 1) stays an eager RCCL call after each replay.
-    launch_mode, dt = "eager", dt_eager
+    launch_mode, dt = "eager", None
     loss = step().detach().clone()      # keep no reference into the autograd graph across the capture
     if not args.no_graph:
         import gc
@@ -595,11 +618,24 @@ def main():
             log(f"hipGraph timed region done: {dt_graph / args.steps * 1e3:.4f} ms/step")
             launch_mode = "hipgraph" + ("+allreduce" if reduce_in_graph else "")
             dt = dt_graph
+    if dt is None:      # --no-graph, or no capture on every rank: the eager launches are the headline
+        dt, loss = time_eager()
+        log(f"eager timed region done: {dt / args.steps * 1e3:.4f} ms/step")
+
+    # what a caller of the timed step receives from its last repetition: the loss and the parameters' gradients (after the
+    # exchange at N > 1), read before anything below runs the network again
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        arrays = {"loss": loss}
+        arrays.update((f"grad.{k}", p.grad) for k, p in net.named_parameters() if p.grad is not None)
+        for name, t in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().float().cpu().numpy())
+        log(f"{len(arrays)} outputs of the last timed step written to {args.dump_outputs}")
 
     # ---- outside the metric: the same K steps with kept parameter images (pack_kernel leaves the step: what inference or
     # gradient accumulation sees), or - under --keep-images - with the packing inside
     alt_ms = None
-    if launch_mode.startswith("hipgraph"):
+    if args.full and launch_mode.startswith("hipgraph"):
         try:
             _pkg.cache_packed_parameters(net, not args.keep_images)
             for _ in range(3):
@@ -635,7 +671,7 @@ def main():
     # ---- outside the metric, N > 1: the OTHER scaling mode in the same run (weak run: global batch 512 split over the ranks =
     # BASELINE configs[3]; strong run: 64 rows per GPU), K graph-replayed steps each, MAX over ranks
     other_mode = None
-    if world > 1 and launch_mode.startswith("hipgraph"):
+    if args.full and world > 1 and launch_mode.startswith("hipgraph"):
         try:
             o_strong = not strong
             o_global = 512 if o_strong else None
@@ -680,18 +716,19 @@ def main():
             torch.cuda.synchronize()
 
     # untimed extra pass: every internal kernel bracketed, for the breakdown
-    lib.vmlmf_profile_enable((1 << _lib.NKERNELS) - 1)
-    for _ in range(10):
-        step()
-    torch.cuda.synchronize()
-    lib.vmlmf_profile_read(usec, cnt, 1)
-    lib.vmlmf_profile_enable(0)
-    kern = {lib.vmlmf_kernel_name(k).decode(): round(usec[k] / max(cnt[k], 1), 2) for k in range(_lib.NKERNELS)}
+    if args.full:
+        lib.vmlmf_profile_enable((1 << _lib.NKERNELS) - 1)
+        for _ in range(10):
+            step()
+        torch.cuda.synchronize()
+        lib.vmlmf_profile_read(usec, cnt, 1)
+        lib.vmlmf_profile_enable(0)
+        kern = {lib.vmlmf_kernel_name(k).decode(): round(usec[k] / max(cnt[k], 1), 2) for k in range(_lib.NKERNELS)}
 
     # the gradient all-reduce on its own ("all-reduce time isolated"): the same in-place RCCL group call
     # the timed steps make, on the gradients of the last step, between barriers
     allreduce_ms = None
-    if collective:
+    if args.full and collective:
         for _ in range(5):
             reducer.reduce()
         barrier()
@@ -705,7 +742,7 @@ def main():
 
     # every rank must hold the SAME reduced gradients after the exchange: the norm each rank computes has to agree bit for bit
     grads_equal = None
-    if collective:
+    if args.full and collective:
         step()
         gn = torch.sqrt(sum((p.grad.double() ** 2).sum() for p in net.parameters() if p.grad is not None)).reshape(1)
         ghi, glo = gn.clone(), gn.clone()
@@ -715,45 +752,46 @@ def main():
 
     # optimizer, outside the metric (train.py:47,65): the stock one and the package's single-launch one, and the
     # whole training step (forward + loss + backward + optimizer) replayed from one hipGraph
-    def time_opt(opt):
-        step()
-        opt.step()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(20):
+    adam_ms = fused_adam_ms = train_step_ms = None
+    if args.full:
+        def time_opt(opt):
+            step()
             opt.step()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t1) / 20 * 1e3
-
-    adam_ms = time_opt(torch.optim.Adam(net.parameters(), lr=0.002))
-    fused_opt = vmlmf_amd.optim.Adam(net.parameters(), lr=0.002)
-    fused_adam_ms = time_opt(fused_opt)
-    train_step_ms = None
-    if launch_mode.startswith("hipgraph") and (not collective or reduce_in_graph):
-        try:
-            def train_step():
-                out = step()
-                fused_opt.step()
-                return out
-            tgraph, _ = capture(train_step)
-            for _ in range(args.warmup):
-                tgraph.replay()
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            for _ in range(args.steps):
-                tgraph.replay()
+            for _ in range(20):
+                opt.step()
             torch.cuda.synchronize()
-            train_step_ms = (time.perf_counter() - t1) / args.steps * 1e3
-        except Exception as e:
-            log(f"training-step capture failed ({type(e).__name__}: {e})")
-            torch.cuda.synchronize()
+            return (time.perf_counter() - t1) / 20 * 1e3
+
+        adam_ms = time_opt(torch.optim.Adam(net.parameters(), lr=0.002))
+        fused_opt = vmlmf_amd.optim.Adam(net.parameters(), lr=0.002)
+        fused_adam_ms = time_opt(fused_opt)
+        if launch_mode.startswith("hipgraph") and (not collective or reduce_in_graph):
+            try:
+                def train_step():
+                    out = step()
+                    fused_opt.step()
+                    return out
+                tgraph, _ = capture(train_step)
+                for _ in range(args.warmup):
+                    tgraph.replay()
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    tgraph.replay()
+                torch.cuda.synchronize()
+                train_step_ms = (time.perf_counter() - t1) / args.steps * 1e3
+            except Exception as e:
+                log(f"training-step capture failed ({type(e).__name__}: {e})")
+                torch.cuda.synchronize()
 
     # what a maintainer's loop gets (verdict r4 item 7), one GPU, after everything the metric needs has been measured - these
     # loops move the parameters: (a) train.py:47,58-65 as written - eager launches, nn.CrossEntropyLoss, torch.optim.Adam; (b) the
     # same loop with the package's pieces, still eager (host-bound: ~20 Python-level calls per step); (c) the two-line opt-in of
     # vmlmf_amd.optim.Adam + GraphedTrainStep (every step through its __call__, input copies included)
     harness = None
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         def loop_ms(body, n=100):
             for _ in range(10):
                 body()
@@ -802,7 +840,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = batches_per_step * T * args.steps / dt
 
-    if rank == 0:
+    rows = rows_gpu * T                                  # sample-timesteps one launch processes
+    if rank == 0 and args.full:
         dom = max(rec, key=rec.get)                      # dominant kernel by measured time
         # HBM traffic of that kernel: PMC counters cannot be read from inside the process; they were collected
         # with rocprofv3 in separate passes on this same command and committed under profiles/
@@ -836,7 +875,6 @@ def main():
             util_note = f"profiles/{util_file} (rocprofv3 --pmc SQ_*; fractions of SQ_WAVE_CYCLES resp. of busy-CU cycles)"
         except (OSError, KeyError, ValueError):
             pass
-        rows = rows_gpu * T                              # sample-timesteps one launch processes
         # 10 H ru per sample-step in either recurrent kernel; a backward launch that carries the weight-gradient workers
         # (no wgrad_mfma_kernel launch in the breakdown pass) also does their products: dpre^T x, dpre^T Q, h^T dQ
         riding = dom == "rec_bwd_kernel" and kern.get("wgrad_mfma_kernel", 0.0) == 0.0     # (riding workers, or the in-row form)
@@ -856,20 +894,11 @@ def main():
             ntg = -(-(192 // 8 + (H + 31) // 32) // wpw)
             nwork = min(32, (cus - 8 - rows_gpu) // ntg) * ntg
         launch_wgs = rows_gpu + nwork
+    if rank == 0:
         out = {
             "metric": "RNN timesteps/sec (fwd+bwd) at B=64 T=128 hid=180 r=16; 1/2/4/8 GPU",
             "value": round(value, 1), "unit": "RNN timesteps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            # beside it: the same step in the other parameter-image mode, and the whole training step (forward + loss + backward
-            # + fused Adam in one graph: packs every step by construction) - config.workload says which one `value` is
-            ("ms_per_step_repack" if args.keep_images else "ms_per_step_kept_images"): None if alt_ms is None else round(alt_ms, 4),
-            "train_step_ms": None if train_step_ms is None else round(train_step_ms, 4),
-            "harness": harness,
-            # the riding weight-gradient workers at the end of the run: False when VMLMF_WRIDE=0 / vmlmf_tune("wride", 0) switched them
-            # off or a launch gave up a bounded wait on a shared GPU and the library fell back to the stand-alone kernel (then
-            # ms_per_step is that form's, not a regression of the riding one)
-            "riding_workers": {"armed": bool(_lib.tune_get("wride")), "stand_alone_weight_gradient_launch_in_step": kern.get("wgrad_mfma_kernel", 0.0) > 0.0,
-                               "status": lib.vmlmf_check_status()},
             "ms_per_step_min_over_ranks": round(dt_min / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32",
@@ -899,52 +928,65 @@ def main():
                        "criterion": "torch.nn.functional.cross_entropy" if args.torch_loss else
                                     ("vmlmf_amd.cross_entropy" if args.separate_loss else
                                      "vmlmf_amd.Net.loss (cross-entropy riding on the forward launch, C ABI vmlmf_ce)")},
-            "eager_ms_per_step": round(dt_eager / args.steps * 1e3, 4),
             "sample_timesteps_per_s": round(value * B_PER_GPU, 1),
             "step_flops": rows * F_STEP * world,
             "step_tflops": round(rows * F_STEP * world / (ms_per_step * 1e-3) / 1e12, 3),
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
-                         "peak": F32_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / F32_MATRIX_PEAK_TFLOPS, 5),
-                         "recurrence_only_achieved": round(achieved_rec, 3),
-                         "recurrence_only_frac": round(achieved_rec / F32_MATRIX_PEAK_TFLOPS, 5), "traffic": traffic,
-                         "traffic_unit": "bytes per launch", "traffic_source": traffic_note,
-                         "launch_us": round(rec[dom], 2), "us_per_timestep": round(rec[dom] / T, 4),
-                         # one batch row per CU: rows_gpu of 256 CUs are busy; the same rate against THEIR share of the peak
-                         "launch_workgroups_one_per_cu": min(launch_wgs, cus),
-                         "frac_of_those_cus": round(achieved / (F32_MATRIX_PEAK_TFLOPS * min(launch_wgs, cus) / float(cus)), 5),
-                         "utilisation": util, "utilisation_source": util_note,
-                         "flops_per_launch": flops,
-                         "contains": ("recurrence (10 H ru per sample-step) + the weight-gradient products formed inside the rows' workgroups "
-                                      "(rec4_bwd_kernel: 8 H I + 8 H ru + 2 H ru per sample-step on fp32 MFMA, operands from LDS)") if (riding and inrow) else
-                                     ("recurrence (10 H ru per sample-step) + the weight-gradient products riding on the launch "
-                                      "(8 H I + 8 H ru + 2 H ru per sample-step, on otherwise idle CUs)") if riding else
-                                     ("the forward's algorithmic work of SURVEY section 8d: input side 2 I rw + 8 H rw (formed by the "
-                                      "launch's x-projection wave) + recurrence 10 H ru per sample-step") if x_inside else
-                                     "recurrence (10 H ru per sample-step)",
-                         "measured": "HIP event pairs on the launch stream over the eager timed region of the same K "
-                                     "steps (events cannot be read inside a replayed hipGraph)",
-                         "note": "fp32: MFMA peak == vector peak on gfx950; the kernel is a 2T-long dependent "
-                                 "chain on 64 of 256 CUs (one batch row per CU), see DESIGN.md"},
-            "kernels_us": kern,
-            "kernels_us_region": "EAGER launches bracketed by HIP event pairs in an untimed breakdown pass - not the replayed hipGraph `value` / "
-                                 "`ms_per_step` come from (a graph node cannot be bracketed), so they need not add up to ms_per_step; "
-                                 "roofline.launch_us is from the eager timed region too (its fraction is the conservative one)",
-            "allreduce_ms": None if allreduce_ms is None else round(allreduce_ms, 4),
             "allreduce_bytes": 4 * reducer.numel() if collective else 0,
-            "adam_ms": round(adam_ms, 4),
-            "fused_adam_ms": round(fused_adam_ms, 4),
-            "other_scaling_mode": other_mode,
             "loss": round(float(loss.item()), 6),
         }
-        if world == 1 and not strong and not args.no_extra:
-            try:
-                out["other_configs"] = other_configs()
-            except Exception as e:   # never at the expense of the line itself
-                log(f"other_configs failed ({type(e).__name__}: {e})")
-        if world == 1 and not strong and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-            out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
+        if args.full:
+            out.update({
+                # beside it: the same step in the other parameter-image mode, and the whole training step (forward + loss + backward
+                # + fused Adam in one graph: packs every step by construction) - config.workload says which one `value` is
+                ("ms_per_step_repack" if args.keep_images else "ms_per_step_kept_images"): None if alt_ms is None else round(alt_ms, 4),
+                "train_step_ms": None if train_step_ms is None else round(train_step_ms, 4),
+                "harness": harness,
+                # the riding weight-gradient workers at the end of the run: False when VMLMF_WRIDE=0 / vmlmf_tune("wride", 0) switched them
+                # off or a launch gave up a bounded wait on a shared GPU and the library fell back to the stand-alone kernel (then
+                # ms_per_step is that form's, not a regression of the riding one)
+                "riding_workers": {"armed": bool(_lib.tune_get("wride")), "stand_alone_weight_gradient_launch_in_step": kern.get("wgrad_mfma_kernel", 0.0) > 0.0,
+                                   "status": lib.vmlmf_check_status()},
+                "eager_ms_per_step": round(dt_eager / args.steps * 1e3, 4),
+                "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3),
+                             "peak": F32_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / F32_MATRIX_PEAK_TFLOPS, 5),
+                             "recurrence_only_achieved": round(achieved_rec, 3),
+                             "recurrence_only_frac": round(achieved_rec / F32_MATRIX_PEAK_TFLOPS, 5), "traffic": traffic,
+                             "traffic_unit": "bytes per launch", "traffic_source": traffic_note,
+                             "launch_us": round(rec[dom], 2), "us_per_timestep": round(rec[dom] / T, 4),
+                             # one batch row per CU: rows_gpu of 256 CUs are busy; the same rate against THEIR share of the peak
+                             "launch_workgroups_one_per_cu": min(launch_wgs, cus),
+                             "frac_of_those_cus": round(achieved / (F32_MATRIX_PEAK_TFLOPS * min(launch_wgs, cus) / float(cus)), 5),
+                             "utilisation": util, "utilisation_source": util_note,
+                             "flops_per_launch": flops,
+                             "contains": ("recurrence (10 H ru per sample-step) + the weight-gradient products formed inside the rows' workgroups "
+                                          "(rec4_bwd_kernel: 8 H I + 8 H ru + 2 H ru per sample-step on fp32 MFMA, operands from LDS)") if (riding and inrow) else
+                                         ("recurrence (10 H ru per sample-step) + the weight-gradient products riding on the launch "
+                                          "(8 H I + 8 H ru + 2 H ru per sample-step, on otherwise idle CUs)") if riding else
+                                         ("the forward's algorithmic work of SURVEY section 8d: input side 2 I rw + 8 H rw (formed by the "
+                                          "launch's x-projection wave) + recurrence 10 H ru per sample-step") if x_inside else
+                                         "recurrence (10 H ru per sample-step)",
+                             "measured": "HIP event pairs on the launch stream over the eager timed region of the same K "
+                                         "steps (events cannot be read inside a replayed hipGraph)",
+                             "note": "fp32: MFMA peak == vector peak on gfx950; the kernel is a 2T-long dependent "
+                                     "chain on 64 of 256 CUs (one batch row per CU), see DESIGN.md"},
+                "kernels_us": kern,
+                "kernels_us_region": "EAGER launches bracketed by HIP event pairs in an untimed breakdown pass - not the replayed hipGraph `value` / "
+                                     "`ms_per_step` come from (a graph node cannot be bracketed), so they need not add up to ms_per_step; "
+                                     "roofline.launch_us is from the eager timed region too (its fraction is the conservative one)",
+                "allreduce_ms": None if allreduce_ms is None else round(allreduce_ms, 4),
+                "adam_ms": round(adam_ms, 4),
+                "fused_adam_ms": round(fused_adam_ms, 4),
+                "other_scaling_mode": other_mode,
+            })
+            if world == 1 and not strong and not args.no_extra:
+                try:
+                    out["other_configs"] = other_configs()
+                except Exception as e:   # never at the expense of the line itself
+                    log(f"other_configs failed ({type(e).__name__}: {e})")
+            if world == 1 and not strong and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline()
+                out["speedup_vs_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if collective:
         dist.destroy_process_group()

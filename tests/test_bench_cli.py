@@ -28,3 +28,8 @@ def test_strong_scaling_shards_tile_the_global_minibatch():
         assert np.array_equal(np.concatenate([b for _, b in xs]), tg)
     # weak mode: every rank draws its own batch
     assert not np.array_equal(bench.synthetic_batch(0)[0], bench.synthetic_batch(1)[0])
+
+
+def test_fewer_than_one_timed_step_is_refused_before_anything_runs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout == ""

@@ -22,7 +22,7 @@ def _bench(args, rehearsal=True, timeout=900):
     if rehearsal:
         env["VMLMF_BENCH_REHEARSAL"] = "1"
     env["VMLMF_BENCH_RANK_TIMEOUT"] = str(timeout - 60)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--no-cpu-baseline", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--full", "--no-cpu-baseline", "--no-extra"],
                        capture_output=True, text=True, env=env, timeout=timeout)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -122,11 +122,11 @@ def test_one_rank_self_tests_of_the_rccl_paths():
 
 
 def test_the_default_single_gpu_line_keeps_its_contract():
-    """`python bench.py` as the driver runs it at N = 1 (shortened): ONE JSON line with the graded fields, the roofline and
+    """`python bench.py --full` at N = 1 (shortened): ONE JSON line with the graded fields, the roofline and
     cpu_baseline objects, the round-5 additions (harness, riding_workers) - and the headline step as three launches: no pack /
     criterion / reduce / finish launch in the per-kernel breakdown, the finishing launch present."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -150,3 +150,34 @@ def test_the_default_single_gpu_line_keeps_its_contract():
     assert h["two_line_opt_in_ms"] < h["eager_package_loop_ms"] <= h["unchanged_loop_ms"] * 1.05, h
     rw = j["riding_workers"]
     assert rw["armed"] is True and rw["stand_alone_weight_gradient_launch_in_step"] is False and rw["status"] == 0, rw
+
+
+def test_a_plain_line_times_the_headline_only_and_dumps_the_step_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` at N = 1: the graded fields and none of what --full measures, and
+    the loss and the ten parameter gradients of the last timed step as float32 .npy files - the same from the hipGraph replays as
+    from eager launches (--no-graph)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    dumps = {}
+    for launch, extra in (("hipgraph", []), ("eager", ["--no-graph"])):
+        out = tmp_path / launch
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "3", "--dump-outputs", str(out)]
+                           + extra, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 7 and j["warmup"] == 3 and j["config"]["launch"] == launch and j["higher_is_better"] is True
+        assert j["dtype"] == "f32" and j["unit"] == "RNN timesteps/s" and j["ms_per_step"] > 0
+        assert abs(j["value"] - 128 * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"]
+        for k in ("roofline", "cpu_baseline", "harness", "kernels_us", "other_configs", "train_step_ms", "eager_ms_per_step", "adam_ms"):
+            assert k not in j, k
+        files = sorted(os.listdir(out))
+        assert len(files) == 11 and "loss.npy" in files and all(f == "loss.npy" or f.startswith("grad.") for f in files), files
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert abs(float(arrays["loss.npy"]) - j["loss"]) <= 1e-6 + 1e-6 * abs(j["loss"])
+        assert all(np.abs(a).max() > 0 for f, a in arrays.items() if f.startswith("grad."))
+        dumps[launch] = arrays
+    for f, a in dumps["hipgraph"].items():
+        np.testing.assert_allclose(a, dumps["eager"][f], rtol=1e-5, atol=1e-6 * max(1.0, float(np.abs(a).max())), err_msg=f)

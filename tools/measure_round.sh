@@ -23,8 +23,8 @@ pmc4() { local tag=$1; shift; local what=$1; shift   # four passes of one comman
   python tools/rocprof_pmc.py $(db ${tag}f) $(db ${tag}w) $O/${RN}_pmc_traffic$tag.json "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, with --kernel-trace only) -- $what; merged by tools/rocprof_pmc.py" > /dev/null 2>&1
   rm -rf $O/${tag}1 $O/${tag}2 $O/${tag}f $O/${tag}w; }
 
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err < /dev/null
-for gb in 512 256 128; do timeout 200 python bench.py --gpus 1 --global-batch $gb --steps 100 --warmup 10 --no-cpu-baseline --no-extra 2>/dev/null < /dev/null; done > $O/bench_strong_1gpu.jsonl
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
+for gb in 512 256 128; do timeout 200 python bench.py --full --gpus 1 --global-batch $gb --steps 100 --warmup 10 --no-cpu-baseline --no-extra 2>/dev/null < /dev/null; done > $O/bench_strong_1gpu.jsonl
 timeout 900 python tools/bench_configs.py > $O/configs.jsonl 2>/dev/null < /dev/null
 timeout 600 python tools/bench_lm.py > $O/lm.jsonl 2>/dev/null < /dev/null
 timeout 600 python tools/bench_lm.py 32 > $O/lm_b32.jsonl 2>/dev/null < /dev/null
@@ -32,25 +32,25 @@ timeout 600 python tools/bench_lm.py 256 --dropout 0.5 > $O/lm_dropout.jsonl 2>/
 timeout 600 python tools/bench_lm.py 32 --dropout 0.5 > $O/lm_dropout_b32.jsonl 2>/dev/null < /dev/null
 timeout 300 python tools/probes/rbx_probe.py 32 64 128 > $O/config_e_two_layers_stacked_vs_chained.jsonl 2>/dev/null < /dev/null
 timeout 300 python tools/probes/rbx_probe.py 32 64 128 --plain >> $O/config_e_two_layers_stacked_vs_chained.jsonl 2>/dev/null < /dev/null
-timeout 300 python bench.py --force-collective --steps 100 --warmup 10 --no-cpu-baseline --no-extra > $O/bench_forced_collective_1rank.json 2>/dev/null < /dev/null
+timeout 300 python bench.py --full --force-collective --steps 100 --warmup 10 --no-cpu-baseline --no-extra > $O/bench_forced_collective_1rank.json 2>/dev/null < /dev/null
 timeout 600 python bench.py --config E --steps 20 --warmup 5 > $O/config_e_lm_1gpu.json 2>/dev/null < /dev/null
 for bp in 128 64 32; do timeout 600 python bench.py --config E --batch-per-gpu $bp --steps 20 --warmup 5 2>/dev/null < /dev/null; done > $O/config_e_lm_1gpu_b128_b64_b32.jsonl
 VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --config E --gpus 2 --steps 10 --warmup 3 > $O/rehearsal_config_e_2ranks.json 2>/dev/null < /dev/null
-VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --gpus 2 --steps 50 --warmup 10 --no-cpu-baseline --no-extra > $O/rehearsal_plain2.json 2>/dev/null < /dev/null
-VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --gpus 2 --global-batch 512 --steps 30 --warmup 5 --no-cpu-baseline --no-extra > $O/rehearsal_strong2.json 2>/dev/null < /dev/null
-VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --gpus 2 --transport p2p --steps 50 --warmup 10 --no-cpu-baseline --no-extra > $O/rehearsal_p2p2.json 2>/dev/null < /dev/null
+VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --full --gpus 2 --steps 50 --warmup 10 --no-cpu-baseline --no-extra > $O/rehearsal_plain2.json 2>/dev/null < /dev/null
+VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --full --gpus 2 --global-batch 512 --steps 30 --warmup 5 --no-cpu-baseline --no-extra > $O/rehearsal_strong2.json 2>/dev/null < /dev/null
+VMLMF_BENCH_REHEARSAL=1 timeout 600 python bench.py --full --gpus 2 --transport p2p --steps 50 --warmup 10 --no-cpu-baseline --no-extra > $O/rehearsal_p2p2.json 2>/dev/null < /dev/null
 timeout 300 python tools/probes/p2p_latency.py 2>/dev/null | tail -1 > $O/p2p_latency_world1.txt
 
-BENCH="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra"
-pmc4 "" "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra; config A (B=64 T=128 H=180 r=16), $RN" $BENCH
-B256="python3 $R/bench.py --global-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra"
-pmc4 "_b256" "python3 bench.py --global-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra; 256 rows on one GPU (rec_fwd_kernel, rec4_bwd_kernel), $RN" $B256
+BENCH="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra"
+pmc4 "" "python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra; config A (B=64 T=128 H=180 r=16), $RN" $BENCH
+B256="python3 $R/bench.py --full --global-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra"
+pmc4 "_b256" "python3 bench.py --full --global-batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-graph --no-extra; 256 rows on one GPU (rec_fwd_kernel, rec4_bwd_kernel), $RN" $B256
 pmc4 "_config_e" "python3 tools/probes/run_e.py --nograph; one PTB group layer, B=256 T=35 (rb_fwd_kernel / rb_bwd_kernel on clusters of 16), $RN" python3 $R/tools/probes/run_e.py --nograph
 pmc4 "_config_c" "python3 tools/probes/run_c.py; config C (2 x 256, rank 24, B 128, T 24, fp32: wf_fwd_kernel / wf_bwd_kernel / wgrad4_stack_kernel), $RN" python3 $R/tools/probes/run_c.py
 pmc4 "_config_e_stack32" "python3 tools/probes/rbx_probe.py 32 --stacked-only; two PTB group layers at 32 rows in one launch per direction (rbx_fwd_kernel / rbx_bwd_kernel), $RN" python3 $R/tools/probes/rbx_probe.py 32 --stacked-only
 
-ks ks ${RN}_kernel_stats.csv "bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extra (config A; eager region + hipGraph replays + untimed breakdown pass), $RN: rocprofv3 --kernel-trace --stats" python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extra
-ks ksb ${RN}_kernel_stats_b256.csv "bench.py --global-batch 256 --steps 50 --warmup 10 --no-cpu-baseline --no-extra (256 rows on one GPU: rec4_bwd_kernel), $RN: rocprofv3 --kernel-trace --stats" python3 $R/bench.py --global-batch 256 --steps 50 --warmup 10 --no-cpu-baseline --no-extra
+ks ks ${RN}_kernel_stats.csv "bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extra (config A; eager region + hipGraph replays + untimed breakdown pass), $RN: rocprofv3 --kernel-trace --stats" python3 $R/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extra
+ks ksb ${RN}_kernel_stats_b256.csv "bench.py --full --global-batch 256 --steps 50 --warmup 10 --no-cpu-baseline --no-extra (256 rows on one GPU: rec4_bwd_kernel), $RN: rocprofv3 --kernel-trace --stats" python3 $R/bench.py --full --global-batch 256 --steps 50 --warmup 10 --no-cpu-baseline --no-extra
 ks kse ${RN}_config_e_layer_kernel_stats.csv "config E layer (V4 group, H=650, ranks 32/[32,32], B=256, T=35), $RN: rocprofv3 --kernel-trace --stats -- python3 tools/probes/run_e.py --nograph" python3 $R/tools/probes/run_e.py --nograph
 ks kss ${RN}_config_e_stack_b32_kernel_stats.csv "two PTB group layers at 32 rows, both in ONE launch per direction (csrc/vmlmf_rbx.hip), $RN: rocprofv3 --kernel-trace --stats -- python3 tools/probes/rbx_probe.py 32 --stacked-only" python3 $R/tools/probes/rbx_probe.py 32 --stacked-only
 ks ksh ${RN}_config_e_chained_b32_kernel_stats.csv "the same two layers at 32 rows as chained per-layer launches (round 5's form), $RN: rocprofv3 --kernel-trace --stats -- python3 tools/probes/rbx_probe.py 32 --chained-only" python3 $R/tools/probes/rbx_probe.py 32 --chained-only
