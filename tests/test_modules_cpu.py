@@ -69,6 +69,26 @@ def test_no_cpu_fallback():
         lm(torch.randn(3, 2, 8), (torch.zeros(2, 8), torch.zeros(2, 8)))
 
 
+def test_net_pickles_and_copies_after_a_call():
+    """The first call builds Net's per-call plan (before it finds the input on the CPU): pickle, torch.save and copy.deepcopy
+    must still work afterwards, and the copy must not carry the plan (it would point at the original's cell and parameters)."""
+    import copy
+    import io
+    import pickle
+    net = Net(9, layer_sizes=[40], w_rank=8, u_rank=[8], model=MyLSTM, cell=MyVMLMFCell)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        net(torch.randn(2, 4, 9))
+    buf = io.BytesIO()
+    torch.save(net, buf)
+    buf.seek(0)
+    for c in (pickle.loads(pickle.dumps(net)), copy.deepcopy(net), torch.load(buf, weights_only=False)):
+        assert "_fast_plan" not in c.__dict__
+        sd, csd = net.state_dict(), c.state_dict()
+        assert list(sd) == list(csd)
+        for k in sd:
+            assert torch.equal(sd[k], csd[k]) and sd[k].data_ptr() != csd[k].data_ptr(), k
+
+
 def test_product_package_never_imports_the_oracle():
     import os
     root = os.path.dirname(vmlmf_amd.__file__)

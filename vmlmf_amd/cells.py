@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .functional import head_linear, stack_mode, vmlmf_sequence, vmlmf_stack
+from .functional import head_linear, stack_mode, torch_ops, vmlmf_sequence, vmlmf_stack
 
 TIME_STEPS = 128
 RECURRENT_MAX = pow(2, 1 / TIME_STEPS)
@@ -348,25 +348,32 @@ class Net(nn.Module):
     def _fast(self, x):
         """The per-call plan of the headline family - ONE VMLMF layer with a narrow input (its x side rides inside the recurrent
         launch) under a classifier of at most 32 classes, fp32 on a HIP device, the C++ binding loaded: everything run_layers() and
-        vmlmf_sequence() would find out again on every call, found out once.  (cell's parameter dict, constants of the C++ op) or None.
-        Invalidated by anything that changes the answer: another device / dtype, kept parameter images, a compute dtype, the
-        VMLMF_STACK mode (read at build time only for mode "1", which routes single layers to the wavefront launch)."""
+        vmlmf_sequence() would find out again on every call, found out once.  The plan is (rnn, lin, lin's weight, rnn.rnncells, cell,
+        cell's parameter dict, lin's parameter dict, w_rank, [u_rank]), or its first three for a model outside the family; this returns
+        it or None.  It holds no op namespace (torch_ops() is looked up at the call) and __getstate__ leaves it out: a pickled, saved
+        or deep-copied Net builds its own.
+        Checked on every call, by identity only: rnn, lin, lin's weight, rnn's cell list and that list's one cell must still be the
+        objects the plan was made from; a reassigned submodule or weight Parameter builds it again (and with it the class count).
+        Dropped by _apply (another device / dtype).  Checked at the call: kept parameter images, a compute dtype.  The VMLMF_STACK mode
+        is read when the plan is built (mode "1" routes single layers to the wavefront launch)."""
         plan = self.__dict__.get("_fast_plan")
-        if plan is None:
-            plan = False
-            rnn = self.rnn
+        m = self._modules
+        if (plan is None or m["rnn"] is not plan[0] or m["lin"] is not plan[1] or plan[1]._parameters.get("weight") is not plan[2]
+                or (len(plan) > 3 and (plan[0]._modules["rnncells"] is not plan[3] or len(plan[3]._modules) != 1
+                                       or plan[3]._modules.get("0") is not plan[4]))):
+            rnn, lin = self.rnn, self.lin
+            w = lin._parameters.get("weight")
+            plan = (rnn, lin, w)
             if (type(rnn) is MyLSTM and rnn.batch_first and len(rnn.rnncells) == 1 and type(rnn.rnncells[0]) is MyVMLMFCell
-                    and stack_mode() != "1"):
+                    and w is not None and w.shape[0] <= _lib.HEAD_MAX_CLASSES and w.dtype == torch.float32
+                    and stack_mode() != "1" and torch_ops() is not None):
                 cell = rnn.rnncells[0]
-                from .functional import torch_ops
-                ops = torch_ops()
-                if (ops is not None and cell.input_size <= 16 and cell.hidden_size <= 192 and self.lin.weight.shape[0] <= _lib.HEAD_MAX_CLASSES
-                        and self.lin.weight.dtype == torch.float32):
-                    plan = (ops, cell, cell._parameters, self.lin._parameters, int(cell.w_rank), [int(cell.u_ranks)])
+                if cell.input_size <= 16 and cell.hidden_size <= 192:
+                    plan = (rnn, lin, w, rnn.rnncells, cell, cell._parameters, lin._parameters, int(cell.w_rank), [int(cell.u_ranks)])
             self.__dict__["_fast_plan"] = plan
-        if plan is False or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+        if len(plan) == 3 or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
             return None
-        cd = plan[1].__dict__
+        cd = plan[4].__dict__
         if cd.get("_pack_cache") is not None or cd.get("compute_dtype", "f32") != "f32":
             return None
         return plan
@@ -375,12 +382,17 @@ class Net(nn.Module):
         self.__dict__.pop("_fast_plan", None)
         return super()._apply(fn, *args, **kwargs)
 
+    def __getstate__(self):                  # pickle / torch.save / copy.deepcopy: a copy builds its own plan
+        state = super().__getstate__()
+        state.pop("_fast_plan", None)
+        return state
+
     def forward(self, x):
         plan = self._fast(x)
         if plan is not None:
-            ops, cell, cp, lp, rw, ur = plan
-            out = ops.sequence(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"], cp["v_h"]],
-                               cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"])
+            cell, cp, lp, rw, ur = plan[4:]
+            out = torch_ops().sequence(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"],
+                                                       cp["v_h"]], cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"])
             return out[3].squeeze(1)
         if isinstance(self.rnn, MyLSTM) and self.rnn.batch_first:
             # y[:, -1] IS the last layer's final h (same kernel value): taking it from there keeps autograd
@@ -411,10 +423,10 @@ class Net(nn.Module):
         plan = self._fast(x) if (target.dtype == torch.int64 and target.dim() == 1) else None
         if plan is not None:
             from .functional import ce_ticket, unit_gradient
-            ops, cell, cp, lp, rw, ur = plan
-            out = ops.sequence_loss(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"], cp["v_h"]],
-                                    cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"], target, int(ignore_index),
-                                    unit_gradient(x.device), ce_ticket(x.device))
+            cell, cp, lp, rw, ur = plan[4:]
+            out = torch_ops().sequence_loss(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"],
+                                                            cp["v_h"]], cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"],
+                                            target, int(ignore_index), unit_gradient(x.device), ce_ticket(x.device))
             return (out[4], out[3]) if return_logits else out[4]
         ride = (isinstance(self.rnn, MyLSTM) and self.rnn.batch_first and x.is_cuda and x.dtype == torch.float32
                 and self.lin.weight.shape[0] <= _lib.HEAD_MAX_CLASSES and self.lin.weight.dtype == torch.float32

@@ -14,6 +14,13 @@ snapshot that is restored).  A batch whose shape differs from the example's (the
 the same body eagerly.  Scalars the kernels take by value are frozen in a capture (the learning rate of
 vmlmf_amd.optim.Adam): when a group's lr / betas / eps / weight_decay has changed since the capture, the step is captured again.
 
+What a replay sees and what it does not.  It sees: the values of parameters and optimizer state changed in place, which includes
+model.load_state_dict() and vmlmf_amd.optim.Adam.load_state_dict() (that one copies the loaded moments and step counts into the
+flat buffers the graph recorded, and zeroes them for parameters without loaded state); hyper-parameters (captured again); the
+library's kernel selection (captured again, see below).  It does not see objects replaced after the capture, such as a submodule
+or a Parameter assigned anew: the graph goes on reading and writing the tensors it recorded, so build a new GraphedTrainStep after
+such a change.  A parameter group added or removed after the capture raises.
+
 A launch inside the graph that gives up a bounded wait (include/vmlmf_hip.h: VMLMF_E_PROTOCOL - a GPU shared with other
 processes can starve the riding weight-gradient workers) leaves NaN gradients.  vmlmf_amd.optim.Adam's device-side gate skips
 the update of such a step, so the parameters stay intact; the host reads the library's status word in front of every replay
@@ -124,6 +131,9 @@ class GraphedTrainStep:
         if x.shape != self.x.shape or target.shape != self.t.shape:
             return self._body(x, target)     # e.g. the last, shorter batch of a DataLoader: same step, eager launches
         if self._hyper() != self._captured_hyper:
+            if len(self.optimizer.param_groups) != len(self._captured_hyper):
+                raise RuntimeError("vmlmf_amd.GraphedTrainStep: a parameter group was added or removed after the capture (its "
+                                   "optimizer state would be created inside the graph): build a new GraphedTrainStep")
             self._capture()                  # a scheduler changed lr (by-value kernel argument): capture it again
         # did a launch of an EARLIER replay give up a bounded wait?  (the status word is host memory: no GPU call)
         lib = _lib.lib()

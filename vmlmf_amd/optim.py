@@ -82,30 +82,48 @@ class Adam(torch.optim.Optimizer):
                 self._guard = torch.zeros(_lib.GUARD_WORDS, device=dev, dtype=torch.int32)
             self._flat[gi] = gs
             for p in ps:
-                o = offs[p]
-                new = dict(step=gs["steps"][sidx[p]], exp_avg=gs["m"][o:o + p.numel()].view_as(p),
-                           exp_avg_sq=gs["v"][o:o + p.numel()].view_as(p))
-                # state that exists already (load_state_dict of a checkpoint, also one written by torch.optim.Adam)
-                # moves into the flat buffers the kernel reads
-                old = self.state.get(p)
-                if old:
-                    for k in ("exp_avg", "exp_avg_sq"):
-                        if k in old:
-                            new[k].copy_(old[k].to(device=dev, dtype=torch.float32).view_as(p))
-                    if "step" in old:
-                        new["step"].fill_(float(old["step"]))
-                self.state[p] = new
+                self._adopt(gs, p, fresh=True)
         return gs
 
+    @torch.no_grad()
+    def _adopt(self, gs, p, fresh=False):
+        """state[p] becomes p's views of the group's flat buffers, holding what state[p] held before: the moments and step count of a
+        loaded checkpoint (also one written by torch.optim.Adam), zeros where it held none - where a fresh optimizer starts (`fresh`:
+        the buffers are new zeros already)."""
+        o, n = gs["offs"][p], p.numel()
+        new = dict(step=gs["steps"][gs["sidx"][p]], exp_avg=gs["m"][o:o + n].view_as(p), exp_avg_sq=gs["v"][o:o + n].view_as(p))
+        old = self.state.get(p) or {}
+        for k in ("exp_avg", "exp_avg_sq"):
+            if k in old:
+                new[k].copy_(old[k].to(device=new[k].device, dtype=torch.float32).view_as(p))
+            elif not fresh:
+                new[k].zero_()
+        if "step" in old:
+            new["step"].fill_(float(old["step"]))
+        elif not fresh:
+            new["step"].zero_()
+        self.state[p] = new
+
     def load_state_dict(self, state_dict):
-        """As torch.optim.Optimizer.load_state_dict; the flat buffers are rebuilt from the loaded moments and step
-        counts at the next step()."""
+        """As torch.optim.Optimizer.load_state_dict.  A group whose flat buffers exist gets the loaded moments and step counts
+        copied INTO them, and zeros for parameters without loaded state (an empty state_dict() resets to a fresh optimizer): the
+        buffers keep their addresses, so the argument blocks step() remembers and a GraphedTrainStep's captured graph stay valid.
+        A group without buffers yet gets them now when it has loaded state."""
         super().load_state_dict(state_dict)
         # converted NOW, not at the next step(): torch hands the checkpoint's own tensors through when device and dtype
         # already match, so a lazily read state would follow whatever the checkpoint's owner does to them meanwhile
+        flat = self.__dict__.get("_flat") or {}
         self._flat = {}
         for gi, group in enumerate(self.param_groups):
-            if any(self.state.get(p) for p in group["params"]):
+            gs, ps = flat.get(gi), group["params"]
+            if gs is not None and len(gs["offs"]) == len(ps) and all(a is b for a, b in zip(gs["offs"], ps)):
+                self._flat[gi] = gs
+                for p in ps:
+                    self._adopt(gs, p)
+                continue
+            if gs is not None:
+                self._step_cache = None   # (the group's old buffers are dropped: no remembered argument block may point at them)
+            if any(self.state.get(p) for p in ps):
                 self._group_state(gi, group)
 
     @torch.no_grad()
