@@ -32,6 +32,11 @@ extern "C" {
 #define VMLMF_E_BADARG (-1)      /* null pointer / inconsistent descriptor                          */
 #define VMLMF_E_SHAPE (-2)       /* shape the reference itself rejects (I > H, I != H for LM, H % g) */
 #define VMLMF_E_UNSUPPORTED (-3) /* valid for the reference, not yet covered by the HIP kernels       */
+/* Rank envelope (f32): padded w_rank <= 32 and padded hidden rank (summed over groups) <= 128 on every kernel family.  Beyond that a
+ * layer is "wide" and is covered on the step-wise family only (padded u_rank > 32, more than 512 thread slots or I > H), with
+ * w_rank <= I, u_rank <= H / g, padded w_rank <= 1024 and padded hidden rank (summed over shifts) <= 1024: e.g. the reference LM's
+ * defaults, MyVMLSTM(650, 650, w_rank=300, u_ranks=300).  Wide layers are fp32 only and are not taken by vmlmf_stack_* (the caller
+ * chains them).  Everything else outside the envelope is VMLMF_E_UNSUPPORTED with the reason in vmlmf_last_error(). */
 #define VMLMF_E_WORKSPACE (-4)   /* workspace / reserve smaller than vmlmf_query() asked for          */
 #define VMLMF_E_COMM (-5)        /* RCCL reported an error (text in vmlmf_last_error())                */
 #define VMLMF_E_PROTOCOL (-6)    /* ABI 8: a launch gave up a bounded wait for another workgroup (riding weight-gradient workers,

@@ -298,13 +298,30 @@ int make_geo(const vmlmf_desc* d, VGeo* out, RbGeo* rbout = nullptr, int force_W
     g.syT = g.H;
     g.syB = (long long)g.T * g.H;
   }
-  if (g.KX > 32) return fail(VMLMF_E_UNSUPPORTED, "padded w_rank > 32 is not covered by the HIP kernels");
-  if (g.G * g.KH > 128) return fail(VMLMF_E_UNSUPPORTED, "padded hidden rank (summed over groups) > 128 is not covered");
   // register-resident persistent kernels need <= 32 ranks per unit and <= 512 thread slots; larger layers
   // (e.g. H = 650, ranks [32,32]) run the step-wise path of vmlmf_generic.hip
   // (the cells without vm accept input_size > hidden_size; the persistent kernels keep x-side quantities in the slots of the
   // first I units, so such a layer takes the step-wise path, whose x side is indexed by input)
   g.generic = (g.KH > 32 || g.NT > 512 || g.I > g.H) ? 1 : 0;
+  // Wide layers (padded w_rank > 32, or padded hidden rank summed over groups > 128, e.g. the reference LM's default ranks 300 / 300):
+  // the step-wise family only, with the x side and the weight gradients as rank-agnostic GEMMs.  The register-resident kernels keep
+  // x-side factor images in registers; a wide x side there stays refused (the message keeps its historical start).
+  g.wide = (g.KX > 32 || g.G * g.KH > 128) ? 1 : 0;
+  if (g.wide) {
+    if (!g.generic) {
+      if (g.KX > 32)
+        return fail(VMLMF_E_UNSUPPORTED, "padded w_rank > 32 is not covered by the HIP kernels on a register-resident layer "
+                                         "(wide ranks need the step-wise path: padded u_rank > 32, more than 512 thread slots or I > H)");
+      return fail(VMLMF_E_UNSUPPORTED, "padded hidden rank (summed over groups) > 128 is not covered on a register-resident layer");
+    }
+    if (g.rw > g.I) return fail(VMLMF_E_UNSUPPORTED, "wide ranks: w_rank larger than input_size (an over-complete factorisation) is not covered");
+    if (g.ru0 > g.Hg || (g.G == 2 && g.ru1 > g.Hg))
+      return fail(VMLMF_E_UNSUPPORTED, "wide ranks: a u_rank larger than the units it factors (hidden_size / g) is not covered");
+    if (g.bf) return fail(VMLMF_E_UNSUPPORTED, "wide ranks: dtype bf16 is not covered (fp32 only)");
+    if (g.KX > 1024 || g.KH > 1024)
+      return fail(VMLMF_E_UNSUPPORTED, "wide ranks: padded w_rank and padded hidden rank (summed over shifts) are capped at 1024, the "
+                                       "bound of the step-wise workspace");
+  }
   // One batch row per workgroup, whatever the batch: with more rows than CUs the workgroups queue up, which
   // measured at least as fast as two rows per workgroup at every size (H = 180, T = 128: B = 512 0.49 vs 0.55 ms,
   // 768 0.71 vs 0.78, 1024 0.98 vs 0.96, 2048 1.84 vs 2.00); the kernels keep their R template parameter.
@@ -338,7 +355,7 @@ int make_geo(const vmlmf_desc* d, VGeo* out, RbGeo* rbout = nullptr, int force_W
       if (!g.generic && g.I <= g.H && rb_geometry(g, 1, &q, g_rb_rows)) g.rb = 1;
       else return fail(VMLMF_E_UNSUPPORTED, "dtype bf16: implemented by the row-block MFMA kernels for one-group layers (V1, V3, V5) "
                                             "with padded rank <= 32 and <= 512 thread slots");
-    } else if (g_rb_mode != 0 && g.I <= g.H) {
+    } else if (g_rb_mode != 0 && g.I <= g.H && !g.wide) {   // (wide layers: the step-wise recurrence only)
       if (g.generic) {          // factors beyond one CU's registers: a cluster of S workgroups per 16-row block
         // measured at H = 650, B = 256 (members of a cluster on one XCD): group layer (ranks 32+32) 2.98 / 2.21 / 2.09 ms with
         // clusters of 4 / 8 / 16, plain layer (rank 32) 1.84 / 1.64 / 1.60 ms: the largest cluster first
@@ -367,9 +384,9 @@ struct Layout {
   // reserve (training) : PACK | qx | gates | cs | Qs
   long long r_pack, r_qx, r_gates, r_cs, r_Qs, r_prog, r_total;
   // forward workspace  : PACK (inference only) | gx
-  long long f_pack, f_gx, f_qx, f_trash, f_Qtmp, f_P, f_ccar, f_zeros, f_part, f_xq, f_flag, f_total;
+  long long f_pack, f_gx, f_qx, f_trash, f_Qtmp, f_P, f_ccar, f_zeros, f_part, f_xq, f_flag, f_xrows, f_total;
   // backward workspace : dpre | dQs | wpart | cgrad
-  long long b_dpre, b_dQs, b_dqx, b_wpart, b_cgrad, b_trash, b_dHrec, b_ehterm, b_dcar, b_part, b_xq, b_flag, b_headdh, b_dux, b_total;
+  long long b_dpre, b_dQs, b_dqx, b_wpart, b_cgrad, b_trash, b_dHrec, b_ehterm, b_dcar, b_part, b_xq, b_flag, b_headdh, b_dux, b_wide, b_total;
 };
 
 Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
@@ -401,6 +418,7 @@ Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
   }
   L.f_xq = o, o += align64(g.rb ? q.xq_floats : 0);
   L.f_flag = o, o += align64(g.rb ? q.flag_words : 0);
+  L.f_xrows = o, o += align64((g.wide && !g.time_major) ? TB * g.I : 0);   // x in (t, b) row order for a wide layer's x-side GEMM
   L.f_total = o;
   o = 0;
   L.b_dpre = o, o += align64(TS * 4);
@@ -410,7 +428,7 @@ Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
   {
     long long blocks = g.nchunk;
     if (!g.generic && !g.rb && rec4_bwd_supported(g) && g.nwg > blocks) blocks = g.nwg;
-    L.b_wpart = o, o += align64(blocks * g.PCH);
+    L.b_wpart = o, o += align64(g.wide ? 0 : blocks * g.PCH);   // (wide layers: dense products in b_wide instead)
   }
   L.b_cgrad = o, o += align64((long long)g.NA * g.NT + (g.I > g.H ? (long long)g.I * g.KX : 0));   // + dU_x by input when I > H
   L.b_trash = o, o += 64;
@@ -427,6 +445,7 @@ Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
   L.b_headdh = o, o += align64((g.rb || g.generic) ? (long long)g.B * g.H : 0);   // d(hT) of a classifier on the row-block / step-wise families
   // the riding workers' shares of d(u_x) (finish2_kernel): [worker index][task][16 x 16]
   L.b_dux = o, o += align64((!g.generic && !g.rb && finish2_ok(g)) ? (long long)g.nchunk * (g.NT / 8) * 256 : 0);
+  L.b_wide = o, o += wide_scratch_floats(g);
   L.b_total = o;
   return L;
 }
@@ -542,7 +561,23 @@ static int backward_tail(const VGeo& g, const Layout& L, const vmlmf_params* p, 
   const WghArgs wh = wgrad_args(L, x, y, h0, rs, ws);
   const bool rode = ride != nullptr && ride->K > 0;
   int ring_nc[3] = {0, 0, 0};
-  if (!rode && inrow_blocks == 0) {
+  if (g.wide) {   // dense GEMMs straight into the canonical gradients (cgrad): no partial blocks, no reduce launch
+    const long long TB = (long long)g.T * g.B, N4 = 4LL * g.NT, GK = (long long)g.G * g.KH;
+    auto al = [](long long n) { return (n + 63) / 64 * 64; };
+    WideBuf wb;
+    wb.x = x, wb.y = y, wb.h0 = h0, wb.dpre = wh.dpre, wb.qx = wh.qx, wb.dqx = wh.dqx, wb.Qs = wh.Qs, wb.dQs = wh.dQs;
+    float* o = ws + L.b_wide;   // (the order of wide_scratch_floats)
+    wb.X = o, o += al(g.time_major ? 0 : TB * g.I);
+    wb.Hp = o, o += al(TB * g.H);
+    wb.dVd = o, o += al(N4 * GK);
+    wb.dUd = o, o += al((long long)g.H * GK);
+    wb.dVx = o, o += al(N4 * g.KX);
+    wb.dUx = o, o += al((long long)g.I * g.KX);
+    wb.csum = o;
+    wb.cgrad = ws + L.b_cgrad;
+    Scope sc(5, s);
+    if ((rc = hip_fail(wide_wgrad(g, wb, s), "wgrad")) != 0) return rc;
+  } else if (!rode && inrow_blocks == 0) {
     Scope sc(5, s);
     // large layers: operands through an LDS ring, long chunks (vmlmf_wgrad_ring.hip); -1: where it was measured faster
     const bool ring = g_wring != 0 && wgrad_ring_ok(g) && (g_wring > 0 || (g.generic && (long long)g.T * g.B >= 1024));
@@ -561,7 +596,7 @@ static int backward_tail(const VGeo& g, const Layout& L, const vmlmf_params* p, 
     Scope sc(12, s);
     return hip_fail(launch_finish2(g, to_refp(p), ws + L.b_wpart, ride->dux, ride->K, og, hb, ride->prog, s, health_word(s)), "finish2");
   }
-  {
+  if (!g.wide) {
     Scope sc(6, s);
     VGeo gr_ = g;
     if (rode) gr_.nchunk = ride->K;   // one partial block per worker index; the progress words go back to zero here
@@ -788,7 +823,8 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
   float* const qxbuf = g.training ? rs + L.r_qx : (g.generic ? ws + L.f_qx : nullptr);
   if (!xwave) {
     Scope sc(1, s);
-    if ((rc = hip_fail(launch_xproj(g, P, pack, x, gx, qxbuf, s), "xproj")) != 0)
+    if ((rc = hip_fail(g.wide ? wide_xproj(g, P, pack, x, ws + L.f_xrows, gx, qxbuf, s) : launch_xproj(g, P, pack, x, gx, qxbuf, s),
+                       "xproj")) != 0)
       return rc;
   }
   if (g.rb) {
@@ -977,6 +1013,10 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
     w.UXP = pack + P.UXP, w.EXT = pack + P.EXT, w.Vd = pack + P.VD;
     w.dpre = ws + L.b_dpre, w.dQs = ws + L.b_dQs, w.dHrec = ws + L.b_dHrec, w.ehterm = ws + L.b_ehterm;
     w.dcar = ws + L.b_dcar, w.dh0 = dh0, w.dc0 = dc0, w.dqx = ws + L.b_dqx, w.dx = dx;
+    if (g.wide) {   // dqx U_x^T goes to the last piece of the wide scratch (wide_scratch_floats)
+      w.UXT = pack + P.UXT;
+      w.dxs = ws + L.b_total - ((long long)g.T * g.B * g.I + 63) / 64 * 64;
+    }
     w.part = ws + L.b_part, w.part_cap = (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64);
     w.ticket = reinterpret_cast<int*>(const_cast<float*>(pack + P.TKT)), w.ticket_cap = VG_GEMM_TICKETS;
     {

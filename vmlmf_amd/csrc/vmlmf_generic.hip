@@ -177,6 +177,8 @@ struct GemmArgs {
   int na;
   long long astride;
   float* Asum;   // gemm_rows16_kernel: where the column-tile-0 workgroups leave A summed over its copies (or nullptr)
+  int at;        // gemm_tile_kernel: `A` is stored transposed (K x M, lda its row stride): C = A^T B, the weight-gradient products
+                 // of the wide layers, whose row operand is the (t, b) rows of a tape
 };
 
 // EPI 1: C = P_t is not stored; each (row, slot) of the tile goes straight through the forward gate math.
@@ -209,6 +211,7 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(GemmArgs a, EpiArgs e) {
   const bool arow_ok = m0 + ar < a.M;
   const float* Ap = a.A + (long long)(arow_ok ? m0 + ar : 0) * a.lda;
   const bool bvec = (a.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.B) & 15) == 0) && (n0 + bn + 3 < a.N);
+  const bool avec_t = (a.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.A) & 15) == 0) && (m0 + bn + 3 < a.M);
 
   f32x16 acc;
 #pragma unroll
@@ -216,10 +219,27 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(GemmArgs a, EpiArgs e) {
   for (int kb = k0; kb < k1; kb += GBK) {
     float ra[GBK / 4];
     float4 rb[GBK / 16];
+    if (!a.at) {
 #pragma unroll
-    for (int i = 0; i < GBK / 4; ++i) {
-      const int k = kb + aj + 4 * i;
-      ra[i] = (arow_ok && k < k1) ? Ap[k] : 0.f;
+      for (int i = 0; i < GBK / 4; ++i) {
+        const int k = kb + aj + 4 * i;
+        ra[i] = (arow_ok && k < k1) ? Ap[k] : 0.f;
+      }
+    } else {   // A^T: thread -> (k = kk + 16 i, 4 consecutive m), the same roles as B's staging
+#pragma unroll
+      for (int i = 0; i < GBK / 16; ++i) {
+        const int k = kb + bk + 16 * i;
+        float4 v = f4zero();
+        if (k < k1) {
+          const float* p = a.A + (long long)k * a.lda + m0 + bn;
+          if (avec_t)
+            v = ld4(p);
+          else
+            v = make_float4(m0 + bn + 0 < a.M ? p[0] : 0.f, m0 + bn + 1 < a.M ? p[1] : 0.f, m0 + bn + 2 < a.M ? p[2] : 0.f,
+                            m0 + bn + 3 < a.M ? p[3] : 0.f);
+        }
+        ra[4 * i] = v.x, ra[4 * i + 1] = v.y, ra[4 * i + 2] = v.z, ra[4 * i + 3] = v.w;
+      }
     }
 #pragma unroll
     for (int i = 0; i < GBK / 16; ++i) {
@@ -235,8 +255,14 @@ __global__ void __launch_bounds__(256) gemm_tile_kernel(GemmArgs a, EpiArgs e) {
       }
     }
     if (kb != k0) __syncthreads();   // the previous stage's MFMAs have read LDS
+    if (!a.at) {
 #pragma unroll
-    for (int i = 0; i < GBK / 4; ++i) As[aj + 4 * i][ar] = ra[i];
+      for (int i = 0; i < GBK / 4; ++i) As[aj + 4 * i][ar] = ra[i];
+    } else {
+#pragma unroll
+      for (int i = 0; i < GBK / 16; ++i)
+        *reinterpret_cast<float4*>(&As[bk + 16 * i][bn]) = make_float4(ra[4 * i], ra[4 * i + 1], ra[4 * i + 2], ra[4 * i + 3]);
+    }
 #pragma unroll
     for (int i = 0; i < GBK / 16; ++i) *reinterpret_cast<float4*>(&Bs[bk + 16 * i][bn]) = rb[i];
     __syncthreads();
@@ -614,11 +640,7 @@ static int launch_dhrec(const float* part, int GK, const float* UdT, int H, floa
   return (int)hipGetLastError();
 }
 
-// Bt / ldbt: the same factor stored transposed (N x K), or nullptr
-static int gemm(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc, int M, int N,
-                int K, float* part, long long part_cap, int* ticket, int ticket_cap, hipStream_t s,
-                const float* Bt = nullptr, long long ldbt = 0, int epi = 0, const EpiArgs* ea = nullptr, bool bquad = false) {
-  GemmArgs a{A, lda, B, ldb, C, ldc, M, N, K, part, ticket};
+static int gemm_raise_lds() {
   static bool raised = false;
   if (!raised) {   // 69 KB of dynamic LDS
     for (const void* f : {reinterpret_cast<const void*>(gemm_tile_kernel<0>), reinterpret_cast<const void*>(gemm_tile_kernel<1>)}) {
@@ -627,6 +649,16 @@ static int gemm(const float* A, long long lda, const float* B, long long ldb, fl
     }
     raised = true;
   }
+  return 0;
+}
+
+// Bt / ldbt: the same factor stored transposed (N x K), or nullptr
+static int gemm(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc, int M, int N,
+                int K, float* part, long long part_cap, int* ticket, int ticket_cap, hipStream_t s,
+                const float* Bt = nullptr, long long ldbt = 0, int epi = 0, const EpiArgs* ea = nullptr, bool bquad = false) {
+  GemmArgs a{A, lda, B, ldb, C, ldc, M, N, K, part, ticket};
+  int rc;
+  if ((rc = gemm_raise_lds()) != 0) return rc;
   if (bquad) {   // B is [k / 4][n][k % 4] (the caller's image; K and lda multiples of four): always the skinny kernel (VMLMF_SKINNY has
                  // no row-major image to fall back to)
     if (N > 128 || K % 4 != 0 || lda % 4 != 0) return -3;
@@ -774,6 +806,8 @@ __global__ void __launch_bounds__(256) dx_kernel(VGeo g, const float* __restrict
   }
 }
 
+static int wide_dqx_dx(const VGeo& g, const GenericBuf& w, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------------
 int generic_forward(const VGeo& g, const GenericBuf& w, hipStream_t s) {
   const int B = g.B, H = g.H, NT = g.NT, GK = g.G * g.KH, T = g.T;
@@ -867,6 +901,7 @@ int generic_backward(const VGeo& g, const GenericBuf& w, hipStream_t s) {
 int generic_dqx_dx(const VGeo& g, const GenericBuf& w, hipStream_t s) {
   const int B = g.B, NT = g.NT, T = g.T;
   int rc;
+  if (g.wide) return wide_dqx_dx(g, w, s);
   // dqx over all rows, then dx
   // (w.VxT is the quad-interleaved image [slot][r][gate]: pack_kernel)
   if ((rc = gemm(w.dpre, (long long)NT * 4, w.VxT, g.KX, w.dqx, g.KX, T * B, g.KX, NT * 4, w.part, w.part_cap, w.ticket,
@@ -890,4 +925,184 @@ int generic_dqx_dx(const VGeo& g, const GenericBuf& w, hipStream_t s) {
 // input width, on the 16 x 16 MFMA tiles of gemm_skinny_kernel.  (xproj_kernel's own form of it took 50 us at H = 650.)
 int generic_qx(const VGeo& g, const float* x, const float* UXP, float* qx, hipStream_t s) {
   return gemm(x, g.I, UXP, g.KX, qx, g.KX, g.T * g.B, g.KX, g.I, nullptr, 0, nullptr, 0, s);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Wide layers (VGeo::wide: padded w_rank > 32 or padded hidden rank > 128, up to 1024 each).  The recurrence is generic_forward /
+// generic_backward as they are; what the narrow layers do with rank-templated kernels runs here as GEMMs on the tile / skinny kernels
+// above plus small element-wise kernels, none of them templated on a rank:
+//   x side      qx = X U_x,  gx = qx VXD (+ x .* ex + b_x + b_h: wide_gx_kernel)
+//   dqx, dx     dqx = dpre VxT (row-major image),  dx = dqx U_x^T (+ dpre . ex: wide_dx_kernel)
+//   gradients   dVd = dpre^T Q, dUd = H_prev^T dQ, dVx = dpre^T qx, dUx = X^T dqx (transposed-A tiles, whole K per workgroup),
+//               the column sums of dpre (bias), dpre .* h_prev (eh) and dpre .* x (ex) in fixed row chunks, and wide_cg_kernel, which
+//               lays it all out as the canonical gradients finish_kernel maps to the reference tensors
+// No atomics on floats and fixed summation orders: a call is bit-identical run to run.
+// ---------------------------------------------------------------------------------------------------
+
+// dst[(t B + b) W + j] = src[(t - shift) sT + b sB + j] (t >= shift), else first[b W + j] (or 0): the rows of a (t, b)-ordered matrix
+__global__ void __launch_bounds__(256) wide_rows_kernel(int B, int W, const float* __restrict__ src, long long sT, long long sB, int shift,
+                                                        const float* __restrict__ first, float* __restrict__ dst) {
+  const long long row = blockIdx.x;
+  const int t = (int)(row / B), b = (int)(row - (long long)t * B);
+  const float* sp = t >= shift ? src + (long long)(t - shift) * sT + (long long)b * sB : (first != nullptr ? first + (long long)b * W : nullptr);
+  for (int j = threadIdx.x; j < W; j += 256) dst[row * W + j] = sp != nullptr ? sp[j] : 0.f;
+}
+
+static int wide_rows(const VGeo& g, int W, const float* src, long long sT, long long sB, int shift, const float* first, float* dst,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(wide_rows_kernel, dim3((unsigned)(g.T * g.B)), dim3(256), 0, s, g.B, W, src, sT, sB, shift, first, dst);
+  return (int)hipGetLastError();
+}
+
+// gx[row][slot][k] += x[row][n] ex[k][n] + bb[k][n] (units n < I carry the x term; pad slots stay zero)
+__global__ void __launch_bounds__(256) wide_gx_kernel(VGeo g, const float* __restrict__ X, const float* __restrict__ ext,
+                                                      const float* __restrict__ bbt, float* __restrict__ gx) {
+  const long long row = blockIdx.x;
+  const int H = g.H;
+  for (int slot = threadIdx.x; slot < g.NT; slot += 256) {
+    int n;
+    if (!vg_slot_unit(g, slot, n)) continue;
+    const float xv = n < g.I ? X[row * g.I + n] : 0.f;
+    float* p = gx + (row * g.NT + slot) * 4;
+    const float4 c4 = ld4(p);
+    st4(p, make_float4(fmaf(xv, ext[0 * H + n], c4.x + bbt[0 * H + n]), fmaf(xv, ext[1 * H + n], c4.y + bbt[1 * H + n]),
+                       fmaf(xv, ext[2 * H + n], c4.z + bbt[2 * H + n]), fmaf(xv, ext[3 * H + n], c4.w + bbt[3 * H + n])));
+  }
+}
+
+int wide_xproj(const VGeo& g, const VPack& L, const float* pack, const float* x, float* xrows, float* gx, float* qx, hipStream_t s) {
+  const int TB = g.T * g.B, N4 = 4 * g.NT;
+  int rc;
+  const float* X = x;
+  if (!g.time_major) {   // GEMM rows in (t, b) order
+    if ((rc = wide_rows(g, g.I, x, g.sxT, g.sxB, 0, nullptr, xrows, s)) != 0) return rc;
+    X = xrows;
+  }
+  if ((rc = gemm(X, g.I, pack + L.UXP, g.KX, qx, g.KX, TB, g.KX, g.I, nullptr, 0, nullptr, 0, s)) != 0) return rc;
+  if ((rc = gemm(qx, g.KX, pack + L.VXD, N4, gx, N4, TB, N4, g.KX, nullptr, 0, nullptr, 0, s)) != 0) return rc;
+  hipLaunchKernelGGL(wide_gx_kernel, dim3((unsigned)TB), dim3(256), 0, s, g, X, pack + L.EXT, pack + L.BBT, gx);
+  return (int)hipGetLastError();
+}
+
+// dx[t, b, m] = dxs[row][m] + sum_k dpre[row][slot(m)][k] ex[k][m]   (dxs = dqx U_x^T; inputs beyond the last unit: no ex term)
+__global__ void __launch_bounds__(256) wide_dx_kernel(VGeo g, const float* __restrict__ dxs, const float* __restrict__ dpre,
+                                                      const float* __restrict__ ext, float* __restrict__ dx) {
+  const long long row = blockIdx.x;
+  const int t = (int)(row / g.B), b = (int)(row - (long long)t * g.B);
+  for (int m = threadIdx.x; m < g.I; m += 256) {
+    float acc = 0.f;
+    if (m < g.H) {
+      const float4 d = ld4(dpre + (row * g.NT + vg_slot(g, m)) * 4);
+      acc = (d.x * ext[0 * g.H + m] + d.y * ext[1 * g.H + m]) + (d.z * ext[2 * g.H + m] + d.w * ext[3 * g.H + m]);
+    }
+    dx[(long long)t * g.sxT + (long long)b * g.sxB + m] = dxs[row * g.I + m] + acc;
+  }
+}
+
+static int wide_dqx_dx(const VGeo& g, const GenericBuf& w, hipStream_t s) {
+  const int TB = g.T * g.B, N4 = 4 * g.NT;
+  int rc;
+  // (w.VxT is the row-major image [slot*4+k][r] on wide layers: pack_kernel)
+  if ((rc = gemm(w.dpre, N4, w.VxT, g.KX, w.dqx, g.KX, TB, g.KX, N4, nullptr, 0, nullptr, 0, s)) != 0) return rc;
+  if (w.dx == nullptr) return 0;
+  if ((rc = gemm(w.dqx, g.KX, w.UXT, g.I, w.dxs, g.I, TB, g.I, g.KX, nullptr, 0, nullptr, 0, s)) != 0) return rc;
+  hipLaunchKernelGGL(wide_dx_kernel, dim3((unsigned)TB), dim3(256), 0, s, g, w.dxs, w.dpre, w.EXT, w.dx);
+  return (int)hipGetLastError();
+}
+
+// C[M x N] = A^T B, A stored K x M: one 64 x 64 tile per workgroup over the whole K (no split: fixed order)
+static int gemm_at(const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc, int M, int N, int K,
+                   hipStream_t s) {
+  int rc;
+  if ((rc = gemm_raise_lds()) != 0) return rc;
+  GemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = A, a.lda = lda, a.B = B, a.ldb = ldb, a.C = C, a.ldc = ldc, a.M = M, a.N = N, a.K = K, a.at = 1;
+  EpiArgs none;
+  memset(&none, 0, sizeof(none));
+  const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+  hipLaunchKernelGGL(gemm_tile_kernel<0>, dim3(tiles, 1), dim3(256), GEMM_LDS, s, a, none);
+  return (int)hipGetLastError();
+}
+
+// Column sums over the (t, b) rows in WIDE_NCH fixed chunks: part[ch][0][j] = sum dpre[row][j] h_prev[row][n],
+// [1] = sum dpre[row][j] x[row][n] (n < I), [2] = sum dpre[row][j]; column j = slot * 4 + gate
+__global__ void __launch_bounds__(256) wide_colsum_kernel(VGeo g, const float* __restrict__ dpre, const float* __restrict__ Hp,
+                                                          const float* __restrict__ X, int per, float* __restrict__ part) {
+  const int N4 = 4 * g.NT, j = blockIdx.x * 256 + threadIdx.x, ch = blockIdx.y, TB = g.T * g.B;
+  if (j >= N4) return;
+  int n;
+  const bool valid = vg_slot_unit(g, j >> 2, n);
+  const bool hx = valid && n < g.I;
+  float seh = 0.f, sex = 0.f, sb = 0.f;
+  const int r0 = ch * per, r1 = r0 + per < TB ? r0 + per : TB;
+  if (valid) {
+    for (int row = r0; row < r1; ++row) {
+      const float d = dpre[(long long)row * N4 + j];
+      seh = fmaf(d, Hp[(long long)row * g.H + n], seh);
+      if (hx) sex = fmaf(d, X[(long long)row * g.I + n], sex);
+      sb += d;
+    }
+  }
+  part[((long long)ch * 3 + 0) * N4 + j] = seh;
+  part[((long long)ch * 3 + 1) * N4 + j] = sex;
+  part[((long long)ch * 3 + 2) * N4 + j] = sb;
+}
+
+// canonical gradients cg[a][slot] (vg accumulator indices va_*; I > H: dU_x by input behind them) from the dense products
+__global__ void __launch_bounds__(256) wide_cg_kernel(VGeo g, WideBuf w, int nch) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x, body = (long long)g.NA * g.NT;
+  const int KX = g.KX, KH = g.KH, GK = g.G * g.KH, N4 = 4 * g.NT;
+  if (e >= body) {
+    const long long e2 = e - body;
+    if (g.I > g.H && e2 < (long long)g.I * KX) w.cgrad[e] = w.dUx[e2];
+    return;
+  }
+  int a = (int)(e / g.NT);
+  const int slot = (int)(e - (long long)a * g.NT);
+  int n;
+  float v = 0.f;
+  if (vg_slot_unit(g, slot, n)) {
+    if (a < 4 * KX) {                        // va_vx(k, r)
+      const int k = a / KX;
+      v = w.dVx[(long long)(slot * 4 + k) * KX + (a - k * KX)];
+    } else if ((a -= 4 * KX) < 4 * KH) {     // va_vc(k, rr): the rank-space vector gate k of unit n reads
+      const int k = a / KH, rr = a - k * KH;
+      const int qsel = g.G == 1 ? 0 : (g.flat ? (k * g.H + n) / (4 * g.Hg) : n / g.Hg);
+      v = w.dVd[(long long)(slot * 4 + k) * GK + qsel * KH + rr];
+    } else if ((a -= 4 * KH) < KH) {         // va_uc(rr): the destination group unit n feeds through block s
+      const int sblk = (g.G == 2 && a >= g.off1) ? 1 : 0;
+      const int dest = (n / g.Hg - sblk + g.G) % g.G;
+      v = w.dUd[(long long)n * GK + dest * KH + a];
+    } else if ((a -= KH) < KX) {             // va_ux(r) of input n (I <= H)
+      v = n < g.I ? w.dUx[(long long)n * KX + a] : 0.f;
+    } else {                                 // va_eh / va_ex / va_b (k): the chunks' partial sums in chunk order
+      a -= KX;
+      const int which = a >> 2, k = a & 3;
+      for (int ch = 0; ch < nch; ++ch) v += w.csum[((long long)ch * 3 + which) * N4 + slot * 4 + k];
+    }
+  }
+  w.cgrad[e] = v;
+}
+
+int wide_wgrad(const VGeo& g, const WideBuf& w, hipStream_t s) {
+  const int TB = g.T * g.B, N4 = 4 * g.NT, GK = g.G * g.KH;
+  int rc;
+  const float* X = w.x;
+  if (!g.time_major) {
+    if ((rc = wide_rows(g, g.I, w.x, g.sxT, g.sxB, 0, nullptr, w.X, s)) != 0) return rc;
+    X = w.X;
+  }
+  if ((rc = wide_rows(g, g.H, w.y, g.syT, g.syB, 1, w.h0, w.Hp, s)) != 0) return rc;
+  if ((rc = gemm_at(w.dpre, N4, w.Qs, GK, w.dVd, GK, N4, GK, TB, s)) != 0) return rc;
+  if ((rc = gemm_at(w.Hp, g.H, w.dQs, GK, w.dUd, GK, g.H, GK, TB, s)) != 0) return rc;
+  if ((rc = gemm_at(w.dpre, N4, w.qx, g.KX, w.dVx, g.KX, N4, g.KX, TB, s)) != 0) return rc;
+  if ((rc = gemm_at(X, g.I, w.dqx, g.KX, w.dUx, g.KX, g.I, g.KX, TB, s)) != 0) return rc;
+  const int nch = TB < WIDE_NCH ? TB : WIDE_NCH, per = (TB + nch - 1) / nch;
+  hipLaunchKernelGGL(wide_colsum_kernel, dim3((unsigned)((N4 + 255) / 256), (unsigned)nch), dim3(256), 0, s, g, w.dpre, w.Hp, X, per,
+                     w.csum);
+  if ((rc = (int)hipGetLastError()) != 0) return rc;
+  const long long total = (long long)g.NA * g.NT + (g.I > g.H ? (long long)g.I * g.KX : 0);
+  hipLaunchKernelGGL(wide_cg_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, w, nch);
+  return (int)hipGetLastError();
 }

@@ -40,6 +40,8 @@ struct VGeo {
                 // bf16-MFMA row blocks pay: fp32 arithmetic everywhere, 8 instead of 16 bytes per unit and step written and read back)
   int rb;       // > 0: the recurrence runs on the row-block MFMA kernels (vmlmf_rb.hip), 16 batch rows per workgroup;
                 //      the value is S, the workgroups a row block's hidden units are split over (1 = no cluster)
+  int wide;     // 1: padded w_rank > 32 or padded hidden rank (summed over groups) > 128 - a step-wise layer whose x side and weight
+                //    gradients run as rank-agnostic GEMMs (vmlmf_generic.hip: wide_xproj, generic_dqx_dx, wide_wgrad)
 };
 
 // Geometry of the row-block kernels (vmlmf_rb.hip).  Valid 16-unit tiles of a group are dealt to "wave slots"
@@ -63,6 +65,7 @@ struct VPack {
   long long UD, VD, UDT, VDT, VXTT;   // dense group factors + V_x^T, step-wise path only
   long long TKT;                      // split-K tickets of the step-wise GEMMs (ints; pack_kernel zeroes them)
   long long VXD;                      // V_x as a (rank x 4*slots) matrix: B operand of the MFMA x-side expansion (large layers)
+  long long UXT;                      // U_x^T (rank x input), row-major: B operand of dx = dqx U_x^T (wide layers only)
   long long WXD;                      // dense x-side matrix W_x[m][k][slot] of the x-projection wave (I <= 16 only)
   long long RB;                       // A-operand images of the row-block kernels (RbGeo offsets are relative to RB)
   long long WF, total;                // rotated images of the wavefront kernels (WfPack offsets are relative to WF)
@@ -99,7 +102,7 @@ VG_HD VPack vg_pack_layout(const VGeo& g, long long rb_floats = 0, long long wf_
   p.UXO = take(pk * 1LL * g.KX * g.NT);
   p.EXI = take(pk * 4LL * g.NT);
   p.UXP = take(1LL * g.I * g.KX);
-  p.VXT = take(4LL * g.KX * g.H);
+  p.VXT = take(g.wide ? 0 : 4LL * g.KX * g.H);   // (xproj_kernel's image; a wide layer's x side is two GEMMs)
   p.EXT = take(4LL * g.H);
   p.BBT = take(4LL * g.H);
   const long long GK = (long long)g.G * g.KH, N4 = 4LL * g.NT;
@@ -107,9 +110,10 @@ VG_HD VPack vg_pack_layout(const VGeo& g, long long rb_floats = 0, long long wf_
   p.VD = take(dense ? GK * N4 : 0);
   p.UDT = take(dense ? GK * g.H : 0);
   p.VDT = take(dense ? N4 * GK : 0);
-  p.VXTT = take(g.generic ? N4 * g.KX : 0);
+  p.VXTT = take(g.generic ? N4 * g.KX : 0);   // quad-interleaved [slot][r][k]; wide layers: row-major [slot*4+k][r]
   p.TKT = take(g.generic ? VG_GEMM_TICKETS : 0);
   p.VXD = take(g.generic ? N4 * g.KX : 0);
+  p.UXT = take(g.wide ? (long long)g.KX * g.I : 0);
   p.WXD = take(vg_xwave_ok(g) ? 4LL * g.I * g.NT : 0);
   p.RB = take(g.rb ? rb_floats : 0);
   p.WF = take(wf_floats);

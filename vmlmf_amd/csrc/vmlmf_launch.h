@@ -108,6 +108,8 @@ struct GenericBuf {
   // backward
   const float *dy, *dhT, *dcT, *UdT, *VdT, *VxT, *UXP, *EXT;
   float *dpre, *dQs, *dHrec, *ehterm, *dcar, *dh0, *dc0, *dqx, *dx;
+  const float* UXT;   // wide layers: U_x^T (rank x input), and dqx U_x^T before its diagonal terms (T*B x I)
+  float* dxs;
   // split-K scratch of the GEMMs: partial products and per-tile tickets (zero between launches)
   float* part;
   long long part_cap;
@@ -120,6 +122,26 @@ int generic_backward(const VGeo& g, const GenericBuf& w, hipStream_t s);
 int generic_dqx_dx(const VGeo& g, const GenericBuf& w, hipStream_t s);
 // qx = x U_x over all rows of a large time-major layer
 int generic_qx(const VGeo& g, const float* x, const float* UXP, float* qx, hipStream_t s);
+// wide layers (VGeo::wide): the x side (qx and gx; xrows: room for x in (t, b) row order when the layer is batch-first) and the weight
+// gradients as GEMMs, laid out as the canonical gradients (cgrad) that launch_finish maps to the reference tensors
+int wide_xproj(const VGeo& g, const VPack& L, const float* pack, const float* x, float* xrows, float* gx, float* qx, hipStream_t s);
+constexpr int WIDE_NCH = 64;   // row chunks of the column sums
+struct WideBuf {
+  const float *x, *y, *h0, *dpre, *qx, *dqx, *Qs, *dQs;
+  float *X, *Hp;                     // (t, b)-ordered rows of x (batch-first layers) and of h_{t-1}
+  float *dVd, *dUd, *dVx, *dUx;      // dense products: (4 slots x G KH), (H x G KH), (4 slots x KX), (I x KX)
+  float *csum;                       // [WIDE_NCH][3][4 slots] column-sum partials
+  float *cgrad;
+};
+// floats of a wide layer's backward scratch for the above (X, Hp, the dense products, csum, dqx U_x^T)
+inline long long wide_scratch_floats(const VGeo& g) {
+  if (!g.wide) return 0;
+  const long long TB = (long long)g.T * g.B, N4 = 4LL * g.NT, GK = (long long)g.G * g.KH;
+  auto al = [](long long n) { return (n + 63) / 64 * 64; };
+  return al(g.time_major ? 0 : TB * g.I) + al(TB * g.H) + al(N4 * GK) + al((long long)g.H * GK) + al(N4 * g.KX) +
+         al((long long)g.I * g.KX) + al((long long)WIDE_NCH * 3 * N4) + al(TB * g.I);
+}
+int wide_wgrad(const VGeo& g, const WideBuf& w, hipStream_t s);
 
 constexpr int RBX_MAXL = 4;   // layers of a clustered stack (vmlmf_rbx.hip)
 // row-block MFMA recurrent kernels (vmlmf_rb.hip)

@@ -216,11 +216,14 @@ __device__ __forceinline__ void pack_body(const VGeo& g, const RefP& p, const VP
         const int le = e - (int)L.VXTT;
         if (le < N4 * g.KX) {
           const int sl = le / (4 * g.KX), rem = le - sl * 4 * g.KX;
-          rr = rem >> 2; k = rem & 3;
+          if (g.wide) { rr = rem % g.KX; k = rem / g.KX; } else { rr = rem >> 2; k = rem & 3; }   // wide: row-major [slot*4+k][r]
           if (vg_slot_unit(g, sl, n)) mode = 3; else n = -1;
         }
       } else if (e >= L.WXD) {  // WXD: dot workgroups
         if (e - (int)L.WXD < D.nWXD) continue;
+      } else if (e >= L.UXT) {  // UXT[r][m] (wide layers)
+        const int le = e - (int)L.UXT;
+        if (le < g.KX * g.I) v = ref_ux(g, p, le % g.I, le / g.I);
       } else if (e >= L.VXD) {  // VXD[r][slot*4+k]
         const int le = e - (int)L.VXD;
         if (le < g.KX * N4) {
