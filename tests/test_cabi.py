@@ -266,18 +266,30 @@ def test_clustered_stacks_are_planned_where_all_clusters_are_co_resident():
 
 def test_the_run_time_switches_follow_the_environment():
     """Round 6: the switches defined inside the extern "C" block came up with other switches' defaults (mangled lambda names shared with the
-    top-of-file block).  A fresh process must see what the environment says."""
+    top-of-file block).  A fresh process must see what the environment says: every key vmlmf_tune_get answers, set from its environment
+    variable, read back; the defaults with no VMLMF_* set; and the parse rules (on unless it starts with 0, integer, positive or the
+    default)."""
     import subprocess
     import sys
+    # key: (environment variable, default, a value that is not the default)
+    switches = {"rbx": ("VMLMF_RBX", 1, 7), "ffb": ("VMLMF_FFB", 0, -1), "rb": ("VMLMF_RB", -1, 0), "inrow": ("VMLMF_INROW", -1, 1),
+                "rec3": ("VMLMF_REC3", 6, 5), "adam_guard": ("VMLMF_ADAM_GUARD", 1, 2), "wring": ("VMLMF_WRING", -1, 1),
+                "direct": ("VMLMF_DIRECT", 1, 0), "finish2": ("VMLMF_FINISH2", 1, 0), "wride": ("VMLMF_WRIDE", 1, 0),
+                "rb_min_batch": ("VMLMF_RB_MINB", 0, 96), "rb_cluster": ("VMLMF_RB_S", 0, 8), "rb_rows": ("VMLMF_RB_ROWS", 0, 4)}
     code = ("import ctypes; from vmlmf_amd import _lib; l = _lib.lib(); v = ctypes.c_int(); out = []\n"
-            "for k in (b'rbx', b'ffb', b'rb', b'inrow'):\n"
-            "    l.vmlmf_tune_get(k, ctypes.byref(v)); out.append(v.value)\n"
+            f"for k in {[k.encode() for k in switches]!r}:\n"
+            "    assert l.vmlmf_tune_get(k, ctypes.byref(v)) == 0, k; out.append(v.value)\n"
             "print(out)")
-    env = dict(os.environ, VMLMF_RBX="7", VMLMF_FFB="-1", VMLMF_RB="0", VMLMF_INROW="1", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert r.stdout.strip().splitlines()[-1] == "[7, -1, 0, 1]", r.stdout
-    env = {k: v for k, v in os.environ.items() if not k.startswith("VMLMF_")}
-    env["PYTHONPATH"] = ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.stdout.strip().splitlines()[-1] == "[1, 0, -1, -1]", r.stdout
+    base = {k: v for k, v in os.environ.items() if not k.startswith("VMLMF_")}
+    base["PYTHONPATH"] = ROOT
+
+    def read(extra):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(base, **extra), timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return dict(zip(switches, eval(r.stdout.strip().splitlines()[-1])))
+
+    assert read({e: str(v) for e, _, v in switches.values()}) == {k: v for k, (_, _, v) in switches.items()}
+    assert read({}) == {k: d for k, (_, d, _) in switches.items()}
+    got = read({"VMLMF_WRIDE": "-1", "VMLMF_DIRECT": "00", "VMLMF_RB_MINB": "-5", "VMLMF_RB_S": "x", "VMLMF_REC3": "3abc"})
+    assert (got["wride"], got["direct"], got["rb_min_batch"], got["rb_cluster"], got["rec3"]) == (1, 0, 0, 0, 3), got
+    assert read({"VMLMF_WRIDE": "0x"})["wride"] == 0

@@ -13,6 +13,19 @@
 #include "../../include/vmlmf_hip.h"
 #include "vmlmf_launch.h"
 
+int vmlmf_env_switch(const char* name, EnvRule rule, int dflt) {
+  const char* e = getenv(name);
+  if (e == nullptr) return dflt;
+  switch (rule) {
+    case ENV_SET: return 1;
+    case ENV_ON: return e[0] != '0';
+    case ENV_INT: return atoi(e);
+    case ENV_POS: break;
+  }
+  const int v = atoi(e);
+  return v >= 1 ? v : dflt;
+}
+
 namespace {
 
 thread_local std::string g_err = "";
@@ -30,9 +43,70 @@ struct Prof {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[NKERN];
 } g_prof;
 
-// VMLMF_DEBUG_SYNC=1: synchronise after every internal launch and name it on stderr (finds the kernel behind an
-// asynchronous GPU fault; never set in production: it serialises everything and breaks hipGraph capture)
-const bool g_debug_sync = getenv("VMLMF_DEBUG_SYNC") != nullptr;
+// ---- process-wide switches: one row each in g_switches (the vmlmf_tune keys are documented in include/vmlmf_hip.h) ----
+int g_debug_sync, g_adam_guard, g_xwave, g_wchunks, g_wmin, g_rc, g_wride, g_wride_k, g_wride_maxb, g_wride_lag, g_wride_rc, g_rb_mode,
+    g_rb_minB, g_rb_S, g_rb_rows, g_rec3, g_inrow, g_wring, g_direct, g_finish2, g_wf_bwd, g_pack_slim, g_finish_units, g_rbx, g_ffb;
+struct Switch {
+  const char* env;
+  const char* key;   // vmlmf_tune / vmlmf_tune_get key, or NULL (environment only)
+  int dflt;
+  EnvRule rule;
+  int* var;
+};
+// ("wride" is no row's key: vmlmf_tune("wride") moves the trip latch below, not VMLMF_WRIDE's setting; vmlmf_tune clamps the rb_* keys)
+const Switch g_switches[] = {
+    // synchronise after every internal launch and name it on stderr (finds the kernel behind an asynchronous GPU fault; never set in
+    // production: it serialises everything and breaks hipGraph capture)
+    {"VMLMF_DEBUG_SYNC", nullptr, 0, ENV_SET, &g_debug_sync},
+    {"VMLMF_ADAM_GUARD", "adam_guard", 1, ENV_INT, &g_adam_guard},
+    {"VMLMF_XWAVE", nullptr, 1, ENV_ON, &g_xwave},   // 0: the x projection always as a launch of its own
+    // weight-gradient chunking (A/B): target row chunks, fewest rows per chunk (config C, 3072 rows: 0.2546 ms at 32 or 48, 0.2428 at
+    // 64, 0.243 at 96), dqx_dx rows per workgroup (0: from the row count).  Positive or the default: a zero divides by zero in make_geo
+    {"VMLMF_WCHUNKS", nullptr, 64, ENV_POS, &g_wchunks},
+    {"VMLMF_WMIN", nullptr, 64, ENV_POS, &g_wmin},
+    {"VMLMF_RC", nullptr, 0, ENV_POS, &g_rc},
+    // weight-gradient workers riding on the recurrent backward launch (vmlmf_atb.inc): on / off, workers per task, the largest batch
+    // that rides (round 3, H = 180, T = 128, ride on / off: B 32 0.158 / 0.165 ms, 64 0.160 / 0.173, 72 0.185 / 0.178, 96 0.192 /
+    // 0.181 - beyond 64 the faster rows outrun the workers), segments a progress word trails, rows per chunk
+    {"VMLMF_WRIDE", nullptr, 1, ENV_ON, &g_wride},
+    {"VMLMF_WRIDE_K", nullptr, 32, ENV_POS, &g_wride_k},
+    {"VMLMF_WRIDE_MAXB", nullptr, 64, ENV_POS, &g_wride_maxb},
+    {"VMLMF_WRIDE_LAG", nullptr, 3, ENV_POS, &g_wride_lag},
+    {"VMLMF_WRIDE_RC", nullptr, 32, ENV_POS, &g_wride_rc},
+    // row-block MFMA kernels (vmlmf_rb.hip).  rb_min_batch 0 = never: measured the one-row-per-CU kernels win
+    // at every batch up to 2048 - sixteen rows' tape traffic through ONE CU's memory pipe costs more than the MFMAs save
+    {"VMLMF_RB", "rb", -1, ENV_INT, &g_rb_mode},
+    {"VMLMF_RB_MINB", "rb_min_batch", 0, ENV_POS, &g_rb_minB},
+    {"VMLMF_RB_S", "rb_cluster", 0, ENV_POS, &g_rb_S},
+    {"VMLMF_RB_ROWS", "rb_rows", 0, ENV_POS, &g_rb_rows},
+    // bit 4: rec3_fwd_kernel needs ~170 VGPRs (two workgroups share a CU), rec_fwd_kernel's x-projection wave 256 (its workgroups run
+    // in rounds): B = 512 138 -> 104 us, 0.402 -> 0.370 ms per step; up to B = 256 the two tie
+    {"VMLMF_REC3", "rec3", 6, ENV_INT, &g_rec3},
+    {"VMLMF_INROW", "inrow", -1, ENV_INT, &g_inrow},
+    {"VMLMF_WRING", "wring", -1, ENV_INT, &g_wring},
+    {"VMLMF_DIRECT", "direct", 1, ENV_INT, &g_direct},
+    {"VMLMF_FINISH2", "finish2", 1, ENV_INT, &g_finish2},
+    // stacks (A/B; 0 = off): the wavefront backward (else the per-layer kernels, chained), the slim pack launch (else every image of
+    // pack_kernel), the one finishing launch (else reduce_cg_stack_kernel + finish_stack_kernel)
+    {"VMLMF_WF_BWD", nullptr, 1, ENV_INT, &g_wf_bwd},
+    {"VMLMF_PACK_SLIM", nullptr, 1, ENV_INT, &g_pack_slim},
+    {"VMLMF_FINISH_UNITS", nullptr, 1, ENV_INT, &g_finish_units},
+    {"VMLMF_RBX", "rbx", 1, ENV_INT, &g_rbx},
+    // ffb 0 by default: measured slower - config C's finish_stack_kernel 25.5 us against reduce 8.1 + finish 6.2 (the repeated block sums
+    // of the d(ex) / d(eh) rows); two PTB group layers at 32 rows 0.710 ms with, 0.702 without
+    {"VMLMF_FFB", "ffb", 0, ENV_INT, &g_ffb},
+};
+int read_switches() {
+  for (const Switch& w : g_switches) *w.var = vmlmf_env_switch(w.env, w.rule, w.dflt);
+  return 0;
+}
+const int g_switches_read = read_switches();
+const Switch* find_switch(const std::string& key) {
+  for (const Switch& w : g_switches)
+    if (w.key != nullptr && key == w.key) return &w;
+  return nullptr;
+}
+
 const char* kernel_label(int k);
 
 struct Scope {
@@ -79,7 +153,6 @@ std::mutex g_status_mu;
 // finite (the NaN partial products of a launch that gave up a wait); the package's Adam reads it in its tick launch and skips
 // that step, then clears it (vmlmf_optim.hip).  Device memory, because the tick launch reads it in every step.
 std::atomic<unsigned*> g_health[MAX_DEV];
-int g_adam_guard = []() { const char* e = getenv("VMLMF_ADAM_GUARD"); return e ? atoi(e) : 1; }();
 
 // `s`: the stream the caller is about to launch on.  The first call on a device allocates the word; that allocation is not
 // capturable, so a first call made while `s` is being captured returns NULL WITHOUT remembering anything (the launch simply
@@ -168,38 +241,6 @@ int debug_status(hipStream_t s) {
   return take_status();
 }
 
-const bool g_xwave = []() {
-  const char* e = getenv("VMLMF_XWAVE");
-  return e == nullptr || e[0] != '0';
-}();
-
-// wgrad chunking (A/B measurements): VMLMF_WCHUNKS = target number of row chunks, VMLMF_WMIN = fewest rows per chunk
-// (non-numeric or non-positive values fall back to the defaults: a zero here would divide by zero in make_geo)
-int env_pos(const char* name, int dflt) {
-  const char* e = getenv(name);
-  if (e == nullptr) return dflt;
-  const int v = atoi(e);
-  return v >= 1 ? v : dflt;
-}
-int env_int(const char* name, int dflt) {   // any integer (switches with a -1 / 0 / 1 meaning)
-  const char* e = getenv(name);
-  return e == nullptr ? dflt : atoi(e);
-}
-const int g_wchunks = env_pos("VMLMF_WCHUNKS", 64);
-const int g_rc = env_pos("VMLMF_RC", 0);   // dqx_dx rows per workgroup (A/B); 0 = derived from the row count
-const int g_wmin = env_pos("VMLMF_WMIN", 64);   // config C (3072 rows): 0.2546 ms at 32 or 48, 0.2428 at 64, 0.243 at 96
-// weight-gradient workers riding on rec_bwd_kernel's launch (vmlmf_atb.inc): VMLMF_WRIDE=0 off; VMLMF_WRIDE_K = workers per
-// task, VMLMF_WRIDE_MAXB = largest batch that rides (beyond it the rows fill the chip and the workers only compete with them)
-const bool g_wride = []() {
-  const char* e = getenv("VMLMF_WRIDE");
-  return e == nullptr || e[0] != '0';
-}();
-const int g_wride_k = env_pos("VMLMF_WRIDE_K", 32);
-const int g_wride_maxb = env_pos("VMLMF_WRIDE_MAXB", 64);   // round 3, rec3_bwd_kernel rows (61 us alone): ride on / off at H = 180, T = 128: B 32 0.158 / 0.165 ms, 64 0.160 / 0.173, 72 0.185 / 0.178, 80 0.187 / 0.177, 96 0.192 / 0.181 (the faster rows outrun the workers once fewer than ~180 CUs are left for them; round 2, slower rows: rode up to 96)
-const int g_wride_lag = env_pos("VMLMF_WRIDE_LAG", 3);
-const int g_wride_rc = env_pos("VMLMF_WRIDE_RC", 32);
-// looks a riding worker takes at the progress words before it gives up; vmlmf_tune("test_wride_spin", n) shortens it so that
-// tests can provoke the failure path (NaN gradients + VMLMF_E_PROTOCOL) on purpose
 int g_cus[MAX_DEV] = {0};   // compute units of the device (hipDeviceProp_t::multiProcessorCount), looked up once
 int device_cus() {
   int dev = 0;
@@ -211,28 +252,6 @@ int device_cus() {
   }
   return g_cus[dev];
 }
-
-// Row-block MFMA kernels (vmlmf_rb.hip): -1 = automatic (large batches, and layers beyond the register-resident VALU kernels),
-// 0 = never, 1 = wherever an instantiation exists.  VMLMF_RB in the environment, or vmlmf_tune("rb", v) at run time.
-int g_rb_mode = []() { const char* e = getenv("VMLMF_RB"); return e ? atoi(e) : -1; }();
-// automatic mode: batch rows from which the row-block kernels take over on layers the VALU kernels cover as well.  0 = never:
-// measured on MI355X the one-row-per-CU kernels win at every batch size up to 2048 - sixteen rows' tape
-// traffic through ONE CU's memory pipe (~25 GB/s) costs more than the MFMAs save
-int g_rb_minB = env_pos("VMLMF_RB_MINB", 0);
-int g_rb_S = env_pos("VMLMF_RB_S", 0);            // cluster size for large layers (0 = the smallest that has an instantiation)
-int g_rb_rows = env_pos("VMLMF_RB_ROWS", 0);      // live batch rows per workgroup: 16 / 8 / 4 (0 = automatic)
-// third form of the recurrent kernels (vmlmf_rec3.inc) where it covers the layer: VMLMF_REC3=0 / vmlmf_tune("rec3", 0) keeps
-// rec_fwd_kernel / rec_bwd_kernel (A/B runs); bit 1 = forward always, bit 2 = backward, bit 4 = forward when there are more
-// batch rows than CUs (rec3_fwd_kernel needs ~170 VGPRs, two workgroups share a CU; rec_fwd_kernel's x-projection wave needs
-// 256, so its workgroups run in rounds: measured B = 512 138 -> 104 us, 0.402 -> 0.370 ms per step; up to B = 256 the two tie)
-int g_rec3 = []() { const char* e = getenv("VMLMF_REC3"); return e ? atoi(e) : 6; }();
-// fourth form of the backward (vmlmf_rec4.inc: weight gradients formed inside the rows' workgroups, no dpre tape, no
-// weight-gradient launch): VMLMF_INROW / vmlmf_tune("inrow", v): 0 = never, 1 = wherever it covers the layer, -1 = automatic
-// (batches beyond the riding workers' range)
-int g_inrow = []() { const char* e = getenv("VMLMF_INROW"); return e ? atoi(e) : -1; }();
-// wgrad_ring_kernel for the weight gradients of large layers: -1 automatic (the step-wise / clustered layers), 0 never, 1 wherever
-// it applies (VMLMF_WRING / vmlmf_tune("wring", v))
-int g_wring = []() { const char* e = getenv("VMLMF_WRING"); return e ? atoi(e) : -1; }();
 
 // ---- geometry ----
 // force_W: at least this many waves of hidden units per group (a stack whose layers differ in hidden_size runs every layer on the
@@ -380,6 +399,8 @@ int make_geo(const vmlmf_desc* d, VGeo* out, RbGeo* rbout = nullptr, int force_W
 }
 
 // ---- buffer layouts (float offsets) ----
+// split-K scratch of a step-wise layer's GEMMs (GenericBuf::part): VG_GEMM_SPLIT partial copies of the largest skinny product (B x G*KH)
+long long gemm_part_floats(const VGeo& g) { return (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64); }
 struct Layout {
   // reserve (training) : PACK | qx | gates | cs | Qs
   long long r_pack, r_qx, r_gates, r_cs, r_Qs, r_prog, r_total;
@@ -414,7 +435,7 @@ Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
     L.f_P = o, o += align64(gen * BN * 4);
     L.f_ccar = o, o += align64(gen * BN);
     L.f_zeros = o, o += align64(gen * (long long)g.B * g.H);
-    L.f_part = o, o += align64(gen * (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64));
+    L.f_part = o, o += align64(gen * gemm_part_floats(g));
   }
   L.f_xq = o, o += align64(g.rb ? q.xq_floats : 0);
   L.f_flag = o, o += align64(g.rb ? q.flag_words : 0);
@@ -438,7 +459,7 @@ Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q) {
     L.b_ehterm = o, o += align64(gen * BN);
     L.b_dcar = o, o += align64(gen * BN);
     // (the dqx product of large layers keeps its split-K scratch under the row-block kernels too)
-    L.b_part = o, o += align64((g.generic ? 1 : 0) * (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64));
+    L.b_part = o, o += align64((g.generic ? 1 : 0) * gemm_part_floats(g));
   }
   L.b_xq = o, o += align64(g.rb ? q.xq_floats : 0);
   L.b_flag = o, o += align64(g.rb ? q.flag_words : 0);
@@ -456,6 +477,13 @@ RefP to_refp(const vmlmf_params* p) {
   r.u_h0 = p->u_h[0], r.u_h1 = p->u_h[1], r.v_h0 = p->v_h[0], r.v_h1 = p->v_h[1];
   for (int k = 0; k < 4; ++k) r.wg[k] = p->w_gate[k], r.ug[k] = p->u_gate[k], r.bg[k] = p->b_gate[k];
   return r;
+}
+RefG to_refg(const vmlmf_grads* gr) {
+  RefG og;
+  og.dia_x = gr->dia_x, og.dia_h = gr->dia_h, og.u_x = gr->u_x, og.v_x = gr->v_x, og.b_x = gr->b_x;
+  og.b_h = gr->b_h, og.u_h0 = gr->u_h[0], og.u_h1 = gr->u_h[1], og.v_h0 = gr->v_h[0], og.v_h1 = gr->v_h[1];
+  for (int k = 0; k < 4; ++k) og.wg[k] = gr->w_gate[k], og.ug[k] = gr->u_gate[k], og.bg[k] = gr->b_gate[k];
+  return og;
 }
 
 // vmlmf_params and vmlmf_grads have the same members; one check serves both
@@ -477,31 +505,90 @@ int check_pointers(const VGeo& g, const P* p, const char* what) {
 
 int check_params(const VGeo& g, const vmlmf_params* p) { return check_pointers(g, p, "params"); }
 
-// Direct mode (vmlmf_direct.inc): the recurrent kernels of a layer build their register images from the reference layouts in their
-// own prologues and pack_kernel leaves the call.  VMLMF_DIRECT=0 / vmlmf_tune("direct", 0): always pack (A/B runs).  The forward and
-// the backward of a call pair must reach the same verdict: it depends on the descriptor, the parameter addresses and the kernel
-// selection only.
-int g_direct = []() { const char* e = getenv("VMLMF_DIRECT"); return e ? atoi(e) : 1; }();
-// finish2_kernel behind a backward with riding workers (one launch instead of reduce_cg_kernel + finish_kernel): VMLMF_FINISH2=0 /
-// vmlmf_tune("finish2", 0) keeps the two launches (A/B runs)
-int g_finish2 = []() { const char* e = getenv("VMLMF_FINISH2"); return e ? atoi(e) : 1; }();
-bool uses_rec3_fwd(const VGeo& g) {
-  return g_xwave && vg_xwave_ok(g) && ((g_rec3 & 1) || ((g_rec3 & 4) && g.nwg > device_cus())) && rec3_fwd_supported(g);
-}
-bool direct_ok(const VGeo& g, const vmlmf_params* p) {
-  if (g_direct == 0 || !(g.variant == VMLMF_V1_CELL || g.variant == VMLMF_V3_LM)) return false;
-  if (g.generic || g.rb || g.bf || g.G != 1 || g.R != 1 || !g.foldx || !(g_xwave && vg_xwave_ok(g)) || uses_rec3_fwd(g)) return false;
-  if (!(g.KH == 8 || g.KH == 16) || g.ru0 != g.KH || !(g.KX == 8 || g.KX == 16) || g.rw != g.KX) return false;
-  // a training call's backward must be one of the kernels that can do the same (rec3_bwd_kernel / rec4_bwd_kernel)
-  if (g.training && !((g_rec3 & 2) && rec3_bwd_supported(g))) return false;   // (its backward: rec3_bwd_kernel / rec4_bwd_kernel)
-  const uintptr_t al = (uintptr_t)p->v_h[0] | (uintptr_t)p->u_h[0] | (uintptr_t)p->v_x | (uintptr_t)p->u_x;
-  return (al & 15u) == 0;   // rows are read as 16-byte loads
-}
-
 int hip_fail(int rc, const char* what) {
   if (rc == 0) return 0;
   if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, std::string(what) + ": no kernel instantiation for this geometry");
   return fail(rc, std::string(what) + ": " + hipGetErrorString((hipError_t)rc));
+}
+
+// ---- the kernels of one layer call ----
+// The forward and the backward of a call build the same plan from the same inputs, so they agree by construction on the family, the
+// x-projection wave and direct mode (the backward of a direct-mode forward reads images its forward never wrote otherwise).
+enum Family { FAM_RB, FAM_STEP, FAM_VALU };   // row-block MFMA recurrence / step-wise path (wide layers included) / VALU kernels
+enum RecKernel { K_REC, K_REC3, K_REC4 };     // rec_*_kernel / rec3_*_kernel / rec4_bwd_kernel (weight gradients in the rows' workgroups)
+// PLAN_CHAINED: a layer of a stack's backward run by the per-layer kernels (its tape comes from a stack launch): no riding workers,
+// no in-row weight gradients, no direct mode
+enum PlanCtx { PLAN_CALL, PLAN_CHAINED };
+struct LayerPlan {
+  Family family;
+  bool xwave;          // the x projection inside the forward recurrence (else xproj_kernel / the wide GEMMs first)
+  RecKernel fwd, bwd;  // the VALU family's recurrent kernels
+  bool direct;         // the recurrent kernels build their images from the reference layouts (vmlmf_direct.inc)
+  bool head_inside;    // the classifier rides inside the recurrent kernels (else the stand-alone head kernels)
+  bool dqx;            // the VALU backward runs dqx_dx (with the x-fold dqx only feeds dx)
+  bool finish2;        // the riding workers' gradients are finished by one launch (finish2_kernel)
+  WRide ride;          // ride.K > 0: weight-gradient workers ride on the backward launch (buffers: ride_buffers)
+};
+
+// Do the weight-gradient products ride on the recurrent backward launch?  Layers of the persistent VALU kernels whose x-side
+// gradient folds into the dpre product (no dqx operand, which only exists after that launch), with few enough batch rows that
+// most of the chip is idle during the recurrence.  Fills the worker counts of w (K = 0: no).
+// (g.flat: a V4 layer small enough for the x-fold - hidden_size <= 16 - takes the stand-alone weight-gradient kernel: the riding
+//  instantiations of the flat layout left the library in round 5 as unreachable, and such a layer's backward was refused since -
+//  found by tools/fuzz_parity.py in round 6)
+void plan_wride(const VGeo& g, WRide* w) {
+  const int n1 = (vg_nb1(g) + 31) / 32, n2 = (g.G * g.KH + 31) / 32;
+  if (!g_wride || g_wride_tripped.load() != 0 || !g.foldx || g.flat || g.R != 1 || g.NT > 256 || g.B > g_wride_maxb || n1 > 2 || n2 > 2) return;
+  // rows per chunk: a part of a step's batch rows when they divide evenly (one batch of loads per chunk: the last chunk's
+  // latency is the tail of the launch), else whole steps of at least 64 rows
+  const int S = (g.B % g_wride_rc == 0 && g_wride_rc % 2 == 0) ? g_wride_rc : g.B * (g.B >= 64 ? 1 : (64 + g.B - 1) / g.B);
+  const int nck = (g.T * g.B + S - 1) / S;
+  int K = g_wride_k < g.nchunk ? g_wride_k : g.nchunk;         // partial blocks: the workspace holds nchunk of them
+  K = K < nck ? K : nck;
+  const int tasks = g.NT / 8 + (g.H + 31) / 32;
+  const int wpw = (g.NT + 128) / 64;
+  const int ntg = (tasks + wpw - 1) / wpw;
+  // every workgroup of the launch has a CU of its own (the launch asks for more than half a CU's LDS): rows + workers must
+  // fit the chip at once, or the workers behind the last CU would only start when the others have finished
+  // (the CU count of THIS device, less a margin of eight for whatever else is resident: on a partitioned or masked device a
+  // fixed 248 would queue workers behind the rows, and a queued worker can only give up)
+  const int room = (device_cus() - 8 - g.nwg) / ntg;
+  K = K < room ? K : room;
+  if (K < 4) return;
+  w->K = K, w->S = S, w->tasks = tasks, w->ntg = ntg;
+  w->lag = g_wride_lag < 8 ? g_wride_lag : 8;
+  w->spin = (unsigned)g_wride_spin;
+}
+
+// want_dx: the backward writes dx (the forward reads no field that depends on it)
+LayerPlan plan_layer(const VGeo& g, const vmlmf_params* p, bool packed, bool head, bool want_dx, PlanCtx ctx = PLAN_CALL) {
+  LayerPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  pl.family = g.rb ? FAM_RB : (g.generic ? FAM_STEP : FAM_VALU);
+  // narrow-input layers compute the x-projection inside rec_fwd_kernel (VMLMF_XWAVE=0: always the separate launch)
+  pl.xwave = g_xwave && vg_xwave_ok(g);
+  pl.head_inside = head && pl.family == FAM_VALU;
+  pl.dqx = !(g.foldx && !want_dx);
+  if (pl.family != FAM_VALU) return pl;
+  const bool call = ctx == PLAN_CALL;
+  if (pl.xwave && ((g_rec3 & 1) || ((g_rec3 & 4) && g.nwg > device_cus())) && rec3_fwd_supported(g)) pl.fwd = K_REC3;
+  const bool rec3_bwd = (g_rec3 & 2) && rec3_bwd_supported(g);
+  // weight gradients inside the rows' workgroups: layers it covers whose input needs no gradient; automatic: batches beyond the
+  // riding workers' range (up to there the idle CUs form the products for free)
+  if (call && g_inrow != 0 && !want_dx && rec4_bwd_supported(g) && (g_inrow > 0 || g.B > g_wride_maxb)) pl.bwd = K_REC4;
+  else pl.bwd = rec3_bwd ? K_REC3 : K_REC;
+  if (call && pl.bwd != K_REC4) plan_wride(g, &pl.ride);
+  if (pl.ride.K > 0 && pl.bwd != K_REC3 && !rec_bwd_rides(g)) memset(&pl.ride, 0, sizeof(pl.ride));
+  // one launch behind the riding workers finishes every gradient where it covers the layer: the workers then contract their
+  // x-fold tiles with v_x themselves
+  pl.finish2 = pl.ride.K > 0 && g_finish2 != 0 && finish2_ok(g) && p->v_x != nullptr;
+  // direct mode: V1 / V3 layers of ranks 8 / 16 on rec_fwd_kernel's x-projection wave; a training call's backward must be one of the
+  // kernels that can do the same (rec3_bwd_kernel / rec4_bwd_kernel); the reference's rows are read as 16-byte loads
+  const uintptr_t al = (uintptr_t)p->v_h[0] | (uintptr_t)p->u_h[0] | (uintptr_t)p->v_x | (uintptr_t)p->u_x;
+  pl.direct = call && !packed && g_direct != 0 && (g.variant == VMLMF_V1_CELL || g.variant == VMLMF_V3_LM) && g.G == 1 && g.R == 1 &&
+              g.foldx && pl.xwave && pl.fwd == K_REC && (g.KH == 8 || g.KH == 16) && g.ru0 == g.KH && (g.KX == 8 || g.KX == 16) &&
+              g.rw == g.KX && (!g.training || rec3_bwd) && (al & 15u) == 0;
+  return pl;
 }
 
 // the batched half of a layer's backward: every weight gradient (MFMA products over all rows), their fixed-order sum, and
@@ -512,54 +599,37 @@ static WghArgs wgrad_args(const Layout& L, const float* x, const float* y, const
   wh.Qs = rs + L.r_Qs, wh.dQs = ws + L.b_dQs, wh.wpart = ws + L.b_wpart;
   return wh;
 }
-
-// Do the weight-gradient products ride on the recurrent backward launch?  Layers of the persistent VALU kernels whose x-side
-// gradient folds into the dpre product (no dqx operand, which only exists after that launch), with few enough batch rows that
-// most of the chip is idle during the recurrence.  Fills w (K = 0: no).
-static void plan_wride(const VGeo& g, const Layout& L, const float* x, const float* y, const float* h0, const float* rs, float* ws,
-                       WRide* w, hipStream_t s, const float* vx = nullptr) {
-  memset(w, 0, sizeof(*w));
-  const int n1 = (vg_nb1(g) + 31) / 32, n2 = (g.G * g.KH + 31) / 32;
-  // (g.flat: a V4 layer small enough for the x-fold - hidden_size <= 16 - takes the stand-alone weight-gradient kernel: the riding
-  //  instantiations of the flat layout left the library in round 5 as unreachable, and such a layer's backward was refused since -
-  //  found by tools/fuzz_parity.py in round 6)
-  if (!g_wride || g_wride_tripped.load() != 0 || g.rb || g.generic || g.bf || !g.foldx || g.flat || g.R != 1 || g.NT > 256 || g.B > g_wride_maxb || n1 > 2 || n2 > 2) return;
-  const WghArgs wh = wgrad_args(L, x, y, h0, rs, ws);
+static WgxArgs wgx_args(const Layout& L, const VPack& P, const float* pack, float* ws, float* dx) {
+  WgxArgs wx;
+  wx.dpre = ws + L.b_dpre, wx.VRX = pack + P.VRX, wx.UXO = pack + P.UXO, wx.EXI = pack + P.EXI;
+  wx.dx = dx, wx.dqx = ws + L.b_dqx;
+  return wx;
+}
+// split-K scratch and tickets of a step-wise call's GEMMs
+static void split_k(GenericBuf* w, const VGeo& g, float* part, const float* pack, const VPack& P) {
+  w->part = part, w->part_cap = gemm_part_floats(g);
+  w->ticket = reinterpret_cast<int*>(const_cast<float*>(pack + P.TKT)), w->ticket_cap = VG_GEMM_TICKETS;
+}
+// the buffers of the plan's riding workers, or of the in-row weight gradients
+static void ride_buffers(LayerPlan* pl, const Layout& L, const WghArgs& wh, const vmlmf_params* p, const float* rs, float* ws, hipStream_t s) {
+  WRide* w = &pl->ride;
+  if (pl->bwd == K_REC4) {
+    w->a.x = wh.x, w->a.y = wh.y, w->a.h0 = wh.h0, w->a.Qs = wh.Qs, w->a.P = wh.wpart;
+    return;
+  }
+  if (w->K == 0) return;
   w->a.dpre = wh.dpre, w->a.x = wh.x, w->a.y = wh.y, w->a.h0 = wh.h0, w->a.qx = wh.qx, w->a.dqx = wh.dqx, w->a.Qs = wh.Qs;
   w->a.dQs = wh.dQs, w->a.P = wh.wpart;
   w->prog = reinterpret_cast<unsigned*>(const_cast<float*>(rs + L.r_prog));
-  // rows per chunk: a part of a step's batch rows when they divide evenly (one batch of loads per chunk: the last chunk's
-  // latency is the tail of the launch), else whole steps of at least 64 rows
-  if (g.B % g_wride_rc == 0 && g_wride_rc % 2 == 0) w->S = g_wride_rc;
-  else w->S = g.B * (g.B >= 64 ? 1 : (64 + g.B - 1) / g.B);
-  const int nck = (g.T * g.B + w->S - 1) / w->S;
-  int K = g_wride_k < g.nchunk ? g_wride_k : g.nchunk;         // partial blocks: the workspace holds nchunk of them
-  K = K < nck ? K : nck;
-  w->tasks = g.NT / 8 + (g.H + 31) / 32;
-  const int wpw = (g.NT + 128) / 64;
-  w->ntg = (w->tasks + wpw - 1) / wpw;
-  // every workgroup of the launch has a CU of its own (the launch asks for more than half a CU's LDS): rows + workers must
-  // fit the chip at once, or the workers behind the last CU would only start when the others have finished
-  // (the CU count of THIS device, less a margin of eight for whatever else is resident: on a partitioned or masked device a
-  // fixed 248 would queue workers behind the rows, and a queued worker can only give up)
-  const int room = (device_cus() - 8 - g.nwg) / w->ntg;
-  K = K < room ? K : room;
-  if (K < 4) return;
-  w->K = K;
-  w->lag = g_wride_lag < 8 ? g_wride_lag : 8;
-  w->spin = (unsigned)g_wride_spin;
   w->status = status_word(s);
-  // one launch behind this one finishes every gradient (finish2_kernel) where it covers the layer: the workers then contract their
-  // x-fold tiles with v_x themselves
-  if (g_finish2 != 0 && finish2_ok(g) && vx != nullptr) w->dux = ws + L.b_dux, w->vx = vx;
+  if (pl->finish2) w->dux = ws + L.b_dux, w->vx = p->v_x;
 }
 
-static int backward_tail(const VGeo& g, const Layout& L, const vmlmf_params* p, const vmlmf_grads* gr, const float* x, const float* y,
-                         const float* h0, const float* rs, float* ws, const HeadBwd& hb, hipStream_t s, const WRide* ride = nullptr,
-                         const int inrow_blocks = 0) {
+static int backward_tail(const VGeo& g, const LayerPlan& pl, const Layout& L, const vmlmf_params* p, const vmlmf_grads* gr, const float* x,
+                         const float* y, const float* h0, const float* rs, float* ws, const HeadBwd& hb, hipStream_t s) {
   int rc;
   const WghArgs wh = wgrad_args(L, x, y, h0, rs, ws);
-  const bool rode = ride != nullptr && ride->K > 0;
+  const bool rode = pl.ride.K > 0, inrow = pl.bwd == K_REC4;
   int ring_nc[3] = {0, 0, 0};
   if (g.wide) {   // dense GEMMs straight into the canonical gradients (cgrad): no partial blocks, no reduce launch
     const long long TB = (long long)g.T * g.B, N4 = 4LL * g.NT, GK = (long long)g.G * g.KH;
@@ -577,7 +647,7 @@ static int backward_tail(const VGeo& g, const Layout& L, const vmlmf_params* p, 
     wb.cgrad = ws + L.b_cgrad;
     Scope sc(5, s);
     if ((rc = hip_fail(wide_wgrad(g, wb, s), "wgrad")) != 0) return rc;
-  } else if (!rode && inrow_blocks == 0) {
+  } else if (!rode && !inrow) {
     Scope sc(5, s);
     // large layers: operands through an LDS ring, long chunks (vmlmf_wgrad_ring.hip); -1: where it was measured faster
     const bool ring = g_wring != 0 && wgrad_ring_ok(g) && (g_wring > 0 || (g.generic && (long long)g.T * g.B >= 1024));
@@ -588,20 +658,17 @@ static int backward_tail(const VGeo& g, const Layout& L, const vmlmf_params* p, 
     }
     if ((rc = hip_fail(rr, "wgrad")) != 0) return rc;
   }
-  RefG og;
-  og.dia_x = gr->dia_x, og.dia_h = gr->dia_h, og.u_x = gr->u_x, og.v_x = gr->v_x, og.b_x = gr->b_x;
-  og.b_h = gr->b_h, og.u_h0 = gr->u_h[0], og.u_h1 = gr->u_h[1], og.v_h0 = gr->v_h[0], og.v_h1 = gr->v_h[1];
-  for (int k = 0; k < 4; ++k) og.wg[k] = gr->w_gate[k], og.ug[k] = gr->u_gate[k], og.bg[k] = gr->b_gate[k];
-  if (rode && ride->dux != nullptr) {   // the riding workers left their d(u_x) shares: ONE launch sums the K blocks and finishes
+  const RefG og = to_refg(gr);
+  if (rode && pl.finish2) {   // the riding workers left their d(u_x) shares: ONE launch sums the K blocks and finishes
     Scope sc(12, s);
-    return hip_fail(launch_finish2(g, to_refp(p), ws + L.b_wpart, ride->dux, ride->K, og, hb, ride->prog, s, health_word(s)), "finish2");
+    return hip_fail(launch_finish2(g, to_refp(p), ws + L.b_wpart, pl.ride.dux, pl.ride.K, og, hb, pl.ride.prog, s, health_word(s)), "finish2");
   }
   if (!g.wide) {
     Scope sc(6, s);
     VGeo gr_ = g;
-    if (rode) gr_.nchunk = ride->K;   // one partial block per worker index; the progress words go back to zero here
-    if (inrow_blocks > 0) gr_.nchunk = inrow_blocks;   // one partial block per workgroup of rec4_bwd_kernel
-    if ((rc = hip_fail(launch_reduce(gr_, ws + L.b_wpart, ws + L.b_cgrad, rode ? ride->prog : nullptr, s,
+    if (rode) gr_.nchunk = pl.ride.K;   // one partial block per worker index; the progress words go back to zero here
+    if (inrow) gr_.nchunk = g.B;        // one partial block per workgroup of rec4_bwd_kernel
+    if ((rc = hip_fail(launch_reduce(gr_, ws + L.b_wpart, ws + L.b_cgrad, rode ? pl.ride.prog : nullptr, s,
                                      ReduceCounts{{ring_nc[0], ring_nc[1], ring_nc[2]}}), "reduce")) != 0) return rc;
   }
   {
@@ -781,8 +848,8 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
   if ((rc = check_head(g, head, true)) != 0) return rc;
   // the classifier rides inside the VALU recurrent kernels; the other families run the stand-alone head kernel after
   // their recurrence (same values up to summation order)
-  const bool head_inside = head != nullptr && !g.rb && !g.generic;
-  if (head != nullptr && !head_inside && hT == nullptr) return fail(VMLMF_E_BADARG, "head on this layer needs the hT output");
+  const LayerPlan pl = plan_layer(g, p, packed != nullptr, head != nullptr, true);
+  if (head != nullptr && !pl.head_inside && hT == nullptr) return fail(VMLMF_E_BADARG, "head on this layer needs the hT output");
   DropArgs drop;
   if ((rc = make_drop(ex != nullptr ? ex->drop : nullptr, g, true, &drop)) != 0) return rc;
   const vmlmf_ce* ce = ex != nullptr ? ex->ce : nullptr;
@@ -813,21 +880,18 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
   }
   float* gx = ws + L.f_gx;
   const RefP rp = to_refp(p);
-  const bool direct = packed == nullptr && direct_ok(g, p);
-  if (packed == nullptr && !direct) {
+  if (packed == nullptr && !pl.direct) {
     Scope sc(0, s);
     if ((rc = hip_fail(launch_pack(g, rp, P, pack, s), "pack")) != 0) return rc;
   }
-  // narrow-input layers compute the x-projection inside rec_fwd_kernel (VMLMF_XWAVE=0: always the separate launch)
-  const bool xwave = g_xwave && vg_xwave_ok(g);
   float* const qxbuf = g.training ? rs + L.r_qx : (g.generic ? ws + L.f_qx : nullptr);
-  if (!xwave) {
+  if (!pl.xwave) {
     Scope sc(1, s);
     if ((rc = hip_fail(g.wide ? wide_xproj(g, P, pack, x, ws + L.f_xrows, gx, qxbuf, s) : launch_xproj(g, P, pack, x, gx, qxbuf, s),
                        "xproj")) != 0)
       return rc;
   }
-  if (g.rb) {
+  if (pl.family == FAM_RB) {
     if (packed == nullptr) {
       Scope sc(0, s);
       if ((rc = hip_fail(launch_rb_pack(g, q, rp, pack + P.RB, s, reinterpret_cast<unsigned*>(ws + L.f_flag)), "rb_pack")) != 0) return rc;
@@ -851,7 +915,7 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
     }
     return ce_after();
   }
-  if (g.generic) {
+  if (pl.family == FAM_STEP) {
     GenericBuf w;
     memset(&w, 0, sizeof(w));
     w.gx = gx, w.EH = pack + P.EH, w.h0 = h0, w.c0 = c0, w.Ud = pack + P.UD, w.Vd = pack + P.VD;
@@ -859,8 +923,7 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
     w.zeros = ws + L.f_zeros, w.y = y, w.hT = hT, w.cT = cT;
     w.gates = g.training ? rs + L.r_gates : nullptr, w.cs = g.training ? rs + L.r_cs : nullptr;
     w.Qs = g.training ? rs + L.r_Qs : nullptr, w.Qtmp = ws + L.f_Qtmp, w.P = ws + L.f_P, w.ccar = ws + L.f_ccar;
-    w.part = ws + L.f_part, w.part_cap = (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64);
-    w.ticket = reinterpret_cast<int*>(pack + P.TKT), w.ticket_cap = VG_GEMM_TICKETS;
+    split_k(&w, g, ws + L.f_part, pack, P);
     if (h0 == nullptr) {
       rc = (int)hipMemsetAsync(ws + L.f_zeros, 0, sizeof(float) * (size_t)g.B * g.H, s);
       if (rc != 0) return hip_fail(rc, "memset");
@@ -885,22 +948,22 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
   XwArgs xw;
   xw.x = x, xw.UXP = pack + P.UXP, xw.WXD = pack + P.WXD, xw.BBT = pack + P.BBT;
   memset(&xw.hd, 0, sizeof(xw.hd));
-  if (head_inside) xw.hd.W = head->weight, xw.hd.bias = head->bias, xw.hd.logits = head->logits, xw.hd.C = head->classes;
+  if (pl.head_inside) xw.hd.W = head->weight, xw.hd.bias = head->bias, xw.hd.logits = head->logits, xw.hd.C = head->classes;
   memset(&xw.ce, 0, sizeof(xw.ce));
-  if (head_inside && ce != nullptr && g.R == 1 && g.B < 65536) {   // one batch row per workgroup: the row's terms are workgroup-local
+  if (pl.head_inside && ce != nullptr && g.R == 1 && g.B < 65536) {   // one batch row per workgroup: the row's terms are workgroup-local
     xw.ce.tgt = (const long long*)ce->target, xw.ce.ignore = (long long)ce->ignore_index, xw.ce.loss = ce->loss, xw.ce.nvalid = ce->nvalid;
     xw.ce.lse = ce->lse, xw.ce.dz = ce->dlogits_unit, xw.ce.ticket = (unsigned long long*)ce->ticket;
   }
-  a.xwave = xwave ? 1 : 0, a.qxw = g.training ? rs + L.r_qx : nullptr;
+  a.xwave = pl.xwave ? 1 : 0, a.qxw = g.training ? rs + L.r_qx : nullptr;
   xw.BH = nullptr, xw.DX = nullptr, xw.direct = 0, xw.pad = 0;
-  if (direct) {   // the reference's own tensors in the places of the images (vmlmf_direct.inc)
+  if (pl.direct) {   // the reference's own tensors in the places of the images (vmlmf_direct.inc)
     a.VE = p->v_h[0], a.UR = p->u_h[0], a.EH = p->dia_h, a.xwave = 3;
     xw.UXP = p->u_x, xw.WXD = p->v_x, xw.BBT = p->b_x, xw.BH = p->b_h, xw.DX = p->dia_x, xw.direct = 1;
   }
   a.prog = g.training ? reinterpret_cast<unsigned*>(rs + L.r_prog) : nullptr;
   {
     Scope sc(2, s);
-    if (xwave && ((g_rec3 & 1) || ((g_rec3 & 4) && g.nwg > device_cus())) && rec3_fwd_supported(g)) {
+    if (pl.fwd == K_REC3) {
       if ((rc = hip_fail(launch_rec3_fwd(g, a, xw, s), "rec3_fwd")) != 0) return rc;
     } else if ((rc = hip_fail(launch_rec_fwd(g, a, xw, s), "rec_fwd")) != 0) return rc;
   }
@@ -943,7 +1006,7 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
     return fail(VMLMF_E_BADARG, "null x / y / reserve / workspace / grads");
   if ((rc = check_pointers(g, gr, "grads")) != 0) return rc;
   if ((rc = check_head(g, head, false)) != 0) return rc;
-  const bool head_inside = head != nullptr && !g.rb && !g.generic;
+  LayerPlan pl = plan_layer(g, p, packed != nullptr, head != nullptr, dx != nullptr);
   DropArgs drop;
   if ((rc = make_drop(ex != nullptr ? ex->drop : nullptr, g, false, &drop)) != 0) return rc;
   const VPack P = vg_pack_layout(g, q.total);
@@ -957,7 +1020,7 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
   const float* hlast = y + (size_t)(g.T - 1) * g.syT;
   HeadBwd hb;
   memset(&hb, 0, sizeof(hb));
-  if (head != nullptr && !head_inside) {
+  if (head != nullptr && !pl.head_inside) {
     // stand-alone head kernel: dh into scratch, which then is the dhT of the recurrence
     if (dhT != nullptr) return fail(VMLMF_E_UNSUPPORTED, "head together with an explicit dhT: only on the VALU recurrent kernels");
     float* tmp = ws + L.b_headdh;
@@ -966,20 +1029,17 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
                                          head->dbias, s);
     if (e != hipSuccess) return hip_fail((int)e, "head_bwd");
     dhT = tmp;
-  } else if (head_inside) {
+  } else if (pl.head_inside) {
     hb.W = head->weight, hb.dl = head->dlogits, hb.hlast = hlast, hb.ldh = g.syB, hb.dW = head->dweight, hb.db = head->dbias;
     hb.C = head->classes;
   }
-  WRide ride;
-  memset(&ride, 0, sizeof(ride));
-  bool inrow = false;
   const float* pack = rs + L.r_pack;
   if (packed != nullptr) {   // the image the matching forward was given
     if (g.generic) return fail(VMLMF_E_UNSUPPORTED, "kept parameter images: not for the step-wise / clustered layers");
     if ((rc = check_packed(packed, g, P, q)) != 0) return rc;
     pack = (const float*)packed + PK_HDR;
   }
-  if (g.rb) {
+  if (pl.family == FAM_RB) {
     RbIo io;
     memset(&io, 0, sizeof(io));
     io.gates = const_cast<float*>(rs + L.r_gates), io.cs = const_cast<float*>(rs + L.r_cs), io.EH = pack + P.EH;
@@ -994,18 +1054,14 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
       GenericBuf w;
       memset(&w, 0, sizeof(w));
       w.dpre = ws + L.b_dpre, w.VxT = pack + P.VXTT, w.dqx = ws + L.b_dqx, w.dx = dx, w.UXP = pack + P.UXP, w.EXT = pack + P.EXT;
-      w.part = ws + L.b_part, w.part_cap = (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64);
-      w.ticket = reinterpret_cast<int*>(const_cast<float*>(pack + P.TKT)), w.ticket_cap = VG_GEMM_TICKETS;
+      split_k(&w, g, ws + L.b_part, pack, P);
       Scope sc(4, s);
       if ((rc = hip_fail(generic_dqx_dx(g, w, s), "dqx_dx")) != 0) return rc;
     } else {
-      WgxArgs wx;
-      wx.dpre = ws + L.b_dpre, wx.VRX = pack + P.VRX, wx.UXO = pack + P.UXO, wx.EXI = pack + P.EXI;
-      wx.dx = dx, wx.dqx = ws + L.b_dqx;
       Scope sc(4, s);
-      if ((rc = hip_fail(launch_wgrad_x(g, wx, s), "dqx_dx")) != 0) return rc;
+      if ((rc = hip_fail(launch_wgrad_x(g, wgx_args(L, P, pack, ws, dx), s), "dqx_dx")) != 0) return rc;
     }
-  } else if (g.generic) {
+  } else if (pl.family == FAM_STEP) {
     GenericBuf w;
     memset(&w, 0, sizeof(w));
     w.EH = pack + P.EH, w.gates = const_cast<float*>(rs + L.r_gates), w.cs = const_cast<float*>(rs + L.r_cs);
@@ -1017,85 +1073,49 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
       w.UXT = pack + P.UXT;
       w.dxs = ws + L.b_total - ((long long)g.T * g.B * g.I + 63) / 64 * 64;
     }
-    w.part = ws + L.b_part, w.part_cap = (long long)VG_GEMM_SPLIT * ((g.B + 63) / 64 * 64) * ((g.G * g.KH + 63) / 64 * 64);
-    w.ticket = reinterpret_cast<int*>(const_cast<float*>(pack + P.TKT)), w.ticket_cap = VG_GEMM_TICKETS;
+    split_k(&w, g, ws + L.b_part, pack, P);
     {
       Scope sc(3, s);
       if ((rc = hip_fail(generic_backward(g, w, s), "generic_backward")) != 0) return rc;
     }
   } else {
-  BwdArgs a;
-  a.gates = rs + L.r_gates, a.cs = rs + L.r_cs, a.c0 = c0, a.dy = dy, a.dhT = dhT, a.dcT = dcT;
-  a.VR = pack + P.VR, a.UE = pack + P.UE, a.EH = pack + P.EH, a.VE = pack + P.VE;
-  a.dpre = ws + L.b_dpre, a.dQs = ws + L.b_dQs, a.dh0 = dh0, a.dc0 = dc0, a.trash = ws + L.b_trash;
-  a.hd = hb;
-  // weight gradients inside the rows' workgroups (vmlmf_rec4.inc)?  Layers it covers whose input needs no gradient; automatic:
-  // batches beyond the riding workers' range (up to there the idle CUs form the products for free)
-  inrow = g_inrow != 0 && dx == nullptr && rec4_bwd_supported(g) && (g_inrow > 0 || g.B > g_wride_maxb);
-  if (inrow) {
-    const WghArgs wh = wgrad_args(L, x, y, h0, rs, ws);
-    ride.a.x = wh.x, ride.a.y = wh.y, ride.a.h0 = wh.h0, ride.a.Qs = wh.Qs, ride.a.P = wh.wpart;
-  } else {
-    plan_wride(g, L, x, y, h0, rs, ws, &ride, s, p->v_x);
-    if (ride.K > 0 && !((g_rec3 & 2) && rec3_bwd_supported(g)) && !rec_bwd_rides(g)) memset(&ride, 0, sizeof(ride));
-  }
-  a.wr = ride;
-  const bool direct = packed == nullptr && direct_ok(g, p);   // the forward of this call packed nothing
-  if (direct) {
-    // the backward builds its own images where its workgroups have a CU each (riding workers, weight gradients in the rows'
-    // workgroups); elsewhere, and for the input's gradient (x-side images), this call packs after all
-    const bool own = inrow || ride.K > 0;
-    if (own) a.VE = p->v_h[0], a.UE = p->u_h[0], a.EH = p->dia_h, a.wr.direct = 1;
-    if (!own || !(g.foldx && dx == nullptr)) {
-      Scope sc(0, s);
-      if ((rc = hip_fail(launch_pack(g, to_refp(p), P, const_cast<float*>(pack), s), "pack")) != 0) return rc;
+    BwdArgs a;
+    a.gates = rs + L.r_gates, a.cs = rs + L.r_cs, a.c0 = c0, a.dy = dy, a.dhT = dhT, a.dcT = dcT;
+    a.VR = pack + P.VR, a.UE = pack + P.UE, a.EH = pack + P.EH, a.VE = pack + P.VE;
+    a.dpre = ws + L.b_dpre, a.dQs = ws + L.b_dQs, a.dh0 = dh0, a.dc0 = dc0, a.trash = ws + L.b_trash;
+    a.hd = hb;
+    ride_buffers(&pl, L, wgrad_args(L, x, y, h0, rs, ws), p, rs, ws, s);
+    a.wr = pl.ride;
+    if (pl.direct) {   // the forward of this call packed nothing
+      // the backward builds its own images where its workgroups have a CU each (riding workers, weight gradients in the rows'
+      // workgroups); elsewhere, and for the input's gradient (x-side images), this call packs after all
+      const bool own = pl.bwd == K_REC4 || pl.ride.K > 0;
+      if (own) a.VE = p->v_h[0], a.UE = p->u_h[0], a.EH = p->dia_h, a.wr.direct = 1;
+      if (!own || pl.dqx) {
+        Scope sc(0, s);
+        if ((rc = hip_fail(launch_pack(g, to_refp(p), P, const_cast<float*>(pack), s), "pack")) != 0) return rc;
+      }
+    }
+    {
+      Scope sc(3, s);
+      if (pl.bwd == K_REC4) {
+        if ((rc = hip_fail(launch_rec4_bwd(g, a, s), "rec4_bwd")) != 0) return rc;
+      } else if (pl.bwd == K_REC3) {
+        if ((rc = hip_fail(launch_rec3_bwd(g, a, s), "rec3_bwd")) != 0) return rc;
+      } else if ((rc = hip_fail(launch_rec_bwd(g, a, s), "rec_bwd")) != 0) return rc;
+    }
+    if (pl.dqx) {
+      Scope sc(4, s);
+      if ((rc = hip_fail(launch_wgrad_x(g, wgx_args(L, P, pack, ws, dx), s), "dqx_dx")) != 0) return rc;
     }
   }
-  {
-    Scope sc(3, s);
-    if (inrow) {
-      if ((rc = hip_fail(launch_rec4_bwd(g, a, s), "rec4_bwd")) != 0) return rc;
-    } else if ((g_rec3 & 2) && rec3_bwd_supported(g)) {
-      if ((rc = hip_fail(launch_rec3_bwd(g, a, s), "rec3_bwd")) != 0) return rc;
-    } else if ((rc = hip_fail(launch_rec_bwd(g, a, s), "rec_bwd")) != 0) return rc;
-  }
-  WgxArgs wx;
-  wx.dpre = ws + L.b_dpre, wx.VRX = pack + P.VRX, wx.UXO = pack + P.UXO, wx.EXI = pack + P.EXI;
-  wx.dx = dx, wx.dqx = ws + L.b_dqx;
-  if (!(g.foldx && dx == nullptr)) {   // with the x-fold dqx only feeds dx
-    Scope sc(4, s);
-    if ((rc = hip_fail(launch_wgrad_x(g, wx, s), "dqx_dx")) != 0) return rc;
-  }
-  }  // persistent path
-  if ((rc = backward_tail(g, L, p, gr, x, y, h0, rs, ws, hb, s, &ride, inrow ? g.B : 0)) != 0) return rc;
+  if ((rc = backward_tail(g, pl, L, p, gr, x, y, h0, rs, ws, hb, s)) != 0) return rc;
   return debug_status(s);
 }
 
 
 // ---- stacked layers: wavefront launches (vmlmf_wave.inc) ----
 namespace {
-// VMLMF_WF_BWD=0: the stack's backward chains the per-layer kernels (A/B runs and bring-up); the forward is the wavefront
-// launch either way
-const bool g_wf_bwd = env_int("VMLMF_WF_BWD", 1) != 0;
-// VMLMF_PACK_SLIM=0: the stack's pack launch produces every image of pack_kernel (A/B; the chained backward needs them anyway)
-const bool g_pack_slim = env_int("VMLMF_PACK_SLIM", 1) != 0;
-// VMLMF_FINISH_UNITS=0: behind a stack's weight-gradient launch, reduce_cg_stack_kernel + finish_stack_kernel instead of the one
-// finishing launch (A/B)
-const bool g_finish_units = env_int("VMLMF_FINISH_UNITS", 1) != 0;
-
-// (No lambdas in the initialisers of this block: this unnamed namespace is reopened INSIDE the file's extern "C" block, and hipcc numbers
-//  the lambdas of a namespace per enclosing linkage specification - "(anonymous namespace)::{lambda()#2}" here got the same mangled name
-//  as lambda #2 of the first block at the top of the file, and ONE body served both: the switches below came up with another switch's
-//  default whatever the environment said.  Found in round 6 through a run-time flag that read 1 with nothing set; VMLMF_WF_BWD had been
-//  answered by VMLMF_RB's lambda since round 2.)
-// VMLMF_RBX=0 / vmlmf_tune("rbx", 0): clustered layers are never stacked into one launch (the caller chains them; A/B runs)
-int g_rbx = env_int("VMLMF_RBX", 1);
-// the stacks' finishing launch sums the partial blocks itself (no reduce launch): 0 = never (default: measured slower - config C's
-// finish_stack_kernel 25.5 us against reduce 8.1 + finish 6.2, the repeated block sums of the d(ex) / d(eh) rows; two PTB group
-// layers at 32 rows 0.710 ms with, 0.702 without), -1 = the clustered stacks, 1 = the wavefront stacks too.  VMLMF_FFB /
-// vmlmf_tune("ffb"); parity-tested both ways
-int g_ffb = env_int("VMLMF_FFB", 0);
-
 struct StackPlan {
   int L;
   bool rbx;    // the clustered form (vmlmf_rbx.hip): every layer on clusters of workgroups, all layers in one launch per direction
@@ -1232,6 +1252,17 @@ static int stack_plan(int L, const vmlmf_stack_layer* ly, StackPlan* out) {
   S.ws_total = o;
   return 0;
 }
+// layer l's input: x, or the rows of the layer below - their dropped copy under dropout (vmlmf_lm.py:438-439)
+static const float* stack_input(const vmlmf_stack_layer* ly, int l, const float* x) {
+  return l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
+}
+// the batched half of layer l's backward through the per-layer launches
+static int stack_tail(const StackPlan& S, const vmlmf_stack_layer* ly, int l, const float* x, float* ws, hipStream_t s) {
+  HeadBwd hb;
+  memset(&hb, 0, sizeof(hb));
+  return backward_tail(S.g[l], plan_layer(S.g[l], ly[l].params, false, false, false, PLAN_CHAINED), S.lay[l], ly[l].params, ly[l].grads,
+                       stack_input(ly, l, x), ly[l].y, ly[l].h0, (const float*)ly[l].reserve, ws + S.ws_layer[l], hb, s);
+}
 // ---- the clustered form (vmlmf_rbx.hip)
 static int rbx_drop(const vmlmf_dropout* dr, bool forward, DropArgs* out) {
   memset(out, 0, sizeof(*out));
@@ -1266,8 +1297,7 @@ static int rbx_stack_forward(const StackPlan& S, const vmlmf_stack_layer* ly, co
     rps[l] = to_refp(ly[l].params), packs[l] = pack, imgs[l] = pack + S.P[l].RB, fflags[l] = reinterpret_cast<unsigned*>(wl + Lr.f_flag);
     RbxLayerF& w = a.l[l];
     if ((rc = rbx_drop(ly[l].drop, true, &w.drop)) != 0) return rc;
-    // the layer's input: x, or the rows of the layer below (their dropped copy under dropout)
-    w.x = l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
+    w.x = stack_input(ly, l, x);
     w.EH = pack + S.P[l].EH, w.EXT = pack + S.P[l].EXT, w.BBT = pack + S.P[l].BBT, w.img = pack + S.P[l].RB;
     w.h0 = ly[l].h0, w.c0 = ly[l].c0, w.y = ly[l].y, w.hT = ly[l].hT, w.cT = ly[l].cT;
     w.gates = training ? rs + Lr.r_gates : nullptr, w.cs = training ? rs + Lr.r_cs : nullptr;
@@ -1330,12 +1360,8 @@ static int rbx_stack_backward(const StackPlan& S, const vmlmf_stack_layer* ly, c
   // every layer's partial blocks and ONE that writes every layer's reference-layout gradients
   const bool ring = g_wring != 0 && wgrad_ring_ok(S.g[0]) && (g_wring > 0 || (long long)S.g[0].T * S.g[0].B >= 1024);
   if (!ring) {
-    for (int l = L - 1; l >= 0; --l) {
-      const float* xl = l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
-      if ((rc = backward_tail(S.g[l], S.lay[l], ly[l].params, ly[l].grads, xl, ly[l].y, ly[l].h0, (const float*)ly[l].reserve,
-                              ws + S.ws_layer[l], hb, s)) != 0)
-        return rc;
-    }
+    for (int l = L - 1; l >= 0; --l)
+      if ((rc = stack_tail(S, ly, l, x, ws, s)) != 0) return rc;
     return 0;
   }
   ReduceCounts wcs[RBX_MAXL];
@@ -1345,20 +1371,15 @@ static int rbx_stack_backward(const StackPlan& S, const vmlmf_stack_layer* ly, c
   RefP rps[RBX_MAXL];
   RefG ogs[RBX_MAXL];
   for (int l = L - 1; l >= 0; --l) {
-    const float* xl = l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
     float* wl = ws + S.ws_layer[l];
-    const WghArgs wh = wgrad_args(S.lay[l], xl, ly[l].y, ly[l].h0, (const float*)ly[l].reserve, wl);
+    const WghArgs wh = wgrad_args(S.lay[l], stack_input(ly, l, x), ly[l].y, ly[l].h0, (const float*)ly[l].reserve, wl);
     int nc[3] = {0, 0, 0};
     {
       Scope sc(5, s);
       const int rr = launch_wgrad_ring(S.g[l], wh, device_cus(), nc, s);
       if (rr == -3) {   // no LDS / instantiation for the ring on this device: the per-layer path for every layer from here
-        for (int k = l; k >= 0; --k) {
-          const float* xk = k == 0 ? x : (ly[k - 1].drop != nullptr ? ly[k - 1].drop->y_dropped : ly[k - 1].y);
-          if ((rc = backward_tail(S.g[k], S.lay[k], ly[k].params, ly[k].grads, xk, ly[k].y, ly[k].h0, (const float*)ly[k].reserve,
-                                  ws + S.ws_layer[k], hb, s)) != 0)
-            return rc;
-        }
+        for (int k = l; k >= 0; --k)
+          if ((rc = stack_tail(S, ly, k, x, ws, s)) != 0) return rc;
         // (the layers above l: their blocks are formed, finish them one by one)
         for (int k = L - 1; k > l; --k) {
           {
@@ -1374,12 +1395,7 @@ static int rbx_stack_backward(const StackPlan& S, const vmlmf_stack_layer* ly, c
     }
     wcs[l] = ReduceCounts{{nc[0], nc[1], nc[2]}};
     wparts[l] = wl + S.lay[l].b_wpart, cgs[l] = wl + S.lay[l].b_cgrad, ccgs[l] = cgs[l];
-    rps[l] = to_refp(ly[l].params);
-    const vmlmf_grads* gr = ly[l].grads;
-    RefG& og = ogs[l];
-    og.dia_x = gr->dia_x, og.dia_h = gr->dia_h, og.u_x = gr->u_x, og.v_x = gr->v_x, og.b_x = gr->b_x;
-    og.b_h = gr->b_h, og.u_h0 = gr->u_h[0], og.u_h1 = gr->u_h[1], og.v_h0 = gr->v_h[0], og.v_h1 = gr->v_h[1];
-    for (int k = 0; k < 4; ++k) og.wg[k] = gr->w_gate[k], og.ug[k] = gr->u_gate[k], og.bg[k] = gr->b_gate[k];
+    rps[l] = to_refp(ly[l].params), ogs[l] = to_refg(ly[l].grads);
   }
   {   // one finishing launch where it covers the layers (one-group layers: the plain rank-32 PTB layers)
     bool fu = g_finish_units;
@@ -1457,8 +1473,7 @@ int vmlmf_stack_forward(int L, const vmlmf_stack_layer* ly, const float* x, cons
     float* pack = training ? rs + Lr.r_pack : ws + S.ws_layer[l] + Lr.f_pack;
     rps[l] = to_refp(ly[l].params), packs[l] = pack;
     WfFwdLayer& w = a.l[l];
-    // the layer's input: x, or the rows of the layer below - their dropped copy under dropout (vmlmf_lm.py:438-439)
-    w.x = l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
+    w.x = stack_input(ly, l, x);
     if ((rc = rbx_drop(ly[l].drop, true, &a.drop[l])) != 0) return rc;
     w.sxT = g.sxT, w.sxB = g.sxB, w.I = g.I;
     w.syT = g.syT, w.syB = g.syB, w.H = g.H, w.Hg = g.Hg;
@@ -1552,8 +1567,7 @@ int vmlmf_stack_backward(int L, const vmlmf_stack_layer* ly, const float* x, con
       Scope sc(3, s);
       if ((rc = hip_fail(launch_wf_bwd(S.g[0], a, s), "wf_bwd")) != 0) return rc;
     }
-  }
-  if (wave) {   // the batched half of every layer's backward: one launch each for the whole stack
+    // the batched half of every layer's backward: one launch each for the whole stack
     WghArgs wh[WF_MAXL];
     RefP rps[WF_MAXL];
     RefG ogs[WF_MAXL];
@@ -1565,16 +1579,11 @@ int vmlmf_stack_backward(int L, const vmlmf_stack_layer* ly, const float* x, con
       const float* rs = (const float*)ly[l].reserve;
       float* wl = ws + S.ws_layer[l];
       WghArgs& w = wh[l];
-      w.dpre = wl + Lr.b_dpre, w.x = l == 0 ? x : (ly[l - 1].drop != nullptr ? ly[l - 1].drop->y_dropped : ly[l - 1].y);
+      w.dpre = wl + Lr.b_dpre, w.x = stack_input(ly, l, x);
       w.y = ly[l].y, w.h0 = ly[l].h0, w.qx = rs + Lr.r_qx, w.dqx = wl + Lr.b_dqx;
       w.Qs = rs + Lr.r_Qs, w.dQs = wl + Lr.b_dQs, w.wpart = wl + Lr.b_wpart;
       wparts[l] = wl + Lr.b_wpart, cgs[l] = wl + Lr.b_cgrad, ccgs[l] = wl + Lr.b_cgrad;
-      rps[l] = to_refp(ly[l].params);
-      const vmlmf_grads* gr = ly[l].grads;
-      RefG& og = ogs[l];
-      og.dia_x = gr->dia_x, og.dia_h = gr->dia_h, og.u_x = gr->u_x, og.v_x = gr->v_x, og.b_x = gr->b_x;
-      og.b_h = gr->b_h, og.u_h0 = gr->u_h[0], og.u_h1 = gr->u_h[1], og.v_h0 = gr->v_h[0], og.v_h1 = gr->v_h[1];
-      for (int k = 0; k < 4; ++k) og.wg[k] = gr->w_gate[k], og.ug[k] = gr->u_gate[k], og.bg[k] = gr->b_gate[k];
+      rps[l] = to_refp(ly[l].params), ogs[l] = to_refg(ly[l].grads);
     }
     {
       Scope sc(5, s);
@@ -1604,37 +1613,33 @@ int vmlmf_stack_backward(int L, const vmlmf_stack_layer* ly, const float* x, con
     }
     return 0;
   }
-  for (int l = L - 1; l >= 0; --l) {
+  for (int l = L - 1; l >= 0; --l) {   // the per-layer kernels, chained through the dx buffers
     const VGeo& g = S.g[l];
     const Layout& Lr = S.lay[l];
     const VPack& P = S.P[l];
     const float* rs = (const float*)ly[l].reserve;
     const float* pack = rs + Lr.r_pack;
     float* wl = ws + S.ws_layer[l];
-    const float* xl = l == 0 ? x : ly[l - 1].y;
-    if (!wave) {   // the per-layer kernels, chained through the dx buffers
-      BwdArgs b;
-      b.gates = rs + Lr.r_gates, b.cs = rs + Lr.r_cs, b.c0 = ly[l].c0, b.dy = l == L - 1 ? dy : ws + S.ws_dx[l + 1];
-      b.dhT = ly[l].dhT, b.dcT = ly[l].dcT;
-      b.VR = pack + P.VR, b.UE = pack + P.UE, b.EH = pack + P.EH, b.VE = pack + P.VE;
-      b.dpre = wl + Lr.b_dpre, b.dQs = wl + Lr.b_dQs, b.dh0 = ly[l].dh0, b.dc0 = ly[l].dc0, b.trash = wl + Lr.b_trash;
-      b.hd = hb;
-      memset(&b.wr, 0, sizeof(b.wr));   // (the tape of a stack launch: its progress words are not this path's)
-      {
-        Scope sc(3, s);
-        if ((g_rec3 & 2) && rec3_bwd_supported(g)) {
-          if ((rc = hip_fail(launch_rec3_bwd(g, b, s), "rec3_bwd")) != 0) return rc;
-        } else if ((rc = hip_fail(launch_rec_bwd(g, b, s), "rec_bwd")) != 0) return rc;
-      }
-      WgxArgs wx;
-      wx.dpre = wl + Lr.b_dpre, wx.VRX = pack + P.VRX, wx.UXO = pack + P.UXO, wx.EXI = pack + P.EXI;
-      wx.dx = l == 0 ? dx : ws + S.ws_dx[l], wx.dqx = wl + Lr.b_dqx;
-      if (!(g.foldx && wx.dx == nullptr)) {
-        Scope sc(4, s);
-        if ((rc = hip_fail(launch_wgrad_x(g, wx, s), "dqx_dx")) != 0) return rc;
-      }
+    float* dxl = l == 0 ? dx : ws + S.ws_dx[l];
+    const LayerPlan pl = plan_layer(g, ly[l].params, false, false, dxl != nullptr, PLAN_CHAINED);
+    BwdArgs b;
+    b.gates = rs + Lr.r_gates, b.cs = rs + Lr.r_cs, b.c0 = ly[l].c0, b.dy = l == L - 1 ? dy : ws + S.ws_dx[l + 1];
+    b.dhT = ly[l].dhT, b.dcT = ly[l].dcT;
+    b.VR = pack + P.VR, b.UE = pack + P.UE, b.EH = pack + P.EH, b.VE = pack + P.VE;
+    b.dpre = wl + Lr.b_dpre, b.dQs = wl + Lr.b_dQs, b.dh0 = ly[l].dh0, b.dc0 = ly[l].dc0, b.trash = wl + Lr.b_trash;
+    b.hd = hb;
+    b.wr = pl.ride;   // (none: the tape of a stack launch, its progress words are not this path's)
+    {
+      Scope sc(3, s);
+      if (pl.bwd == K_REC3) {
+        if ((rc = hip_fail(launch_rec3_bwd(g, b, s), "rec3_bwd")) != 0) return rc;
+      } else if ((rc = hip_fail(launch_rec_bwd(g, b, s), "rec_bwd")) != 0) return rc;
     }
-    if ((rc = backward_tail(g, Lr, ly[l].params, ly[l].grads, xl, ly[l].y, ly[l].h0, rs, wl, hb, s)) != 0) return rc;
+    if (pl.dqx) {
+      Scope sc(4, s);
+      if ((rc = hip_fail(launch_wgrad_x(g, wgx_args(Lr, P, pack, wl, dxl), s), "dqx_dx")) != 0) return rc;
+    }
+    if ((rc = backward_tail(g, pl, Lr, ly[l].params, ly[l].grads, stack_input(ly, l, x), ly[l].y, ly[l].h0, rs, wl, hb, s)) != 0) return rc;
   }
   return 0;
 }
@@ -1646,24 +1651,15 @@ int vmlmf_check_status(void) { return take_status(); }
 int vmlmf_tune(const char* key, int value) {
   if (key == nullptr) return fail(VMLMF_E_BADARG, "tune: null key");
   const std::string k(key);
-  if (k == "rbx") g_rbx = value;
-  else if (k == "ffb") g_ffb = value;
-  else if (k == "rb") g_rb_mode = value;
-  else if (k == "rec3") g_rec3 = value;
-  else if (k == "test_wride_spin") g_wride_spin = value < 1 ? WRIDE_SPIN_DEFAULT : value;
-  else if (k == "inrow") g_inrow = value;
-  else if (k == "adam_guard") g_adam_guard = value;
+  const Switch* sw = find_switch(k);
+  if (k == "test_wride_spin") g_wride_spin = value < 1 ? WRIDE_SPIN_DEFAULT : value;
   else if (k == "clear_health") {   // forget a non-finite gradient no guarded optimizer step has consumed (synchronises the device)
     unsigned* hw = vmlmf_health_word_if_any();
     if (hw != nullptr && hipMemset(hw, 0, sizeof(unsigned)) != hipSuccess) (void)hipGetLastError();
   }
-  else if (k == "wring") g_wring = value;
-  else if (k == "direct") g_direct = value;
-  else if (k == "finish2") g_finish2 = value;
   else if (k == "wride") g_wride_tripped.store(value != 0 ? 0 : 1);   // 0: stand-alone weight-gradient kernel; 1: ride again (where VMLMF_WRIDE allows)
-  else if (k == "rb_min_batch") g_rb_minB = value < 0 ? 0 : value;   // (0 = never, the default)
-  else if (k == "rb_cluster") g_rb_S = value < 0 ? 0 : value;
-  else if (k == "rb_rows") g_rb_rows = value < 0 ? 0 : value;
+  else if (k == "rb_min_batch" || k == "rb_cluster" || k == "rb_rows") *sw->var = value < 0 ? 0 : value;   // (rb_min_batch: 0 = never, the default)
+  else if (sw != nullptr) *sw->var = value;
   else return fail(VMLMF_E_BADARG, "tune: unknown key " + k);
   ++g_tune_generation;
   return 0;
@@ -1672,19 +1668,9 @@ int vmlmf_tune(const char* key, int value) {
 int vmlmf_tune_get(const char* key, int* value) {
   if (key == nullptr || value == nullptr) return fail(VMLMF_E_BADARG, "tune_get: null pointer");
   const std::string k(key);
-  if (k == "rbx") *value = g_rbx;
-  else if (k == "ffb") *value = g_ffb;
-  else if (k == "rb") *value = g_rb_mode;
-  else if (k == "rec3") *value = g_rec3;
-  else if (k == "inrow") *value = g_inrow;
-  else if (k == "adam_guard") *value = g_adam_guard;
-  else if (k == "wring") *value = g_wring;
-  else if (k == "direct") *value = g_direct;
-  else if (k == "finish2") *value = g_finish2;
-  else if (k == "wride") *value = (g_wride && g_wride_tripped.load() == 0) ? 1 : 0;   // 0 also after a bounded wait gave up (VMLMF_ST_WRIDE)
-  else if (k == "rb_min_batch") *value = g_rb_minB;
-  else if (k == "rb_cluster") *value = g_rb_S;
-  else if (k == "rb_rows") *value = g_rb_rows;
+  const Switch* sw = find_switch(k);
+  if (k == "wride") *value = (g_wride && g_wride_tripped.load() == 0) ? 1 : 0;   // 0 also after a bounded wait gave up (VMLMF_ST_WRIDE)
+  else if (sw != nullptr) *value = *sw->var;
   else return fail(VMLMF_E_BADARG, "tune_get: unknown key " + k);
   return 0;
 }

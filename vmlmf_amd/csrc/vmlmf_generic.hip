@@ -603,21 +603,12 @@ static int launch_dhrec(const float* part, int GK, const float* UdT, int H, floa
 // largest skinny product (B x G*KH) and one ticket per tile of it
 constexpr int GEMM_MAX_SPLIT = VG_GEMM_SPLIT;
 // VMLMF_SKINNY=0 keeps the split-K tiles for those products (A/B measurements)
-static const int g_skinny_mode = []() {
-  const char* e = getenv("VMLMF_SKINNY");
-  return e == nullptr ? 1 : atoi(e);
-}();
+static const int g_skinny_mode = vmlmf_env_switch("VMLMF_SKINNY", ENV_INT, 1);
 static const bool g_skinny = g_skinny_mode != 0;
 // VMLMF_DQ_SPLIT=0: dQ_t as one product per tile (A/B measurements)
-static const bool g_dq_split = []() {
-  const char* e = getenv("VMLMF_DQ_SPLIT");
-  return (e == nullptr || e[0] != '0') && g_skinny_mode == 1;
-}();
+static const bool g_dq_split = vmlmf_env_switch("VMLMF_DQ_SPLIT", ENV_ON, 1) && g_skinny_mode == 1;
 // VMLMF_FUSE_GATES=0: element-wise halves of a step as kernels of their own (A/B measurements)
-static const int g_fuse_mode = []() {
-  const char* e = getenv("VMLMF_FUSE_GATES");
-  return e == nullptr ? 1 : atoi(e);
-}();
+static const int g_fuse_mode = vmlmf_env_switch("VMLMF_FUSE_GATES", ENV_INT, 1);
 static const bool g_fuse = g_fuse_mode != 0;       // forward: gate math as the epilogue of P_t = Q_t Vd
 static const bool g_fuse_bwd = g_fuse_mode != 3 && g_fuse_mode != 0;   // backward: gate derivatives as the epilogue of dH_rec
                                                                        // (3: 64 x 64 tiles and a gates kernel, for A/B runs)

@@ -9,6 +9,11 @@
 // tools/experiments/ablation_switches.patch, -DVMLMF_STW7.)
 #define VG_REC_BOUNDS (MAXT + 128)
 
+// A process-wide switch read from the environment (vmlmf_api.hip; the switch table there lists them): dflt when `name` is unset,
+// else by the rule - ENV_SET 1, ENV_ON 1 unless the value starts with '0', ENV_INT atoi, ENV_POS atoi if >= 1 else dflt
+enum EnvRule { ENV_SET, ENV_ON, ENV_INT, ENV_POS };
+int vmlmf_env_switch(const char* name, EnvRule rule, int dflt);
+
 // Classifier riding on a layer (Net.lin on the final hidden state, vmlmf.py:345,353-355): logits in the epilogue of the
 // forward recurrence, d(hT) = dlogits W in the prologue of the backward one, dW / db among finish_kernel's outputs.  C = 0: none.
 struct HeadFwd {

@@ -625,7 +625,7 @@ int launch_xproj(const VGeo& g, const VPack& L, const float* pack, const float* 
   const int TBp = g.T * g.Bp;
   // rows per workgroup: 4 for short sequences of rows (config C, 3072 rows: 0.2390 ms per step against 0.2426 with 8 and
   // 0.2565 with 16), 8 otherwise (8192 rows: 15.5 us against 19.1 with 4); VMLMF_XR = 4 / 8 / 16 overrides (A/B runs)
-  static const int xr_env = []() { const char* e = getenv("VMLMF_XR"); return e ? atoi(e) : 0; }();
+  static const int xr_env = vmlmf_env_switch("VMLMF_XR", ENV_INT, 0);
   const int xr = xr_env == 16 ? 16 : (xr_env == 8 ? 8 : (xr_env == 4 ? 4 : (TBp <= 4096 ? 4 : 8)));
   const dim3 grid((TBp + xr - 1) / xr), block(256);
   const size_t lds = sizeof(float) * ((size_t)xr * g.I + (size_t)xr * g.KX + (size_t)(256 / g.KX) * xr * g.KX);
@@ -646,7 +646,7 @@ int launch_xproj(const VGeo& g, const VPack& L, const float* pack, const float* 
     }                                                                                                       \
     break;
   // large layers: qx by this kernel (gx = nullptr), the expansion on the matrix cores.  VMLMF_XEXP=0 keeps the VALU form (A/B)
-  static const bool xexp_on = []() { const char* e = getenv("VMLMF_XEXP"); return e == nullptr || e[0] != '0'; }();
+  static const bool xexp_on = vmlmf_env_switch("VMLMF_XEXP", ENV_ON, 1);
   const bool xexp = xexp_on && g.generic && !g.bf && g.Bp == g.B && qx != nullptr;
   float* const gx_final = gx;
   if (xexp) gx = nullptr;

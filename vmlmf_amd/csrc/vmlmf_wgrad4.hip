@@ -18,8 +18,7 @@ __global__ void __launch_bounds__(256) wgrad4_stack_kernel(AtbStack S) {
   else if (task < MT1 + MT2 + MT3) atb4_task<3, 1, ABL>(g, a, task - MT1 - MT2, blockIdx.y, lane);
 }
 // VMLMF_WGRAD4=0: the stacks' weight gradients through wgrad_mfma_stack_kernel always (A/B)
-static bool wgrad4_enabled() { const char* e = getenv("VMLMF_WGRAD4"); return e == nullptr || atoi(e) != 0; }
-static const bool g_wgrad4 = wgrad4_enabled();
+static const bool g_wgrad4 = vmlmf_env_switch("VMLMF_WGRAD4", ENV_INT, 1) != 0;
 static bool wgrad4_geo_ok(const VGeo& g) {
   return g.G == 1 && !g.flat && !g.bf && !g.foldx && !g.generic && g.KH <= 32 && g.KX <= 32 && g.I <= g.NT && (g.H & 3) == 0 &&
          (g.B & 1) == 0 &&   // (a row pair never straddles two time steps)
