@@ -57,6 +57,56 @@ def test_query_refuses_outside_the_wide_envelope(desc, start):
     assert str(ei.value).startswith(f"vmlmf_hip error {_lib.E_UNSUPPORTED}: {start}"), str(ei.value)
 
 
+# ---- the caps exactly: padded 1024 accepted, the next padded width (1025 -> 1032) refused ----------------------------------------
+AT_CAP = [
+    # (variant, I, H, w_rank, u_ranks, g)
+    (_lib.V3_LM, 1024, 1024, 1024, [1024], 1),              # both caps on one layer
+    (_lib.V1_CELL, 1024, 1024, 1017, [40], 1),              # w_rank 1017 pads to 1024
+    (_lib.V4_LM_GROUP, 1024, 1024, 64, [512, 512], 2),      # the hidden rank summed over the two shifts: 512 + 512
+    (_lib.V2_GROUP_CELL, 64, 1040, 16, [505, 512], 2),      # 505 pads to 512: summed 1024
+    (_lib.V5_LMF_CELL, 1100, 160, 1020, [40], 1),           # more inputs than units, w_rank pads to 1024
+]
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("case", AT_CAP, ids=lambda c: f"v{c[0]}_I{c[1]}_H{c[2]}_w{c[3]}_u{'x'.join(map(str, c[4]))}")
+def test_query_accepts_exactly_the_caps(case, training):
+    variant, I, H, rw, ru, g = case
+    s = _lib.query(_lib.make_desc(variant, 2, 3, I, H, rw, ru, g=g, time_major=True, training=training))
+    assert s.workspace_bytes > 0 and (s.reserve_bytes > 0 or not training)
+    assert s.kx == (rw + 7) // 8 * 8 and s.kx <= 1024
+    assert s.kh == sum((r + 7) // 8 * 8 for r in ru) and s.kh <= 1024
+    assert max(s.kx, s.kh) == 1024
+
+
+PAST_CAP = [
+    dict(variant=_lib.V3_LM, I=1032, H=1032, w_rank=1025, u_ranks=[40]),             # padded w_rank 1032
+    dict(variant=_lib.V5_LMF_CELL, I=1100, H=160, w_rank=1025, u_ranks=[40]),        # ... with I > H
+    dict(variant=_lib.V1_CELL, I=64, H=1100, w_rank=16, u_ranks=[1025]),             # padded u_rank 1032
+    dict(variant=_lib.V4_LM_GROUP, I=1040, H=1040, w_rank=64, u_ranks=[512, 513], g=2),   # summed 512 + 520
+    dict(variant=_lib.V2_GROUP_CELL, I=64, H=1040, w_rank=16, u_ranks=[513, 512], g=2),   # summed 520 + 512
+]
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("desc", PAST_CAP, ids=lambda d: f"v{d['variant']}_w{d['w_rank']}_u{'x'.join(map(str, d['u_ranks']))}")
+def test_query_refuses_one_past_the_caps(desc, training):
+    with pytest.raises(_lib.VmlmfError) as ei:
+        _lib.query(_lib.make_desc(B=2, T=3, time_major=True, training=training, **desc))
+    assert ei.value.code == _lib.E_UNSUPPORTED
+    assert str(ei.value).startswith(f"vmlmf_hip error {_lib.E_UNSUPPORTED}: wide ranks: padded w_rank"), str(ei.value)
+
+
+# ---- large hidden sizes on the step-wise path (not wide): the 12-stage skinny forms of Q (H >= 1536) and dQ (H >= 705) --------
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("H", [705, 1536])
+def test_query_accepts_large_one_group_layers(H, training):
+    s = _lib.query(_lib.make_desc(_lib.V1_CELL, 3, 3, 64, H, 16, [40], training=training))
+    assert (s.kx, s.kh) == (16, 40)
+    # the step-wise path: one batch row per workgroup, every thread slot of the layer in it (NT = 64 per 64 units)
+    assert (s.rows_per_wg, s.threads_per_wg, s.workgroups) == (1, (H + 63) // 64 * 64, 3)
+
+
 def test_stack_of_wide_layers_is_refused():
     """The stack entry points do not take wide layers: MyLSTM / Model chain them through the per-layer calls."""
     lib = _lib.lib()

@@ -1,7 +1,11 @@
 """Randomised parity sweep of the sequence entry point against the fp64 literal oracle (tests/hip_util.py's run_hip /
 run_literal / compare_all at the tolerances of the test suite): shapes, ranks, variants, optional initial states and upstream
 gradients drawn at random from a seed.  Prints every case that fails or that the library refuses, and a summary line.
-    python tools/fuzz_parity.py [cases] [seed] [seq|stack|rb|big]
+    python tools/fuzz_parity.py [cases] [seed] [seq|stack|rb|big|wide]
+wide: layers at wide ranks (padded w_rank > 32 or padded hidden rank summed over groups > 128) inside the envelope the library
+documents for them (include/vmlmf_hip.h): the step-wise path, fp32, w_rank <= input_size, u_rank <= hidden_size / g, padded ranks
+<= 1024; mostly ranks 33 - 320, sometimes up to the cap
+seq, wide: a drawn case the library refuses is a failure (the draws stay inside the envelope)
 big: batches up to 1100 rows, sequences up to 200 steps, H up to 700 (more rows than CUs, the stand-alone weight-gradient
 kernels, the clustered layers)
 stack: 2 - 4 like layers through vmlmf_stack (the wavefront launches; initial states of every layer at random) against the
@@ -43,7 +47,7 @@ def draw():
     if lm:
         H = min(H, 160)
     I = H if lm else pick(2, 150 if novm else min(H, 150), 0.4)   # (I = 1: the reference's own squeeze() breaks the literal oracle)
-    rw = pick(1, 32, 0.3)             # the kernels cover padded ranks up to 32 (beyond: VMLMF_E_UNSUPPORTED, by design)
+    rw = pick(1, 32, 0.3)             # narrow ranks (padded <= 32 / hidden <= 128 summed): every kernel family; wider: MODE "wide"
     ru = [pick(1, 32, 0.3), pick(1, 32, 0.3)] if group else pick(1, 32, 0.3)
     B, T = pick(1, 200, 0.4), pick(1, 40, 0.4)
     if MODE == "big":
@@ -64,9 +68,59 @@ def draw():
                 dy=bool(rng.random() < 0.8), dh=bool(rng.random() < 0.5), dc=bool(rng.random() < 0.4), seed=int(rng.integers(0, 2**31)))
 
 
+def pad8(r):
+    return (r + 7) // 8 * 8
+
+
+def in_wide_envelope(v, I, H, rw, ru):
+    """make_geo's rule for a wide layer it runs (vmlmf_api.hip), restated: wide, on the step-wise path (padded u_rank > 32, more
+    than 512 thread slots or I > H), no rank above the dimension it factors, both padded ranks <= 1024; plus the shape rules of
+    every layer (LM: I == H; a cell with vm: I <= H; groups divide H)."""
+    G = 2 if v in (O.V2, O.V4, O.V6) else 1
+    rus = ru if G == 2 else [ru]
+    if H % G or (v in (O.V3, O.V4) and I != H) or (v in (O.V1, O.V2) and I > H):
+        return False
+    KX, KH, NT = pad8(rw), sum(pad8(r) for r in rus), G * ((H // G + 63) // 64) * 64
+    wide = KX > 32 or G * KH > 128
+    stepwise = KH > 32 or NT > 512 or I > H
+    return wide and stepwise and rw <= I and max(rus) <= H // G and KX <= 1024 and KH <= 1024
+
+
+def wide_rank(cap):
+    """mostly 33 - 320, sometimes up to cap"""
+    return int(rng.integers(33, min(cap, 320) + 1)) if rng.random() < 0.85 or cap <= 320 else int(rng.integers(321, cap + 1))
+
+
+def draw_wide():
+    while True:
+        v = VARIANTS[int(rng.integers(0, len(VARIANTS)))]
+        G = 2 if v in (O.V2, O.V4, O.V6) else 1
+        # one side wide (sometimes both), the other from the narrow range
+        side = rng.random()
+        rw = wide_rank(1024) if side < 0.7 else pick(1, 32, 0.3)
+        ru = [wide_rank(1024 // G) if side >= 0.35 else pick(8, 40, 0.3) for _ in range(G)]
+        need_h = max(max(ru) * G, 0 if v in (O.V5, O.V6) else rw)
+        H = need_h + int(rng.integers(0, 160))
+        H += H % G
+        I = H if v in (O.V3, O.V4) else (rw + int(rng.integers(0, H - rw + 1)) if v in (O.V1, O.V2) else rw + int(rng.integers(0, 300)))
+        if H > 1100 or I > 1100 or not in_wide_envelope(v, I, H, rw, ru if G == 2 else ru[0]):
+            continue
+        B, T = pick(1, 48, 0.5), pick(1, 24, 0.5)
+        if rng.random() < 0.15 and H <= 256:          # many rows: the chunked column sums and K = T B of the weight gradients
+            B, T = int(rng.integers(64, 257)), int(rng.integers(16, 65))
+        if v == O.V4 and B == 1:
+            B = 2
+        # parameters at 1 / sqrt(fan-in) past a contraction of 100: at the default 0.1 a K ~ 1000 layer's pre-activations reach ~10,
+        # and fp32 rounding alone (a host fp32 evaluation too) then misses the outputs' absolute tolerance
+        scale = min(0.1, 1.0 / float(np.sqrt(max(I, H, rw, sum(ru)))))
+        return dict(v=v, B=B, T=T, I=I, H=H, rw=rw, ru=ru if G == 2 else ru[0], states=bool(rng.random() < 0.5),
+                    tm=bool(rng.random() < 0.4), dy=bool(rng.random() < 0.8), dh=bool(rng.random() < 0.5), dc=bool(rng.random() < 0.4),
+                    seed=int(rng.integers(0, 2**31)), scale=scale)
+
+
 def run(c):
     r = np.random.Generator(np.random.PCG64(c["seed"]))
-    P = O.make_params(c["v"], c["I"], c["H"], c["rw"], c["ru"], seed=c["seed"] % 1000)
+    P = O.make_params(c["v"], c["I"], c["H"], c["rw"], c["ru"], seed=c["seed"] % 1000, scale=c.get("scale", 0.1))
     shp = (c["T"], c["B"], c["I"]) if c["tm"] else (c["B"], c["T"], c["I"])
     x = r.standard_normal(shp).astype(np.float32)
     h0 = c0 = None
@@ -170,7 +224,7 @@ def draw_stack():
 ok = refused = failed = uncovered = 0
 t0 = time.time()
 for n in range(N):
-    c = draw_stack() if MODE == "stack" else draw()
+    c = draw_stack() if MODE == "stack" else (draw_wide() if MODE == "wide" else draw())
     try:
         if MODE == "stack":
             run_stack(c)
@@ -187,6 +241,8 @@ for n in range(N):
         if "error -3" in msg or "error -2" in msg or "unsupported" in msg.lower():
             refused += 1
             print("refused", c, msg[:160], flush=True)
+            if MODE in ("seq", "wide"):   # the draw is inside the envelope: a refusal is a regression
+                failed += 1
         else:
             failed += 1
             print("ERROR", c, msg[:400], flush=True)
