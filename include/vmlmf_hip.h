@@ -399,6 +399,34 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t *tokens, con
 int vmlmf_embed_backward(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, void *scratch,
                          size_t scratch_bytes, void *stream);
 
+/* ---- decoding the LM: one launch per token (Model.generate in vmlmf_amd/lm.py; csrc/vmlmf_sample.hip) ----
+ * vmlmf_lm_sample  the vocabulary projection of the top layer's output h (B, H) - scores[b][v] = bias[v] + sum_k h[b][k] weight[v][k],
+ *                  weight (V, H) and bias (V, may be NULL) laid out as the reference's Linear (V/src/models/vmlmf_lm.py:345-361), fp32 in a
+ *                  fixed order - and per row the choice of the next token, without a (B, V) score tensor:
+ *                    inv_temperature == 0: greedy, argmax_v scores[b][v] (ties: the lowest index); `state` may be NULL
+ *                    inv_temperature  > 0: Gumbel-max, argmax_v scores[b][v] * inv_temperature + G[b][v], an exact draw from
+ *                                          softmax(scores[b] * inv_temperature).  G = -log(-log u), u = ((word >> 8) + 0.5) 2^-24 from
+ *                                          Philox4x32-10 as the dropout's (vmlmf_dropout): counter = (step * B + b, v >> 2,
+ *                                          VMLMF_SITE_SAMPLE, offset low word), key = (seed low word, seed high word + offset high
+ *                                          word), word = output[v & 3]; state = the {seed, offset} snapshot of vmlmf_dropout_advance.
+ *                  Outputs: tokens_out (B, int64); logprob_out (B, or NULL) = scores[b][token] - logsumexp_v scores[b][v] (untempered:
+ *                  what nll_loss charges for the token); x_next (B, H, or NULL, needs embed (V, H)) = embed[token], the next step's input.
+ *                  The last workgroup to finish merges the others' partials behind a ticket: `ticket` is one int64 of device memory,
+ *                  zero before the launch and zero again after it (launches sharing one are ordered on one stream).  No workgroup
+ *                  waits for another.  workspace: vmlmf_lm_sample_workspace_bytes(B, V) bytes (host only; monotone in B and V). */
+#define VMLMF_SITE_SAMPLE 0x53414D50 /* the sampler's Philox site ("SAMP"); the dropout sites are 0 .. layers */
+size_t vmlmf_lm_sample_workspace_bytes(int B, int V);
+int vmlmf_lm_sample(int B, int H, int V, const float *h, const float *weight, const float *bias, const float *embed,
+                    float inv_temperature, const int64_t *state, int step, int64_t *tokens_out, float *logprob_out, float *x_next,
+                    int64_t *ticket, void *workspace, size_t workspace_bytes, void *stream);
+/* vmlmf_lm_choose  the same choice, log-probability and x_next from scores (B, V) that a library GEMM produced (h weight^T, WITHOUT the
+ *                  bias: it is added here), one workgroup per row, the row read once.  Same Philox layout, same outputs, no ticket or
+ *                  workspace.  vmlmf_lm_sample walks its vocabulary strips once per 16 rows of the batch, and its fixed cost is the
+ *                  last workgroup's merge: from about 8 rows on the GEMM and this launch are faster (measured at the PTB size:
+ *                  docs/design/lm_sampling.md); vmlmf_amd.lm_sample switches above 4 rows. */
+int vmlmf_lm_choose(int B, int H, int V, const float *scores, const float *bias, const float *embed, float inv_temperature,
+                    const int64_t *state, int step, int64_t *tokens_out, float *logprob_out, float *x_next, void *stream);
+
 /* dst (cols x rows, dense) = src (rows x cols, dense)^T, fp32, out of place.  The LM head's weight gradient dW = dz^T h is fastest as
  * the library GEMM that yields dW^T; this turns it into the (V, H) tensor fc.w.grad is (vmlmf_amd/functional.py: LmHeadLossFn). */
 int vmlmf_transpose(int rows, int cols, const float *src, float *dst, void *stream);

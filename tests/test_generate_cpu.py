@@ -1,0 +1,103 @@
+"""Decoding the LM (Model.generate, C ABI vmlmf_lm_sample): what can be checked without a GPU - the entry points' argument checks
+(host only: they refuse before anything reaches a device), the workspace size, and the numpy restatement of the sampler's draw that
+the GPU tests hold the kernel to."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import vmlmf_oracle as O
+from vmlmf_amd import _lib
+
+HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "vmlmf_hip.h")
+
+
+def _sample(B=2, H=8, V=16, h=1, w=1, bias=None, embed=None, inv=0.0, state=None, step=0, tokens=1, logp=None, xn=None,
+            ticket=1, ws=1, nbytes=1 << 20):
+    """vmlmf_lm_sample with fake, never dereferenced pointers (1 = some non-null address)."""
+    p = lambda v: None if v is None else ctypes.c_void_p(v)
+    lib = _lib.lib()
+    rc = lib.vmlmf_lm_sample(B, H, V, p(h), p(w), p(bias), p(embed), inv, p(state), step, p(tokens), p(logp), p(xn), p(ticket), p(ws),
+                             nbytes, None)
+    return rc, lib.vmlmf_last_error().decode()
+
+
+def test_the_sampler_refuses_bad_arguments_on_the_host():
+    cases = [
+        (dict(B=0), _lib.E_BADARG, "B, H, V"), (dict(H=0), _lib.E_BADARG, "B, H, V"), (dict(V=-3), _lib.E_BADARG, "B, H, V"),
+        (dict(h=None), _lib.E_BADARG, "null"), (dict(w=None), _lib.E_BADARG, "null"), (dict(tokens=None), _lib.E_BADARG, "null"),
+        (dict(ticket=None), _lib.E_BADARG, "null"), (dict(ws=None), _lib.E_BADARG, "null"),
+        (dict(inv=-1.0), _lib.E_BADARG, "temperature"), (dict(inv=float("nan")), _lib.E_BADARG, "temperature"),
+        (dict(inv=float("inf")), _lib.E_BADARG, "temperature"),
+        (dict(inv=1.0, state=None), _lib.E_BADARG, "snapshot"),
+        (dict(xn=1, embed=None), _lib.E_BADARG, "embedding"),
+        (dict(step=-1), _lib.E_BADARG, "step"),
+        (dict(B=1 << 16, step=1 << 16), _lib.E_UNSUPPORTED, "2^32"),
+        (dict(nbytes=0), _lib.E_WORKSPACE, "workspace"),
+    ]
+    for kw, code, words in cases:
+        rc, msg = _sample(**kw)
+        assert rc == code and words in msg, (kw, rc, msg)
+
+
+def test_workspace_size_is_monotone_in_rows_and_vocabulary():
+    lib = _lib.lib()
+    assert lib.vmlmf_lm_sample_workspace_bytes(0, 100) == 0 and lib.vmlmf_lm_sample_workspace_bytes(4, 0) == 0
+    prev_v = 0
+    for V in (1, 15, 16, 17, 97, 1000, 8191, 8192, 8193, 10000, 50000, 262144):
+        prev_b = 0
+        for B in (1, 2, 16, 17, 32, 256, 4096):
+            n = lib.vmlmf_lm_sample_workspace_bytes(B, V)
+            assert n >= prev_b and n > 0
+            prev_b = n
+        n = lib.vmlmf_lm_sample_workspace_bytes(32, V)
+        assert n >= prev_v
+        prev_v = n
+    # at the PTB size one step holds (B rows x strips) partials of 32 bytes: 2 MB at B = 256
+    assert lib.vmlmf_lm_sample_workspace_bytes(256, 10000) <= 4 << 20
+
+
+def gumbel_restated(seed, offset, step, B, V):
+    """(B, V) Gumbel noise of the sampler at `step`: counter (step B + b, v >> 2, SITE_SAMPLE, offset low word), key (seed low,
+    seed high + offset high), word = out[v & 3], u = ((word >> 8) + 0.5) 2^-24, G = -log(-log u) in fp64."""
+    v = np.arange(V)
+    ctr = np.zeros((B, V, 4), dtype=np.uint32)
+    ctr[..., 0] = (step * B + np.arange(B, dtype=np.int64)).astype(np.uint32)[:, None]
+    ctr[..., 1] = (v >> 2).astype(np.uint32)[None, :]
+    ctr[..., 2] = np.uint32(_lib.SITE_SAMPLE)
+    ctr[..., 3] = np.uint32(offset & 0xFFFFFFFF)
+    key = np.array([seed & 0xFFFFFFFF, ((seed >> 32) + (offset >> 32)) & 0xFFFFFFFF], dtype=np.uint32)
+    w = O.philox4x32_10(ctr, key)
+    word = np.take_along_axis(w, np.broadcast_to((v & 3)[None, :, None], (B, V, 1)), axis=2)[..., 0]
+    u = ((word >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
+    return u, -np.log(-np.log(u))
+
+
+def test_the_restated_draw_stays_inside_the_unit_interval_on_a_site_of_its_own():
+    u, g = gumbel_restated(0x1234_5678_9ABC_DEF, 3, 5, 64, 1000)
+    assert (u > 0).all() and (u < 1).all() and np.isfinite(g).all()
+    assert ((0x00 + 0.5) * 2.0 ** -24) > 0 and ((0xFFFFFF + 0.5) * 2.0 ** -24) < 1   # the extreme words
+    assert abs(u.mean() - 0.5) < 5 * np.sqrt(1 / 12 / u.size)
+    assert abs(g.mean() - np.euler_gamma) < 5 * np.sqrt(np.pi ** 2 / 6 / g.size)      # Gumbel(0, 1): mean = Euler's gamma
+    # the header and the binding name the same site, and no dropout site (0 = the embedding, l + 1 = layer l) can be it
+    m = re.search(r"#define VMLMF_SITE_SAMPLE (0x[0-9A-Fa-f]+)", open(HEADER).read())
+    assert m and int(m.group(1), 16) == _lib.SITE_SAMPLE
+    assert _lib.SITE_SAMPLE > 1 << 16
+    # a different step, row, seed or offset is a different stream of words
+    for args in ((0x1234_5678_9ABC_DEF, 3, 6), (0x1234_5678_9ABC_DEF, 4, 5), (7, 3, 5)):
+        u2, _ = gumbel_restated(*args, 64, 1000)
+        assert not np.array_equal(u, u2)
+
+
+def test_generate_refuses_cpu_tensors():
+    from vmlmf_amd import Model
+    torch.manual_seed(0)
+    m = Model(97, 32, 2, 0.0, 0.1, w_rank=8, u_ranks=[8], lstm_type="vmlmf")
+    with pytest.raises(RuntimeError, match="cuda"):
+        m.generate(torch.zeros((3, 2), dtype=torch.int64), 4)
+    from vmlmf_amd import lm_sample
+    with pytest.raises(RuntimeError, match="cuda"):
+        lm_sample(torch.zeros(2, 32), m.fc.w.detach(), m.fc.b.detach(), 0.0)

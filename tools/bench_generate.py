@@ -1,0 +1,145 @@
+"""Decoding speed of the PTB LM (Model.generate): ms per token and tokens/s, V 10 000, H 650, two layers, MyVMLSTM rank 32 and
+MyVMLSTMGroup ranks [32, 32], for B in {1, 8, 32, 256}.  Paths, same process, same device:
+  eager        Model.generate's decode steps (temperature 1), eager: per token the sampler launch + the layers at T = 1 on kept images
+  eager_stack  the same with layer_path="stack" (stack_layers' one launch, which packs on every call)
+  graph        a DecodeGraph of 16 steps, replayed
+  naive        the stock-op loop a user writes without it: embed -> 2 x layer call at T = 1 -> addmm -> softmax -> multinomial
+  sampler_*    the sampler alone, both forms (functional.lm_sample form "fused" / "gemm"), 50 launches replayed from a graph
+All four step timings cover the decode steps only (the prompt's pass is outside them); best of --reps, and the spread (max / min).
+One JSON object per line.  `python tools/bench_generate.py [--out FILE] [--batches 1,8,32,256] [--tokens 64] [--sampler-only]`."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def _model(group):
+    from vmlmf_amd import Model
+    torch.manual_seed(0)
+    if group:
+        m = Model.with_group_layers(10000, 650, 2, 0.0, 0.05, w_rank=32, u_ranks=[32, 32])
+    else:
+        m = Model(10000, 650, 2, 0.0, 0.05, w_rank=32, u_ranks=[32], lstm_type="vmlmf")
+    return m.cuda().eval()
+
+
+def _timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    _timed.spread = max(ts) / min(ts)
+    return min(ts)
+
+
+def _rec(t, B, steps):
+    return {"ms_per_token": 1e3 * t / steps, "tokens_per_s": B * steps / t, "spread": round(_timed.spread, 3)}
+
+
+def sampler_us(h, w, b, e, snap, form, n=50):
+    from vmlmf_amd import lm_sample
+    for _ in range(3):
+        lm_sample(h, w, b, 1.0, snap, 0, embed=e, form=form)
+    gs = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gs):
+        for j in range(n):
+            lm_sample(h, w, b, 1.0, snap, j, embed=e, form=form)
+    gs.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    best = float("inf")
+    for _ in range(3):
+        e0.record()
+        gs.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        best = min(best, 1e3 * e0.elapsed_time(e1) / n)
+    return best
+
+
+def naive(m, x, states, steps):
+    """The loop of the issue: no package sampler, no kept images."""
+    toks = []
+    with torch.no_grad():
+        for _ in range(steps):
+            h = m.embed.w[x].unsqueeze(0)
+            for i, rnn in enumerate(m.rnns):
+                h, states[i] = rnn(h, states[i])
+            p = torch.softmax(torch.addmm(m.fc.b, h[0], m.fc.w.t()), -1)
+            x = torch.multinomial(p, 1)[:, 0]
+            toks.append(x)
+    return torch.stack(toks)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batches", default="1,8,32,256")
+    ap.add_argument("--tokens", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sampler-only", action="store_true", help="only the sampler launch (e.g. of a probe build named by VMLMF_LIB)")
+    a = ap.parse_args()
+    from vmlmf_amd import DecodeGraph, dropout_advance
+    from vmlmf_amd.lm import _KeptImages
+    dev = torch.device("cuda")
+    rows = []
+    out = open(a.out, "w") if a.out else None
+
+    def emit(rec):
+        rec["device"] = torch.cuda.get_device_name(0)
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+        rows.append(rec)
+
+    K = 16
+    steps = a.tokens
+    for group in (False, True):
+        m = _model(group)
+        name = "group[32,32]" if group else "plain32"
+        for B in [int(b) for b in a.batches.split(",")]:
+            prompt = torch.randint(0, 10000, (4, B), device=dev)
+            res = {"model": name, "B": B, "V": 10000, "H": 650, "tokens": steps}
+            with torch.no_grad():
+                h, st = m.features(prompt, m.state_init(B))
+            snap = dropout_advance(m.sampler_state())
+            hv = h[-1].contiguous()
+            for form in ("fused", "gemm"):
+                us = sampler_us(hv, m.fc.w, m.fc.b, m.embed.w, snap, form)
+                res["sampler_%s_us" % form] = us
+                res["sampler_%s_fc_w_GBps" % form] = 10000 * 650 * 4 / (us * 1e-6) / 1e9
+            if a.sampler_only:
+                emit(res)
+                continue
+            for path in ("layers", "stack"):
+                def eager():
+                    with torch.no_grad(), _KeptImages(m):
+                        m._decode(hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path)
+                t = _timed(eager, a.reps)
+                res["eager" if path == "layers" else "eager_stack"] = _rec(t, B, steps)
+            g = DecodeGraph(m, hv, st, K, temperature=1.0)
+            t = _timed(lambda: [g.replay() for _ in range(steps // K)], a.reps)
+            res["graph"] = dict(_rec(t, B, steps), chunk=K)
+            del g
+            x0 = prompt[-1]
+            t = _timed(lambda: naive(m, x0, [(s0.clone(), s1.clone()) for s0, s1 in st], steps), a.reps)
+            res["naive"] = _rec(t, B, steps)
+            emit(res)
+        del m
+        torch.cuda.empty_cache()
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -1830,6 +1830,52 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, con
   return rc == 0 ? 0 : fail(rc, hipGetErrorString((hipError_t)rc));
 }
 
+// ---- decoding the LM (vmlmf_sample.hip) ----
+size_t vmlmf_lm_sample_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_workspace_bytes(B, V); }
+
+int vmlmf_lm_sample(int B, int H, int V, const float* h, const float* weight, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, int64_t* ticket, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (B < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "lm_sample: B, H, V must be >= 1");
+  if (!h || !weight || !tokens_out || !ticket || !workspace) return fail(VMLMF_E_BADARG, "lm_sample: null pointer");
+  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+    return fail(VMLMF_E_BADARG, "lm_sample: the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_sample: sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_sample: x_next needs the embedding table");
+  if (step < 0) return fail(VMLMF_E_BADARG, "lm_sample: step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_sample: 2^32 positions (step * B + b) and more");
+  if (workspace_bytes < lm_sample_workspace_bytes(B, V))
+    return fail(VMLMF_E_WORKSPACE, "lm_sample: workspace smaller than vmlmf_lm_sample_workspace_bytes()");
+  LmSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.h = h, a.w = weight, a.bias = bias, a.embed = embed;
+  a.state = reinterpret_cast<const unsigned long long*>(state);
+  a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
+  a.part = static_cast<float*>(workspace), a.ticket = reinterpret_cast<unsigned long long*>(ticket);
+  a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  const int rc = launch_lm_sample(a, (hipStream_t)stream);
+  return rc == 0 ? 0 : fail(rc, hipGetErrorString((hipError_t)rc));
+}
+
+int vmlmf_lm_choose(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, void* stream) {
+  if (B < 1 || V < 1 || (x_next && H < 1)) return fail(VMLMF_E_BADARG, "lm_choose: B, V (and H with x_next) must be >= 1");
+  if (!scores || !tokens_out) return fail(VMLMF_E_BADARG, "lm_choose: null pointer");
+  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+    return fail(VMLMF_E_BADARG, "lm_choose: the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_choose: sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_choose: x_next needs the embedding table");
+  if (step < 0) return fail(VMLMF_E_BADARG, "lm_choose: step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_choose: 2^32 positions (step * B + b) and more");
+  LmChooseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.scores = scores, a.bias = bias, a.embed = embed, a.state = reinterpret_cast<const unsigned long long*>(state);
+  a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
+  a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  const int rc = launch_lm_choose(a, (hipStream_t)stream);
+  return rc == 0 ? 0 : fail(rc, hipGetErrorString((hipError_t)rc));
+}
+
 int vmlmf_transpose(int rows, int cols, const float* src, float* dst, void* stream) {
   if (rows < 1 || cols < 1) return fail(VMLMF_E_BADARG, "transpose: rows, cols must be >= 1");
   if (!src || !dst || src == dst) return fail(VMLMF_E_BADARG, "transpose: two distinct buffers");

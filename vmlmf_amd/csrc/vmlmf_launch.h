@@ -287,6 +287,29 @@ int launch_embed_bwd(int R, int H, int V, const long long* tokens, const float* 
 int launch_drop_advance(unsigned long long* state, unsigned long long* snap, hipStream_t s);
 int launch_drop_rows(int mode, long long R, int H, int V, const DropArgs& d, const DropCols& cm, const float* x, const long long* tokens, float* y,
                      hipStream_t s);
+// one decoded token of the LM: head + greedy / Gumbel-max choice + log-probability (+ the next input row), vmlmf_sample.hip
+struct LmSampleArgs {
+  const float *h, *w, *bias, *embed;      // (B, H), (V, H), (V) or NULL, (V, H) or NULL
+  const unsigned long long* state;        // {seed, offset} snapshot (sampling only)
+  long long* tokens;                      // (B)
+  float *logprob, *x_next;                // (B) or NULL, (B, H) or NULL
+  float* part;                            // lm_sample_workspace_bytes(B, V): per-strip partials
+  unsigned long long* ticket;             // zero between launches
+  float inv_temp;                         // 0: greedy
+  int B, H, V, step, tpw;                 // tpw: set by the launcher
+};
+size_t lm_sample_workspace_bytes(int B, int V);
+int launch_lm_sample(LmSampleArgs a, hipStream_t s);
+// the same choice over the (B, V) scores of a library GEMM (without the bias), one workgroup per row
+struct LmChooseArgs {
+  const float *scores, *bias, *embed;     // (B, V), (V) or NULL, (V, H) or NULL
+  const unsigned long long* state;        // {seed, offset} snapshot (sampling only)
+  long long* tokens;                      // (B)
+  float *logprob, *x_next;                // (B) or NULL, (B, H) or NULL
+  float inv_temp;                         // 0: greedy
+  int B, H, V, step;
+};
+int launch_lm_choose(const LmChooseArgs& a, hipStream_t s);
 
 // ---- wavefront kernels for stacked layers (vmlmf_wave.inc) ----
 // One launch runs every layer of a stack: workgroup = (layer, batch row).  Besides the recurrence's compute waves a

@@ -174,18 +174,28 @@ def ce_ticket(device):
     memset node in the graph): a captured forward takes the next pair of a block of 16 that the first call outside a capture set
     aside for the device, so different graphs - replayed on whatever streams - do not meet on one pair either.  Only a process whose
     very first forward is captured pays a zeroing node in that graph (the pair is then the graph's own and is not kept here)."""
+    return _stream_ticket(device, "ce")
+
+
+def sample_ticket(device):
+    """The ticket of the token sampler (vmlmf_lm_sample: the last workgroup to finish merges the others' partials and puts the
+    word back to zero), kept by ce_ticket's rules: per (device, stream), nothing allocated inside a stream capture."""
+    return _stream_ticket(device, "sample")
+
+
+def _stream_ticket(device, kind):
     device = torch.device(device)
     capturing = torch.cuda.is_current_stream_capturing()
-    block = _TICKET.get((device.index, "capture"))
+    block = _TICKET.get((kind, device.index, "capture"))
     if block is None and not capturing:
-        block = _TICKET[(device.index, "capture")] = [torch.zeros(2 * _TICKET_CAPTURE_SLOTS, device=device, dtype=torch.int64), 0]
+        block = _TICKET[(kind, device.index, "capture")] = [torch.zeros(2 * _TICKET_CAPTURE_SLOTS, device=device, dtype=torch.int64), 0]
     if capturing:
         if block is None:
             return torch.zeros(2, device=device, dtype=torch.int64)
         i = block[1] % _TICKET_CAPTURE_SLOTS
         block[1] += 1
         return block[0][2 * i:2 * i + 2]
-    key = (device.index, _lib.raw_stream(device).value)
+    key = (kind, device.index, _lib.raw_stream(device).value)
     t = _TICKET.get(key)
     if t is None:
         t = _TICKET[key] = torch.zeros(2, device=device, dtype=torch.int64)
@@ -1255,3 +1265,70 @@ def linear_nll(h, weight, bias, y, chunk_rows=2048, fused=None):
     if use and h.is_cuda:
         return LinearNllFn.apply(h, weight, bias, y, chunk_rows)
     return nll_loss(torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t()), y)
+
+
+# ---- decoding the LM: head + token choice in one launch per token (C ABI: vmlmf_lm_sample; csrc/vmlmf_sample.hip) ---------------
+def _sample_workspace(dev, nbytes):
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, device=dev, dtype=torch.uint8)      # graph-private pool
+    key = ("sample", dev.index, _lib.raw_stream(dev).value)
+    buf = _WORKSPACE.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    return buf
+
+
+SAMPLE_FUSED_MAX_ROWS = 4   # measured at the PTB size: fused 25.6 us against 37.2 at 1 row, 40.5 against 37.8 at 8 (lm_sampling.md)
+
+
+def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None):
+    """The next token of every row of h (B, H) - the top layer's output - under Linear(weight (V, H), bias (V)), in ONE launch that
+    never writes the (B, V) scores.  temperature 0: greedy (argmax, ties to the lowest index); tau > 0: a draw from softmax(scores / tau)
+    by Gumbel-max, its noise from Philox4x32-10 at (state = a {seed, offset} snapshot of dropout_advance(), position step * B + b,
+    vocabulary row, the sampler's own site _lib.SITE_SAMPLE).  Returns (tokens (B) int64, logprobs (B)) - logprobs are the untempered
+    log-softmax of the chosen tokens, what nll_loss charges for them - and, with embed (V, H), x_next = embed[tokens] (B, H).
+    form: "fused" (vmlmf_lm_sample: head and choice in one launch, no score tensor), "gemm" (the library GEMM's (B, V) scores, then
+    vmlmf_lm_choose: one workgroup per row), None: fused up to SAMPLE_FUSED_MAX_ROWS rows, gemm beyond (docs/design/lm_sampling.md).
+    Both forms draw the same noise; their scores differ in fp32 rounding only."""
+    for t, what in ((h, "h"), (weight, "weight")):
+        _require_hip(t, what)
+    if bias is not None:
+        _require_hip(bias, "bias")
+    if embed is not None:
+        _require_hip(embed, "embedding table")
+    temperature = float(temperature)
+    if not temperature >= 0.0:
+        raise ValueError(f"vmlmf_amd.lm_sample: temperature must be >= 0, got {temperature}")
+    inv = 0.0 if temperature == 0.0 else 1.0 / temperature
+    if inv > 0.0 and (state is None or not state.is_cuda or state.dtype != torch.int64 or state.numel() != 2):
+        raise RuntimeError("vmlmf_amd.lm_sample: sampling (temperature > 0) needs a {seed, offset} snapshot: two int64 on the device")
+    h2 = h.reshape(-1, h.shape[-1]).contiguous()
+    B, H = h2.shape
+    w = weight.contiguous()
+    V = w.shape[0]
+    if w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
+        raise RuntimeError(f"vmlmf_amd.lm_sample: h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias / embed must be (V) / (V, H)")
+    dev = h2.device
+    lib = _lib.lib()
+    tokens = torch.empty(B, device=dev, dtype=torch.int64)
+    logp = torch.empty(B, device=dev, dtype=torch.float32)
+    xn = torch.empty((B, H), device=dev, dtype=torch.float32) if embed is not None else None
+    if form is None:
+        form = "fused" if B <= SAMPLE_FUSED_MAX_ROWS else "gemm"
+    if form == "gemm":
+        scores = torch.mm(h2, w.t())
+        with _lib.on_device(dev):
+            _lib.check(lib.vmlmf_lm_choose(B, H, V, _ptr(scores), _ptr(None if bias is None else bias.contiguous()),
+                                           _ptr(None if embed is None else embed.contiguous()), inv, None if inv == 0.0 else _ptr(state),
+                                           int(step), _ptr(tokens), _ptr(logp), _ptr(xn), _lib.raw_stream(dev)))
+        return (tokens, logp) if xn is None else (tokens, logp, xn)
+    if form != "fused":
+        raise ValueError(f"vmlmf_amd.lm_sample: form must be 'fused', 'gemm' or None, got {form!r}")
+    nbytes = lib.vmlmf_lm_sample_workspace_bytes(B, V)
+    ws = _sample_workspace(dev, nbytes)
+    with _lib.on_device(dev):
+        _lib.check(lib.vmlmf_lm_sample(B, H, V, _ptr(h2), _ptr(w), _ptr(None if bias is None else bias.contiguous()),
+                                       _ptr(None if embed is None else embed.contiguous()), inv,
+                                       None if inv == 0.0 else _ptr(state), int(step), _ptr(tokens), _ptr(logp), _ptr(xn),
+                                       _ptr(sample_ticket(dev)), _ptr(ws), nbytes, _lib.raw_stream(dev)))
+    return (tokens, logp) if xn is None else (tokens, logp, xn)

@@ -336,3 +336,162 @@ class Model(nn.Module):
             from .functional import dropout_state
             st = self._drop_state = dropout_state(dev, seed)
         return st
+
+    def sampler_state(self, seed=None):
+        """{seed, offset} of the generator generate() samples from - its own, apart from the dropout generator, so sampling leaves
+        training's masks where they were (created on first use; seed=None draws it from torch's CPU generator; a seed re-seeds)."""
+        dev = self.embed.w.device
+        st = getattr(self, "_sample_state", None)
+        if st is None or st.device != dev or seed is not None:
+            from .functional import dropout_state
+            st = self._sample_state = dropout_state(dev, seed)
+        return st
+
+    def _decode_layers(self, x, states, layer_path):
+        """The layers at T = 1: x (1, B, H) -> (y (1, B, H), states).  layer_path "stack": stack_layers' one launch where it covers the
+        layers (it packs the parameters on every call); otherwise a call per layer - VMLMF layers reuse kept images (_KeptImages)."""
+        if layer_path == "stack":
+            stacked = stack_layers(self.rnns, x, states)
+            if stacked is not None:
+                return stacked[0], list(stacked[1])
+        states = list(states)
+        for i, rnn in enumerate(self.rnns):
+            x, states[i] = rnn(x, states[i])
+        return x, states
+
+    def _decode(self, h, states, steps, temperature, snap, layer_path):
+        """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
+        the next input row), then the layers at T = 1 on that row.  No host synchronisation: capturable (DecodeGraph)."""
+        from .functional import lm_sample
+        toks, lps = [], []
+        for j in range(steps):
+            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w)
+            toks.append(tok)
+            lps.append(lp)
+            y, states = self._decode_layers(x.unsqueeze(0), states, layer_path)
+            h = y[-1]
+        return torch.stack(toks), torch.stack(lps), h, states
+
+    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers"):
+        """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
+        int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
+        have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
+        The prompt runs once through features() without dropout; each further token is one vmlmf_lm_sample launch (functional.lm_sample)
+        and the layers at T = 1.  temperature 0: greedy; tau > 0: softmax(scores / tau) draws from sampler_state() (seed: re-seed it
+        first), snapshotted and advanced once per call - the same seed gives the same tokens, the next call fresh ones.
+        chunk=K (steps % K == 0): the decode steps run as a captured hipGraph of K steps (DecodeGraph), replayed steps / K times, the
+        generator snapshotted and advanced once per REPLAY (the eager form: once per call) - so with one seed the chunked and the eager
+        form draw the same first K tokens and different ones after them; greedy decoding is the same either way.  layer_path: "layers"
+        (one call per layer on kept parameter images; the default) or "stack" (stack_layers' one launch where it covers the layers;
+        measured at the PTB size: docs/design/lm_sampling.md).  Every module's train / eval flag is as the caller left it afterwards."""
+        if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
+            raise RuntimeError("vmlmf_amd: Model.generate runs on the HIP sampler kernel (vmlmf_lm_sample) only: move the model and the "
+                               "prompt to 'cuda' (no CPU fallback)")
+        if prompt.dim() != 2 or prompt.dtype != torch.int64:
+            raise RuntimeError("vmlmf_amd: Model.generate takes a (T0, B) int64 prompt")
+        steps, temperature = int(steps), float(temperature)
+        if chunk is not None and (int(chunk) < 1 or steps % int(chunk) != 0):
+            raise ValueError(f"vmlmf_amd: Model.generate: chunk={chunk} must divide steps={steps}")
+        B = prompt.shape[1]
+        states = self.state_init(B) if states is None else list(states)
+        gen = self.sampler_state(seed) if temperature > 0 else None
+        modes = [(mod, mod.training) for mod in self.modules()]
+        self.train(False)
+        try:
+            with torch.no_grad(), _KeptImages(self):
+                h, states = self.features(prompt, list(states))
+                h = h[-1]
+                if steps == 0:
+                    return (torch.empty((0, B), dtype=torch.int64, device=prompt.device),
+                            torch.empty((0, B), device=prompt.device), states)
+                if chunk is None:
+                    from .functional import dropout_advance
+                    snap = dropout_advance(gen) if gen is not None else None
+                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path)
+                    return tokens, logprobs, states
+            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path)
+            outs = [graph.replay() for _ in range(steps // int(chunk))]
+            return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
+                    [(a.clone(), c.clone()) for a, c in graph.states])
+        finally:
+            for mod, was in modes:
+                mod.training = was
+
+
+class _KeptImages:
+    """`with _KeptImages(model[, caches]):` every VMLMF layer of the model keeps its packed parameter images for the duration
+    (functional.cache_packed_parameters) - a layer that already keeps them keeps its own cache -, and the caller's setting comes back
+    afterwards.  caches: the PackCache of each such layer, in order (DecodeGraph holds its own: its graph reads their buffers)."""
+
+    def __init__(self, model, caches=None):
+        self.layers = [m for m in model.modules() if hasattr(m, "kernel_params")]
+        self.caches = caches
+
+    def __enter__(self):
+        from .functional import PackCache
+        self.saved = [m.__dict__.get("_pack_cache", _UNSET) for m in self.layers]
+        for i, (m, was) in enumerate(zip(self.layers, self.saved)):
+            if self.caches is not None:
+                m._pack_cache = self.caches[i]
+            elif was is _UNSET or was is None:
+                m._pack_cache = PackCache()
+        return self
+
+    def __exit__(self, *exc):
+        for m, was in zip(self.layers, self.saved):
+            if was is _UNSET:
+                m.__dict__.pop("_pack_cache", None)
+            else:
+                m._pack_cache = was
+        return False
+
+
+_UNSET = object()
+
+
+class DecodeGraph:
+    """`steps` decode steps of a Model (Model._decode: per step the vmlmf_lm_sample launch and the layers at T = 1) captured once into
+    a hipGraph - linear, on one stream.  replay() continues from where the previous replay stopped (the top layer's output and the
+    layers' states live in this object's buffers, h / states) and returns (tokens (steps, B), logprobs (steps, B)); with temperature > 0
+    the first node snapshots and advances the model's sampler_state(), so every replay draws fresh tokens and a new capture from the same
+    seed and inputs repeats the first replay.  The generator is the sampler_state() tensor of construction time: re-seeding the model
+    (sampler_state(seed)) puts a new tensor in its place, which this graph does not see - build a new DecodeGraph after re-seeding, as
+    after the parameters change (the layers read kept parameter images packed at construction).  Replay DecodeGraphs one after
+    another, never two at once on different streams: the sampler's ticket words are taken from a ring of 16 per device (as the
+    criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count."""
+
+    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers"):
+        from .functional import PackCache
+        self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
+        dev = h.device
+        self.h = h.detach().clone()
+        self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
+        self.gen = model.sampler_state() if self.temperature > 0 else None
+        self.caches = [PackCache() for m in model.modules() if hasattr(m, "kernel_params")]
+        with torch.no_grad(), _KeptImages(model, self.caches):
+            # warm-up outside the capture, on copies: packs the images, creates the tickets and workspaces; the generator is put back
+            saved = None if self.gen is None else self.gen.clone()
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states])
+            torch.cuda.current_stream(dev).wait_stream(side)
+            if saved is not None:
+                self.gen.copy_(saved)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.tokens, self.logprobs = self._body(self.h, self.states)
+
+    def _body(self, h, states):
+        from .functional import dropout_advance
+        snap = dropout_advance(self.gen) if self.gen is not None else None
+        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path)
+        h.copy_(hn)
+        for (a, c), (a2, c2) in zip(states, st):
+            a.copy_(a2)
+            c.copy_(c2)
+        return toks, lps
+
+    def replay(self):
+        self.graph.replay()
+        return self.tokens.clone(), self.logprobs.clone()
