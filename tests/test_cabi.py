@@ -208,6 +208,27 @@ def test_every_documented_kernel_switch_is_accepted():
     assert lib.vmlmf_tune_get(b"no_such_switch", ctypes.byref(ctypes.c_int(0))) == _lib.E_BADARG
 
 
+def test_a_switch_flipped_through_the_raw_symbol_reaches_the_descriptor_cache():
+    """functional's host caches carry vmlmf_tune_generation() in their keys, so a switch that did not go through _lib.tune() - the
+    raw symbol, as above, or the library's own switch after a riding worker gave up - is seen by the next descriptor lookup:
+    the cached entry before the call, a freshly queried one after it (host-only: vmlmf_query)."""
+    from vmlmf_amd import functional as F
+    lib = _lib.lib()
+    shape = ((_lib.V1_CELL, 1, 16, (16,), False, _lib.DT_F32), 64, 128, 9, 180, True)
+    first = F._desc_for(*shape)
+    assert F._desc_for(*shape) is first
+    was = _lib.tune_get("rec3")
+    try:
+        assert lib.vmlmf_tune(b"rec3", 6 if was == 7 else 7) == 0
+        fresh = F._desc_for(*shape)
+        assert fresh is not first and fresh[0] is not first[0]
+        now = _lib.query(fresh[0])
+        assert all(getattr(fresh[1], f) == getattr(now, f) for f, _ in _lib.Sizes._fields_)
+        assert F._desc_for(*shape) is fresh
+    finally:
+        assert lib.vmlmf_tune(b"rec3", was) == 0
+
+
 def test_the_product_library_stays_pruned():
     """Verdict r4 item 6: no probe-only / unreachable instantiations in the shipped library - under 9 MB, and none of the ablation
     template parameters' names in its kernel symbols."""

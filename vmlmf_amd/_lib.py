@@ -230,10 +230,9 @@ def ranks_share_a_device():
 
 
 def tune(key, value):
-    """Kernel-selection switches of the library (include/vmlmf_hip.h: vmlmf_tune).  Cached descriptors are dropped."""
+    """Kernel-selection switches of the library (include/vmlmf_hip.h: vmlmf_tune).  Every call moves vmlmf_tune_generation(), which
+    the host caches of functional.py carry in their keys."""
     check(lib().vmlmf_tune(key.encode(), int(value)))
-    from . import functional
-    functional._DESC_CACHE.clear()
 
 
 def check_status():

@@ -58,7 +58,13 @@ class MyVMLMFCell(nn.Module):
 
     # kernel-facing view of the parameters (order fixed by functional.py)
     def kernel_params(self):
-        return (self.dia_x, self.dia_h, self.u_x, self.v_x, self.b_x, self.b_h, self.u_h, self.v_h)
+        return tuple(self.live_kernel_params(self._parameters))
+
+    @staticmethod
+    def live_kernel_params(cp):
+        """The kernels' parameter list read from a cell's live `_parameters` dict (Net's per-call plan: a reassigned Parameter is
+        picked up)."""
+        return [cp[k] for k in ("dia_x", "dia_h", "u_x", "v_x", "b_x", "b_h", "u_h", "v_h")]
 
     def kernel_cfg(self):
         return dict(variant=self.variant, w_rank=self.w_rank, u_ranks=[self.u_ranks], g=1,
@@ -391,8 +397,8 @@ class Net(nn.Module):
         plan = self._fast(x)
         if plan is not None:
             cell, cp, lp, rw, ur = plan[4:]
-            out = torch_ops().sequence(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"],
-                                                       cp["v_h"]], cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"])
+            out = torch_ops().sequence(x, None, None, cell.live_kernel_params(cp), cell.variant, 1, rw, ur, False, 0, None, lp["weight"],
+                                       lp["bias"])
             return out[3].squeeze(1)
         if isinstance(self.rnn, MyLSTM) and self.rnn.batch_first:
             # y[:, -1] IS the last layer's final h (same kernel value): taking it from there keeps autograd
@@ -424,9 +430,8 @@ class Net(nn.Module):
         if plan is not None:
             from .functional import ce_ticket, unit_gradient
             cell, cp, lp, rw, ur = plan[4:]
-            out = torch_ops().sequence_loss(x, None, None, [cp["dia_x"], cp["dia_h"], cp["u_x"], cp["v_x"], cp["b_x"], cp["b_h"], cp["u_h"],
-                                                            cp["v_h"]], cell.variant, 1, rw, ur, False, 0, None, lp["weight"], lp["bias"],
-                                            target, int(ignore_index), unit_gradient(x.device), ce_ticket(x.device))
+            out = torch_ops().sequence_loss(x, None, None, cell.live_kernel_params(cp), cell.variant, 1, rw, ur, False, 0, None, lp["weight"],
+                                            lp["bias"], target, int(ignore_index), unit_gradient(x.device), ce_ticket(x.device))
             return (out[4], out[3]) if return_logits else out[4]
         ride = (isinstance(self.rnn, MyLSTM) and self.rnn.batch_first and x.is_cuda and x.dtype == torch.float32
                 and self.lin.weight.shape[0] <= _lib.HEAD_MAX_CLASSES and self.lin.weight.dtype == torch.float32

@@ -91,8 +91,60 @@ vmlmf_desc make_desc(int variant, int64_t B, int64_t T, int64_t I, int64_t H, in
   return d;
 }
 
+Tensor contiguous_or_undefined(const c10::optional<Tensor>& t) { return t.has_value() ? t->contiguous() : Tensor(); }
+
+// Does this call record the tape?  Grad mode is off inside Function::forward, so the three entry points decide it here, from the
+// tensors autograd will differentiate: input, initial states, parameters, the classifier's weight and bias (false under
+// torch.no_grad(): inference kernels, no reserve buffer).  functional.py: _needs_tape is the same rule.
+bool needs_tape(const Tensor& x, const c10::optional<Tensor>& h0, const c10::optional<Tensor>& c0, at::TensorList params,
+                const c10::optional<Tensor>& head_w, const c10::optional<Tensor>& head_b) {
+  if (!at::GradMode::is_enabled()) return false;
+  for (const auto* t : {&h0, &c0, &head_w, &head_b})
+    if (t->has_value() && (*t)->requires_grad()) return true;
+  for (const auto& p : params)
+    if (p.requires_grad()) return true;
+  return x.requires_grad();
+}
+
+// a classifier riding on a launch's final hidden state (Net.lin), forward side: checks the (contiguous) weight, fills `hd` and
+// returns the (B, C) logits it allocated - an empty tensor, and `hd` zeroed, without a classifier
+Tensor fill_head_forward(vmlmf_head& hd, const Tensor& head_w, const Tensor& head_b, int64_t B, int64_t H, const Tensor& x) {
+  memset(&hd, 0, sizeof(hd));
+  if (!head_w.defined()) return at::empty({0}, x.options());
+  require_hip_f32(head_w, "head weight");
+  TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H, "vmlmf_amd: head weight must be (classes, hidden_size)");
+  Tensor logits = at::empty({B, head_w.size(0)}, x.options());
+  hd.classes = (int)head_w.size(0), hd.weight = head_w.data_ptr<float>(), hd.bias = cptr(head_b), hd.logits = logits.data_ptr<float>();
+  return logits;
+}
+
+// The gradient buffer of a layer or stack backward, by the layout contract stated in functional.py: _flat_grads (vmlmf_amd/dp.py
+// reduces it in place): ONE allocation - the gradients of `params` in call order, then, when the classifier takes part
+// (`dlogits` defined), dW (C, H) and db (C); db is a view only with a bias.  Fills grads, dW, db and `hd`; returns the buffer.
+Tensor flat_grads(const Tensor& x, const std::vector<Tensor>& params, const Tensor& head_w, bool has_head_b, const Tensor& dlogits,
+                  std::vector<Tensor>& grads, Tensor& dW, Tensor& db, vmlmf_head& hd) {
+  int64_t total = 0;
+  for (const auto& p : params) total += p.numel();
+  const int64_t C = dlogits.defined() ? head_w.size(0) : 0, H = dlogits.defined() ? head_w.size(1) : 0;
+  Tensor flat = at::empty({total + C * H + C}, x.options());
+  int64_t o = 0;
+  for (const auto& p : params) {
+    grads.push_back(flat.as_strided(p.sizes(), p.strides(), o));   // one op per view (narrow + view were two)
+    o += p.numel();
+  }
+  memset(&hd, 0, sizeof(hd));
+  if (dlogits.defined()) {
+    dW = flat.narrow(0, total, C * H).view({C, H});
+    if (has_head_b) db = flat.narrow(0, total + C * H, C);
+    hd.classes = (int)C, hd.weight = head_w.data_ptr<float>(), hd.dlogits = dlogits.data_ptr<float>();
+    hd.dweight = dW.data_ptr<float>(), hd.dbias = has_head_b ? db.data_ptr<float>() : nullptr;
+  }
+  return flat;
+}
+
 struct SeqFn : public torch::autograd::Function<SeqFn> {
   // args: x, h0 (maybe undefined), c0, params..., then the integer configuration
+  // saved for the backward, in this order: x, y, reserve, params..., [h0], [c0], [packed], [head_w], [dz_unit]
   // (the parameter list must reach apply() as an at::TensorList: a std::vector would match the "not a tensor" overload
   // of autograd's argument walker and the parameters would get no gradient)
   static variable_list forward(AutogradContext* ctx, Tensor x, c10::optional<Tensor> h0o, c10::optional<Tensor> c0o,
@@ -104,9 +156,7 @@ struct SeqFn : public torch::autograd::Function<SeqFn> {
     // head_w / head_b: a classifier riding on the layer's final hidden state (Net.lin): its logits are the 4th output
     // target (+ the package's unit-gradient tensor and ticket word): the criterion on those logits riding too (vmlmf_ce): its
     // loss is the 5th output, the logits' gradient for d(loss) = 1 is kept for the backward
-    Tensor head_w = head_w_o.has_value() ? head_w_o->contiguous() : Tensor();
-    Tensor head_b = head_b_o.has_value() ? head_b_o->contiguous() : Tensor();
-    if (head_w.defined()) require_hip_f32(head_w, "head weight");
+    Tensor head_w = contiguous_or_undefined(head_w_o), head_b = contiguous_or_undefined(head_b_o);
     // packed_o: parameter images kept by the caller (vmlmf_pack_params; functional.PackCache): nothing is packed in this call.
     // It travels as a non-differentiable input and is saved for the backward, which reads the same images.
     Tensor packed = packed_o.has_value() ? *packed_o : Tensor();
@@ -118,7 +168,7 @@ struct SeqFn : public torch::autograd::Function<SeqFn> {
       require_hip_f32(p, "parameter");
       params.push_back(p.contiguous());
     }
-    Tensor h0 = h0o.has_value() ? h0o->contiguous() : Tensor(), c0 = c0o.has_value() ? c0o->contiguous() : Tensor();
+    Tensor h0 = contiguous_or_undefined(h0o), c0 = contiguous_or_undefined(c0o);
     const int64_t B = time_major ? x.size(1) : x.size(0), T = time_major ? x.size(0) : x.size(1), I = x.size(2);
     const int64_t H = hidden_size((int)variant, params);
     const vmlmf_desc d = make_desc((int)variant, B, T, I, H, w_rank, u_ranks, g, time_major, training, dtype);
@@ -131,13 +181,8 @@ struct SeqFn : public torch::autograd::Function<SeqFn> {
     Tensor reserve = training ? at::empty({(int64_t)sz.reserve_bytes}, x.options().dtype(at::kByte)) : Tensor();
     vmlmf_params ps;
     fill_params(ps, params, (int)variant, (int)g);
-    Tensor logits = head_w.defined() ? at::empty({B, head_w.size(0)}, x.options()) : at::empty({0}, x.options());
     vmlmf_head hd;
-    memset(&hd, 0, sizeof(hd));
-    if (head_w.defined()) {
-      TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H, "vmlmf_amd: head weight must be (classes, hidden_size)");
-      hd.classes = (int)head_w.size(0), hd.weight = head_w.data_ptr<float>(), hd.bias = cptr(head_b), hd.logits = logits.data_ptr<float>();
-    }
+    Tensor logits = fill_head_forward(hd, head_w, head_b, B, H, x);
     vmlmf_extra ex;
     memset(&ex, 0, sizeof(ex));
     ex.packed = packed.defined() ? packed.data_ptr() : nullptr, ex.head = head_w.defined() ? &hd : nullptr, ex.ce = nullptr;
@@ -214,36 +259,15 @@ struct SeqFn : public torch::autograd::Function<SeqFn> {
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
     Tensor dx = ctx->needs_input_grad(0) ? at::empty_like(x) : Tensor();
     Tensor dh0 = has_h0 ? at::empty({B, H}, x.options()) : Tensor(), dc0 = has_c0 ? at::empty({B, H}, x.options()) : Tensor();
-    // one flat buffer for all parameter gradients (views are returned): a single allocation, contiguous for the
-    // data-parallel all-reduce (vmlmf_amd/dp.py)
-    // (the classifier's weight and bias gradients are the tail of the same allocation: ONE flat buffer, ONE all-reduce per step,
-    // SURVEY section 8e)
-    int64_t total = 0;
-    for (const auto& p : params) total += p.numel();
-    const int64_t head_floats = dlogits.defined() ? head_w.size(0) * H + head_w.size(0) : 0;
-    Tensor flat = at::empty({total + head_floats}, x.options());
     std::vector<Tensor> grads;
-    int64_t o = 0;
-    for (const auto& p : params) {
-      grads.push_back(flat.as_strided(p.sizes(), p.strides(), o));   // one op per view (narrow + view were two)
-      o += p.numel();
-    }
+    Tensor dW, db;
+    vmlmf_head hd;
+    Tensor flat = flat_grads(x, params, head_w, has_head_b, dlogits, grads, dW, db, hd);
     Tensor ws = workspace(x, sz.workspace_bytes);
     vmlmf_params ps;
     vmlmf_grads gs;
     fill_params(ps, params, (int)variant, (int)g);
     fill_params(gs, grads, (int)variant, (int)g);
-    // classifier gradients: behind the layer's in the same allocation
-    Tensor dW, db;
-    vmlmf_head hd;
-    memset(&hd, 0, sizeof(hd));
-    if (dlogits.defined()) {
-      const int64_t C = head_w.size(0);
-      dW = flat.narrow(0, total, C * H).view({C, H});
-      if (has_head_b) db = flat.narrow(0, total + C * H, C);
-      hd.classes = (int)C, hd.weight = head_w.data_ptr<float>(), hd.dlogits = dlogits.data_ptr<float>();
-      hd.dweight = dW.data_ptr<float>(), hd.dbias = has_head_b ? db.data_ptr<float>() : nullptr;
-    }
     vmlmf_extra ex;
     memset(&ex, 0, sizeof(ex));
     ex.packed = packed.defined() ? packed.data_ptr() : nullptr, ex.head = dlogits.defined() ? &hd : nullptr, ex.ce = nullptr;
@@ -260,19 +284,23 @@ struct SeqFn : public torch::autograd::Function<SeqFn> {
   }
 };
 
+// vmlmf::sequence is vmlmf::sequence_loss without a target: both come through here (y, hT, cT, logits, loss)
+variable_list run_sequence(const Tensor& x, const c10::optional<Tensor>& h0, const c10::optional<Tensor>& c0, at::TensorList params,
+                           int64_t variant, int64_t g, int64_t w_rank, at::IntArrayRef u_ranks, bool time_major, int64_t dtype,
+                           const c10::optional<Tensor>& packed, const c10::optional<Tensor>& head_w, const c10::optional<Tensor>& head_b,
+                           const c10::optional<Tensor>& target, int64_t ignore_index, const c10::optional<Tensor>& unit,
+                           const c10::optional<Tensor>& ticket) {
+  return SeqFn::apply(x, h0, c0, params, variant, g, w_rank, u_ranks.vec(), time_major, needs_tape(x, h0, c0, params, head_w, head_b),
+                      dtype, packed, head_w, head_b, target, ignore_index, unit, ticket);
+}
+
 std::tuple<Tensor, Tensor, Tensor, Tensor> sequence(const Tensor& x, const c10::optional<Tensor>& h0, const c10::optional<Tensor>& c0,
-                                            at::TensorList params, int64_t variant, int64_t g, int64_t w_rank,
-                                            at::IntArrayRef u_ranks, bool time_major, int64_t dtype,
-                                            const c10::optional<Tensor>& packed, const c10::optional<Tensor>& head_w,
-                                            const c10::optional<Tensor>& head_b) {
-  // grad mode is off inside Function::forward: whether the tape is needed is decided here (False under torch.no_grad():
-  // inference kernels, no reserve buffer)
-  bool training = x.requires_grad() || (h0.has_value() && h0->requires_grad()) || (c0.has_value() && c0->requires_grad());
-  for (const auto& p : params) training = training || p.requires_grad();
-  training = training || (head_w.has_value() && head_w->requires_grad()) || (head_b.has_value() && head_b->requires_grad());
-  training = training && at::GradMode::is_enabled();
-  auto out = SeqFn::apply(x, h0, c0, params, variant, g, w_rank, u_ranks.vec(), time_major, training, dtype, packed, head_w, head_b,
-                          c10::optional<Tensor>(), (int64_t)-100, c10::optional<Tensor>(), c10::optional<Tensor>());
+                                                    at::TensorList params, int64_t variant, int64_t g, int64_t w_rank,
+                                                    at::IntArrayRef u_ranks, bool time_major, int64_t dtype,
+                                                    const c10::optional<Tensor>& packed, const c10::optional<Tensor>& head_w,
+                                                    const c10::optional<Tensor>& head_b) {
+  auto out = run_sequence(x, h0, c0, params, variant, g, w_rank, u_ranks, time_major, dtype, packed, head_w, head_b, c10::nullopt,
+                          (int64_t)-100, c10::nullopt, c10::nullopt);
   return {out[0], out[1], out[2], out[3]};
 }
 
@@ -283,13 +311,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sequence_loss(const Tensor& x
                                                                  int64_t dtype, const c10::optional<Tensor>& packed, const Tensor& head_w,
                                                                  const c10::optional<Tensor>& head_b, const Tensor& target,
                                                                  int64_t ignore_index, const Tensor& unit, const Tensor& ticket) {
-  bool training = x.requires_grad() || (h0.has_value() && h0->requires_grad()) || (c0.has_value() && c0->requires_grad());
-  for (const auto& p : params) training = training || p.requires_grad();
-  training = training || head_w.requires_grad() || (head_b.has_value() && head_b->requires_grad());
-  training = training && at::GradMode::is_enabled();
-  auto out = SeqFn::apply(x, h0, c0, params, variant, g, w_rank, u_ranks.vec(), time_major, training, dtype, packed,
-                          c10::optional<Tensor>(head_w), head_b, c10::optional<Tensor>(target), ignore_index, c10::optional<Tensor>(unit),
-                          c10::optional<Tensor>(ticket));
+  auto out = run_sequence(x, h0, c0, params, variant, g, w_rank, u_ranks, time_major, dtype, packed, head_w, head_b, target, ignore_index,
+                          unit, ticket);
   return {out[0], out[1], out[2], out[3], out[4]};
 }
 
@@ -297,12 +320,11 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> sequence_loss(const Tensor& x
 // outputs: y of the top layer, hT and cT as (L, B, H) tensors, the logits of a classifier riding on the top layer (or an
 // empty tensor).  Initial states are zero (MyLSTM.forward).
 struct StackFn : public torch::autograd::Function<StackFn> {
+  // saved for the backward, in this order: x, y of every layer, reserve of every layer, params..., [head_w]
   static variable_list forward(AutogradContext* ctx, Tensor x, at::TensorList params_in, int64_t L, int64_t variant, int64_t w_rank,
                                std::vector<int64_t> u_ranks, int64_t g, bool time_major, bool training,
                                c10::optional<Tensor> head_w_o, c10::optional<Tensor> head_b_o) {
-    Tensor head_w = head_w_o.has_value() ? head_w_o->contiguous() : Tensor();
-    Tensor head_b = head_b_o.has_value() ? head_b_o->contiguous() : Tensor();
-    if (head_w.defined()) require_hip_f32(head_w, "head weight");
+    Tensor head_w = contiguous_or_undefined(head_w_o), head_b = contiguous_or_undefined(head_b_o);
     ctx->set_materialize_grads(false);
     require_hip_f32(x, "input");
     x = x.contiguous();
@@ -337,13 +359,8 @@ struct StackFn : public torch::autograd::Function<StackFn> {
       ly[l].y = ys[l].data_ptr<float>(), ly[l].hT = hT.data_ptr<float>() + l * B * H, ly[l].cT = cT.data_ptr<float>() + l * B * H;
       ly[l].reserve = training ? reserves[l].data_ptr() : nullptr;
     }
-    Tensor logits = head_w.defined() ? at::empty({B, head_w.size(0)}, x.options()) : at::empty({0}, x.options());
     vmlmf_head hd;
-    memset(&hd, 0, sizeof(hd));
-    if (head_w.defined()) {
-      TORCH_CHECK(head_w.dim() == 2 && head_w.size(1) == H, "vmlmf_amd: head weight must be (classes, hidden_size)");
-      hd.classes = (int)head_w.size(0), hd.weight = head_w.data_ptr<float>(), hd.bias = cptr(head_b), hd.logits = logits.data_ptr<float>();
-    }
+    Tensor logits = fill_head_forward(hd, head_w, head_b, B, H, x);
     check(vmlmf_stack_forward((int)L, ly.data(), x.data_ptr<float>(), head_w.defined() ? &hd : nullptr, ws.data_ptr(), wbytes,
                               stream_of(x)));
     if (training) {
@@ -355,6 +372,7 @@ struct StackFn : public torch::autograd::Function<StackFn> {
       ctx->save_for_backward(saved);
       ctx->saved_data["cfg"] = std::vector<int64_t>{L, variant, w_rank, g, time_major ? 1 : 0, B, T, I, H, (int64_t)nper};
       ctx->saved_data["ur"] = u_ranks;
+      ctx->saved_data["wbytes"] = (int64_t)wbytes;   // (the backward runs in the workspace the forward's query sized)
       ctx->saved_data["head"] = head_w.defined();
       ctx->saved_data["head_b"] = head_b.defined();
     }
@@ -377,22 +395,14 @@ struct StackFn : public torch::autograd::Function<StackFn> {
     Tensor dcT = gout[2].defined() ? gout[2].contiguous() : Tensor();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
     Tensor dx = ctx->needs_input_grad(0) ? at::empty_like(x) : Tensor();
-    int64_t total = 0;
-    for (const auto& p : params) total += p.numel();
-    const int64_t head_floats = dlogits.defined() ? head_w.size(0) * H + head_w.size(0) : 0;
-    // the parameter gradients of the whole stack AND of the classifier in one allocation (views are returned): one all-reduce
-    Tensor flat = at::empty({total + head_floats}, x.options());
     std::vector<Tensor> grads;
-    int64_t o = 0;
-    for (const auto& p : params) {
-      grads.push_back(flat.as_strided(p.sizes(), p.strides(), o));   // one op per view (narrow + view were two)
-      o += p.numel();
-    }
+    Tensor dW, db;
+    vmlmf_head hd;
+    Tensor flat = flat_grads(x, params, head_w, has_head_b, dlogits, grads, dW, db, hd);   // the whole stack's and the classifier's
     std::vector<vmlmf_stack_layer> ly(L);
     std::vector<vmlmf_params> ps(L);
     std::vector<vmlmf_grads> gs(L);
-    std::vector<size_t> rbytes(L);
-    size_t wbytes = 0;
+    const size_t wbytes = (size_t)ctx->saved_data["wbytes"].toInt();
     memset(ly.data(), 0, sizeof(vmlmf_stack_layer) * L);
     for (int64_t l = 0; l < L; ++l) {
       ly[l].desc = make_desc((int)variant, B, T, l == 0 ? I : H, H, w_rank, u_ranks, g, time_major, true, VMLMF_DT_F32);
@@ -406,18 +416,7 @@ struct StackFn : public torch::autograd::Function<StackFn> {
       ly[l].dhT = dhT.defined() ? dhT.data_ptr<float>() + l * B * H : nullptr;
       ly[l].dcT = dcT.defined() ? dcT.data_ptr<float>() + l * B * H : nullptr;
     }
-    check(vmlmf_stack_query((int)L, ly.data(), rbytes.data(), &wbytes));
     Tensor ws = workspace(x, wbytes);
-    Tensor dW, db;
-    vmlmf_head hd;
-    memset(&hd, 0, sizeof(hd));
-    if (dlogits.defined()) {   // classifier gradients: the tail of the stack's allocation
-      const int64_t C = head_w.size(0);
-      dW = flat.narrow(0, total, C * H).view({C, H});
-      if (has_head_b) db = flat.narrow(0, total + C * H, C);
-      hd.classes = (int)C, hd.weight = head_w.data_ptr<float>(), hd.dlogits = dlogits.data_ptr<float>();
-      hd.dweight = dW.data_ptr<float>(), hd.dbias = has_head_b ? db.data_ptr<float>() : nullptr;
-    }
     check(vmlmf_stack_backward((int)L, ly.data(), x.data_ptr<float>(), cptr(dy), mptr(dx), dlogits.defined() ? &hd : nullptr,
                                ws.data_ptr(), wbytes, stream_of(x)));
     variable_list out = {dx};
@@ -432,10 +431,7 @@ struct StackFn : public torch::autograd::Function<StackFn> {
 std::tuple<Tensor, Tensor, Tensor, Tensor> stack(const Tensor& x, at::TensorList params, int64_t L, int64_t variant, int64_t w_rank,
                                                  at::IntArrayRef u_ranks, int64_t g, bool time_major,
                                                  const c10::optional<Tensor>& head_w, const c10::optional<Tensor>& head_b) {
-  bool training = x.requires_grad();
-  for (const auto& p : params) training = training || p.requires_grad();
-  training = training || (head_w.has_value() && head_w->requires_grad()) || (head_b.has_value() && head_b->requires_grad());
-  training = training && at::GradMode::is_enabled();
+  const bool training = needs_tape(x, c10::nullopt, c10::nullopt, params, head_w, head_b);
   auto out = StackFn::apply(x, params, L, variant, w_rank, u_ranks.vec(), g, time_major, training, head_w, head_b);
   return {out[0], out[1], out[2], out[3]};
 }

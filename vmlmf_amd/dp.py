@@ -4,7 +4,7 @@ The reference has no distributed code.  Batch rows are ind
 whole forward/backward, so the only exchange is the sum over ranks of the parameter gradients.  The
 payload is tiny (HAR Net: 30 951 floats = 121 KiB), i.e. latency-bound on xGMI: bucketing would only add
 launches.  The kernels already write a layer's gradients AND those of the classifier riding on it into one flat
-allocation (functional.VmlmfSeqFn.backward), so the exchange is ONE in-place all-reduce on the compute stream,
+allocation (its layout is stated once: functional._flat_grads), so the exchange is ONE in-place all-reduce on the compute stream,
 with no staging copies (torch.distributed backend "nccl" == RCCL on ROCm; "gloo" in the CPU tests).
 
 Reduction op must reproduce single-process semantics:
@@ -170,8 +170,8 @@ class FlatGradAllReduce:
 
     @staticmethod
     def _spans(grads):
-        """Group gradient tensors by the allocation they live in.  The VMLMF layer (functional.VmlmfSeqFn) and
-        the classifier head hand autograd views of ONE flat buffer each, so a group usually tiles a contiguous
+        """Group gradient tensors by the allocation they live in.  The VMLMF layer or stack (layout: functional._flat_grads)
+        and the classifier head hand autograd views of ONE flat buffer each, so a group usually tiles a contiguous
         range that can be reduced in place; a gradient alone in its allocation goes through the staging buffer with
         the other loners (one collective for all of them).  Returns [(flat_view_or_None, [grads])]."""
         groups = {}

@@ -74,15 +74,38 @@ def _hidden_size(variant, params):
     return params[1].shape[-1]                 # dia_h (1, H)
 
 
-# (variant, g, w_rank, u_ranks, time_major, dtype, B, T, I, H, training) -> (Desc, Sizes): host-side descriptor cache
+def _layer_cfg(variant, g, w_rank, u_ranks, time_major, dtype):
+    """The configuration of a layer call as the 6-tuple (variant, g, w_rank, u_ranks, time_major, dtype) that the autograd classes
+    take and every host cache below keys on."""
+    ur = tuple(u_ranks) if isinstance(u_ranks, (list, tuple)) else (int(u_ranks),)
+    return (variant, g, int(w_rank), ur, bool(time_major), _lib.DTYPES[dtype] if isinstance(dtype, str) else int(dtype))
+
+
+def _tbi(x, time_major):
+    """(T, B, I) of a layer's input."""
+    return (x.shape[0], x.shape[1], x.shape[2]) if time_major else (x.shape[1], x.shape[0], x.shape[2])
+
+
+def _needs_tape(x, params, h0=None, c0=None, head=None):
+    """Will this call run in training mode (tape kept, reserve buffer allocated)?  Asked of exactly the tensors that reach
+    Function.apply as differentiable inputs - input, parameters, initial states, the classifier's weight and bias - so it is what
+    any(ctx.needs_input_grad) says inside VmlmfSeqFn / VmlmfStackFn.forward (False under torch.no_grad(): inference kernels)."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, h0, c0, *params, *(head or ())))
+
+
+# The host caches (_DESC_CACHE, _STACK_CACHE, PackCache) all carry the library's switch generation (vmlmf_tune_generation) in their
+# keys: whoever flips a switch - _lib.tune(), a raw vmlmf_tune call, the library itself after a riding worker gave up - is seen
+# by the next lookup.
+# cfg + (B, T, I, H, training, generation) -> (Desc, Sizes): host-side descriptor cache
 _DESC_CACHE = {}
-# one grow-only scratch buffer per device: workspace contents never outlive the call that fills them and all
-# calls on a device are serialised on the current stream
+# grow-only scratch buffers, one per (kind, device, stream): the contents never outlive the call that fills them and all calls
+# on a stream are serialised.  Kinds stay distinct objects ("layer": workspaces; "embed"; "sample": the two may be live in one
+# captured region)
 _WORKSPACE = {}
 
 
 def _desc_for(cfg, B, T, I, H, training):
-    key = cfg + (B, T, I, H, training)
+    key = cfg + (B, T, I, H, training, _lib.lib().vmlmf_tune_generation())
     hit = _DESC_CACHE.get(key)
     if hit is None:
         variant, g, w_rank, u_ranks, time_major, dtype = cfg
@@ -92,15 +115,55 @@ def _desc_for(cfg, B, T, I, H, training):
     return hit
 
 
-def _workspace(dev, nbytes):
+def _workspace(dev, nbytes, kind="layer"):
     if torch.cuda.is_current_stream_capturing():
         return torch.empty(nbytes, device=dev, dtype=torch.uint8)      # graph-private pool
-    key = (dev.index, _lib.raw_stream(dev).value)
+    key = (kind, dev.index, _lib.raw_stream(dev).value)
     buf = _WORKSPACE.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        _WORKSPACE[key] = buf
+        buf = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
     return buf
+
+
+def _head_forward(head_w, head_b, B, dev):
+    """A classifier riding on a launch's final hidden state (Net.lin), forward side: (weight, bias, logits, _lib.Head) with weight
+    and bias contiguous and the (B, C) logits allocated - or (None, None, an empty tensor, None) without a classifier."""
+    if head_w is None:
+        return None, None, torch.empty((0,), device=dev, dtype=torch.float32), None
+    hw = head_w.contiguous()
+    hb = None if head_b is None else head_b.contiguous()
+    _require_hip(hw, "head weight")
+    logits = torch.empty((B, hw.shape[0]), device=dev, dtype=torch.float32)
+    hd = _lib.Head()
+    hd.classes, hd.weight, hd.logits = hw.shape[0], hw.data_ptr(), logits.data_ptr()
+    hd.bias = None if hb is None else hb.data_ptr()
+    return hw, hb, logits, hd
+
+
+def _flat_grads(params, hw, has_head_b, dlogits):
+    """The gradient buffer of a layer or stack backward: (flat, grads, dW, db, _lib.Head or None).
+
+    THE LAYOUT CONTRACT (vmlmf_amd/dp.py reduces `flat` in place; csrc/torch_binding.cpp: flat_grads lays out the same bytes):
+    ONE fp32 allocation holds the gradients of `params` in call order, each dense in its parameter's shape, followed - whenever
+    the classifier takes part, i.e. there is a head weight `hw` AND a gradient `dlogits` (contiguous) for its logits - by
+    dW (C, H), then db (C).  The tail is C * H + C floats with or without a bias; db is a view of it only with one.  grads, dW
+    and db are views, so one all-reduce of `flat` exchanges everything the launch produced."""
+    total = sum(p.numel() for p in params)
+    use_head = hw is not None and dlogits is not None
+    flat = torch.empty(total + (hw.numel() + hw.shape[0] if use_head else 0), device=params[0].device, dtype=torch.float32)
+    grads, o = [], 0
+    for p in params:
+        grads.append(flat[o:o + p.numel()].view(p.shape))
+        o += p.numel()
+    if not use_head:
+        return flat, tuple(grads), None, None, None
+    C, H = hw.shape
+    dW = flat[total:total + C * H].view(C, H)
+    db = flat[total + C * H:] if has_head_b else None
+    hd = _lib.Head()
+    hd.classes, hd.weight, hd.dlogits, hd.dweight = C, hw.data_ptr(), dlogits.data_ptr(), dW.data_ptr()
+    hd.dbias = None if db is None else db.data_ptr()
+    return flat, tuple(grads), dW, db, hd
 
 
 class PackCache:
@@ -215,12 +278,9 @@ class VmlmfSeqFn(torch.autograd.Function):
             _require_hip(p, "parameter")
         x = x.contiguous()
         params = tuple(p.contiguous() for p in params)
-        if time_major:
-            T, B, I = x.shape
-        else:
-            B, T, I = x.shape
+        T, B, I = _tbi(x, time_major)
         H = _hidden_size(variant, params)
-        training = bool(any(ctx.needs_input_grad))   # False under torch.no_grad(): inference kernels
+        training = bool(any(ctx.needs_input_grad))   # (what _needs_tape says of this call's tensors)
         ctx.packed = packed                           # kept parameter images (PackCache) or None
         desc, sizes = _desc_for(cfg, B, T, I, H, training)
         dev = x.device
@@ -233,18 +293,10 @@ class VmlmfSeqFn(torch.autograd.Function):
         c0c = None if c0 is None else c0.contiguous()
         ps = _params_struct(params, g, variant)
         stream = _lib.raw_stream(dev)
-        # a classifier riding on the final hidden state (Net.lin): its logits are the 4th output
-        hw = None if head_w is None else head_w.contiguous()
-        hb = None if head_b is None else head_b.contiguous()
-        logits = torch.empty((B, hw.shape[0]) if hw is not None else (0,), device=dev, dtype=torch.float32)
-        hd = _lib.Head()
-        if hw is not None:
-            _require_hip(hw, "head weight")
-            hd.classes, hd.weight, hd.logits = hw.shape[0], hw.data_ptr(), logits.data_ptr()
-            hd.bias = None if hb is None else hb.data_ptr()
+        hw, hb, logits, hd = _head_forward(head_w, head_b, B, dev)   # the riding classifier's logits are the 4th output
         ex = _lib.Extra()
         ex.packed = None if packed is None else packed.data_ptr()
-        ex.head = ctypes.pointer(hd) if hw is not None else None
+        ex.head = ctypes.pointer(hd) if hd is not None else None
         # the criterion on those logits: loss | nvalid | lse[B] in one allocation, the unit gradient of the logits beside it
         stats = dz_unit = None
         ce = _lib.Ce()
@@ -298,8 +350,7 @@ class VmlmfSeqFn(torch.autograd.Function):
         if dz is not None and dloss is not None:
             # the criterion's share of d(logits): what the forward launch wrote for d(loss) = 1 - as it is when the incoming
             # gradient IS the package's constant one (vmlmf_amd.unit_gradient), scaled otherwise
-            unit = _UNIT.get(dz.device)
-            if not (unit is not None and dloss.data_ptr() == unit.data_ptr()):
+            if not _is_unit(dloss):
                 dz = dz * dloss
             dlogits = dz if dlogits is None else dlogits + dz
         snap = rest.pop(0) if ctx.drop is not None else None
@@ -308,39 +359,20 @@ class VmlmfSeqFn(torch.autograd.Function):
         dy = None if dy is None else dy.contiguous()
         dhT = None if dhT is None else dhT.contiguous()
         dcT = None if dcT is None else dcT.contiguous()
+        dlogits = None if dlogits is None else dlogits.contiguous()
         need_dx = ctx.needs_input_grad[2]   # (cfg, packed, x, h0, c0, head_w, head_b, target, ignore_index, drop, *params)
         dx = torch.empty_like(x) if need_dx else None
         B, H = y.shape[1 if time_major else 0], y.shape[2]
         dh0 = torch.empty((B, H), device=dev, dtype=torch.float32) if ctx.has_h0 else None
         dc0 = torch.empty((B, H), device=dev, dtype=torch.float32) if ctx.has_c0 else None
-        # one flat buffer for all parameter gradients (views are returned): a single allocation, and the
-        # gradients of a layer are contiguous for the data-parallel all-reduce
-        # (the classifier's weight and bias gradients are the tail of the same allocation: ONE flat buffer, ONE all-reduce per
-        # step)
-        use_head = hw is not None and dlogits is not None
-        total = sum(p.numel() for p in params)
-        flat = torch.empty(total + ((hw.shape[0] * H + hw.shape[0]) if use_head else 0), device=dev, dtype=torch.float32)
-        grads, o = [], 0
-        for p in params:
-            grads.append(flat[o:o + p.numel()].view(p.shape))
-            o += p.numel()
-        grads = tuple(grads)
+        flat, grads, dW, db, hd = _flat_grads(params, hw, ctx.has_head_b, dlogits)
         ws = _workspace(dev, sizes.workspace_bytes)
         ps = _params_struct(params, g, variant)
         gs = _params_struct(grads, g, variant)
         stream = _lib.raw_stream(dev)
-        dW = db = None
-        hd = _lib.Head()
-        if use_head:
-            dl = dlogits.contiguous()
-            C = hw.shape[0]
-            dW = flat[total:total + C * H].view(C, H)
-            db = flat[total + C * H:] if ctx.has_head_b else None
-            hd.classes, hd.weight, hd.dlogits, hd.dweight = C, hw.data_ptr(), dl.data_ptr(), dW.data_ptr()
-            hd.dbias = None if db is None else db.data_ptr()
         ex = _lib.Extra()
         ex.packed = None if ctx.packed is None else ctx.packed.data_ptr()
-        ex.head = ctypes.pointer(hd) if use_head else None
+        ex.head = ctypes.pointer(hd) if hd is not None else None
         if snap is not None:   # dy is the gradient of the dropped copy: the launch regenerates the forward's factors
             dr = _lib.Dropout(ctx.drop[0], ctx.drop[1], snap.data_ptr(), None)
             ex.drop = ctypes.pointer(dr)
@@ -366,41 +398,30 @@ def vmlmf_sequence(variant, x, h0, c0, params, w_rank, u_ranks, g=1, time_major=
     default arguments, train.py:58-65) comes back as a fifth element, formed inside the same forward launch.
     drop: (p, snapshot, site) - nn.Dropout(p) behind the layer (vmlmf_lm.py:438-439) without a mask tensor: the returned y is the
     dropped activation; inside the layer's own launches where the library takes it (vmlmf_dropout_fused: the row-block kernels,
-    time-major), one launch of the package's otherwise (dropout()).
+    time-major), one launch of the package's otherwise (dropout()).  Not together with a head.
     """
-    dt = _lib.DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
-    if drop is not None and head is None and x.is_cuda:
-        ur_ = tuple(u_ranks) if isinstance(u_ranks, (list, tuple)) else (int(u_ranks),)
-        cfg = (variant, g, int(w_rank), ur_, bool(time_major), dt)
-        T, B = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
-        training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-        desc, _ = _desc_for(cfg, B, T, x.shape[2], _hidden_size(variant, params), training)
+    cfg = _layer_cfg(variant, g, w_rank, u_ranks, time_major, dtype)
+    hw, hb = (None, None) if head is None else head
+    if drop is not None and head is not None:
+        raise RuntimeError("vmlmf_amd: dropout behind a layer and a classifier riding on it do not combine")
+    if x.is_cuda and (drop is not None or pack_cache is not None):
+        (T, B, I), H = _tbi(x, cfg[4]), _hidden_size(variant, params)
+    if drop is not None and x.is_cuda:      # in-launch dropout: the ctypes class, where the library takes it
+        desc, _ = _desc_for(cfg, B, T, I, H, _needs_tape(x, params, h0, c0))
         if _lib.lib().vmlmf_dropout_fused(ctypes.byref(desc)) == 1:
             return VmlmfSeqFn.apply(cfg, None, x, h0, c0, None, None, None, ignore_index, tuple(drop), *params)[:3]
-    if drop is not None:
-        y, hT, cT = vmlmf_sequence(variant, x, h0, c0, params, w_rank, u_ranks, g=g, time_major=time_major, dtype=dtype,
-                                   pack_cache=pack_cache)
-        return dropout(y, drop[0], drop[1], drop[2]), hT, cT
-    packed = None
-    if pack_cache is not None and x.is_cuda:
-        T, B = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
-        cfg0 = (variant, g, int(w_rank), tuple(u_ranks) if isinstance(u_ranks, (list, tuple)) else (int(u_ranks),), bool(time_major), dt)
-        packed = pack_cache.get(cfg0, params, x, B, T, x.shape[2], _hidden_size(variant, params))
-    ur = tuple(u_ranks) if isinstance(u_ranks, (list, tuple)) else (int(u_ranks),)
+    packed = pack_cache.get(cfg, params, x, B, T, I, H) if pack_cache is not None and x.is_cuda else None
     ops = torch_ops()
-    if ops is not None:
-        if target is not None:
-            return ops.sequence_loss(x, h0, c0, list(params), variant, g, int(w_rank), list(ur), bool(time_major), dt, packed,
-                                     head[0], head[1], target, int(ignore_index), unit_gradient(x.device), ce_ticket(x.device))
-        out = ops.sequence(x, h0, c0, list(params), variant, g, int(w_rank), list(ur), bool(time_major), dt, packed,
-                           None if head is None else head[0], None if head is None else head[1])
-        return out if head is not None else out[:3]
-    cfg = (variant, g, int(w_rank), ur, bool(time_major), dt)
-    out = VmlmfSeqFn.apply(cfg, packed, x, h0, c0, None if head is None else head[0], None if head is None else head[1],
-                           target, ignore_index, None, *params)
-    if target is not None:
-        return out
-    return out[:4] if head is not None else out[:3]
+    if ops is None:
+        out = VmlmfSeqFn.apply(cfg, packed, x, h0, c0, hw, hb, target, ignore_index, None, *params)
+    elif target is not None:
+        out = ops.sequence_loss(x, h0, c0, list(params), variant, g, cfg[2], list(cfg[3]), cfg[4], cfg[5], packed, hw, hb, target,
+                                int(ignore_index), unit_gradient(x.device), ce_ticket(x.device))
+    else:
+        out = ops.sequence(x, h0, c0, list(params), variant, g, cfg[2], list(cfg[3]), cfg[4], cfg[5], packed, hw, hb)
+    if drop is not None:                    # ... and as one launch of the package's behind the layer otherwise
+        return dropout(out[0], drop[0], drop[1], drop[2]), out[1], out[2]
+    return out[:3 if head is None else 4 if target is None else 5]
 
 
 # ---- stacked layers: one wavefront launch per direction (C ABI 7: vmlmf_stack_*) ----------------------------------------
@@ -462,12 +483,9 @@ class VmlmfStackFn(torch.autograd.Function):
         x = x.contiguous()
         params = tuple(p.contiguous() for p in params)
         nper = len(params) // L
-        if time_major:
-            T, B, I = x.shape
-        else:
-            B, T, I = x.shape
+        T, B, I = _tbi(x, time_major)
         Hs = tuple(_hidden_size(variant, params[l * nper:(l + 1) * nper]) for l in range(L))
-        training = bool(any(ctx.needs_input_grad))
+        training = bool(any(ctx.needs_input_grad))   # (what _needs_tape said when vmlmf_stack looked the plan up)
         plan = _stack_plan(cfg, L, B, T, I, Hs, training)
         if plan is None:
             raise RuntimeError("vmlmf_amd: this stack is not covered by the wavefront kernels (vmlmf_stack_supported)")
@@ -498,18 +516,10 @@ class VmlmfStackFn(torch.autograd.Function):
             ly.reserve = None if reserves[l] is None else reserves[l].data_ptr()
             ly.h0 = None if h0c is None else h0c[l].data_ptr()
             ly.c0 = None if c0c is None else c0c[l].data_ptr()
-        # a classifier riding on the top layer's final hidden state (Net.lin): its logits are the last output
-        hw = None if head_w is None else head_w.contiguous()
-        hb = None if head_b is None else head_b.contiguous()
-        logits = torch.empty((B, hw.shape[0]) if hw is not None else (0,), device=dev, dtype=torch.float32)
-        hd = _lib.Head()
-        if hw is not None:
-            _require_hip(hw, "head weight")
-            hd.classes, hd.weight, hd.logits = hw.shape[0], hw.data_ptr(), logits.data_ptr()
-            hd.bias = None if hb is None else hb.data_ptr()
+        hw, hb, logits, hd = _head_forward(head_w, head_b, B, dev)   # riding on the top layer: its logits are the last output
         with _lib.on_device(dev):
             _lib.check(_lib.lib().vmlmf_stack_forward(L, ctypes.addressof(layers), x.data_ptr(),
-                                                      ctypes.addressof(hd) if hw is not None else None, ws.data_ptr(), wbytes,
+                                                      None if hd is None else ctypes.addressof(hd), ws.data_ptr(), wbytes,
                                                       _lib.raw_stream(dev)))
         if training:
             ctx.cfg, ctx.L, ctx.nper, ctx.plan = cfg, L, nper, plan
@@ -539,21 +549,14 @@ class VmlmfStackFn(torch.autograd.Function):
         c0 = params.pop() if ctx.has_c0 else None
         h0 = params.pop() if ctx.has_h0 else None
         hw = params.pop() if ctx.has_head else None
-        dlogits = dstates[2 * L]
+        dlogits = None if dstates[2 * L] is None else dstates[2 * L].contiguous()
         dev = x.device
         dy = None if dy is None else dy.contiguous()
         dhT = [None if d is None else d.contiguous() for d in dstates[:L]]
         dcT = [None if d is None else d.contiguous() for d in dstates[L:2 * L]]
         need_dx = ctx.needs_input_grad[2]
         dx = torch.empty_like(x) if need_dx else None
-        # one flat buffer for the parameter gradients of the whole stack and of the classifier (views are returned)
-        use_head = hw is not None and dlogits is not None
-        total = sum(p.numel() for p in params)
-        flat = torch.empty(total + ((hw.shape[0] * hw.shape[1] + hw.shape[0]) if use_head else 0), device=dev, dtype=torch.float32)
-        grads, o = [], 0
-        for p in params:
-            grads.append(flat[o:o + p.numel()].view(p.shape))
-            o += p.numel()
+        flat, grads, dW, db, hd = _flat_grads(params, hw, ctx.has_head_b, dlogits)   # the whole stack's and the classifier's
         ws = _workspace(dev, wbytes)
         B, H = ys[0].shape[1 if time_major else 0], ys[0].shape[2]
         dh0 = torch.empty((L, B, H), device=dev, dtype=torch.float32) if ctx.has_h0 else None
@@ -577,20 +580,11 @@ class VmlmfStackFn(torch.autograd.Function):
             ly.dc0 = None if dc0 is None else dc0[l].data_ptr()
             ly.dhT = None if dhT[l] is None else dhT[l].data_ptr()
             ly.dcT = None if dcT[l] is None else dcT[l].data_ptr()
-        dW = db = None
-        hd = _lib.Head()
-        if use_head:
-            dl = dlogits.contiguous()
-            C, H = hw.shape
-            dW = flat[total:total + C * H].view(C, H)
-            db = flat[total + C * H:] if ctx.has_head_b else None
-            hd.classes, hd.weight, hd.dlogits, hd.dweight = C, hw.data_ptr(), dl.data_ptr(), dW.data_ptr()
-            hd.dbias = None if db is None else db.data_ptr()
         with _lib.on_device(dev):
             _lib.check(_lib.lib().vmlmf_stack_backward(L, ctypes.addressof(layers), x.data_ptr(), _ptr(dy), _ptr(dx),
-                                                       ctypes.addressof(hd) if use_head else None, ws.data_ptr(), wbytes,
+                                                       None if hd is None else ctypes.addressof(hd), ws.data_ptr(), wbytes,
                                                        _lib.raw_stream(dev)))
-        return (None, None, dx, dW, db, dh0, dc0, None) + tuple(grads)
+        return (None, None, dx, dW, db, dh0, dc0, None) + grads
 
 
 def stack_mode():
@@ -613,39 +607,35 @@ def vmlmf_stack(variant, x, layer_params, w_rank, u_ranks, g=1, time_major=False
     L = len(layer_params)
     if mode == "0" or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
         return None
-    dt = _lib.DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
-    ur = tuple(u_ranks) if isinstance(u_ranks, (list, tuple)) else (int(u_ranks),)
-    cfg = (variant, g, int(w_rank), ur, bool(time_major), dt)
-    T, B = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
+    cfg = _layer_cfg(variant, g, w_rank, u_ranks, time_major, dtype)
+    T, B, I = _tbi(x, cfg[4])
     Hs = tuple(_hidden_size(variant, ps) for ps in layer_params)
     H = Hs[0]
     if len(set(Hs)) > 1:
         if h0 is not None or c0 is not None or drops is not None:
             return None     # (carried states / dropout: the LM's stacks, whose layers are alike)
         H = Hs
-    xwave = x.shape[2] <= 16 and Hs[0] <= 192 and g == 1       # (vg_xwave_ok of the C side: <= 3 waves of units, one group)
+    xwave = I <= 16 and Hs[0] <= 192 and g == 1       # (vg_xwave_ok of the C side: <= 3 waves of units, one group)
     if mode != "1" and L == 1 and (xwave or T > 96):
         return None          # (a single layer with a narrow input already forms its x side inside the recurrent kernel; with a wide
                              #  one the x-team's per-step cost overtakes the two launches it saves at T ~ 128:
                              #  profiles/r02_stack_vs_chained_over_T.txt)
     # (the classifier's weight and bias count: with a frozen RNN under a trainable head the launch runs in training mode, and the
     #  coverage check must be made for that mode - otherwise an uncovered stack raised instead of falling back to chained layers)
-    training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for ps in layer_params for p in ps)
-                                            or (h0 is not None and h0.requires_grad) or (c0 is not None and c0.requires_grad)
-                                            or (head is not None and any(t is not None and t.requires_grad for t in head)))
-    if _stack_plan(cfg, L, B, T, x.shape[2], H, training) is None:
+    flat = [p for ps in layer_params for p in ps]
+    training = _needs_tape(x, flat, h0, c0, head)
+    if _stack_plan(cfg, L, B, T, I, H, training) is None:
         return None
     if drops is not None and any(d is not None for d in drops):
         # drops: per layer None / (p, snapshot, site) - only the clustered form applies dropout inside its launches
-        if not stack_takes_dropout(cfg, L, B, T, x.shape[2], H, training):
+        if not stack_takes_dropout(cfg, L, B, T, I, H, training):
             return None
     else:
         drops = None
-    flat = [p for ps in layer_params for p in ps]
     hw, hb = (None, None) if head is None else head
     ops = torch_ops()
-    if ops is not None and h0 is None and c0 is None and dt == _lib.DT_F32 and drops is None and len(set(Hs)) == 1:      # (initial states, the bf16 tape, dropout, unequal sizes: the ctypes form below)
-        y, hT, cT, logits = ops.stack(x, flat, L, variant, int(w_rank), list(ur), int(g), bool(time_major), hw, hb)
+    if ops is not None and h0 is None and c0 is None and cfg[5] == _lib.DT_F32 and drops is None and len(set(Hs)) == 1:      # (initial states, the bf16 tape, dropout, unequal sizes: the ctypes form below)
+        y, hT, cT, logits = ops.stack(x, flat, L, variant, cfg[2], list(cfg[3]), int(g), cfg[4], hw, hb)
         out = (y, list(hT.unbind(0)), list(cT.unbind(0)))
         return out + (logits,) if head is not None else out
     res = VmlmfStackFn.apply(cfg, L, x, hw, hb, h0, c0, drops, *flat)
@@ -727,6 +717,12 @@ def head_linear(h, weight, bias):
 _UNIT = {}
 
 
+def _is_unit(dloss):
+    """Is this incoming gradient the package's constant one (unit_gradient) - the very tensor, not an equal value?"""
+    unit = _UNIT.get(dloss.device)
+    return unit is not None and dloss.data_ptr() == unit.data_ptr()
+
+
 def unit_gradient(device):
     """The constant 1.0 as a 0-d fp32 tensor on `device`, one object per device, never written.  `loss.backward()` makes
     autograd fill a fresh ones_like(loss) in every step; `loss.backward(vmlmf_amd.unit_gradient(loss.device))` is the
@@ -768,8 +764,7 @@ class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss):
         logits, target, stats = ctx.saved_tensors[:3]
-        unit = _UNIT.get(logits.device)
-        if unit is not None and dloss.data_ptr() == unit.data_ptr() and len(ctx.saved_tensors) == 4:
+        if _is_unit(dloss) and len(ctx.saved_tensors) == 4:
             # d(loss) is the package's constant one: forward wrote this.  Logits produced by another node (the classifier
             # head) just pass it on.  When the logits are a LEAF, AccumulateGrad adopts what it is handed as .grad (views
             # included), and in-place work on that gradient (zero_grad(set_to_none=False), clip_grad_norm_, a further
@@ -1064,8 +1059,7 @@ class LmHeadLossFn(torch.autograd.Function):
     def backward(ctx, dloss):
         h2, w, dz = ctx.saved_tensors[:3]
         dbias = ctx.saved_tensors[3] if ctx.has_b else None
-        unit = _UNIT.get(dz.device)
-        scaled = not (unit is not None and dloss.data_ptr() == unit.data_ptr())
+        scaled = not _is_unit(dloss)
         dh = _run_form(ctx.forms["dh"], dz, w) if ctx.needs_input_grad[0] else None
         dw = _run_form(ctx.forms["dw"], dz, h2) if ctx.needs_input_grad[1] else None
         db = dbias if (ctx.has_b and ctx.needs_input_grad[2]) else None
@@ -1107,13 +1101,7 @@ class EmbedFn(torch.autograd.Function):
         dw = torch.empty((V, H), device=dy.device, dtype=torch.float32)
         lib = _lib.lib()
         nbytes = lib.vmlmf_embed_backward_scratch_bytes(R, V)
-        if torch.cuda.is_current_stream_capturing():
-            scratch = torch.empty(nbytes, device=dy.device, dtype=torch.uint8)
-        else:
-            key = ("embed", dy.device.index, _lib.raw_stream(dy.device).value)
-            scratch = _WORKSPACE.get(key)
-            if scratch is None or scratch.numel() < nbytes:
-                scratch = _WORKSPACE[key] = torch.empty(nbytes, device=dy.device, dtype=torch.uint8)
+        scratch = _workspace(dy.device, nbytes, "embed")
         with _lib.on_device(dy.device):
             _lib.check(lib.vmlmf_embed_backward(R, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), scratch.data_ptr(), nbytes,
                                                 _lib.raw_stream(dy.device)))
@@ -1216,21 +1204,11 @@ class EmbedDropFn(torch.autograd.Function):
         dw = torch.empty((V, H), device=dy.device, dtype=torch.float32)
         lib = _lib.lib()
         nbytes = lib.vmlmf_embed_backward_scratch_bytes(R, V)
-        scratch = _embed_scratch(dy.device, nbytes)
+        scratch = _workspace(dy.device, nbytes, "embed")
         with _lib.on_device(dy.device):
             _lib.check(lib.vmlmf_embed_dropout_backward(R, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), scratch.data_ptr(), nbytes, ctx.p,
                                                         snap.data_ptr(), ctx.site, _lib.raw_stream(dy.device)))
         return dw, None, None, None, None
-
-
-def _embed_scratch(dev, nbytes):
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    key = ("embed", dev.index, _lib.raw_stream(dev).value)
-    scratch = _WORKSPACE.get(key)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return scratch
 
 
 def _embed_covered(weight, tokens):
@@ -1250,8 +1228,7 @@ def embedding_dropout(weight, tokens, p, snap, site=0):
 
 def embedding(weight, tokens):
     """weight[tokens] with the package's backward on HIP fp32 tables up to 1024 wide and 64 MB of position bits; the stock op otherwise."""
-    if (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 2 and weight.shape[1] <= 1024 and tokens.dtype == torch.int64
-            and weight.is_contiguous() and weight.shape[0] * ((tokens.numel() + 31) // 32) * 4 <= (64 << 20)):
+    if _embed_covered(weight, tokens):
         return EmbedFn.apply(weight, tokens)
     return weight[tokens]
 
@@ -1269,13 +1246,7 @@ def linear_nll(h, weight, bias, y, chunk_rows=2048, fused=None):
 
 # ---- decoding the LM: head + token choice in one launch per token (C ABI: vmlmf_lm_sample; csrc/vmlmf_sample.hip) ---------------
 def _sample_workspace(dev, nbytes):
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty(nbytes, device=dev, dtype=torch.uint8)      # graph-private pool
-    key = ("sample", dev.index, _lib.raw_stream(dev).value)
-    buf = _WORKSPACE.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _WORKSPACE[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    return buf
+    return _workspace(dev, nbytes, "sample")
 
 
 SAMPLE_FUSED_MAX_ROWS = 4   # measured at the PTB size: fused 25.6 us against 37.2 at 1 row, 40.5 against 37.8 at 8 (lm_sampling.md)
