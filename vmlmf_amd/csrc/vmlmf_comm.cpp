@@ -15,7 +15,7 @@
 
 #include "../../include/vmlmf_hip.h"
 
-int vmlmf_set_error(int code, const std::string& msg);   // vmlmf_api.hip
+int vmlmf_set_error(int code, const std::string& msg);   // vmlmf_state.hip
 
 namespace {
 

@@ -1,0 +1,195 @@
+// The thin entry points of the C ABI: argument checks and one launch each (head, criterion, embedding, dropout, sampler, transpose).
+#include "vmlmf_host.h"
+
+using namespace vmlmf_host;
+
+extern "C" {
+
+int vmlmf_head_forward(int B, int H, int C, const float* h, long long ldh, const float* weight,
+                       const float* bias, float* logits, void* stream) {
+  if (B < 1 || H < 1 || C < 1 || ldh < H) return fail(VMLMF_E_BADARG, "head: B, H, C must be >= 1 and ldh >= H");
+  if (C > head_max_classes()) return fail(VMLMF_E_UNSUPPORTED, "head: more than 32 classes");
+  if (h == nullptr || weight == nullptr || logits == nullptr) return fail(VMLMF_E_BADARG, "head: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(SL_HEAD_FWD, s);
+  return hip_tail((int)launch_head_fwd(B, H, C, h, ldh, weight, bias, logits, s));
+}
+
+int vmlmf_head_backward(int B, int H, int C, const float* h, long long ldh, const float* weight,
+                        const float* dlogits, float* dh, float* dweight, float* dbias, void* stream) {
+  if (B < 1 || H < 1 || C < 1 || ldh < H) return fail(VMLMF_E_BADARG, "head: B, H, C must be >= 1 and ldh >= H");
+  if (C > head_max_classes()) return fail(VMLMF_E_UNSUPPORTED, "head: more than 32 classes");
+  if (h == nullptr || weight == nullptr || dlogits == nullptr) return fail(VMLMF_E_BADARG, "head: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(SL_HEAD_BWD, s);
+  return hip_tail((int)launch_head_bwd(B, H, C, h, ldh, weight, dlogits, dh, dweight, dbias, s));
+}
+
+int vmlmf_ce_forward(int B, int C, const float* logits, const int64_t* target, int64_t ignore_index, float* loss,
+                     float* lse, float* nvalid, float* dlogits_unit, void* stream) {
+  if (B < 1 || C < 1) return fail(VMLMF_E_BADARG, "ce: B and C must be >= 1");
+  if (!logits || !target || !loss || !lse || !nvalid) return fail(VMLMF_E_BADARG, "ce: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(SL_CE_FWD, s);
+  return hip_tail((int)launch_ce_fwd(B, C, logits, (const long long*)target, (long long)ignore_index, loss, lse, nvalid, dlogits_unit, s));
+}
+
+int vmlmf_ce_backward(int B, int C, const float* logits, const int64_t* target, int64_t ignore_index,
+                      const float* lse, const float* nvalid, const float* dloss, float* dlogits, void* stream) {
+  if (B < 1 || C < 1) return fail(VMLMF_E_BADARG, "ce: B and C must be >= 1");
+  if (!logits || !target || !lse || !nvalid || !dloss || !dlogits) return fail(VMLMF_E_BADARG, "ce: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  Scope sc(SL_CE_BWD, s);
+  return hip_tail((int)launch_ce_bwd(B, C, logits, (const long long*)target, (long long)ignore_index, lse, nvalid, dloss, dlogits, s));
+}
+
+int vmlmf_nll_forward(int R, int V, const float* scores, const int64_t* y, float scale, float* loss, float* lse,
+                      float* rowloss, void* stream) {
+  if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "nll: R and V must be >= 1");
+  if (!scores || !y || !loss || !lse || !rowloss) return fail(VMLMF_E_BADARG, "nll: null pointer");
+  return hip_tail((int)launch_nll_fwd(R, V, scores, (const long long*)y, scale, loss, lse, rowloss, (hipStream_t)stream));
+}
+
+int vmlmf_nll_backward(int R, int V, const float* scores, const int64_t* y, float scale, const float* lse,
+                       const float* dloss, float* dscores, void* stream) {
+  if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "nll: R and V must be >= 1");
+  if (!scores || !y || !lse || !dloss || !dscores) return fail(VMLMF_E_BADARG, "nll: null pointer");
+  return hip_tail((int)launch_nll_bwd(R, V, scores, (const long long*)y, scale, lse, dloss, dscores, (hipStream_t)stream));
+}
+
+size_t vmlmf_nll_grad_scratch_floats(int R, int V) { return (size_t)nll_grad_workgroups(R < 1 ? 1 : R) * (size_t)(V < 1 ? 1 : V); }
+
+int vmlmf_nll_forward_grad(int R, int V, float* scores, const float* bias, const int64_t* y, float scale, float* loss,
+                           float* rowloss, float* dbias, float* scratch, void* stream) {
+  if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "nll: R and V must be >= 1");
+  if (!scores || !y || !loss || !rowloss || !scratch) return fail(VMLMF_E_BADARG, "nll: null pointer");
+  const int rc = launch_nll_fwd_grad(R, V, scores, bias, (const long long*)y, scale, loss, rowloss, dbias, scratch, (hipStream_t)stream);
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "nll_forward_grad: rows must be 16-byte aligned, a multiple of four and at most 12288 wide");
+  return hip_tail(rc);
+}
+
+size_t vmlmf_embed_backward_scratch_bytes(int R, int V) { return embed_bwd_scratch_bytes(R < 1 ? 1 : R, V < 1 ? 1 : V); }
+
+int vmlmf_embed_backward(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, void* scratch,
+                         size_t scratch_bytes, void* stream) {
+  if (R < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R, H, V must be >= 1");
+  if (!tokens || !dy || !dweight) return fail(VMLMF_E_BADARG, "embed: null pointer");
+  const int rc = launch_embed_bwd(R, H, V, (const long long*)tokens, dy, dweight, scratch, scratch_bytes, (hipStream_t)stream);
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "embed_backward: embedding width > 1024");
+  if (rc == -4) return fail(VMLMF_E_WORKSPACE, "embed_backward: scratch smaller than vmlmf_embed_backward_scratch_bytes()");
+  return hip_tail(rc);
+}
+
+// ---- dropout of the LM network (ABI 11; vmlmf_dropout.h) ----
+int vmlmf_dropout_fused(const vmlmf_desc* d) {
+  VGeo g;
+  RbGeo q;
+  if (make_geo(d, &g, &q) != 0) return 0;
+  return drop_fused(g) ? 1 : 0;
+}
+
+int vmlmf_dropout_advance(int64_t* state, int64_t* snapshot, void* stream) {
+  if (!state || !snapshot || state == snapshot) return fail(VMLMF_E_BADARG, "dropout_advance: two distinct device words pairs");
+  return hip_tail(launch_drop_advance(reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(snapshot), (hipStream_t)stream));
+}
+
+static int drop_rows(int mode, int64_t R, int H, int V, float p, const int64_t* state, int site, const DropCols& cm, const float* x,
+                     const int64_t* tokens, float* y, void* stream) {
+  if (R < 0 || H < 1) return fail(VMLMF_E_BADARG, "dropout: R >= 0, H >= 1");
+  DropArgs d;
+  const int rc = drop_args(p, state, site, nullptr, &d);
+  if (rc != 0) return rc;
+  if (!state || !y || (mode != 1 && !x) || (mode == 2 && !tokens)) return fail(VMLMF_E_BADARG, "dropout: null pointer");
+  if (R >= (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "dropout: 2^32 positions and more");
+  return hip_tail(launch_drop_rows(mode, R, H, V, d, cm, x, (const long long*)tokens, y, (hipStream_t)stream));
+}
+
+int vmlmf_dropout_apply(int64_t R, int H, const float* x, float* y, float p, const int64_t* state, int site, void* stream) {
+  const DropCols cm = {H, 0};
+  return drop_rows(0, R, H, 0, p, state, site, cm, x, nullptr, y, stream);
+}
+
+int vmlmf_dropout_factors(const vmlmf_desc* d, int64_t R, int H, float p, const int64_t* state, int site, float* factors, void* stream) {
+  DropCols cm = {H, 0};
+  if (d != nullptr) {
+    VGeo g;
+    RbGeo q;
+    int rc = make_geo(d, &g, &q);
+    if (rc != 0) return rc;
+    if (g.H != H) return fail(VMLMF_E_BADARG, "dropout_factors: H is not the layer's hidden size");
+    if (g.rb) cm.Hg = g.Hg, cm.gstride = 64 * g.W;
+  }
+  return drop_rows(1, R, H, 0, p, state, site, cm, nullptr, nullptr, factors, stream);
+}
+
+int vmlmf_embed_dropout_forward(int R, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, const int64_t* state,
+                                int site, void* stream) {
+  if (V < 1) return fail(VMLMF_E_BADARG, "embed: V must be >= 1");
+  const DropCols cm = {H, 0};
+  return drop_rows(2, R, H, V, p, state, site, cm, weight, tokens, out, stream);
+}
+
+int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, void* scratch,
+                                 size_t scratch_bytes, float p, const int64_t* state, int site, void* stream) {
+  if (R < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R, H, V must be >= 1");
+  if (!tokens || !dy || !dweight || !state) return fail(VMLMF_E_BADARG, "embed: null pointer");
+  DropArgs d;
+  int rc = drop_args(p, state, site, nullptr, &d);
+  if (rc != 0) return rc;
+  rc = launch_embed_bwd(R, H, V, (const long long*)tokens, dy, dweight, scratch, scratch_bytes, (hipStream_t)stream, &d);
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "embed_dropout_backward: embedding width > 1024");
+  if (rc == -4) return fail(VMLMF_E_WORKSPACE, "embed_backward: scratch smaller than vmlmf_embed_backward_scratch_bytes()");
+  return hip_tail(rc);
+}
+
+// ---- decoding the LM (vmlmf_sample.hip) ----
+size_t vmlmf_lm_sample_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_workspace_bytes(B, V); }
+
+int vmlmf_lm_sample(int B, int H, int V, const float* h, const float* weight, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, int64_t* ticket, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (B < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "lm_sample: B, H, V must be >= 1");
+  if (!h || !weight || !tokens_out || !ticket || !workspace) return fail(VMLMF_E_BADARG, "lm_sample: null pointer");
+  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+    return fail(VMLMF_E_BADARG, "lm_sample: the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_sample: sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_sample: x_next needs the embedding table");
+  if (step < 0) return fail(VMLMF_E_BADARG, "lm_sample: step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_sample: 2^32 positions (step * B + b) and more");
+  if (workspace_bytes < lm_sample_workspace_bytes(B, V))
+    return fail(VMLMF_E_WORKSPACE, "lm_sample: workspace smaller than vmlmf_lm_sample_workspace_bytes()");
+  LmSampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.h = h, a.w = weight, a.bias = bias, a.embed = embed;
+  a.state = reinterpret_cast<const unsigned long long*>(state);
+  a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
+  a.part = static_cast<float*>(workspace), a.ticket = reinterpret_cast<unsigned long long*>(ticket);
+  a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  return hip_tail(launch_lm_sample(a, (hipStream_t)stream));
+}
+
+int vmlmf_lm_choose(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, void* stream) {
+  if (B < 1 || V < 1 || (x_next && H < 1)) return fail(VMLMF_E_BADARG, "lm_choose: B, V (and H with x_next) must be >= 1");
+  if (!scores || !tokens_out) return fail(VMLMF_E_BADARG, "lm_choose: null pointer");
+  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+    return fail(VMLMF_E_BADARG, "lm_choose: the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_choose: sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_choose: x_next needs the embedding table");
+  if (step < 0) return fail(VMLMF_E_BADARG, "lm_choose: step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_choose: 2^32 positions (step * B + b) and more");
+  LmChooseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.scores = scores, a.bias = bias, a.embed = embed, a.state = reinterpret_cast<const unsigned long long*>(state);
+  a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
+  a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  return hip_tail(launch_lm_choose(a, (hipStream_t)stream));
+}
+
+int vmlmf_transpose(int rows, int cols, const float* src, float* dst, void* stream) {
+  if (rows < 1 || cols < 1) return fail(VMLMF_E_BADARG, "transpose: rows, cols must be >= 1");
+  if (!src || !dst || src == dst) return fail(VMLMF_E_BADARG, "transpose: two distinct buffers");
+  return hip_tail(launch_transpose(rows, cols, src, dst, (hipStream_t)stream));
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@
 
 #include "../../include/vmlmf_hip.h"
 
-// the library's per-device gradient-health word and the guard mode (vmlmf_api.hip)
+// the library's per-device gradient-health word and the guard mode (vmlmf_state.hip)
 unsigned* vmlmf_health_word_if_any();
 int vmlmf_adam_guard_mode();
 

@@ -25,8 +25,8 @@
 #include "vmlmf_launch.h"
 #include "vmlmf_device.h"
 
-int vmlmf_set_error(int code, const std::string& msg);   // vmlmf_api.hip
-unsigned* vmlmf_status_word(void* stream);                // vmlmf_api.hip (mapped host word, or NULL)
+int vmlmf_set_error(int code, const std::string& msg);   // vmlmf_state.hip
+unsigned* vmlmf_status_word(void* stream);                // vmlmf_state.hip (mapped host word, or NULL)
 
 namespace {
 

@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(512) wgrad_ring_kernel(VGeo g, RingArgs q) {
 
 // Layers this kernel takes: fp32 tapes, one tape row per batch row, contiguous (t, b) rows of x and y, 16-byte aligned rank
 // rows, at least one full tile of columns.  (Whether it PAYS - enough rows for a chip-wide launch of long chunks - is the
-// caller's question: vmlmf_api.hip.)
+// caller's question: vmlmf_api.hip, vmlmf_stack.hip.)
 bool wgrad_ring_ok(const VGeo& g) {
   return !g.bf && !g.foldx && g.Bp == g.B && g.NT % 64 == 0 && g.NT >= 256 && g.I <= g.H && g.KX % 4 == 0 &&
          (g.G * g.KH) % 4 == 0 && g.sxT == (long long)g.B * g.sxB && g.syT == (long long)g.B * g.syB && g.KX <= 32 && g.G * g.KH <= 128;
