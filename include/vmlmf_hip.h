@@ -426,6 +426,34 @@ int vmlmf_lm_sample(int B, int H, int V, const float *h, const float *weight, co
  *                  docs/design/lm_sampling.md); vmlmf_amd.lm_sample switches above 4 rows. */
 int vmlmf_lm_choose(int B, int H, int V, const float *scores, const float *bias, const float *embed, float inv_temperature,
                     const int64_t *state, int step, int64_t *tokens_out, float *logprob_out, float *x_next, void *stream);
+/* Filters: top-k and nucleus (top-p) sampling.  vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered are the two launches above with
+ * the choice restricted to a kept set (everything those refuse, these refuse in the same way; same Philox layout, same outputs).
+ *   The filters act on the tempered scores z = scores * inv_temperature, in the order temperature, top-k, top-p over the renormalised
+ *   survivors of top-k, under ONE total order on tokens: larger z first, equal z to the lower index.
+ *   top_k = k   exactly the first min(k, V) tokens of that order are kept; 0 and k >= V: off; k < 0: VMLMF_E_BADARG.
+ *   top_p = p   0 < p <= 1 (else, NaN included, VMLMF_E_BADARG): of the tokens top-k kept, the shortest prefix of the order whose mass
+ *               reaches p - the token at sorted position j is kept iff the mass of the tokens before it is < p, so the first token always
+ *               is; 1: off.  Mass is exp(z_v - z_max) over the set top-k kept, normalised by its own sum; the kernel holds it in fixed
+ *               point with 40 fractional bits (the largest token weighs 2^40) and sums it with integer atomics, so the kept set does
+ *               not depend on the order of arrival and is bit-identical from run to run.
+ *   token       argmax over the kept set of z + G, G[b][v] exactly the noise of the unfiltered launches for (step * B + b, v).
+ *   logprob_out stays the untempered, unfiltered log-softmax of the chosen token over the whole vocabulary.
+ *   kept_out    (B, int32, or NULL) how many tokens survived per row.  Where no selection runs - both filters off, or
+ *               inv_temperature == 0: greedy, whose argmax every filter keeps - the unfiltered kernels run, tokens_out / logprob_out /
+ *               x_next carry exactly the bits of vmlmf_lm_sample / vmlmf_lm_choose, and kept_out is set to V.
+ *   vmlmf_lm_sample_filtered still is ONE launch behind the same ticket: the strips write their scores (B x V floats) into the
+ *   workspace and the last workgroup to arrive selects and chooses row by row; workspace:
+ *   vmlmf_lm_sample_filtered_workspace_bytes(B, V) bytes (host only; monotone in B and V; >= vmlmf_lm_sample_workspace_bytes).
+ *   Measured at the PTB size it is slower than the library GEMM + vmlmf_lm_choose_filtered at every width, one row included
+ *   (docs/design/lm_sampling.md): vmlmf_amd.lm_sample takes it only on request (form="fused"). */
+size_t vmlmf_lm_sample_filtered_workspace_bytes(int B, int V);
+int vmlmf_lm_sample_filtered(int B, int H, int V, const float *h, const float *weight, const float *bias, const float *embed,
+                             float inv_temperature, int top_k, float top_p, const int64_t *state, int step, int64_t *tokens_out,
+                             float *logprob_out, float *x_next, int32_t *kept_out, int64_t *ticket, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int vmlmf_lm_choose_filtered(int B, int H, int V, const float *scores, const float *bias, const float *embed, float inv_temperature,
+                             int top_k, float top_p, const int64_t *state, int step, int64_t *tokens_out, float *logprob_out,
+                             float *x_next, int32_t *kept_out, void *stream);
 
 /* dst (cols x rows, dense) = src (rows x cols, dense)^T, fp32, out of place.  The LM head's weight gradient dW = dz^T h is fastest as
  * the library GEMM that yields dW^T; this turns it into the (V, H) tensor fc.w.grad is (vmlmf_amd/functional.py: LmHeadLossFn). */

@@ -6,7 +6,10 @@ MyVMLSTMGroup ranks [32, 32], for B in {1, 8, 32, 256}.  Paths, same process, sa
   naive        the stock-op loop a user writes without it: embed -> 2 x layer call at T = 1 -> addmm -> softmax -> multinomial
   sampler_*    the sampler alone, both forms (functional.lm_sample form "fused" / "gemm"), 50 launches replayed from a graph
 All four step timings cover the decode steps only (the prompt's pass is outside them); best of --reps, and the spread (max / min).
-One JSON object per line.  `python tools/bench_generate.py [--out FILE] [--batches 1,8,32,256] [--tokens 64] [--sampler-only]`."""
+--top-k K / --top-p P put the filters on in the eager, graph and sampler_* paths (the stock-op loop stays unfiltered); the record carries
+them.  --models plain,group picks the models.
+One JSON object per line.  `python tools/bench_generate.py [--out FILE] [--batches 1,8,32,256] [--tokens 64] [--sampler-only]
+[--top-k K] [--top-p P] [--models plain,group]`."""
 import argparse
 import json
 import os
@@ -45,24 +48,26 @@ def _rec(t, B, steps):
     return {"ms_per_token": 1e3 * t / steps, "tokens_per_s": B * steps / t, "spread": round(_timed.spread, 3)}
 
 
-def sampler_us(h, w, b, e, snap, form, n=50):
+def sampler_us(h, w, b, e, snap, form, n=50, reps=3, **filters):
+    """us per sampler step (best of `reps` replays of a graph of n steps); sampler_us.spread: max / min over the replays."""
     from vmlmf_amd import lm_sample
     for _ in range(3):
-        lm_sample(h, w, b, 1.0, snap, 0, embed=e, form=form)
+        lm_sample(h, w, b, 1.0, snap, 0, embed=e, form=form, **filters)
     gs = torch.cuda.CUDAGraph()
     with torch.cuda.graph(gs):
         for j in range(n):
-            lm_sample(h, w, b, 1.0, snap, j, embed=e, form=form)
+            lm_sample(h, w, b, 1.0, snap, j, embed=e, form=form, **filters)
     gs.replay()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    best = float("inf")
-    for _ in range(3):
+    ts = []
+    for _ in range(reps):
         e0.record()
         gs.replay()
         e1.record()
         torch.cuda.synchronize()
-        best = min(best, 1e3 * e0.elapsed_time(e1) / n)
-    return best
+        ts.append(1e3 * e0.elapsed_time(e1) / n)
+    sampler_us.spread = max(ts) / min(ts)
+    return min(ts)
 
 
 def naive(m, x, states, steps):
@@ -86,7 +91,11 @@ def main():
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sampler-only", action="store_true", help="only the sampler launch (e.g. of a probe build named by VMLMF_LIB)")
+    ap.add_argument("--top-k", type=int, default=None, help="keep the k most likely tokens (Model.generate's top_k)")
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling (Model.generate's top_p)")
+    ap.add_argument("--models", default="plain,group")
     a = ap.parse_args()
+    filters = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p)) if v is not None}
     from vmlmf_amd import DecodeGraph, dropout_advance
     from vmlmf_amd.lm import _KeptImages
     dev = torch.device("cuda")
@@ -104,19 +113,20 @@ def main():
 
     K = 16
     steps = a.tokens
-    for group in (False, True):
+    for group in [g == "group" for g in a.models.split(",")]:
         m = _model(group)
         name = "group[32,32]" if group else "plain32"
         for B in [int(b) for b in a.batches.split(",")]:
             prompt = torch.randint(0, 10000, (4, B), device=dev)
-            res = {"model": name, "B": B, "V": 10000, "H": 650, "tokens": steps}
+            res = dict({"model": name, "B": B, "V": 10000, "H": 650, "tokens": steps}, **filters)
             with torch.no_grad():
                 h, st = m.features(prompt, m.state_init(B))
             snap = dropout_advance(m.sampler_state())
             hv = h[-1].contiguous()
             for form in ("fused", "gemm"):
-                us = sampler_us(hv, m.fc.w, m.fc.b, m.embed.w, snap, form)
+                us = sampler_us(hv, m.fc.w, m.fc.b, m.embed.w, snap, form, reps=a.reps, **filters)
                 res["sampler_%s_us" % form] = us
+                res["sampler_%s_spread" % form] = round(sampler_us.spread, 3)
                 res["sampler_%s_fc_w_GBps" % form] = 10000 * 650 * 4 / (us * 1e-6) / 1e9
             if a.sampler_only:
                 emit(res)
@@ -124,10 +134,10 @@ def main():
             for path in ("layers", "stack"):
                 def eager():
                     with torch.no_grad(), _KeptImages(m):
-                        m._decode(hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path)
+                        m._decode(hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path, **filters)
                 t = _timed(eager, a.reps)
                 res["eager" if path == "layers" else "eager_stack"] = _rec(t, B, steps)
-            g = DecodeGraph(m, hv, st, K, temperature=1.0)
+            g = DecodeGraph(m, hv, st, K, temperature=1.0, **filters)
             t = _timed(lambda: [g.replay() for _ in range(steps // K)], a.reps)
             res["graph"] = dict(_rec(t, B, steps), chunk=K)
             del g

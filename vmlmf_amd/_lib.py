@@ -139,6 +139,10 @@ SYMBOLS = {
     "vmlmf_lm_sample_workspace_bytes": (_sz, [_i, _i]),
     "vmlmf_lm_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vmlmf_lm_choose": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp]),
+    "vmlmf_lm_sample_filtered_workspace_bytes": (_sz, [_i, _i]),
+    "vmlmf_lm_sample_filtered": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_float, _i, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _sz, _vp]),
+    "vmlmf_lm_choose_filtered": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _i, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "vmlmf_transpose": (_i, [_i, _i, _vp, _vp, _vp]),
     "vmlmf_adam_step": (_i, [ctypes.POINTER(TensorList), _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,
                              ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),

@@ -297,8 +297,14 @@ struct LmSampleArgs {
   unsigned long long* ticket;             // zero between launches
   float inv_temp;                         // 0: greedy
   int B, H, V, step, tpw;                 // tpw: set by the launcher
+  // filters (the unfiltered entry point leaves them 0 / 1 / NULL): with one on, `part` spans lm_sample_filtered_workspace_bytes(B, V)
+  int top_k;                              // 0: off, else < V
+  float top_p;                            // (0, 1], 1: off
+  int* kept;                              // (B) or NULL: tokens that survived the filters
+  float* scores;                          // set by the launcher: the (B, V) scores behind the partials
 };
 size_t lm_sample_workspace_bytes(int B, int V);
+size_t lm_sample_filtered_workspace_bytes(int B, int V);
 int launch_lm_sample(LmSampleArgs a, hipStream_t s);
 // the same choice over the (B, V) scores of a library GEMM (without the bias), one workgroup per row
 struct LmChooseArgs {
@@ -308,6 +314,9 @@ struct LmChooseArgs {
   float *logprob, *x_next;                // (B) or NULL, (B, H) or NULL
   float inv_temp;                         // 0: greedy
   int B, H, V, step;
+  int top_k;                              // filters, as LmSampleArgs'
+  float top_p;
+  int* kept;
 };
 int launch_lm_choose(const LmChooseArgs& a, hipStream_t s);
 

@@ -144,20 +144,45 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, con
 
 // ---- decoding the LM (vmlmf_sample.hip) ----
 size_t vmlmf_lm_sample_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_workspace_bytes(B, V); }
+size_t vmlmf_lm_sample_filtered_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_filtered_workspace_bytes(B, V); }
 
-int vmlmf_lm_sample(int B, int H, int V, const float* h, const float* weight, const float* bias, const float* embed, float inv_temperature,
-                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, int64_t* ticket, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  if (B < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "lm_sample: B, H, V must be >= 1");
-  if (!h || !weight || !tokens_out || !ticket || !workspace) return fail(VMLMF_E_BADARG, "lm_sample: null pointer");
+}  // extern "C"
+
+namespace {
+
+// "<entry point>: <text>" (one copy of the string work for all the refusals below)
+__attribute__((noinline)) int refuse(int code, const char* name, const char* text) { return fail(code, std::string(name) + ": " + text); }
+
+// what both forms of the sampler step refuse, under the entry point's name
+int sampler_refusal(const char* name, int B, float inv_temperature, const void* state, const void* embed, const void* x_next, int step) {
   if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-    return fail(VMLMF_E_BADARG, "lm_sample: the inverse temperature must be finite and >= 0 (0: greedy)");
-  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_sample: sampling needs the {seed, offset} snapshot");
-  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_sample: x_next needs the embedding table");
-  if (step < 0) return fail(VMLMF_E_BADARG, "lm_sample: step must be >= 0");
-  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_sample: 2^32 positions (step * B + b) and more");
-  if (workspace_bytes < lm_sample_workspace_bytes(B, V))
-    return fail(VMLMF_E_WORKSPACE, "lm_sample: workspace smaller than vmlmf_lm_sample_workspace_bytes()");
+    return refuse(VMLMF_E_BADARG, name, "the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return refuse(VMLMF_E_BADARG, name, "sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return refuse(VMLMF_E_BADARG, name, "x_next needs the embedding table");
+  if (step < 0) return refuse(VMLMF_E_BADARG, name, "step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return refuse(VMLMF_E_UNSUPPORTED, name, "2^32 positions (step * B + b) and more");
+  return 0;
+}
+int filter_refusal(const char* name, int top_k, float top_p) {
+  if (top_k < 0) return refuse(VMLMF_E_BADARG, name, "top_k must be >= 0 (0: off)");
+  if (!(top_p > 0.f && top_p <= 1.f)) return refuse(VMLMF_E_BADARG, name, "top_p must lie in (0, 1] (1: off)");
+  return 0;
+}
+// the launch where no selection runs (filters off, or greedy: the argmax is always kept) writes no counts: the whole row then
+int kept_is_the_row(int B, int V, float inv_temperature, int top_k, float top_p, int32_t* kept_out, hipStream_t s) {
+  if (kept_out == nullptr || (inv_temperature > 0.f && (top_k > 0 || top_p < 1.f))) return 0;
+  return (int)hipMemsetD32Async((hipDeviceptr_t)kept_out, V, (size_t)B, s);
+}
+
+int lm_sample_entry(const char* name, size_t need, int B, int H, int V, const float* h, const float* weight, const float* bias,
+                    const float* embed, float inv_temperature, int top_k, float top_p, const int64_t* state, int step, int64_t* tokens_out,
+                    float* logprob_out, float* x_next, int32_t* kept_out, int64_t* ticket, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+  if (B < 1 || H < 1 || V < 1) return refuse(VMLMF_E_BADARG, name, "B, H, V must be >= 1");
+  if (!h || !weight || !tokens_out || !ticket || !workspace) return refuse(VMLMF_E_BADARG, name, "null pointer");
+  if (int rc = sampler_refusal(name, B, inv_temperature, state, embed, x_next, step)) return rc;
+  if (int rc = filter_refusal(name, top_k, top_p)) return rc;
+  if (workspace_bytes < need) return fail(VMLMF_E_WORKSPACE, std::string(name) + ": workspace smaller than vmlmf_" + name + "_workspace_bytes()");
   LmSampleArgs a;
   memset(&a, 0, sizeof(a));
   a.h = h, a.w = weight, a.bias = bias, a.embed = embed;
@@ -165,25 +190,59 @@ int vmlmf_lm_sample(int B, int H, int V, const float* h, const float* weight, co
   a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
   a.part = static_cast<float*>(workspace), a.ticket = reinterpret_cast<unsigned long long*>(ticket);
   a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  a.top_k = top_k >= V ? 0 : top_k, a.top_p = top_p, a.kept = kept_out;
+  if (int rc = kept_is_the_row(B, V, inv_temperature, a.top_k, top_p, kept_out, (hipStream_t)stream)) return hip_tail(rc);
   return hip_tail(launch_lm_sample(a, (hipStream_t)stream));
 }
 
-int vmlmf_lm_choose(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature,
-                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, void* stream) {
-  if (B < 1 || V < 1 || (x_next && H < 1)) return fail(VMLMF_E_BADARG, "lm_choose: B, V (and H with x_next) must be >= 1");
-  if (!scores || !tokens_out) return fail(VMLMF_E_BADARG, "lm_choose: null pointer");
-  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-    return fail(VMLMF_E_BADARG, "lm_choose: the inverse temperature must be finite and >= 0 (0: greedy)");
-  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "lm_choose: sampling needs the {seed, offset} snapshot");
-  if (x_next && !embed) return fail(VMLMF_E_BADARG, "lm_choose: x_next needs the embedding table");
-  if (step < 0) return fail(VMLMF_E_BADARG, "lm_choose: step must be >= 0");
-  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "lm_choose: 2^32 positions (step * B + b) and more");
+int lm_choose_entry(const char* name, int B, int H, int V, const float* scores, const float* bias, const float* embed,
+                    float inv_temperature, int top_k, float top_p, const int64_t* state, int step, int64_t* tokens_out, float* logprob_out,
+                    float* x_next, int32_t* kept_out, void* stream) {
+  if (B < 1 || V < 1 || (x_next && H < 1)) return refuse(VMLMF_E_BADARG, name, "B, V (and H with x_next) must be >= 1");
+  if (!scores || !tokens_out) return refuse(VMLMF_E_BADARG, name, "null pointer");
+  if (int rc = sampler_refusal(name, B, inv_temperature, state, embed, x_next, step)) return rc;
+  if (int rc = filter_refusal(name, top_k, top_p)) return rc;
   LmChooseArgs a;
   memset(&a, 0, sizeof(a));
   a.scores = scores, a.bias = bias, a.embed = embed, a.state = reinterpret_cast<const unsigned long long*>(state);
   a.tokens = reinterpret_cast<long long*>(tokens_out), a.logprob = logprob_out, a.x_next = x_next;
   a.inv_temp = inv_temperature, a.B = B, a.H = H, a.V = V, a.step = step;
+  a.top_k = top_k >= V ? 0 : top_k, a.top_p = top_p, a.kept = kept_out;
+  if (int rc = kept_is_the_row(B, V, inv_temperature, a.top_k, top_p, kept_out, (hipStream_t)stream)) return hip_tail(rc);
   return hip_tail(launch_lm_choose(a, (hipStream_t)stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmlmf_lm_sample(int B, int H, int V, const float* h, const float* weight, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, int64_t* ticket, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  return lm_sample_entry("lm_sample", B < 1 || V < 1 ? 0 : lm_sample_workspace_bytes(B, V), B, H, V, h, weight, bias, embed, inv_temperature,
+                         0, 1.f, state, step, tokens_out, logprob_out, x_next, nullptr, ticket, workspace, workspace_bytes, stream);
+}
+
+int vmlmf_lm_sample_filtered(int B, int H, int V, const float* h, const float* weight, const float* bias, const float* embed,
+                             float inv_temperature, int top_k, float top_p, const int64_t* state, int step, int64_t* tokens_out,
+                             float* logprob_out, float* x_next, int32_t* kept_out, int64_t* ticket, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  return lm_sample_entry("lm_sample_filtered", B < 1 || V < 1 ? 0 : lm_sample_filtered_workspace_bytes(B, V), B, H, V, h, weight, bias, embed,
+                         inv_temperature, top_k, top_p, state, step, tokens_out, logprob_out, x_next, kept_out, ticket, workspace,
+                         workspace_bytes, stream);
+}
+
+int vmlmf_lm_choose(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature,
+                    const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next, void* stream) {
+  return lm_choose_entry("lm_choose", B, H, V, scores, bias, embed, inv_temperature, 0, 1.f, state, step, tokens_out, logprob_out, x_next,
+                         nullptr, stream);
+}
+
+int vmlmf_lm_choose_filtered(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature,
+                             int top_k, float top_p, const int64_t* state, int step, int64_t* tokens_out, float* logprob_out, float* x_next,
+                             int32_t* kept_out, void* stream) {
+  return lm_choose_entry("lm_choose_filtered", B, H, V, scores, bias, embed, inv_temperature, top_k, top_p, state, step, tokens_out,
+                         logprob_out, x_next, kept_out, stream);
 }
 
 int vmlmf_transpose(int rows, int cols, const float* src, float* dst, void* stream) {

@@ -359,20 +359,21 @@ class Model(nn.Module):
             x, states[i] = rnn(x, states[i])
         return x, states
 
-    def _decode(self, h, states, steps, temperature, snap, layer_path):
+    def _decode(self, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None):
         """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
-        the next input row), then the layers at T = 1 on that row.  No host synchronisation: capturable (DecodeGraph)."""
+        the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
+        capturable (DecodeGraph)."""
         from .functional import lm_sample
         toks, lps = [], []
         for j in range(steps):
-            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w)
+            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w, top_k=top_k, top_p=top_p)
             toks.append(tok)
             lps.append(lp)
             y, states = self._decode_layers(x.unsqueeze(0), states, layer_path)
             h = y[-1]
         return torch.stack(toks), torch.stack(lps), h, states
 
-    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers"):
+    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
@@ -383,7 +384,14 @@ class Model(nn.Module):
         generator snapshotted and advanced once per REPLAY (the eager form: once per call) - so with one seed the chunked and the eager
         form draw the same first K tokens and different ones after them; greedy decoding is the same either way.  layer_path: "layers"
         (one call per layer on kept parameter images; the default) or "stack" (stack_layers' one launch where it covers the layers;
-        measured at the PTB size: docs/design/lm_sampling.md).  Every module's train / eval flag is as the caller left it afterwards."""
+        measured at the PTB size: docs/design/lm_sampling.md).  Every module's train / eval flag is as the caller left it afterwards.
+        top_k / top_p cut the tail of the tempered distribution before the draw: temperature first, then the top_k tokens with the
+        largest scores (equal scores: the lower index first), then of those the shortest prefix whose renormalised mass reaches top_p
+        (functional.lm_sample; None, top_k = 0 and top_p = 1.0: off; ValueError for top_k < 0 and top_p outside (0, 1]).  The generator
+        is snapshotted and advanced exactly as without them, so a filtered and an unfiltered call from one seed see the same noise;
+        logprobs stay those of the unfiltered distribution; greedy decoding is unchanged."""
+        from .functional import sample_filters
+        sample_filters(top_k, top_p)
         if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
             raise RuntimeError("vmlmf_amd: Model.generate runs on the HIP sampler kernel (vmlmf_lm_sample) only: move the model and the "
                                "prompt to 'cuda' (no CPU fallback)")
@@ -407,9 +415,9 @@ class Model(nn.Module):
                 if chunk is None:
                     from .functional import dropout_advance
                     snap = dropout_advance(gen) if gen is not None else None
-                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path)
+                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path, top_k, top_p)
                     return tokens, logprobs, states
-            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path)
+            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path, top_k, top_p)
             outs = [graph.replay() for _ in range(steps // int(chunk))]
             return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
                     [(a.clone(), c.clone()) for a, c in graph.states])
@@ -458,11 +466,14 @@ class DecodeGraph:
     (sampler_state(seed)) puts a new tensor in its place, which this graph does not see - build a new DecodeGraph after re-seeding, as
     after the parameters change (the layers read kept parameter images packed at construction).  Replay DecodeGraphs one after
     another, never two at once on different streams: the sampler's ticket words are taken from a ring of 16 per device (as the
-    criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count."""
+    criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count.
+    top_k / top_p: the filters of Model.generate, fixed at construction."""
 
-    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers"):
-        from .functional import PackCache
+    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None):
+        from .functional import PackCache, sample_filters
         self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
+        sample_filters(top_k, top_p)
+        self.top_k, self.top_p = top_k, top_p
         dev = h.device
         self.h = h.detach().clone()
         self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
@@ -485,7 +496,7 @@ class DecodeGraph:
     def _body(self, h, states):
         from .functional import dropout_advance
         snap = dropout_advance(self.gen) if self.gen is not None else None
-        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path)
+        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path, self.top_k, self.top_p)
         h.copy_(hn)
         for (a, c), (a2, c2) in zip(states, st):
             a.copy_(a2)
