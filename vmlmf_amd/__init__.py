@@ -6,13 +6,13 @@ MI355X (gfx950), behind the reference's own nn.Module API.
     from vmlmf_amd import nll_loss                                     #       (train_test/lm_test.py)
 """
 from .cells import MyVMLMFCell, MyVMLMFCellg2, MyVMLMFgCellg2, MyLSTMCell, MyLSTM, Net, TIME_STEPS, RECURRENT_MAX, RECURRENT_MIN
-from .lm import MyVMLSTM, MyVMLSTMGroup, Embed, Linear, LSTM, Model, DecodeGraph
+from .lm import MyVMLSTM, MyVMLSTMGroup, Embed, Linear, LSTM, Model, DecodeGraph, BeamGraph
 from .functional import (vmlmf_sequence, vmlmf_stack, head_linear, cross_entropy, CrossEntropyLoss, nll_loss, linear_nll, lm_head_loss, embedding, unit_gradient,
                          set_compute_dtype, cache_packed_parameters, dropout, dropout_state, dropout_advance, embedding_dropout,
-                         lm_sample)
+                         lm_sample, lm_beam_step, beam_gather, beam_backtrack)
 from . import optim
 from .graphed import GraphedTrainStep
 
 __all__ = ["GraphedTrainStep", "vmlmf_stack", "optim", "head_linear", "cross_entropy", "CrossEntropyLoss", "MyVMLMFCell", "MyVMLMFCellg2", "MyVMLMFgCellg2", "MyLSTMCell", "MyLSTM", "Net", "MyVMLSTM", "MyVMLSTMGroup",
-           "Embed", "Linear", "LSTM", "Model", "DecodeGraph", "nll_loss", "linear_nll", "lm_head_loss", "embedding", "unit_gradient", "vmlmf_sequence", "dropout", "dropout_state", "dropout_advance", "lm_sample",
+           "Embed", "Linear", "LSTM", "Model", "DecodeGraph", "BeamGraph", "lm_beam_step", "beam_gather", "beam_backtrack", "nll_loss", "linear_nll", "lm_head_loss", "embedding", "unit_gradient", "vmlmf_sequence", "dropout", "dropout_state", "dropout_advance", "lm_sample",
            "embedding_dropout"]

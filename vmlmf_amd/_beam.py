@@ -1,0 +1,217 @@
+"""ctypes binding of the C ABI in include/vmlmf_beam.h (libvmlmf_beam.so, built in-tree by csrc/Makefile beside libvmlmf_hip.so):
+the beam-search step of the LM decoder.  The library is loaded on the first beam call - a training process never opens it.
+
+There is no fallback: if the library is missing, or a call fails, this raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+
+LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_beam.so")
+ABI_VERSION = 1
+MAX_BEAMS = 32
+MAX_TENSORS = 16
+
+# every symbol include/vmlmf_beam.h declares: (restype, argtypes)
+_vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+SYMBOLS = {
+    "vmlmf_beam_abi_version": (_i, []),
+    "vmlmf_beam_last_error": (ctypes.c_char_p, []),
+    "vmlmf_beam_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vmlmf_beam_step": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vmlmf_beam_gather": (_i, [_i, _i, _i, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp]),
+    "vmlmf_beam_backtrack": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
+_handle = None
+
+
+def lib():
+    """The loaded libvmlmf_beam.so.  Raises if it has not been built: there is no fallback path."""
+    global _handle
+    if _handle is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                f"{LIB_PATH} is missing: build it with `make -C {_lib.CSRC}` (or __graft_entry__.build()). "
+                "vmlmf_amd has no stock-op fallback for the beam-search step.")
+        handle = ctypes.CDLL(LIB_PATH)
+        for name, (res, args) in SYMBOLS.items():
+            fn = getattr(handle, name)  # AttributeError if the export is missing
+            fn.restype, fn.argtypes = res, args
+        if handle.vmlmf_beam_abi_version() != ABI_VERSION:
+            raise RuntimeError("libvmlmf_beam.so ABI version mismatch: rebuild")
+        _handle = handle
+    return _handle
+
+
+def loaded():
+    """Whether this process has opened libvmlmf_beam.so."""
+    return _handle is not None
+
+
+def check(rc):
+    if rc != 0:
+        raise _lib.VmlmfError(rc, lib().vmlmf_beam_last_error().decode())
+
+
+def check_beams(beams, V=None):
+    """beams as the C ABI takes it; ValueError for beams < 1, beams > MAX_BEAMS and beams > V."""
+    W = int(beams)
+    if W < 1 or W > MAX_BEAMS:
+        raise ValueError(f"vmlmf_amd: beams must lie in [1, {MAX_BEAMS}], got {beams}")
+    if V is not None and W > V:
+        raise ValueError(f"vmlmf_amd: beams={W} exceeds the vocabulary ({V} tokens): a beam offers V candidates")
+    return W
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _require(t, what, dtype=torch.float32):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"vmlmf_amd: {what} is not on a HIP device; the beam-search step runs only as HIP kernels on an MI355X "
+                           "(no CPU fallback). Move the model and inputs to 'cuda'.")
+    if t.dtype != dtype:
+        raise RuntimeError(f"vmlmf_amd: {what} must be {dtype}, got {t.dtype}")
+
+
+_BUFFERS = {}
+
+
+def step_buffers(dev, B, W, V):
+    """(ticket (B) int32 - zero, and left zero by every launch -, workspace) of vmlmf_beam_step, kept per (device, stream): launches
+    that share them must be ordered on one stream.  Not to be called inside a stream capture (BeamGraph brings its own)."""
+    nbytes = lib().vmlmf_beam_workspace_bytes(B, W, V)
+    key = (dev.index, _lib.raw_stream(dev).value)
+    got = _BUFFERS.get(key)
+    if got is None or got[0].numel() < B or got[1].numel() * 8 < nbytes:
+        if got is not None:
+            B, nbytes = max(B, got[0].numel()), max(nbytes, got[1].numel() * 8)
+        got = _BUFFERS[key] = (torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64))
+    return got
+
+
+def new_step_buffers(dev, B, W, V):
+    """A ticket and a workspace of one's own (a captured graph's: its launches must not meet another stream's on one ticket)."""
+    nbytes = lib().vmlmf_beam_workspace_bytes(B, W, V)
+    return torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+
+
+def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None):
+    """One step of beam search over B batch rows of W beams (cum is (B, W)): the head's GEMM over the beams' top-layer outputs h (B W, H)
+    - row b W + w is beam w of batch row b -, then ONE launch (vmlmf_beam_step, csrc/vmlmf_beam.hip) that forms every candidate's total
+    cum[b, w] + log_softmax(h fc.w^T + bias)[v] in fp32, keeps the W best of each batch row under the total order (larger total first,
+    equal totals to the lower flat index w V + v) and writes them in that order.  A finished beam (finished[b, w] set and eos given)
+    offers (w, eos) alone, at its total so far.
+    finished: (B, W) bool or int32; length: (B, W) int32; eos: a token, or None - then no beam is finished, whatever `finished` says.
+    Returns (parent (B, W) int32, token (B, W) int64, total (B, W) fp32, finished (B, W) int32, length (B, W) int32,
+    x_next (B W, H) = embed[token] or None without embed, src_row (B W) int32 = b W + parent: the state row a survivor continues).
+    buffers: (ticket, workspace) of new_step_buffers() - default: the current stream's."""
+    for t, what in ((h, "h"), (weight, "weight"), (cum, "cum")):
+        _require(t, what)
+    if bias is not None:
+        _require(bias, "bias")
+    if embed is not None:
+        _require(embed, "embedding table")
+    if cum.dim() != 2:
+        raise RuntimeError(f"vmlmf_amd.lm_beam_step: cum must be (B, W), got {tuple(cum.shape)}")
+    B, W = cum.shape
+    h2 = h.reshape(-1, h.shape[-1]).contiguous()
+    H = h2.shape[1]
+    w = weight.contiguous()
+    V = w.shape[0]
+    check_beams(W, V)
+    if h2.shape[0] != B * W or w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
+        raise RuntimeError(f"vmlmf_amd.lm_beam_step: h {tuple(h.shape)} must be (B W, H) for cum {tuple(cum.shape)}, weight "
+                           f"{tuple(weight.shape)} (V, H), bias / embed (V) / (V, H)")
+    if tuple(finished.shape) != (B, W) or tuple(length.shape) != (B, W):
+        raise RuntimeError("vmlmf_amd.lm_beam_step: finished and length must be (B, W) like cum")
+    _require(length, "length", torch.int32)
+    if finished.dtype == torch.bool:
+        finished = finished.to(torch.int32)
+    _require(finished, "finished", torch.int32)
+    eos_c = -1 if eos is None else int(eos)
+    if eos is not None and not 0 <= eos_c < V:
+        raise ValueError(f"vmlmf_amd.lm_beam_step: eos={eos} is not a token of the vocabulary ({V})")
+    return beam_select(torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
+                       length.contiguous(), eos_c, None if embed is None else embed.contiguous(), buffers)
+
+
+def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
+    """The vmlmf_beam_step launch on checked, contiguous arguments: scores (B W, V) without the bias, eos an int (-1: none).
+    lm_beam_step's results."""
+    B, W = cum.shape
+    V = scores.shape[1]
+    dev = scores.device
+    handle = lib()
+    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
+    H = embed.shape[1] if embed is not None else 1
+    parent = torch.empty((B, W), device=dev, dtype=torch.int32)
+    token = torch.empty((B, W), device=dev, dtype=torch.int64)
+    total = torch.empty((B, W), device=dev, dtype=torch.float32)
+    fin = torch.empty((B, W), device=dev, dtype=torch.int32)
+    ln = torch.empty((B, W), device=dev, dtype=torch.int32)
+    src = torch.empty(B * W, device=dev, dtype=torch.int32)
+    xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
+    with _lib.on_device(dev):
+        check(handle.vmlmf_beam_step(B, W, H, V, _ptr(scores), _ptr(bias), _ptr(cum), _ptr(finished), _ptr(length), eos, _ptr(embed),
+                                     _ptr(parent), _ptr(token), _ptr(total), _ptr(fin), _ptr(ln), _ptr(xn), _ptr(src), _ptr(ticket),
+                                     _ptr(ws), ws.numel() * 8, _lib.raw_stream(dev)))
+    return parent, token, total, fin, ln, xn, src
+
+
+def beam_gather(tensors, src_row):
+    """[t.index_select(0, src_row) for t in tensors] in ONE launch (vmlmf_beam_gather): up to MAX_TENSORS fp32 tensors of one shape
+    (..., H) whose leading dimensions flatten to the src_row.numel() rows (a layer's (B W, H) state, or nn.LSTM's (1, B W, H)).
+    src_row: int32.  Returns new tensors; the inputs are not written."""
+    tensors = list(tensors)
+    if not 1 <= len(tensors) <= MAX_TENSORS:
+        raise ValueError(f"vmlmf_amd.beam_gather: 1 .. {MAX_TENSORS} tensors a launch, got {len(tensors)}")
+    _require(src_row, "src_row", torch.int32)
+    rows = src_row.numel()
+    shape = tensors[0].shape
+    H = shape[-1]
+    for t in tensors:
+        _require(t, "a state tensor")
+        if t.shape != shape or t.numel() != rows * H:
+            raise RuntimeError(f"vmlmf_amd.beam_gather: every tensor must be {tuple(shape)} with {rows} rows of {H}, got {tuple(t.shape)}")
+    srcs = [t.contiguous() for t in tensors]
+    dsts = [torch.empty_like(t) for t in srcs]
+    n = len(srcs)
+    sp = (_vp * n)(*[t.data_ptr() for t in srcs])
+    dp = (_vp * n)(*[t.data_ptr() for t in dsts])
+    dev = srcs[0].device
+    rows_c = src_row.contiguous()
+    with _lib.on_device(dev):
+        check(lib().vmlmf_beam_gather(n, rows, H, _ptr(rows_c), sp, dp, _lib.raw_stream(dev)))
+    return dsts
+
+
+def beam_backtrack(parent, token, order=None):
+    """The hypotheses behind the last step's slots: parent (steps, B, W) int32 and token (steps, B, W) int64 as lm_beam_step wrote
+    them -> (steps, B, W) int64 where [:, b, w] is the hypothesis ending in slot order[b, w] (None: slot w), read back through the parent
+    pointers (vmlmf_beam_backtrack: one thread per (b, w))."""
+    _require(parent, "parent", torch.int32)
+    _require(token, "token", torch.int64)
+    if parent.dim() != 3 or parent.shape != token.shape:
+        raise RuntimeError("vmlmf_amd.beam_backtrack: parent and token must both be (steps, B, W)")
+    steps, B, W = parent.shape
+    if order is not None:
+        _require(order, "order", torch.int32)
+        if tuple(order.shape) != (B, W):
+            raise RuntimeError("vmlmf_amd.beam_backtrack: order must be (B, W)")
+        order = order.contiguous()
+    out = torch.empty_like(token, memory_format=torch.contiguous_format)
+    if steps == 0:
+        return out
+    p, t = parent.contiguous(), token.contiguous()
+    dev = p.device
+    with _lib.on_device(dev):
+        check(lib().vmlmf_beam_backtrack(steps, B, W, _ptr(p), _ptr(t), _ptr(order), _ptr(out), _lib.raw_stream(dev)))
+    return out

@@ -1345,3 +1345,8 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
             _lib.check(lib.vmlmf_lm_sample(B, H, V, _ptr(h2), _ptr(w), bias_p, embed_p, inv, state_p, int(step), _ptr(tokens),
                                            _ptr(logp), _ptr(xn), _ptr(sample_ticket(dev)), _ptr(ws), nbytes, _lib.raw_stream(dev)))
     return outs()
+
+
+# ---- beam search: the selection step, the state reorder and the read-back (C ABI: include/vmlmf_beam.h, a library of its own that
+# the first beam call loads; vmlmf_amd/_beam.py) --------------------------------------------------------------------------------
+from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: E402,F401

@@ -425,6 +425,95 @@ class Model(nn.Module):
             for mod, was in modes:
                 mod.training = was
 
+    def _beam_steps(self, h, states, cum, finished, length, steps, eos, buffers=None):
+        """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
+        (functional.lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
+        2 L state tensors follow their hypotheses (functional.beam_gather), then the layers at T = 1 on the B W rows.  No host
+        synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length)."""
+        from .functional import beam_gather, lm_beam_step
+        parents, toks = [], []
+        for _ in range(steps):
+            par, tok, cum, finished, length, x, src = lm_beam_step(h, self.fc.w, self.fc.b, cum, finished, length, eos, self.embed.w,
+                                                                   buffers=buffers)
+            parents.append(par)
+            toks.append(tok)
+            flat = beam_gather([t for st in states for t in st], src)
+            states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
+            y, states = self._decode_layers(x.unsqueeze(0), states, "layers")
+            h = y[-1]
+        return torch.stack(parents), torch.stack(toks), h, states, cum, finished, length
+
+    def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
+        """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
+        (steps, B, W) int64, scores (B, W) fp32, lengths (B, W) int32, states): tokens[:, b, w] is hypothesis w of row b, best first;
+        its score is the fp32 sum of the untempered log-softmax (bias included) of its tokens - what nll_loss charges -; states are per
+        layer (h, c) of (B W, H), row b W + w, after every returned token of the hypothesis (Model.forward over
+        torch.cat([prompt, tokens[:, b, w]]) ends in them).
+        The prompt runs once through features() without dropout.  Beam 0 of each row then starts at score 0, beams 1 .. W - 1 at -inf,
+        all on the prompt's state.  A step keeps the W best of a row's candidates under one total order - larger total first, equal
+        totals to the lower flat index w V + v - and leaves them in that order (functional.lm_beam_step: one launch behind the head's
+        GEMM; a second launch reorders the layers' states, then the layers run at T = 1 on kept parameter images).
+        eos: a beam that has emitted it is finished - it offers (w, eos) alone at its score so far, its length stops growing and its
+        later tokens are eos (which the layers keep taking in: the states cover the padding).  None: no beam ever finishes.
+        length_penalty = a > 0: the W hypotheses of a row are finally re-sorted by score / length ** a, stably, best first; scores stay the
+        raw sums.  Decoding always runs the full `steps`: an early exit would need a host synchronisation, and the step loop has none.
+        chunk=K (steps % K == 0): K steps are captured into a linear hipGraph on one stream and replayed steps / K times (BeamGraph):
+        the eager call's bits.  ValueError for beams < 1, beams > 32 and beams > V; no random generator is touched; every module's
+        train / eval flag is as the caller left it afterwards."""
+        from . import _beam
+        W = _beam.check_beams(beams, self.vocab_size)
+        steps, alpha = int(steps), float(length_penalty)
+        if eos is not None and not 0 <= int(eos) < self.vocab_size:
+            raise ValueError(f"vmlmf_amd: Model.beam_search: eos={eos} is not a token of the vocabulary ({self.vocab_size})")
+        if not alpha >= 0.0:
+            raise ValueError(f"vmlmf_amd: Model.beam_search: length_penalty must be >= 0, got {length_penalty}")
+        if steps < 0:
+            raise ValueError(f"vmlmf_amd: Model.beam_search: steps must be >= 0, got {steps}")
+        if chunk is not None and (int(chunk) < 1 or steps % int(chunk) != 0):
+            raise ValueError(f"vmlmf_amd: Model.beam_search: chunk={chunk} must divide steps={steps}")
+        if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
+            raise RuntimeError("vmlmf_amd: Model.beam_search runs on the HIP beam-step kernel (vmlmf_beam_step) only: move the model and "
+                               "the prompt to 'cuda' (no CPU fallback)")
+        if prompt.dim() != 2 or prompt.dtype != torch.int64:
+            raise RuntimeError("vmlmf_amd: Model.beam_search takes a (T0, B) int64 prompt")
+        B, dev = prompt.shape[1], prompt.device
+        states = self.state_init(B) if states is None else list(states)
+        modes = [(mod, mod.training) for mod in self.modules()]
+        self.train(False)
+        try:
+            with torch.no_grad(), _KeptImages(self):
+                h, states = self.features(prompt, list(states))
+                h = h[-1].repeat_interleave(W, 0)
+                states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+                cum = torch.full((B, W), float("-inf"), device=dev)
+                cum[:, 0] = 0.0
+                finished = torch.zeros((B, W), dtype=torch.int32, device=dev)
+                length = torch.zeros((B, W), dtype=torch.int32, device=dev)
+                if steps == 0:
+                    return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
+                if chunk is None:
+                    parents, toks, _, states, cum, finished, length = self._beam_steps(h, states, cum, finished, length, steps, eos)
+            if chunk is not None:
+                graph = BeamGraph(self, h, states, int(chunk), W, eos, cum, finished, length)
+                outs = [graph.replay() for _ in range(steps // int(chunk))]
+                parents, toks = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+                states = [(a.clone(), c.clone()) for a, c in graph.states]
+                cum, length = graph.cum.clone(), graph.length.clone()
+            with torch.no_grad():
+                order = None
+                if alpha > 0.0:
+                    key = cum / length.to(torch.float32) ** alpha
+                    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+                    cum, length = cum.gather(1, order), length.gather(1, order)
+                    rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
+                    flat = _beam.beam_gather([t for st in states for t in st], rows)
+                    states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
+                    order = order.to(torch.int32)
+                return _beam.beam_backtrack(parents, toks, order), cum, length, states
+        finally:
+            for mod, was in modes:
+                mod.training = was
+
 
 class _KeptImages:
     """`with _KeptImages(model[, caches]):` every VMLMF layer of the model keeps its packed parameter images for the duration
@@ -506,3 +595,57 @@ class DecodeGraph:
     def replay(self):
         self.graph.replay()
         return self.tokens.clone(), self.logprobs.clone()
+
+
+class BeamGraph:
+    """`steps` steps of Model.beam_search (Model._beam_steps: per step the head's GEMM, the vmlmf_beam_step launch, the vmlmf_beam_gather
+    launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are the beams' (row
+    b W + w) of `beams` = W beams per batch row; cum / finished / length (B, W) default to a fresh search (beam 0 at 0, the others at -inf).  replay() continues from where
+    the previous replay stopped - h, states, cum, finished and length live in this object's buffers - and returns (parents, tokens),
+    both (steps, B, W), for functional.beam_backtrack.  The ticket words and the workspace of the selection are this graph's own, so
+    graphs may be replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after
+    the parameters change."""
+
+    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None):
+        from . import _beam
+        from .functional import PackCache
+        self.model, self.steps, self.eos = model, int(steps), eos
+        dev = h.device
+        W = _beam.check_beams(beams, model.vocab_size)
+        B = h.shape[0] // W
+        if cum is None:
+            cum = torch.full((B, W), float("-inf"), device=dev)
+            cum[:, 0] = 0.0
+        self.h = h.detach().clone()
+        self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
+        self.cum = cum.detach().clone()
+        self.finished = torch.zeros((B, W), dtype=torch.int32, device=dev) if finished is None else finished.to(torch.int32).clone()
+        self.length = torch.zeros((B, W), dtype=torch.int32, device=dev) if length is None else length.to(torch.int32).clone()
+        self.buffers = _beam.new_step_buffers(dev, B, W, model.vocab_size)
+        self.caches = [PackCache() for m in model.modules() if hasattr(m, "kernel_params")]
+        with torch.no_grad(), _KeptImages(model, self.caches):
+            # warm-up outside the capture, on copies: packs the images, loads the library, creates the layers' workspaces
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states], self.cum.clone(), self.finished.clone(),
+                           self.length.clone())
+            torch.cuda.current_stream(dev).wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.parents, self.tokens = self._body(self.h, self.states, self.cum, self.finished, self.length)
+
+    def _body(self, h, states, cum, finished, length):
+        par, tok, hn, st, cn, fn, ln = self.model._beam_steps(h, list(states), cum, finished, length, self.steps, self.eos, self.buffers)
+        h.copy_(hn)
+        for (a, c), (a2, c2) in zip(states, st):
+            a.copy_(a2)
+            c.copy_(c2)
+        cum.copy_(cn)
+        finished.copy_(fn)
+        length.copy_(ln)
+        return par, tok
+
+    def replay(self):
+        self.graph.replay()
+        return self.parents.clone(), self.tokens.clone()
