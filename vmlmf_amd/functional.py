@@ -1270,7 +1270,8 @@ def sample_filters(top_k, top_p, V=None):
     return k, p
 
 
-def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None, top_k=None, top_p=None, return_kept=False):
+def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None, top_k=None, top_p=None, return_kept=False,
+              controls=None):
     """The next token of every row of h (B, H) - the top layer's output - under Linear(weight (V, H), bias (V)), in ONE launch that
     never writes the (B, V) scores.  temperature 0: greedy (argmax, ties to the lowest index); tau > 0: a draw from softmax(scores / tau)
     by Gumbel-max, its noise from Philox4x32-10 at (state = a {seed, offset} snapshot of dropout_advance(), position step * B + b,
@@ -1284,7 +1285,11 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     top_p (vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered; include/vmlmf_hip.h has the contract).  The noise and the
     log-probabilities are those of the unfiltered call; greedy decoding is unchanged by any filter.  With a filter on form=None is
     fused up to SAMPLE_FILTERED_FUSED_MAX_ROWS rows (0: measured, the GEMM form is faster at every width).  return_kept: a last result, kept (B) int32 - how many tokens survived per row
-    (V where no selection ran: filters off, or greedy)."""
+    (V where no selection ran: filters off, or greedy).
+    controls: a DecodeControls (eos, min_length, repetition_penalty, logit_bias / bans and the rows' seen / finished / length state):
+    the choice runs on the controlled scores in ONE launch of its own library behind the head's GEMM (vmlmf_decode_choose,
+    include/vmlmf_decode.h has the contract; form "gemm" only), which updates the controls' state in place; the noise and the
+    log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf."""
     for t, what in ((h, "h"), (weight, "weight")):
         _require_hip(t, what)
     if bias is not None:
@@ -1312,16 +1317,22 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     xn = torch.empty((B, H), device=dev, dtype=torch.float32) if embed is not None else None
     if not return_kept:
         kept = None
-    elif filtered:
+    elif filtered or controls is not None:
         kept = torch.empty(B, device=dev, dtype=torch.int32)
     else:
         kept = torch.full((B,), V, device=dev, dtype=torch.int32)
+    if controls is not None and form not in (None, "gemm"):
+        raise ValueError(f"vmlmf_amd.lm_sample: the controlled choice has no fused-head form (form must be 'gemm' or None, got {form!r})")
     if form is None:
         form = "fused" if B <= (SAMPLE_FILTERED_FUSED_MAX_ROWS if filtered else SAMPLE_FUSED_MAX_ROWS) else "gemm"
     outs = lambda: tuple(t for t in (tokens, logp, xn, kept) if t is not None)
     state_p = None if inv == 0.0 else _ptr(state)
     bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
     bias_p, embed_p = _ptr(bias_c), _ptr(embed_c)
+    if controls is not None:
+        from ._decode import decode_choose
+        decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn, kept)
+        return outs()
     if form == "gemm":
         scores = torch.mm(h2, w.t())
         with _lib.on_device(dev):

@@ -359,21 +359,24 @@ class Model(nn.Module):
             x, states[i] = rnn(x, states[i])
         return x, states
 
-    def _decode(self, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None):
+    def _decode(self, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None, controls=None):
         """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
         the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
-        capturable (DecodeGraph)."""
+        capturable (DecodeGraph).  controls: a DecodeControls - the choice is then the controlled launch behind the head's GEMM
+        (vmlmf_decode_choose), which moves the controls' state on in place."""
         from .functional import lm_sample
         toks, lps = [], []
         for j in range(steps):
-            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w, top_k=top_k, top_p=top_p)
+            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w, top_k=top_k, top_p=top_p,
+                                   controls=controls)
             toks.append(tok)
             lps.append(lp)
             y, states = self._decode_layers(x.unsqueeze(0), states, layer_path)
             h = y[-1]
         return torch.stack(toks), torch.stack(lps), h, states
 
-    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None):
+    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+                 eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
@@ -389,9 +392,28 @@ class Model(nn.Module):
         largest scores (equal scores: the lower index first), then of those the shortest prefix whose renormalised mass reaches top_p
         (functional.lm_sample; None, top_k = 0 and top_p = 1.0: off; ValueError for top_k < 0 and top_p outside (0, 1]).  The generator
         is snapshotted and advanced exactly as without them, so a filtered and an unfiltered call from one seed see the same noise;
-        logprobs stay those of the unfiltered distribution; greedy decoding is unchanged."""
+        logprobs stay those of the unfiltered distribution; greedy decoding is unchanged.
+        Stopping and token controls (all off by default; with any of eos, repetition_penalty != 1, logit_bias, banned_tokens given the
+        choice of every step is ONE launch of a library of its own behind the head's GEMM - vmlmf_decode_choose, include/vmlmf_decode.h -
+        and without them this is the call above, launch for launch).  Per step and row, on the fp32 scores x, in this order:
+        repetition_penalty = theta > 0 turns the score of a token the row has held - prompt included - into x / theta (x > 0) or x theta
+        (Keskar et al., CTRL); logit_bias (V) fp32, entries finite or -inf, is added (banned_tokens: indices, shorthand for -inf); while a
+        row has emitted fewer than min_length tokens eos is held at -inf; then temperature, top_k, top_p and the draw as above, on the
+        same noise - a token at -inf is never chosen.  A row that has emitted eos is finished: its later tokens are eos with
+        log-probability 0, which the layers keep taking in (the states cover the padding, as beam_search's).  logprobs stay the
+        unprocessed log-softmax.  Decoding always runs the full `steps`: the step loop has no host synchronisation.
+        return_lengths=True: (tokens, logprobs, lengths (B) int32 - tokens up to and including eos -, states).  ValueError, before any
+        device work, for repetition_penalty <= 0 or not finite, min_length < 0 or without eos, eos or a banned index outside the
+        vocabulary, a logit_bias that is not (V) fp32, holds NaN or +inf (its values are read back once), or leaves nothing to choose."""
+        from . import _decode as _dc
         from .functional import sample_filters
         sample_filters(top_k, top_p)
+        ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
+                        banned_tokens=banned_tokens)
+        eos_c, min_c, _, banned = _dc.check_controls(self.vocab_size, **ctl_args)
+        controlled = _dc.controls_on(eos, repetition_penalty, logit_bias, banned_tokens)
+        if controlled:
+            _dc.check_bias(self.vocab_size, logit_bias, banned, eos_c, min_c)
         if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
             raise RuntimeError("vmlmf_amd: Model.generate runs on the HIP sampler kernel (vmlmf_lm_sample) only: move the model and the "
                                "prompt to 'cuda' (no CPU fallback)")
@@ -409,18 +431,25 @@ class Model(nn.Module):
             with torch.no_grad(), _KeptImages(self):
                 h, states = self.features(prompt, list(states))
                 h = h[-1]
+                controls = _dc.DecodeControls(B, self.vocab_size, prompt.device, prompt=prompt, _checked=True, **ctl_args) if controlled else None
+
+                def result(tokens, logprobs, states):
+                    if not return_lengths:
+                        return tokens, logprobs, states
+                    lengths = controls.length.clone() if controls is not None else torch.full((B,), steps, dtype=torch.int32, device=prompt.device)
+                    return tokens, logprobs, lengths, states
                 if steps == 0:
-                    return (torch.empty((0, B), dtype=torch.int64, device=prompt.device),
-                            torch.empty((0, B), device=prompt.device), states)
+                    return result(torch.empty((0, B), dtype=torch.int64, device=prompt.device),
+                                  torch.empty((0, B), device=prompt.device), states)
                 if chunk is None:
                     from .functional import dropout_advance
                     snap = dropout_advance(gen) if gen is not None else None
-                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path, top_k, top_p)
-                    return tokens, logprobs, states
-            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path, top_k, top_p)
+                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path, top_k, top_p, controls)
+                    return result(tokens, logprobs, states)
+            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path, top_k, top_p, controls)
             outs = [graph.replay() for _ in range(steps // int(chunk))]
-            return (torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
-                    [(a.clone(), c.clone()) for a, c in graph.states])
+            return result(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
+                          [(a.clone(), c.clone()) for a, c in graph.states])
         finally:
             for mod, was in modes:
                 mod.training = was
@@ -556,13 +585,15 @@ class DecodeGraph:
     after the parameters change (the layers read kept parameter images packed at construction).  Replay DecodeGraphs one after
     another, never two at once on different streams: the sampler's ticket words are taken from a ring of 16 per device (as the
     criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count.
-    top_k / top_p: the filters of Model.generate, fixed at construction."""
+    top_k / top_p: the filters of Model.generate, fixed at construction.
+    controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
+    length -, so replays continue one decode: finished rows stay finished, seen accumulates (the warm-up runs on a clone)."""
 
-    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None):
+    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None):
         from .functional import PackCache, sample_filters
         self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
         sample_filters(top_k, top_p)
-        self.top_k, self.top_p = top_k, top_p
+        self.top_k, self.top_p, self.controls = top_k, top_p, controls
         dev = h.device
         self.h = h.detach().clone()
         self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
@@ -574,18 +605,19 @@ class DecodeGraph:
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
-                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states])
+                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states], None if controls is None else controls.clone())
             torch.cuda.current_stream(dev).wait_stream(side)
             if saved is not None:
                 self.gen.copy_(saved)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.tokens, self.logprobs = self._body(self.h, self.states)
+                self.tokens, self.logprobs = self._body(self.h, self.states, controls)
 
-    def _body(self, h, states):
+    def _body(self, h, states, controls):
         from .functional import dropout_advance
         snap = dropout_advance(self.gen) if self.gen is not None else None
-        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path, self.top_k, self.top_p)
+        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path, self.top_k, self.top_p,
+                                               controls)
         h.copy_(hn)
         for (a, c), (a2, c2) in zip(states, st):
             a.copy_(a2)
