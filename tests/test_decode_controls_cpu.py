@@ -269,12 +269,14 @@ def test_the_entry_point_refuses_on_the_host():
         assert rc == code and words in msg and msg.startswith("vmlmf_decode_choose: "), (kw, rc, msg)
 
 
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _decode
-    monkeypatch.setattr(_decode, "_handle", None)
-    monkeypatch.setattr(_decode, "LIB_PATH", str(tmp_path / "libvmlmf_decode.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_decode.so is missing: build it"):
-        _decode.lib()
+@pytest.mark.parametrize("module, handle, name", [("_decode", "_handle", "libvmlmf_decode.so"), ("_lib", "_lib", "libvmlmf_hip.so")])
+def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path, module, handle, name):
+    import importlib
+    binding = importlib.import_module("vmlmf_amd." + module)
+    monkeypatch.setattr(binding, handle, None)
+    monkeypatch.setattr(binding, "LIB_PATH", str(tmp_path / name))
+    with pytest.raises(RuntimeError, match=name + " is missing: build it"):
+        binding.lib()
 
 
 def test_the_library_is_loaded_by_the_first_controlled_call_only():

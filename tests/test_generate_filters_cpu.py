@@ -233,7 +233,7 @@ def test_the_filtered_workspace_is_monotone_and_holds_the_unfiltered_one():
 def test_generate_refuses_bad_filters_before_any_device_work():
     """The filters are checked first: a ValueError, even where the tensors would be refused next (they live on the CPU here)."""
     from vmlmf_amd import Model, lm_sample
-    from vmlmf_amd.functional import sample_filters
+    from vmlmf_amd.decoding import sample_filters
     torch.manual_seed(0)
     m = Model(97, 32, 2, 0.0, 0.1, w_rank=8, u_ranks=[8], lstm_type="vmlmf")
     prompt = torch.zeros((3, 2), dtype=torch.int64)

@@ -203,7 +203,7 @@ def test_gather_and_backtrack_against_stock_ops(H):
 # ---- 6. Model.beam_search, teacher-forced ----
 def _history(m, prompt, W, steps, eos):
     """The search's per-step (parents, tokens) and its last (cum, finished, length): Model.beam_search's own prologue and step loop."""
-    from vmlmf_amd.lm import _KeptImages
+    from vmlmf_amd.decoding import _KeptImages, beam_steps
     B = prompt.shape[1]
     m.eval()
     with torch.no_grad(), _KeptImages(m):
@@ -213,7 +213,7 @@ def _history(m, prompt, W, steps, eos):
         cum = torch.full((B, W), float("-inf"), device=DEV)
         cum[:, 0] = 0.0
         zero = torch.zeros((B, W), dtype=torch.int32, device=DEV)
-        par, tok, _, st, cum, fin, ln = m._beam_steps(h, st, cum, zero, zero.clone(), steps, eos)
+        par, tok, _, st, cum, fin, ln = beam_steps(m, h, st, cum, zero, zero.clone(), steps, eos)
     return par.cpu(), tok.cpu(), cum.cpu(), fin.cpu(), ln.cpu()
 
 
@@ -353,7 +353,7 @@ def test_ptb_size_against_the_stock_op_step():
     topk, div / mod, embedding, index_select) runs on the same T = 1 layer outputs the kernel saw.  Where the stock totals separate the
     W-th from the (W + 1)-th candidate by more than 1e-4 the token sets are equal; the survivors' totals agree to 1e-4 everywhere."""
     from vmlmf_amd import Model, beam_backtrack, beam_gather, lm_beam_step
-    from vmlmf_amd.lm import _KeptImages
+    from vmlmf_amd.decoding import _KeptImages, decode_layers
     torch.manual_seed(7)
     m = Model(10000, 650, 2, 0.0, 0.1, w_rank=32, u_ranks=[32], lstm_type="vmlmf").to(DEV).eval()
     B, W, V, steps = 2, 4, 10000, 6
@@ -383,7 +383,7 @@ def test_ptb_size_against_the_stock_op_step():
             for t, o in zip([t for s in st for t in s], flat):
                 assert torch.equal(o, t.index_select(0, src.long()))
             st = [(flat[0], flat[1]), (flat[2], flat[3])]
-            y, st = m._decode_layers(x.unsqueeze(0), st, "layers")
+            y, st = decode_layers(m, x.unsqueeze(0), st, "layers")
             h = y[-1]
             pars.append(par)
             toks.append(tok)

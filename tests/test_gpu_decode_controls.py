@@ -1,5 +1,5 @@
 """Stopping and token controls on the GPU: vmlmf_decode_choose (csrc/vmlmf_decode.hip, libvmlmf_decode.so) through
-functional.lm_sample(controls=...), Model.generate and DecodeGraph, against the fp64 oracle of test_decode_controls_cpu.py
+decoding.lm_sample(controls=...), Model.generate and DecodeGraph, against the fp64 oracle of test_decode_controls_cpu.py
 (controlled_scores: repetition penalty, logit bias and bans, eos held back below the minimum length) and, for the choice on those
 scores, the oracle of the filters (test_generate_filters_cpu.filtered_sets / judge).
 

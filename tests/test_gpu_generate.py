@@ -225,6 +225,37 @@ def test_layer_paths_agree_and_the_callers_cache_setting_comes_back():
     assert [r._pack_cache for r in m.rnns] == kept and all(c.fills >= 1 for c in kept)
 
 
+def test_every_decode_call_leaves_the_flags_and_the_caches_as_it_found_them():
+    """generate and beam_search, eager and as graphs, and a call that raises behind the prompt's checks: afterwards every module's
+    train / eval flag is the caller's, a layer without kept images has no _pack_cache attribute and a layer with them its own cache."""
+    from vmlmf_amd import Model, cache_packed_parameters
+    torch.manual_seed(11)
+    m = Model(32, 16, 2, 0.0, 0.3, w_rank=4, u_ranks=[4], lstm_type="vmlmf").to(DEV)
+    m.train()
+    m.rnns[1].eval()
+    cache_packed_parameters(m.rnns[0])
+    kept = m.rnns[0]._pack_cache
+    flags = [(mod, mod.training) for mod in m.modules()]
+    assert len({was for _, was in flags}) == 2
+    prompt = _prompt(2, T0=2, V=32, seed=12)
+
+    def untouched(what):
+        assert all(mod.training == was for mod, was in flags), what
+        assert m.rnns[0]._pack_cache is kept and "_pack_cache" not in m.rnns[1].__dict__, what
+
+    calls = {"generate": lambda **kw: m.generate(prompt, 2, **kw), "generate chunk": lambda **kw: m.generate(prompt, 2, chunk=2, **kw),
+             "beam_search": lambda **kw: m.beam_search(prompt, 2, beams=2, **kw),
+             "beam_search chunk": lambda **kw: m.beam_search(prompt, 2, beams=2, chunk=2, **kw)}
+    for what, call in calls.items():
+        out = call()
+        assert out[0].shape[:2] == (2, 2), what
+        untouched(what)
+    for what, call in calls.items():
+        with pytest.raises(IndexError):
+            call(states=m.state_init(2)[:1])       # one layer's states for two layers: raised in Python, in front of any launch
+        untouched(what + ", raising")
+
+
 def test_lm_sample_alone_matches_the_projection():
     from vmlmf_amd import lm_sample
     torch.manual_seed(3)
@@ -289,7 +320,8 @@ def test_a_captured_chunk_on_the_stack_path():
 def test_null_bias_and_null_logprob_through_the_c_abi():
     import ctypes
     from vmlmf_amd import _lib, lm_sample
-    from vmlmf_amd.functional import sample_ticket, _sample_workspace
+    from vmlmf_amd.functional import sample_ticket
+    from vmlmf_amd.decoding import _sample_workspace
     torch.manual_seed(11)
     B, H, V = 5, 48, 301
     h = torch.randn(B, H, device=DEV)

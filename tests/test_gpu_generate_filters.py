@@ -1,5 +1,5 @@
 """Top-k and nucleus (top-p) sampling on the GPU: vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered (csrc/vmlmf_sample.hip) through
-functional.lm_sample, Model.generate and DecodeGraph, against the fp64 oracle of test_generate_filters_cpu.py.
+decoding.lm_sample, Model.generate and DecodeGraph, against the fp64 oracle of test_generate_filters_cpu.py.
 
 A filtered token passes when it lies in the oracle's `hi` set (the tokens possibly kept), its z + G is at least the best of the `lo`
 set (the tokens certainly kept) minus the margin, and lo <= kept <= hi in size; where the argmax of z + G over lo and over hi is one
@@ -68,7 +68,8 @@ def test_lm_sample_filtered_against_the_oracle(shape, name, tau, form):
 @pytest.mark.parametrize("B", [3, 19])
 def test_filters_off_is_the_unfiltered_call_to_the_bit(B):
     from vmlmf_amd import _lib, lm_sample
-    from vmlmf_amd.functional import _sample_workspace, sample_ticket
+    from vmlmf_amd.functional import sample_ticket
+    from vmlmf_amd.decoding import _sample_workspace
     h, w, b, e = _on_device(*{3: (3, 32, 97), 19: (19, 40, 33)}[B])
     H, V = h.shape[1], w.shape[0]
     snap = _snap(5)
@@ -197,9 +198,9 @@ def test_token_frequencies_follow_the_renormalised_softmax(form, kw):
 def test_generate_with_filters_against_the_oracle(kind, B, monkeypatch):
     """B = 3 on the fused form (lm_sample's switch is moved for it: the measured default takes the GEMM form at every width),
     B = 40 on the GEMM form."""
-    from vmlmf_amd import functional
+    from vmlmf_amd import decoding
     if B == 3:
-        monkeypatch.setattr(functional, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 4)
+        monkeypatch.setattr(decoding, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 4)
     m = _small(kind)
     prompt = _prompt(B, seed=11)
     seed, tau, k, p, steps = 0x0F117E2, 0.7, 10, 0.9, 16
@@ -257,14 +258,14 @@ def test_filtered_draws_repeat_with_the_seed_and_replay_fresh_from_a_graph():
 
 def test_a_graphed_chunk_on_the_fused_filtered_form(monkeypatch):
     """The one-launch form with filters captures and replays: its ticket and its score workspace live through a graph."""
-    from vmlmf_amd import functional
-    monkeypatch.setattr(functional, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 4)
+    from vmlmf_amd import decoding
+    monkeypatch.setattr(decoding, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 4)
     m = _small("plain").eval()
     prompt = _prompt(2, seed=3)
     kw = dict(temperature=0.8, top_k=12, top_p=0.95)
     e = m.generate(prompt, 8, seed=5, **kw)
     c = m.generate(prompt, 8, seed=5, chunk=8, **kw)
     assert torch.equal(e[0], c[0]) and torch.equal(e[1], c[1])
-    monkeypatch.setattr(functional, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 0)
+    monkeypatch.setattr(decoding, "SAMPLE_FILTERED_FUSED_MAX_ROWS", 0)
     g = m.generate(prompt, 8, seed=5, **kw)                                # the GEMM form: same noise, scores equal up to fp32 rounding
     assert (g[0] == e[0]).float().mean().item() >= 0.75 and torch.allclose(g[1][g[0] == e[0]], e[1][g[0] == e[0]], atol=1e-4)

@@ -66,10 +66,11 @@ def stock_select(scores, bias, cum, embed, states, B, W):
 
 
 def stock_steps(m, h, states, cum, steps, B, W):
+    from vmlmf_amd.decoding import decode_layers
     for _ in range(steps):
         cum, tok, x, flat = stock_select(torch.mm(h, m.fc.w.t()), m.fc.b, cum, m.embed.w, [t for st in states for t in st], B, W)
         states = [(flat[2 * i], flat[2 * i + 1]) for i in range(L)]
-        y, states = m._decode_layers(x.unsqueeze(0), states, "layers")
+        y, states = decode_layers(m, x.unsqueeze(0), states, "layers")
         h = y[-1]
     return h, states, cum
 
@@ -83,7 +84,7 @@ def main():
     a = ap.parse_args()
     from vmlmf_amd import BeamGraph, Model, _beam, beam_gather
     from vmlmf_amd.functional import PackCache
-    from vmlmf_amd.lm import _KeptImages
+    from vmlmf_amd.decoding import _KeptImages, beam_steps
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(0)
     m = Model(V, H, L, 0.0, 0.05, w_rank=32, u_ranks=[32], lstm_type="vmlmf").cuda().eval()
@@ -129,7 +130,7 @@ def main():
                 rec["stock_step_ms"], rec["stock_step_spread"] = _wall_ms(sg.replay, K, a.reps)
                 del sg, keep
                 zero2 = zero.clone()
-                rec["eager_step_ms"], rec["eager_step_spread"] = _wall_ms(lambda: m._beam_steps(h, st, cum, zero, zero2, K, None), K, a.reps)
+                rec["eager_step_ms"], rec["eager_step_spread"] = _wall_ms(lambda: beam_steps(m, h, st, cum, zero, zero2, K, None), K, a.reps)
                 rec["stock_eager_step_ms"], rec["stock_eager_step_spread"] = _wall_ms(lambda: stock_steps(m, h, st, cum, K, B, W), K, a.reps)
         line = json.dumps(rec)
         print(line, flush=True)

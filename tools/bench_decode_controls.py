@@ -30,10 +30,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 V, H, TOP_K, TOP_P, N = 10000, 650, 40, 0.9, 50
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def replayed_us(launch, reps, n=N):
     """us per call of launch(j) (best of `reps` replays of a graph of n calls); replayed_us.spread: max / min over the replays."""
     for j in range(3):
@@ -86,6 +82,7 @@ def main():
     ap.add_argument("--skip-controls", action="store_true")
     a = ap.parse_args()
     from vmlmf_amd import DecodeGraph, Model, _lib, dropout_advance
+    _ptr = _lib.ptr
     dev = torch.device("cuda", torch.cuda.current_device())
     out = open(a.out, "a") if a.out else None
     libs = [("", _lib.lib())] + ([("parent_", open_parent(a.parent_lib))] if a.parent_lib else [])

@@ -4,7 +4,7 @@ MyVMLSTMGroup ranks [32, 32], for B in {1, 8, 32, 256}.  Paths, same process, sa
   eager_stack  the same with layer_path="stack" (stack_layers' one launch, which packs on every call)
   graph        a DecodeGraph of 16 steps, replayed
   naive        the stock-op loop a user writes without it: embed -> 2 x layer call at T = 1 -> addmm -> softmax -> multinomial
-  sampler_*    the sampler alone, both forms (functional.lm_sample form "fused" / "gemm"), 50 launches replayed from a graph
+  sampler_*    the sampler alone, both forms (decoding.lm_sample form "fused" / "gemm"), 50 launches replayed from a graph
 All four step timings cover the decode steps only (the prompt's pass is outside them); best of --reps, and the spread (max / min).
 --top-k K / --top-p P put the filters on in the eager, graph and sampler_* paths (the stock-op loop stays unfiltered); the record carries
 them.  --models plain,group picks the models.
@@ -97,7 +97,7 @@ def main():
     a = ap.parse_args()
     filters = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p)) if v is not None}
     from vmlmf_amd import DecodeGraph, dropout_advance
-    from vmlmf_amd.lm import _KeptImages
+    from vmlmf_amd.decoding import _KeptImages, decode_steps
     dev = torch.device("cuda")
     rows = []
     out = open(a.out, "w") if a.out else None
@@ -134,7 +134,7 @@ def main():
             for path in ("layers", "stack"):
                 def eager():
                     with torch.no_grad(), _KeptImages(m):
-                        m._decode(hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path, **filters)
+                        decode_steps(m, hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path, **filters)
                 t = _timed(eager, a.reps)
                 res["eager" if path == "layers" else "eager_stack"] = _rec(t, B, steps)
             g = DecodeGraph(m, hv, st, K, temperature=1.0, **filters)

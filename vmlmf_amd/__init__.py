@@ -6,11 +6,10 @@ MI355X (gfx950), behind the reference's own nn.Module API.
     from vmlmf_amd import nll_loss                                     #       (train_test/lm_test.py)
 """
 from .cells import MyVMLMFCell, MyVMLMFCellg2, MyVMLMFgCellg2, MyLSTMCell, MyLSTM, Net, TIME_STEPS, RECURRENT_MAX, RECURRENT_MIN
-from .lm import MyVMLSTM, MyVMLSTMGroup, Embed, Linear, LSTM, Model, DecodeGraph, BeamGraph
+from .lm import MyVMLSTM, MyVMLSTMGroup, Embed, Linear, LSTM, Model
 from .functional import (vmlmf_sequence, vmlmf_stack, head_linear, cross_entropy, CrossEntropyLoss, nll_loss, linear_nll, lm_head_loss, embedding, unit_gradient,
-                         set_compute_dtype, cache_packed_parameters, dropout, dropout_state, dropout_advance, embedding_dropout,
-                         lm_sample, lm_beam_step, beam_gather, beam_backtrack)
-from ._decode import DecodeControls
+                         set_compute_dtype, cache_packed_parameters, dropout, dropout_state, dropout_advance, embedding_dropout)
+from .decoding import DecodeGraph, BeamGraph, DecodeControls, lm_sample, lm_beam_step, beam_gather, beam_backtrack
 from . import optim
 from .graphed import GraphedTrainStep
 

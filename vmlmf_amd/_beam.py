@@ -11,6 +11,7 @@ import os
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_beam.so")
 ABI_VERSION = 1
@@ -35,17 +36,7 @@ def lib():
     """The loaded libvmlmf_beam.so.  Raises if it has not been built: there is no fallback path."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `make -C {_lib.CSRC}` (or __graft_entry__.build()). "
-                "vmlmf_amd has no stock-op fallback for the beam-search step.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)  # AttributeError if the export is missing
-            fn.restype, fn.argtypes = res, args
-        if handle.vmlmf_beam_abi_version() != ABI_VERSION:
-            raise RuntimeError("libvmlmf_beam.so ABI version mismatch: rebuild")
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, SYMBOLS, "vmlmf_beam_abi_version", ABI_VERSION, "stock-op fallback for the beam-search step")
     return _handle
 
 
@@ -67,10 +58,6 @@ def check_beams(beams, V=None):
     if V is not None and W > V:
         raise ValueError(f"vmlmf_amd: beams={W} exceeds the vocabulary ({V} tokens): a beam offers V candidates")
     return W
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _require(t, what, dtype=torch.float32):
@@ -160,9 +147,9 @@ def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
     src = torch.empty(B * W, device=dev, dtype=torch.int32)
     xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
     with _lib.on_device(dev):
-        check(handle.vmlmf_beam_step(B, W, H, V, _ptr(scores), _ptr(bias), _ptr(cum), _ptr(finished), _ptr(length), eos, _ptr(embed),
-                                     _ptr(parent), _ptr(token), _ptr(total), _ptr(fin), _ptr(ln), _ptr(xn), _ptr(src), _ptr(ticket),
-                                     _ptr(ws), ws.numel() * 8, _lib.raw_stream(dev)))
+        check(handle.vmlmf_beam_step(B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
+                                     ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket),
+                                     ptr(ws), ws.numel() * 8, _lib.raw_stream(dev)))
     return parent, token, total, fin, ln, xn, src
 
 
@@ -189,7 +176,7 @@ def beam_gather(tensors, src_row):
     dev = srcs[0].device
     rows_c = src_row.contiguous()
     with _lib.on_device(dev):
-        check(lib().vmlmf_beam_gather(n, rows, H, _ptr(rows_c), sp, dp, _lib.raw_stream(dev)))
+        check(lib().vmlmf_beam_gather(n, rows, H, ptr(rows_c), sp, dp, _lib.raw_stream(dev)))
     return dsts
 
 
@@ -213,5 +200,5 @@ def beam_backtrack(parent, token, order=None):
     p, t = parent.contiguous(), token.contiguous()
     dev = p.device
     with _lib.on_device(dev):
-        check(lib().vmlmf_beam_backtrack(steps, B, W, _ptr(p), _ptr(t), _ptr(order), _ptr(out), _lib.raw_stream(dev)))
+        check(lib().vmlmf_beam_backtrack(steps, B, W, ptr(p), ptr(t), ptr(order), ptr(out), _lib.raw_stream(dev)))
     return out

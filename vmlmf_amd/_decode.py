@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_decode.so")
 ABI_VERSION = 1
@@ -39,17 +40,8 @@ def lib():
     """The loaded libvmlmf_decode.so.  Raises if it has not been built: there is no fallback path."""
     global _handle
     if _handle is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `make -C {_lib.CSRC}` (or __graft_entry__.build()). "
-                "vmlmf_amd has no stock-op fallback for the controlled choice of Model.generate.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)  # AttributeError if the export is missing
-            fn.restype, fn.argtypes = res, args
-        if handle.vmlmf_decode_abi_version() != ABI_VERSION:
-            raise RuntimeError("libvmlmf_decode.so ABI version mismatch: rebuild")
-        _handle = handle
+        _handle = _lib.load(LIB_PATH, SYMBOLS, "vmlmf_decode_abi_version", ABI_VERSION,
+                            "stock-op fallback for the controlled choice of Model.generate")
     return _handle
 
 
@@ -163,10 +155,6 @@ class DecodeControls:
                         self.seen.data_ptr(), self.finished.data_ptr(), self.length.data_ptr())
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def decode_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls, tokens, logp, xn, kept):
     """The vmlmf_decode_choose launch on checked, contiguous arguments: scores (B, V) without the bias; outputs are written in place."""
     B, V = scores.shape
@@ -177,5 +165,5 @@ def decode_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls,
     handle = lib()
     c = controls.struct()
     with _lib.on_device(dev):
-        check(handle.vmlmf_decode_choose(B, H, V, _ptr(scores), _ptr(bias), _ptr(embed), inv, top_k, top_p, _ptr(state), int(step),
-                                         ctypes.byref(c), _ptr(tokens), _ptr(logp), _ptr(xn), _ptr(kept), _lib.raw_stream(dev)))
+        check(handle.vmlmf_decode_choose(B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
+                                         ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept), _lib.raw_stream(dev)))

@@ -189,21 +189,31 @@ def build_torch_binding():
     return os.path.join(_HERE, "lib", "libvmlmf_torch.so")
 
 
+def load(path, symbols, abi_symbol, abi_version, no_fallback):
+    """The shared library at `path`, opened, with every entry of `symbols` ({name: (restype, argtypes)}) bound and its `abi_symbol`() compared
+    with `abi_version`.  RuntimeError if the file has not been built (`no_fallback`: what the caller has no other path for)."""
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()). "
+                           f"vmlmf_amd has no {no_fallback}.")
+    handle = ctypes.CDLL(path)
+    for name, (res, args) in symbols.items():
+        fn = getattr(handle, name)  # AttributeError if the export is missing
+        fn.restype, fn.argtypes = res, args
+    if getattr(handle, abi_symbol)() != abi_version:
+        raise RuntimeError(f"{os.path.basename(path)} ABI version mismatch: rebuild")
+    return handle
+
+
+def ptr(t):
+    """A tensor's device address as the C ABI takes it (None stays a null pointer)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
 def lib():
     """The loaded shared library.  Raises if it has not been built: there is no fallback path."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()). "
-                "vmlmf_amd has no CPU / PyTorch fallback for the hot path.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)  # AttributeError if the export is missing
-            fn.restype, fn.argtypes = res, args
-        if handle.vmlmf_abi_version() != ABI_VERSION:
-            raise RuntimeError("libvmlmf_hip.so ABI version mismatch: rebuild")
-        _lib = handle
+        _lib = handle = load(LIB_PATH, SYMBOLS, "vmlmf_abi_version", ABI_VERSION, "CPU / PyTorch fallback for the hot path")
         if ranks_share_a_device() and "VMLMF_WRIDE" not in os.environ:
             # the riding weight-gradient workers wait for row workgroups of their own launch; when several processes queue
             # launches on ONE device a resident worker can starve the rows it waits for (DESIGN.md section 6): such jobs

@@ -1,0 +1,431 @@
+"""Decoding the language model (lm.Model): what stands behind Model.generate and Model.beam_search.  The reference has no decoder;
+lm.py holds its layers, this module everything that continues a prompt with them.
+
+  lm_sample, sample_filters                  the head and the choice of the next token in one launch (C ABI: vmlmf_lm_sample ...)
+  lm_beam_step, beam_gather, beam_backtrack  the beam step, the state reorder and the read-back (_beam.py, a library of its own)
+  decode_steps, beam_steps                   the step loops: a choice, then the layers at T = 1 - no host synchronisation
+  DecodeGraph, BeamGraph                     those loops captured into a hipGraph
+  generate, beam_search                      the calls behind Model's methods of the same names, where the contract is written down
+"""
+from __future__ import annotations
+
+import contextlib
+
+import torch
+
+from . import _beam, _decode, _lib
+from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
+from ._decode import DecodeControls
+from ._lib import ptr
+from .functional import PackCache, _require_hip, _workspace, dropout_advance, sample_ticket
+from .lm import stack_layers
+
+
+# ---- head + token choice in one launch per token (C ABI: vmlmf_lm_sample; csrc/vmlmf_sample.hip) ---------------------------------
+def _sample_workspace(dev, nbytes):
+    return _workspace(dev, nbytes, "sample")
+
+
+SAMPLE_FUSED_MAX_ROWS = 4   # measured at the PTB size: fused 25.6 us against 37.2 at 1 row, 40.5 against 37.8 at 8 (lm_sampling.md)
+# ... with a filter on (top_k / top_p) the fused launch's last workgroup selects and chooses its rows one after the other, 256 threads
+# a row; the choice launch behind the GEMM gives every row 1024.  Measured at the PTB size, top_k 40 / top_p 0.9 / both: fused 87.5 /
+# 105.9 / 125.6 us at 1 row against 47.4 / 56.7 / 65.4 for GEMM + choice (291 / 364 / 445 against 47.9 / 57.3 / 66.1 at 4 rows): the GEMM
+# form at every width; form="fused" still reaches the one-launch form (lm_sampling.md)
+SAMPLE_FILTERED_FUSED_MAX_ROWS = 0
+
+
+def sample_filters(top_k, top_p, V=None):
+    """(top_k, top_p) as the C ABI takes them: (0, 1.0) is off.  ValueError for top_k < 0 and for top_p outside (0, 1]."""
+    k = 0 if top_k is None else int(top_k)
+    p = 1.0 if top_p is None else float(top_p)
+    if k < 0:
+        raise ValueError(f"vmlmf_amd: top_k must be >= 0 (None / 0: off), got {top_k}")
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"vmlmf_amd: top_p must lie in (0, 1] (None / 1: off), got {top_p}")
+    if V is not None and k >= V:
+        k = 0
+    return k, p
+
+
+def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None, top_k=None, top_p=None, return_kept=False,
+              controls=None):
+    """The next token of every row of h (B, H) - the top layer's output - under Linear(weight (V, H), bias (V)), in ONE launch that
+    never writes the (B, V) scores.  temperature 0: greedy (argmax, ties to the lowest index); tau > 0: a draw from softmax(scores / tau)
+    by Gumbel-max, its noise from Philox4x32-10 at (state = a {seed, offset} snapshot of dropout_advance(), position step * B + b,
+    vocabulary row, the sampler's own site _lib.SITE_SAMPLE).  Returns (tokens (B) int64, logprobs (B)) - logprobs are the untempered
+    log-softmax of the chosen tokens, what nll_loss charges for them - and, with embed (V, H), x_next = embed[tokens] (B, H).
+    form: "fused" (vmlmf_lm_sample: head and choice in one launch, no score tensor), "gemm" (the library GEMM's (B, V) scores, then
+    vmlmf_lm_choose: one workgroup per row), None: fused up to SAMPLE_FUSED_MAX_ROWS rows, gemm beyond (docs/design/lm_sampling.md).
+    Both forms draw the same noise; their scores differ in fp32 rounding only.
+    top_k / top_p (None: off; 0, k >= V and 1.0 too): the draw is restricted to the first k tokens of the order (larger score first,
+    equal scores to the lower index) and, of those, to the shortest prefix whose renormalised mass under softmax(scores / tau) reaches
+    top_p (vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered; include/vmlmf_hip.h has the contract).  The noise and the
+    log-probabilities are those of the unfiltered call; greedy decoding is unchanged by any filter.  With a filter on form=None is
+    fused up to SAMPLE_FILTERED_FUSED_MAX_ROWS rows (0: measured, the GEMM form is faster at every width).  return_kept: a last result, kept (B) int32 - how many tokens survived per row
+    (V where no selection ran: filters off, or greedy).
+    controls: a DecodeControls (eos, min_length, repetition_penalty, logit_bias / bans and the rows' seen / finished / length state):
+    the choice runs on the controlled scores in ONE launch of its own library behind the head's GEMM (vmlmf_decode_choose,
+    include/vmlmf_decode.h has the contract; form "gemm" only), which updates the controls' state in place; the noise and the
+    log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf."""
+    for t, what in ((h, "h"), (weight, "weight")):
+        _require_hip(t, what)
+    if bias is not None:
+        _require_hip(bias, "bias")
+    if embed is not None:
+        _require_hip(embed, "embedding table")
+    temperature = float(temperature)
+    if not temperature >= 0.0:
+        raise ValueError(f"vmlmf_amd.lm_sample: temperature must be >= 0, got {temperature}")
+    inv = 0.0 if temperature == 0.0 else 1.0 / temperature
+    if inv > 0.0 and (state is None or not state.is_cuda or state.dtype != torch.int64 or state.numel() != 2):
+        raise RuntimeError("vmlmf_amd.lm_sample: sampling (temperature > 0) needs a {seed, offset} snapshot: two int64 on the device")
+    h2 = h.reshape(-1, h.shape[-1]).contiguous()
+    B, H = h2.shape
+    w = weight.contiguous()
+    V = w.shape[0]
+    if w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
+        raise RuntimeError(f"vmlmf_amd.lm_sample: h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias / embed must be (V) / (V, H)")
+    k, p = sample_filters(top_k, top_p, V)
+    filtered = inv > 0.0 and (k > 0 or p < 1.0)      # greedy: the argmax is always kept, the existing kernels run
+    dev = h2.device
+    lib = _lib.lib()
+    tokens = torch.empty(B, device=dev, dtype=torch.int64)
+    logp = torch.empty(B, device=dev, dtype=torch.float32)
+    xn = torch.empty((B, H), device=dev, dtype=torch.float32) if embed is not None else None
+    if not return_kept:
+        kept = None
+    elif filtered or controls is not None:
+        kept = torch.empty(B, device=dev, dtype=torch.int32)
+    else:
+        kept = torch.full((B,), V, device=dev, dtype=torch.int32)
+    if controls is not None and form not in (None, "gemm"):
+        raise ValueError(f"vmlmf_amd.lm_sample: the controlled choice has no fused-head form (form must be 'gemm' or None, got {form!r})")
+    if form is None:
+        form = "fused" if B <= (SAMPLE_FILTERED_FUSED_MAX_ROWS if filtered else SAMPLE_FUSED_MAX_ROWS) else "gemm"
+    outs = lambda: tuple(t for t in (tokens, logp, xn, kept) if t is not None)
+    state_p = None if inv == 0.0 else ptr(state)
+    bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
+    bias_p, embed_p = ptr(bias_c), ptr(embed_c)
+    if controls is not None:
+        _decode.decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn,
+                              kept)
+        return outs()
+    if form == "gemm":
+        scores = torch.mm(h2, w.t())
+        with _lib.on_device(dev):
+            if filtered:
+                _lib.check(lib.vmlmf_lm_choose_filtered(B, H, V, ptr(scores), bias_p, embed_p, inv, k, p, state_p, int(step), ptr(tokens),
+                                                        ptr(logp), ptr(xn), ptr(kept), _lib.raw_stream(dev)))
+            else:
+                _lib.check(lib.vmlmf_lm_choose(B, H, V, ptr(scores), bias_p, embed_p, inv, state_p, int(step), ptr(tokens), ptr(logp),
+                                               ptr(xn), _lib.raw_stream(dev)))
+        return outs()
+    if form != "fused":
+        raise ValueError(f"vmlmf_amd.lm_sample: form must be 'fused', 'gemm' or None, got {form!r}")
+    nbytes = (lib.vmlmf_lm_sample_filtered_workspace_bytes if filtered else lib.vmlmf_lm_sample_workspace_bytes)(B, V)
+    ws = _sample_workspace(dev, nbytes)
+    with _lib.on_device(dev):
+        if filtered:
+            _lib.check(lib.vmlmf_lm_sample_filtered(B, H, V, ptr(h2), ptr(w), bias_p, embed_p, inv, k, p, state_p, int(step),
+                                                    ptr(tokens), ptr(logp), ptr(xn), ptr(kept), ptr(sample_ticket(dev)), ptr(ws),
+                                                    nbytes, _lib.raw_stream(dev)))
+        else:
+            _lib.check(lib.vmlmf_lm_sample(B, H, V, ptr(h2), ptr(w), bias_p, embed_p, inv, state_p, int(step), ptr(tokens),
+                                           ptr(logp), ptr(xn), ptr(sample_ticket(dev)), ptr(ws), nbytes, _lib.raw_stream(dev)))
+    return outs()
+
+
+# ---- the step loops ----------------------------------------------------------------------------------------------------------------
+def decode_layers(model, x, states, layer_path):
+    """The layers at T = 1: x (1, B, H) -> (y (1, B, H), states).  layer_path "stack": stack_layers' one launch where it covers the
+    layers (it packs the parameters on every call); otherwise a call per layer - VMLMF layers reuse kept images (_KeptImages)."""
+    if layer_path == "stack":
+        stacked = stack_layers(model.rnns, x, states)
+        if stacked is not None:
+            return stacked[0], list(stacked[1])
+    states = list(states)
+    for i, rnn in enumerate(model.rnns):
+        x, states[i] = rnn(x, states[i])
+    return x, states
+
+
+def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None, controls=None):
+    """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
+    the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
+    capturable (DecodeGraph).  controls: a DecodeControls - the choice is then the controlled launch behind the head's GEMM
+    (vmlmf_decode_choose), which moves the controls' state on in place."""
+    toks, lps = [], []
+    for j in range(steps):
+        tok, lp, x = lm_sample(h, model.fc.w, model.fc.b, temperature, snap, j, embed=model.embed.w, top_k=top_k, top_p=top_p,
+                               controls=controls)
+        toks.append(tok)
+        lps.append(lp)
+        y, states = decode_layers(model, x.unsqueeze(0), states, layer_path)
+        h = y[-1]
+    return torch.stack(toks), torch.stack(lps), h, states
+
+
+def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None):
+    """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
+    (lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
+    2 L state tensors follow their hypotheses (beam_gather), then the layers at T = 1 on the B W rows.  No host
+    synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length)."""
+    parents, toks = [], []
+    for _ in range(steps):
+        par, tok, cum, finished, length, x, src = lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w,
+                                                               buffers=buffers)
+        parents.append(par)
+        toks.append(tok)
+        flat = beam_gather([t for st in states for t in st], src)
+        states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
+        y, states = decode_layers(model, x.unsqueeze(0), states, "layers")
+        h = y[-1]
+    return torch.stack(parents), torch.stack(toks), h, states, cum, finished, length
+
+
+# What a decode carries from step to step, as one flat list: [h, h_0, c_0, ... h_L-1, c_L-1] and, for beams, cum, finished and length
+# behind them.  The two forms below are the step loops above on such a list: carried -> (outputs, carried after the steps).
+def _pairs(flat):
+    return [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
+
+
+def _sampled(model, gen, carried, steps, temperature, layer_path, top_k, top_p, controls):
+    """decode_steps, the generator `gen` (None: greedy) snapshotted and advanced in front."""
+    snap = dropout_advance(gen) if gen is not None else None
+    toks, lps, h, states = decode_steps(model, carried[0], _pairs(carried[1:]), steps, temperature, snap, layer_path, top_k, top_p, controls)
+    return (toks, lps), [h, *(t for st in states for t in st)]
+
+
+def _beamed(model, carried, steps, eos, buffers=None):
+    h, *flat, cum, finished, length = carried
+    par, tok, h, states, cum, finished, length = beam_steps(model, h, _pairs(flat), cum, finished, length, steps, eos, buffers)
+    return (par, tok), [h, *(t for st in states for t in st), cum, finished, length]
+
+
+def _fresh_beams(B, W, dev):
+    """(cum, finished, length), each (B, W), of a search that starts: beam 0 of a row at score 0, the others at -inf."""
+    cum = torch.full((B, W), float("-inf"), device=dev)
+    cum[:, 0] = 0.0
+    return cum, torch.zeros((B, W), dtype=torch.int32, device=dev), torch.zeros((B, W), dtype=torch.int32, device=dev)
+
+
+# ---- the step loops as captured graphs ---------------------------------------------------------------------------------------------
+class _KeptImages:
+    """`with _KeptImages(model[, caches]):` every VMLMF layer of the model keeps its packed parameter images for the duration
+    (functional.cache_packed_parameters) - a layer that already keeps them keeps its own cache -, and the caller's setting comes back
+    afterwards.  caches: the PackCache of each such layer, in order (a captured graph holds its own: the graph reads their buffers)."""
+
+    def __init__(self, model, caches=None):
+        self.layers = [m for m in model.modules() if hasattr(m, "kernel_params")]
+        self.caches = caches
+
+    def __enter__(self):
+        self.saved = [m.__dict__.get("_pack_cache", _UNSET) for m in self.layers]
+        for i, (m, was) in enumerate(zip(self.layers, self.saved)):
+            if self.caches is not None:
+                m._pack_cache = self.caches[i]
+            elif was is _UNSET or was is None:
+                m._pack_cache = PackCache()
+        return self
+
+    def __exit__(self, *exc):
+        for m, was in zip(self.layers, self.saved):
+            if was is _UNSET:
+                m.__dict__.pop("_pack_cache", None)
+            else:
+                m._pack_cache = was
+        return False
+
+
+_UNSET = object()
+
+
+class _StepGraph:
+    """What DecodeGraph and BeamGraph share: steps of a model captured once into a hipGraph - linear, on one stream - over buffers
+    this object owns, so that a replay continues where the previous one stopped."""
+
+    def _capture(self, model, carried, step, warm_up=None):
+        """carried: the tensors a step reads and hands on, cloned into `self.carried`; step(carried) -> (outputs, carried after it).
+        One PackCache per VMLMF layer (`self.caches`: the graph reads their buffers); a warm-up outside the capture, on a side stream
+        and on copies - warm_up(copies), default step - packs the images, loads the libraries and creates tickets and workspaces;
+        then the capture on the owned buffers, the copy-back of every carried tensor its last work."""
+        self.carried = [t.detach().clone() for t in carried]
+        self.caches = [PackCache() for m in model.modules() if hasattr(m, "kernel_params")]
+        dev = self.carried[0].device
+        with torch.no_grad(), _KeptImages(model, self.caches):
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                (warm_up or step)([t.clone() for t in self.carried])
+            torch.cuda.current_stream(dev).wait_stream(side)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self.outputs, after = step(self.carried)
+                for t, new in zip(self.carried, after):
+                    t.copy_(new)
+
+    def replay(self):
+        self.graph.replay()
+        return tuple(t.clone() for t in self.outputs)
+
+
+class DecodeGraph(_StepGraph):
+    """`steps` decode steps of a Model (decode_steps: per step the vmlmf_lm_sample launch and the layers at T = 1) captured once into
+    a hipGraph - linear, on one stream.  replay() continues from where the previous replay stopped (the top layer's output and the
+    layers' states live in this object's buffers, h / states) and returns (tokens (steps, B), logprobs (steps, B)); with temperature > 0
+    the first node snapshots and advances the model's sampler_state(), so every replay draws fresh tokens and a new capture from the same
+    seed and inputs repeats the first replay.  The generator is the sampler_state() tensor of construction time: re-seeding the model
+    (sampler_state(seed)) puts a new tensor in its place, which this graph does not see - build a new DecodeGraph after re-seeding, as
+    after the parameters change (the layers read kept parameter images packed at construction).  Replay DecodeGraphs one after
+    another, never two at once on different streams: the sampler's ticket words are taken from a ring of 16 per device (as the
+    criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count.
+    top_k / top_p: the filters of Model.generate, fixed at construction.
+    controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
+    length -, so replays continue one decode: finished rows stay finished, seen accumulates (the warm-up runs on a clone)."""
+
+    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None):
+        self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
+        sample_filters(top_k, top_p)
+        self.top_k, self.top_p, self.controls = top_k, top_p, controls
+        self.gen = model.sampler_state() if self.temperature > 0 else None
+
+        def step(carried, controls=controls):
+            return _sampled(model, self.gen, carried, self.steps, self.temperature, layer_path, top_k, top_p, controls)
+
+        def warm_up(carried):           # on a clone of the controls; the generator is put back
+            saved = None if self.gen is None else self.gen.clone()
+            step(carried, None if controls is None else controls.clone())
+            if saved is not None:
+                self.gen.copy_(saved)
+        self._capture(model, [h, *(t for st in states for t in st)], step, warm_up)
+        self.h, *flat = self.carried
+        self.states, (self.tokens, self.logprobs) = _pairs(flat), self.outputs
+
+
+class BeamGraph(_StepGraph):
+    """`steps` steps of Model.beam_search (beam_steps: per step the head's GEMM, the vmlmf_beam_step launch, the vmlmf_beam_gather
+    launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are the beams' (row
+    b W + w) of `beams` = W beams per batch row; cum / finished / length (B, W) default to a fresh search (beam 0 at 0, the others at -inf).  replay() continues from where
+    the previous replay stopped - h, states, cum, finished and length live in this object's buffers - and returns (parents, tokens),
+    both (steps, B, W), for beam_backtrack.  The ticket words and the workspace of the selection are this graph's own, so
+    graphs may be replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after
+    the parameters change."""
+
+    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None):
+        self.model, self.steps, self.eos = model, int(steps), eos
+        W = _beam.check_beams(beams, model.vocab_size)
+        B = h.shape[0] // W
+        fresh = _fresh_beams(B, W, h.device)
+        cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), fresh))
+        self.buffers = _beam.new_step_buffers(h.device, B, W, model.vocab_size)
+        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32)],
+                      lambda carried: _beamed(model, carried, self.steps, eos, self.buffers))
+        self.h, *flat, self.cum, self.finished, self.length = self.carried
+        self.states, (self.parents, self.tokens) = _pairs(flat), self.outputs
+
+
+# ---- one call: the checks, the prompt, the steps -----------------------------------------------------------------------------------
+def _check_call(model, prompt, method, kernel):
+    """RuntimeError unless the model and the prompt live on a HIP device and the prompt is (T0, B) int64."""
+    if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and model.embed.w.is_cuda):
+        raise RuntimeError(f"vmlmf_amd: Model.{method} runs on the HIP {kernel} only: move the model and the prompt to 'cuda' "
+                           "(no CPU fallback)")
+    if prompt.dim() != 2 or prompt.dtype != torch.int64:
+        raise RuntimeError(f"vmlmf_amd: Model.{method} takes a (T0, B) int64 prompt")
+
+
+def _check_chunk(method, chunk, steps):
+    if chunk is not None and (int(chunk) < 1 or steps % int(chunk) != 0):
+        raise ValueError(f"vmlmf_amd: Model.{method}: chunk={chunk} must divide steps={steps}")
+
+
+@contextlib.contextmanager
+def _session(model, prompt, states):
+    """`with _session(model, prompt, states) as (h, states):` the model in eval mode, without autograd and on kept parameter images
+    for the duration; h (B, H) is the top layer's output behind the prompt's last token, states (default: state_init) have taken the
+    prompt in.  Every module's train / eval flag is as the caller left it afterwards, whatever was raised."""
+    states = model.state_init(prompt.shape[1]) if states is None else list(states)
+    modes = [(mod, mod.training) for mod in model.modules()]
+    model.train(False)
+    try:
+        with torch.no_grad(), _KeptImages(model):
+            h, states = model.features(prompt, list(states))
+            yield h[-1], states
+    finally:
+        for mod, was in modes:
+            mod.training = was
+
+
+def _run(steps, chunk, eager, graph):
+    """The steps of one call, as (outputs, carried after them): eager(), or - chunk=K - graph()'s K captured steps replayed
+    steps / K times: the replays' outputs concatenated, the carried tensors cloned out of the graph's buffers."""
+    if chunk is None:
+        return eager()
+    g = graph()
+    outs = [g.replay() for _ in range(steps // int(chunk))]
+    return tuple(torch.cat(o) for o in zip(*outs)), [t.clone() for t in g.carried]
+
+
+def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+             eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False):
+    """Model.generate (lm.py has the contract)."""
+    sample_filters(top_k, top_p)
+    ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
+                    banned_tokens=banned_tokens)
+    eos_c, min_c, _, banned = _decode.check_controls(model.vocab_size, **ctl_args)
+    controlled = _decode.controls_on(eos, repetition_penalty, logit_bias, banned_tokens)
+    if controlled:
+        _decode.check_bias(model.vocab_size, logit_bias, banned, eos_c, min_c)
+    _check_call(model, prompt, "generate", "sampler kernel (vmlmf_lm_sample)")
+    steps, temperature = int(steps), float(temperature)
+    _check_chunk("generate", chunk, steps)
+    B, dev = prompt.shape[1], prompt.device
+    gen = model.sampler_state(seed) if temperature > 0 else None
+    with _session(model, prompt, states) as (h, states):
+        controls = DecodeControls(B, model.vocab_size, dev, prompt=prompt, _checked=True, **ctl_args) if controlled else None
+        if steps == 0:
+            tokens, logprobs = torch.empty((0, B), dtype=torch.int64, device=dev), torch.empty((0, B), device=dev)
+        else:
+            (tokens, logprobs), (_, *flat) = _run(
+                steps, chunk,
+                lambda: _sampled(model, gen, [h, *(t for st in states for t in st)], steps, temperature, layer_path, top_k, top_p, controls),
+                lambda: DecodeGraph(model, h, states, int(chunk), temperature, layer_path, top_k, top_p, controls))
+            states = _pairs(flat)
+        if not return_lengths:
+            return tokens, logprobs, states
+        lengths = controls.length.clone() if controls is not None else torch.full((B,), steps, dtype=torch.int32, device=dev)
+        return tokens, logprobs, lengths, states
+
+
+def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
+    """Model.beam_search (lm.py has the contract)."""
+    W = _beam.check_beams(beams, model.vocab_size)
+    steps, alpha = int(steps), float(length_penalty)
+    if eos is not None and not 0 <= int(eos) < model.vocab_size:
+        raise ValueError(f"vmlmf_amd: Model.beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
+    if not alpha >= 0.0:
+        raise ValueError(f"vmlmf_amd: Model.beam_search: length_penalty must be >= 0, got {length_penalty}")
+    if steps < 0:
+        raise ValueError(f"vmlmf_amd: Model.beam_search: steps must be >= 0, got {steps}")
+    _check_chunk("beam_search", chunk, steps)
+    _check_call(model, prompt, "beam_search", "beam-step kernel (vmlmf_beam_step)")
+    B, dev = prompt.shape[1], prompt.device
+    with _session(model, prompt, states) as (h, states):
+        h = h.repeat_interleave(W, 0)
+        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        cum, finished, length = _fresh_beams(B, W, dev)
+        if steps == 0:
+            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
+        (parents, toks), (_, *flat, cum, finished, length) = _run(
+            steps, chunk,
+            lambda: _beamed(model, [h, *(t for st in states for t in st), cum, finished, length], steps, eos),
+            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length))
+        order = None
+        if alpha > 0.0:
+            key = cum / length.to(torch.float32) ** alpha
+            order = torch.sort(key, dim=1, descending=True, stable=True).indices
+            cum, length = cum.gather(1, order), length.gather(1, order)
+            rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
+            flat = beam_gather(flat, rows)
+            order = order.to(torch.int32)
+        return beam_backtrack(parents, toks, order), cum, length, _pairs(flat)

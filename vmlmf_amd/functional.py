@@ -10,16 +10,13 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 # order in which parameter tensors are passed to VmlmfSeqFn (and gradients come back)
 #   V1-V4: dia_x dia_h u_x v_x b_x b_h u_h[0] v_h[0] (u_h[1] v_h[1])
 #   V6:    u_x v_x b_x b_h u_h[0] v_h[0] u_h[1] v_h[1]                       (no vm vectors)
 #   V5:    w u w1 w2 w3 w4 u1 u2 u3 u4 bias_i bias_f bias_o bias_c          (gate order of the kernels: i, f, o, c~)
 N_FIXED = 6
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 # ---- C++ binding (csrc/torch_binding.cpp: TORCH_LIBRARY "vmlmf" with C++ autograd functions over the same C ABI) --------
@@ -1242,122 +1239,3 @@ def linear_nll(h, weight, bias, y, chunk_rows=2048, fused=None):
     if use and h.is_cuda:
         return LinearNllFn.apply(h, weight, bias, y, chunk_rows)
     return nll_loss(torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t()), y)
-
-
-# ---- decoding the LM: head + token choice in one launch per token (C ABI: vmlmf_lm_sample; csrc/vmlmf_sample.hip) ---------------
-def _sample_workspace(dev, nbytes):
-    return _workspace(dev, nbytes, "sample")
-
-
-SAMPLE_FUSED_MAX_ROWS = 4   # measured at the PTB size: fused 25.6 us against 37.2 at 1 row, 40.5 against 37.8 at 8 (lm_sampling.md)
-# ... with a filter on (top_k / top_p) the fused launch's last workgroup selects and chooses its rows one after the other, 256 threads
-# a row; the choice launch behind the GEMM gives every row 1024.  Measured at the PTB size, top_k 40 / top_p 0.9 / both: fused 87.5 /
-# 105.9 / 125.6 us at 1 row against 47.4 / 56.7 / 65.4 for GEMM + choice (291 / 364 / 445 against 47.9 / 57.3 / 66.1 at 4 rows): the GEMM
-# form at every width; form="fused" still reaches the one-launch form (lm_sampling.md)
-SAMPLE_FILTERED_FUSED_MAX_ROWS = 0
-
-
-def sample_filters(top_k, top_p, V=None):
-    """(top_k, top_p) as the C ABI takes them: (0, 1.0) is off.  ValueError for top_k < 0 and for top_p outside (0, 1]."""
-    k = 0 if top_k is None else int(top_k)
-    p = 1.0 if top_p is None else float(top_p)
-    if k < 0:
-        raise ValueError(f"vmlmf_amd: top_k must be >= 0 (None / 0: off), got {top_k}")
-    if not (0.0 < p <= 1.0):
-        raise ValueError(f"vmlmf_amd: top_p must lie in (0, 1] (None / 1: off), got {top_p}")
-    if V is not None and k >= V:
-        k = 0
-    return k, p
-
-
-def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None, top_k=None, top_p=None, return_kept=False,
-              controls=None):
-    """The next token of every row of h (B, H) - the top layer's output - under Linear(weight (V, H), bias (V)), in ONE launch that
-    never writes the (B, V) scores.  temperature 0: greedy (argmax, ties to the lowest index); tau > 0: a draw from softmax(scores / tau)
-    by Gumbel-max, its noise from Philox4x32-10 at (state = a {seed, offset} snapshot of dropout_advance(), position step * B + b,
-    vocabulary row, the sampler's own site _lib.SITE_SAMPLE).  Returns (tokens (B) int64, logprobs (B)) - logprobs are the untempered
-    log-softmax of the chosen tokens, what nll_loss charges for them - and, with embed (V, H), x_next = embed[tokens] (B, H).
-    form: "fused" (vmlmf_lm_sample: head and choice in one launch, no score tensor), "gemm" (the library GEMM's (B, V) scores, then
-    vmlmf_lm_choose: one workgroup per row), None: fused up to SAMPLE_FUSED_MAX_ROWS rows, gemm beyond (docs/design/lm_sampling.md).
-    Both forms draw the same noise; their scores differ in fp32 rounding only.
-    top_k / top_p (None: off; 0, k >= V and 1.0 too): the draw is restricted to the first k tokens of the order (larger score first,
-    equal scores to the lower index) and, of those, to the shortest prefix whose renormalised mass under softmax(scores / tau) reaches
-    top_p (vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered; include/vmlmf_hip.h has the contract).  The noise and the
-    log-probabilities are those of the unfiltered call; greedy decoding is unchanged by any filter.  With a filter on form=None is
-    fused up to SAMPLE_FILTERED_FUSED_MAX_ROWS rows (0: measured, the GEMM form is faster at every width).  return_kept: a last result, kept (B) int32 - how many tokens survived per row
-    (V where no selection ran: filters off, or greedy).
-    controls: a DecodeControls (eos, min_length, repetition_penalty, logit_bias / bans and the rows' seen / finished / length state):
-    the choice runs on the controlled scores in ONE launch of its own library behind the head's GEMM (vmlmf_decode_choose,
-    include/vmlmf_decode.h has the contract; form "gemm" only), which updates the controls' state in place; the noise and the
-    log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf."""
-    for t, what in ((h, "h"), (weight, "weight")):
-        _require_hip(t, what)
-    if bias is not None:
-        _require_hip(bias, "bias")
-    if embed is not None:
-        _require_hip(embed, "embedding table")
-    temperature = float(temperature)
-    if not temperature >= 0.0:
-        raise ValueError(f"vmlmf_amd.lm_sample: temperature must be >= 0, got {temperature}")
-    inv = 0.0 if temperature == 0.0 else 1.0 / temperature
-    if inv > 0.0 and (state is None or not state.is_cuda or state.dtype != torch.int64 or state.numel() != 2):
-        raise RuntimeError("vmlmf_amd.lm_sample: sampling (temperature > 0) needs a {seed, offset} snapshot: two int64 on the device")
-    h2 = h.reshape(-1, h.shape[-1]).contiguous()
-    B, H = h2.shape
-    w = weight.contiguous()
-    V = w.shape[0]
-    if w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
-        raise RuntimeError(f"vmlmf_amd.lm_sample: h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias / embed must be (V) / (V, H)")
-    k, p = sample_filters(top_k, top_p, V)
-    filtered = inv > 0.0 and (k > 0 or p < 1.0)      # greedy: the argmax is always kept, the existing kernels run
-    dev = h2.device
-    lib = _lib.lib()
-    tokens = torch.empty(B, device=dev, dtype=torch.int64)
-    logp = torch.empty(B, device=dev, dtype=torch.float32)
-    xn = torch.empty((B, H), device=dev, dtype=torch.float32) if embed is not None else None
-    if not return_kept:
-        kept = None
-    elif filtered or controls is not None:
-        kept = torch.empty(B, device=dev, dtype=torch.int32)
-    else:
-        kept = torch.full((B,), V, device=dev, dtype=torch.int32)
-    if controls is not None and form not in (None, "gemm"):
-        raise ValueError(f"vmlmf_amd.lm_sample: the controlled choice has no fused-head form (form must be 'gemm' or None, got {form!r})")
-    if form is None:
-        form = "fused" if B <= (SAMPLE_FILTERED_FUSED_MAX_ROWS if filtered else SAMPLE_FUSED_MAX_ROWS) else "gemm"
-    outs = lambda: tuple(t for t in (tokens, logp, xn, kept) if t is not None)
-    state_p = None if inv == 0.0 else _ptr(state)
-    bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
-    bias_p, embed_p = _ptr(bias_c), _ptr(embed_c)
-    if controls is not None:
-        from ._decode import decode_choose
-        decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn, kept)
-        return outs()
-    if form == "gemm":
-        scores = torch.mm(h2, w.t())
-        with _lib.on_device(dev):
-            if filtered:
-                _lib.check(lib.vmlmf_lm_choose_filtered(B, H, V, _ptr(scores), bias_p, embed_p, inv, k, p, state_p, int(step), _ptr(tokens),
-                                                        _ptr(logp), _ptr(xn), _ptr(kept), _lib.raw_stream(dev)))
-            else:
-                _lib.check(lib.vmlmf_lm_choose(B, H, V, _ptr(scores), bias_p, embed_p, inv, state_p, int(step), _ptr(tokens), _ptr(logp),
-                                               _ptr(xn), _lib.raw_stream(dev)))
-        return outs()
-    if form != "fused":
-        raise ValueError(f"vmlmf_amd.lm_sample: form must be 'fused', 'gemm' or None, got {form!r}")
-    nbytes = (lib.vmlmf_lm_sample_filtered_workspace_bytes if filtered else lib.vmlmf_lm_sample_workspace_bytes)(B, V)
-    ws = _sample_workspace(dev, nbytes)
-    with _lib.on_device(dev):
-        if filtered:
-            _lib.check(lib.vmlmf_lm_sample_filtered(B, H, V, _ptr(h2), _ptr(w), bias_p, embed_p, inv, k, p, state_p, int(step),
-                                                    _ptr(tokens), _ptr(logp), _ptr(xn), _ptr(kept), _ptr(sample_ticket(dev)), _ptr(ws),
-                                                    nbytes, _lib.raw_stream(dev)))
-        else:
-            _lib.check(lib.vmlmf_lm_sample(B, H, V, _ptr(h2), _ptr(w), bias_p, embed_p, inv, state_p, int(step), _ptr(tokens),
-                                           _ptr(logp), _ptr(xn), _ptr(sample_ticket(dev)), _ptr(ws), nbytes, _lib.raw_stream(dev)))
-    return outs()
-
-
-# ---- beam search: the selection step, the state reorder and the read-back (C ABI: include/vmlmf_beam.h, a library of its own that
-# the first beam call loads; vmlmf_amd/_beam.py) --------------------------------------------------------------------------------
-from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: E402,F401

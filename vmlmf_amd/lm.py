@@ -347,40 +347,12 @@ class Model(nn.Module):
             st = self._sample_state = dropout_state(dev, seed)
         return st
 
-    def _decode_layers(self, x, states, layer_path):
-        """The layers at T = 1: x (1, B, H) -> (y (1, B, H), states).  layer_path "stack": stack_layers' one launch where it covers the
-        layers (it packs the parameters on every call); otherwise a call per layer - VMLMF layers reuse kept images (_KeptImages)."""
-        if layer_path == "stack":
-            stacked = stack_layers(self.rnns, x, states)
-            if stacked is not None:
-                return stacked[0], list(stacked[1])
-        states = list(states)
-        for i, rnn in enumerate(self.rnns):
-            x, states[i] = rnn(x, states[i])
-        return x, states
-
-    def _decode(self, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None, controls=None):
-        """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
-        the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
-        capturable (DecodeGraph).  controls: a DecodeControls - the choice is then the controlled launch behind the head's GEMM
-        (vmlmf_decode_choose), which moves the controls' state on in place."""
-        from .functional import lm_sample
-        toks, lps = [], []
-        for j in range(steps):
-            tok, lp, x = lm_sample(h, self.fc.w, self.fc.b, temperature, snap, j, embed=self.embed.w, top_k=top_k, top_p=top_p,
-                                   controls=controls)
-            toks.append(tok)
-            lps.append(lp)
-            y, states = self._decode_layers(x.unsqueeze(0), states, layer_path)
-            h = y[-1]
-        return torch.stack(toks), torch.stack(lps), h, states
-
     def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
                  eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
-        The prompt runs once through features() without dropout; each further token is one vmlmf_lm_sample launch (functional.lm_sample)
+        The prompt runs once through features() without dropout; each further token is one vmlmf_lm_sample launch (decoding.lm_sample)
         and the layers at T = 1.  temperature 0: greedy; tau > 0: softmax(scores / tau) draws from sampler_state() (seed: re-seed it
         first), snapshotted and advanced once per call - the same seed gives the same tokens, the next call fresh ones.
         chunk=K (steps % K == 0): the decode steps run as a captured hipGraph of K steps (DecodeGraph), replayed steps / K times, the
@@ -390,7 +362,7 @@ class Model(nn.Module):
         measured at the PTB size: docs/design/lm_sampling.md).  Every module's train / eval flag is as the caller left it afterwards.
         top_k / top_p cut the tail of the tempered distribution before the draw: temperature first, then the top_k tokens with the
         largest scores (equal scores: the lower index first), then of those the shortest prefix whose renormalised mass reaches top_p
-        (functional.lm_sample; None, top_k = 0 and top_p = 1.0: off; ValueError for top_k < 0 and top_p outside (0, 1]).  The generator
+        (decoding.lm_sample; None, top_k = 0 and top_p = 1.0: off; ValueError for top_k < 0 and top_p outside (0, 1]).  The generator
         is snapshotted and advanced exactly as without them, so a filtered and an unfiltered call from one seed see the same noise;
         logprobs stay those of the unfiltered distribution; greedy decoding is unchanged.
         Stopping and token controls (all off by default; with any of eos, repetition_penalty != 1, logit_bias, banned_tokens given the
@@ -405,72 +377,9 @@ class Model(nn.Module):
         return_lengths=True: (tokens, logprobs, lengths (B) int32 - tokens up to and including eos -, states).  ValueError, before any
         device work, for repetition_penalty <= 0 or not finite, min_length < 0 or without eos, eos or a banned index outside the
         vocabulary, a logit_bias that is not (V) fp32, holds NaN or +inf (its values are read back once), or leaves nothing to choose."""
-        from . import _decode as _dc
-        from .functional import sample_filters
-        sample_filters(top_k, top_p)
-        ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
-                        banned_tokens=banned_tokens)
-        eos_c, min_c, _, banned = _dc.check_controls(self.vocab_size, **ctl_args)
-        controlled = _dc.controls_on(eos, repetition_penalty, logit_bias, banned_tokens)
-        if controlled:
-            _dc.check_bias(self.vocab_size, logit_bias, banned, eos_c, min_c)
-        if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
-            raise RuntimeError("vmlmf_amd: Model.generate runs on the HIP sampler kernel (vmlmf_lm_sample) only: move the model and the "
-                               "prompt to 'cuda' (no CPU fallback)")
-        if prompt.dim() != 2 or prompt.dtype != torch.int64:
-            raise RuntimeError("vmlmf_amd: Model.generate takes a (T0, B) int64 prompt")
-        steps, temperature = int(steps), float(temperature)
-        if chunk is not None and (int(chunk) < 1 or steps % int(chunk) != 0):
-            raise ValueError(f"vmlmf_amd: Model.generate: chunk={chunk} must divide steps={steps}")
-        B = prompt.shape[1]
-        states = self.state_init(B) if states is None else list(states)
-        gen = self.sampler_state(seed) if temperature > 0 else None
-        modes = [(mod, mod.training) for mod in self.modules()]
-        self.train(False)
-        try:
-            with torch.no_grad(), _KeptImages(self):
-                h, states = self.features(prompt, list(states))
-                h = h[-1]
-                controls = _dc.DecodeControls(B, self.vocab_size, prompt.device, prompt=prompt, _checked=True, **ctl_args) if controlled else None
-
-                def result(tokens, logprobs, states):
-                    if not return_lengths:
-                        return tokens, logprobs, states
-                    lengths = controls.length.clone() if controls is not None else torch.full((B,), steps, dtype=torch.int32, device=prompt.device)
-                    return tokens, logprobs, lengths, states
-                if steps == 0:
-                    return result(torch.empty((0, B), dtype=torch.int64, device=prompt.device),
-                                  torch.empty((0, B), device=prompt.device), states)
-                if chunk is None:
-                    from .functional import dropout_advance
-                    snap = dropout_advance(gen) if gen is not None else None
-                    tokens, logprobs, _, states = self._decode(h, states, steps, temperature, snap, layer_path, top_k, top_p, controls)
-                    return result(tokens, logprobs, states)
-            graph = DecodeGraph(self, h, states, int(chunk), temperature, layer_path, top_k, top_p, controls)
-            outs = [graph.replay() for _ in range(steps // int(chunk))]
-            return result(torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]),
-                          [(a.clone(), c.clone()) for a, c in graph.states])
-        finally:
-            for mod, was in modes:
-                mod.training = was
-
-    def _beam_steps(self, h, states, cum, finished, length, steps, eos, buffers=None):
-        """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
-        (functional.lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
-        2 L state tensors follow their hypotheses (functional.beam_gather), then the layers at T = 1 on the B W rows.  No host
-        synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length)."""
-        from .functional import beam_gather, lm_beam_step
-        parents, toks = [], []
-        for _ in range(steps):
-            par, tok, cum, finished, length, x, src = lm_beam_step(h, self.fc.w, self.fc.b, cum, finished, length, eos, self.embed.w,
-                                                                   buffers=buffers)
-            parents.append(par)
-            toks.append(tok)
-            flat = beam_gather([t for st in states for t in st], src)
-            states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
-            y, states = self._decode_layers(x.unsqueeze(0), states, "layers")
-            h = y[-1]
-        return torch.stack(parents), torch.stack(toks), h, states, cum, finished, length
+        from . import decoding
+        return decoding.generate(self, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length,
+                                 repetition_penalty, logit_bias, banned_tokens, return_lengths)
 
     def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
         """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
@@ -480,7 +389,7 @@ class Model(nn.Module):
         torch.cat([prompt, tokens[:, b, w]]) ends in them).
         The prompt runs once through features() without dropout.  Beam 0 of each row then starts at score 0, beams 1 .. W - 1 at -inf,
         all on the prompt's state.  A step keeps the W best of a row's candidates under one total order - larger total first, equal
-        totals to the lower flat index w V + v - and leaves them in that order (functional.lm_beam_step: one launch behind the head's
+        totals to the lower flat index w V + v - and leaves them in that order (decoding.lm_beam_step: one launch behind the head's
         GEMM; a second launch reorders the layers' states, then the layers run at T = 1 on kept parameter images).
         eos: a beam that has emitted it is finished - it offers (w, eos) alone at its score so far, its length stops growing and its
         later tokens are eos (which the layers keep taking in: the states cover the padding).  None: no beam ever finishes.
@@ -489,195 +398,5 @@ class Model(nn.Module):
         chunk=K (steps % K == 0): K steps are captured into a linear hipGraph on one stream and replayed steps / K times (BeamGraph):
         the eager call's bits.  ValueError for beams < 1, beams > 32 and beams > V; no random generator is touched; every module's
         train / eval flag is as the caller left it afterwards."""
-        from . import _beam
-        W = _beam.check_beams(beams, self.vocab_size)
-        steps, alpha = int(steps), float(length_penalty)
-        if eos is not None and not 0 <= int(eos) < self.vocab_size:
-            raise ValueError(f"vmlmf_amd: Model.beam_search: eos={eos} is not a token of the vocabulary ({self.vocab_size})")
-        if not alpha >= 0.0:
-            raise ValueError(f"vmlmf_amd: Model.beam_search: length_penalty must be >= 0, got {length_penalty}")
-        if steps < 0:
-            raise ValueError(f"vmlmf_amd: Model.beam_search: steps must be >= 0, got {steps}")
-        if chunk is not None and (int(chunk) < 1 or steps % int(chunk) != 0):
-            raise ValueError(f"vmlmf_amd: Model.beam_search: chunk={chunk} must divide steps={steps}")
-        if not (isinstance(prompt, torch.Tensor) and prompt.is_cuda and self.embed.w.is_cuda):
-            raise RuntimeError("vmlmf_amd: Model.beam_search runs on the HIP beam-step kernel (vmlmf_beam_step) only: move the model and "
-                               "the prompt to 'cuda' (no CPU fallback)")
-        if prompt.dim() != 2 or prompt.dtype != torch.int64:
-            raise RuntimeError("vmlmf_amd: Model.beam_search takes a (T0, B) int64 prompt")
-        B, dev = prompt.shape[1], prompt.device
-        states = self.state_init(B) if states is None else list(states)
-        modes = [(mod, mod.training) for mod in self.modules()]
-        self.train(False)
-        try:
-            with torch.no_grad(), _KeptImages(self):
-                h, states = self.features(prompt, list(states))
-                h = h[-1].repeat_interleave(W, 0)
-                states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
-                cum = torch.full((B, W), float("-inf"), device=dev)
-                cum[:, 0] = 0.0
-                finished = torch.zeros((B, W), dtype=torch.int32, device=dev)
-                length = torch.zeros((B, W), dtype=torch.int32, device=dev)
-                if steps == 0:
-                    return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
-                if chunk is None:
-                    parents, toks, _, states, cum, finished, length = self._beam_steps(h, states, cum, finished, length, steps, eos)
-            if chunk is not None:
-                graph = BeamGraph(self, h, states, int(chunk), W, eos, cum, finished, length)
-                outs = [graph.replay() for _ in range(steps // int(chunk))]
-                parents, toks = torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
-                states = [(a.clone(), c.clone()) for a, c in graph.states]
-                cum, length = graph.cum.clone(), graph.length.clone()
-            with torch.no_grad():
-                order = None
-                if alpha > 0.0:
-                    key = cum / length.to(torch.float32) ** alpha
-                    order = torch.sort(key, dim=1, descending=True, stable=True).indices
-                    cum, length = cum.gather(1, order), length.gather(1, order)
-                    rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
-                    flat = _beam.beam_gather([t for st in states for t in st], rows)
-                    states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
-                    order = order.to(torch.int32)
-                return _beam.beam_backtrack(parents, toks, order), cum, length, states
-        finally:
-            for mod, was in modes:
-                mod.training = was
-
-
-class _KeptImages:
-    """`with _KeptImages(model[, caches]):` every VMLMF layer of the model keeps its packed parameter images for the duration
-    (functional.cache_packed_parameters) - a layer that already keeps them keeps its own cache -, and the caller's setting comes back
-    afterwards.  caches: the PackCache of each such layer, in order (DecodeGraph holds its own: its graph reads their buffers)."""
-
-    def __init__(self, model, caches=None):
-        self.layers = [m for m in model.modules() if hasattr(m, "kernel_params")]
-        self.caches = caches
-
-    def __enter__(self):
-        from .functional import PackCache
-        self.saved = [m.__dict__.get("_pack_cache", _UNSET) for m in self.layers]
-        for i, (m, was) in enumerate(zip(self.layers, self.saved)):
-            if self.caches is not None:
-                m._pack_cache = self.caches[i]
-            elif was is _UNSET or was is None:
-                m._pack_cache = PackCache()
-        return self
-
-    def __exit__(self, *exc):
-        for m, was in zip(self.layers, self.saved):
-            if was is _UNSET:
-                m.__dict__.pop("_pack_cache", None)
-            else:
-                m._pack_cache = was
-        return False
-
-
-_UNSET = object()
-
-
-class DecodeGraph:
-    """`steps` decode steps of a Model (Model._decode: per step the vmlmf_lm_sample launch and the layers at T = 1) captured once into
-    a hipGraph - linear, on one stream.  replay() continues from where the previous replay stopped (the top layer's output and the
-    layers' states live in this object's buffers, h / states) and returns (tokens (steps, B), logprobs (steps, B)); with temperature > 0
-    the first node snapshots and advances the model's sampler_state(), so every replay draws fresh tokens and a new capture from the same
-    seed and inputs repeats the first replay.  The generator is the sampler_state() tensor of construction time: re-seeding the model
-    (sampler_state(seed)) puts a new tensor in its place, which this graph does not see - build a new DecodeGraph after re-seeding, as
-    after the parameters change (the layers read kept parameter images packed at construction).  Replay DecodeGraphs one after
-    another, never two at once on different streams: the sampler's ticket words are taken from a ring of 16 per device (as the
-    criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count.
-    top_k / top_p: the filters of Model.generate, fixed at construction.
-    controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
-    length -, so replays continue one decode: finished rows stay finished, seen accumulates (the warm-up runs on a clone)."""
-
-    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None):
-        from .functional import PackCache, sample_filters
-        self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
-        sample_filters(top_k, top_p)
-        self.top_k, self.top_p, self.controls = top_k, top_p, controls
-        dev = h.device
-        self.h = h.detach().clone()
-        self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
-        self.gen = model.sampler_state() if self.temperature > 0 else None
-        self.caches = [PackCache() for m in model.modules() if hasattr(m, "kernel_params")]
-        with torch.no_grad(), _KeptImages(model, self.caches):
-            # warm-up outside the capture, on copies: packs the images, creates the tickets and workspaces; the generator is put back
-            saved = None if self.gen is None else self.gen.clone()
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states], None if controls is None else controls.clone())
-            torch.cuda.current_stream(dev).wait_stream(side)
-            if saved is not None:
-                self.gen.copy_(saved)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.tokens, self.logprobs = self._body(self.h, self.states, controls)
-
-    def _body(self, h, states, controls):
-        from .functional import dropout_advance
-        snap = dropout_advance(self.gen) if self.gen is not None else None
-        toks, lps, hn, st = self.model._decode(h, list(states), self.steps, self.temperature, snap, self.layer_path, self.top_k, self.top_p,
-                                               controls)
-        h.copy_(hn)
-        for (a, c), (a2, c2) in zip(states, st):
-            a.copy_(a2)
-            c.copy_(c2)
-        return toks, lps
-
-    def replay(self):
-        self.graph.replay()
-        return self.tokens.clone(), self.logprobs.clone()
-
-
-class BeamGraph:
-    """`steps` steps of Model.beam_search (Model._beam_steps: per step the head's GEMM, the vmlmf_beam_step launch, the vmlmf_beam_gather
-    launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are the beams' (row
-    b W + w) of `beams` = W beams per batch row; cum / finished / length (B, W) default to a fresh search (beam 0 at 0, the others at -inf).  replay() continues from where
-    the previous replay stopped - h, states, cum, finished and length live in this object's buffers - and returns (parents, tokens),
-    both (steps, B, W), for functional.beam_backtrack.  The ticket words and the workspace of the selection are this graph's own, so
-    graphs may be replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after
-    the parameters change."""
-
-    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None):
-        from . import _beam
-        from .functional import PackCache
-        self.model, self.steps, self.eos = model, int(steps), eos
-        dev = h.device
-        W = _beam.check_beams(beams, model.vocab_size)
-        B = h.shape[0] // W
-        if cum is None:
-            cum = torch.full((B, W), float("-inf"), device=dev)
-            cum[:, 0] = 0.0
-        self.h = h.detach().clone()
-        self.states = [(a.detach().clone(), c.detach().clone()) for a, c in states]
-        self.cum = cum.detach().clone()
-        self.finished = torch.zeros((B, W), dtype=torch.int32, device=dev) if finished is None else finished.to(torch.int32).clone()
-        self.length = torch.zeros((B, W), dtype=torch.int32, device=dev) if length is None else length.to(torch.int32).clone()
-        self.buffers = _beam.new_step_buffers(dev, B, W, model.vocab_size)
-        self.caches = [PackCache() for m in model.modules() if hasattr(m, "kernel_params")]
-        with torch.no_grad(), _KeptImages(model, self.caches):
-            # warm-up outside the capture, on copies: packs the images, loads the library, creates the layers' workspaces
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                self._body(self.h.clone(), [(a.clone(), c.clone()) for a, c in self.states], self.cum.clone(), self.finished.clone(),
-                           self.length.clone())
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.parents, self.tokens = self._body(self.h, self.states, self.cum, self.finished, self.length)
-
-    def _body(self, h, states, cum, finished, length):
-        par, tok, hn, st, cn, fn, ln = self.model._beam_steps(h, list(states), cum, finished, length, self.steps, self.eos, self.buffers)
-        h.copy_(hn)
-        for (a, c), (a2, c2) in zip(states, st):
-            a.copy_(a2)
-            c.copy_(c2)
-        cum.copy_(cn)
-        finished.copy_(fn)
-        length.copy_(ln)
-        return par, tok
-
-    def replay(self):
-        self.graph.replay()
-        return self.parents.clone(), self.tokens.clone()
+        from . import decoding
+        return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
