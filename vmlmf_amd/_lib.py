@@ -176,7 +176,8 @@ class VmlmfError(RuntimeError):
 
 
 def build(force=False, jobs=8):
-    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so, libvmlmf_beam.so and libvmlmf_decode.so (hipcc cross-compiles)."""
+    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so, libvmlmf_beam.so, libvmlmf_decode.so and
+    libvmlmf_score.so (hipcc cross-compiles)."""
     if force:
         subprocess.run(["make", "-C", CSRC, "clean"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}"], check=True, stdout=subprocess.DEVNULL)

@@ -6,6 +6,7 @@ lm.py holds its layers, this module everything that continues a prompt with them
   decode_steps, beam_steps                   the step loops: a choice, then the layers at T = 1 - no host synchronisation
   DecodeGraph, BeamGraph                     those loops captured into a hipGraph
   generate, beam_search                      the calls behind Model's methods of the same names, where the contract is written down
+(scoring.py - Model.score - runs on this module's session too.)
 """
 from __future__ import annotations
 
@@ -340,20 +341,27 @@ def _check_chunk(method, chunk, steps):
 
 
 @contextlib.contextmanager
-def _session(model, prompt, states):
-    """`with _session(model, prompt, states) as (h, states):` the model in eval mode, without autograd and on kept parameter images
-    for the duration; h (B, H) is the top layer's output behind the prompt's last token, states (default: state_init) have taken the
-    prompt in.  Every module's train / eval flag is as the caller left it afterwards, whatever was raised."""
-    states = model.state_init(prompt.shape[1]) if states is None else list(states)
+def _activations(model, tokens, states):
+    """`with _activations(model, tokens, states) as (h, states):` the model in eval mode, without autograd and on kept parameter images
+    for the duration; h (T, B, H) are features()'s activations - the top layer's output behind every token -, states (default:
+    state_init) have taken the tokens in.  Every module's train / eval flag is as the caller left it afterwards, whatever was raised."""
+    states = model.state_init(tokens.shape[1]) if states is None else list(states)
     modes = [(mod, mod.training) for mod in model.modules()]
     model.train(False)
     try:
         with torch.no_grad(), _KeptImages(model):
-            h, states = model.features(prompt, list(states))
-            yield h[-1], states
+            h, states = model.features(tokens, list(states))
+            yield h, states
     finally:
         for mod, was in modes:
             mod.training = was
+
+
+@contextlib.contextmanager
+def _session(model, prompt, states):
+    """_activations for a decode: h (B, H) is the top layer's output behind the prompt's last token."""
+    with _activations(model, prompt, states) as (h, states):
+        yield h[-1], states
 
 
 def _run(steps, chunk, eager, graph):

@@ -400,3 +400,27 @@ class Model(nn.Module):
         train / eval flag is as the caller left it afterwards."""
         from . import decoding
         return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
+
+    def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
+        """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
+        tokens[:-1] and the targets tokens[1:].  Otherwise tokens and targets are both (T, B) int64, as lm_test.minibatch hands them
+        out.  Returns (logprobs (T, B) fp32, ranks (T, B) int32, states): logprobs[t, b] is the untempered log-softmax (bias included)
+        of targets[t, b] behind inputs[:t + 1, b] - what nll_loss charges for it, and what generate and beam_search report for the
+        tokens they choose -; ranks[t, b] is the number of tokens ahead of the target in the project's one total order (larger score
+        first, equal scores to the lower index): 0 where greedy decoding would have chosen it.  states (default: state_init) are those
+        of Model.forward over the inputs.
+        top in [1, min(32, V)]: returns (logprobs, ranks, top_tokens (T, B, top) int64, top_logprobs (T, B, top), states) - the first
+        `top` tokens of that order at every position, in order, and their log-probabilities.
+        lengths (B) integer: positions t >= lengths[b] have no target, as has every position whose target is negative: logprob 0.0
+        exactly, rank -1 (their top outputs are those of any position), so logprobs.sum(0) is a padded row's total.  lengths on the
+        device keep the call free of host synchronisation (capturable); lengths on the CPU cost one blocking host-to-device copy.
+        The inputs run once through features() in eval mode, without autograd and on kept parameter images, whatever mode the model is
+        in; then per chunk of at most chunk_rows of the T B positions the head's GEMM and ONE launch of a library of its own
+        (scoring.lm_score: vmlmf_score_rows, include/vmlmf_score.h), so no more than chunk_rows x V scores exist at a time.  Every
+        module's train / eval flag and pack cache are as the caller left them afterwards, whatever is raised; no random generator is
+        touched.  ValueError, before any device work, for top outside [0, min(32, V)], chunk_rows < 1, tokens that are not 2-D int64,
+        targets of another shape or type, fewer than one position, and lengths that are not (B) integers; RuntimeError for CPU
+        tensors.  An input token outside the vocabulary and a target >= V are the caller's errors: the call never
+        reads a value back from the device, so it does not to look for them (such a target's position gives NaN and -1)."""
+        from . import scoring
+        return scoring.score(self, tokens, targets, states, lengths, top, chunk_rows)
