@@ -1,6 +1,6 @@
 """Decoding the LM (Model.generate, C ABI vmlmf_lm_sample): what can be checked without a GPU - the entry points' argument checks
 (host only: they refuse before anything reaches a device), the workspace size, and the numpy restatement of the sampler's draw that
-the GPU tests hold the kernel to."""
+the GPU tests hold the kernel to (vmlmf_decode_oracle.gumbel_restated), checked on itself."""
 import ctypes
 import os
 import re
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-import vmlmf_oracle as O
 from vmlmf_amd import _lib
+from vmlmf_decode_oracle import SITE_SAMPLE, gumbel_restated
 
 HEADER = os.path.join(os.path.dirname(__file__), "..", "include", "vmlmf_hip.h")
 
@@ -60,22 +60,6 @@ def test_workspace_size_is_monotone_in_rows_and_vocabulary():
     assert lib.vmlmf_lm_sample_workspace_bytes(256, 10000) <= 4 << 20
 
 
-def gumbel_restated(seed, offset, step, B, V):
-    """(B, V) Gumbel noise of the sampler at `step`: counter (step B + b, v >> 2, SITE_SAMPLE, offset low word), key (seed low,
-    seed high + offset high), word = out[v & 3], u = ((word >> 8) + 0.5) 2^-24, G = -log(-log u) in fp64."""
-    v = np.arange(V)
-    ctr = np.zeros((B, V, 4), dtype=np.uint32)
-    ctr[..., 0] = (step * B + np.arange(B, dtype=np.int64)).astype(np.uint32)[:, None]
-    ctr[..., 1] = (v >> 2).astype(np.uint32)[None, :]
-    ctr[..., 2] = np.uint32(_lib.SITE_SAMPLE)
-    ctr[..., 3] = np.uint32(offset & 0xFFFFFFFF)
-    key = np.array([seed & 0xFFFFFFFF, ((seed >> 32) + (offset >> 32)) & 0xFFFFFFFF], dtype=np.uint32)
-    w = O.philox4x32_10(ctr, key)
-    word = np.take_along_axis(w, np.broadcast_to((v & 3)[None, :, None], (B, V, 1)), axis=2)[..., 0]
-    u = ((word >> 8).astype(np.float64) + 0.5) * 2.0 ** -24
-    return u, -np.log(-np.log(u))
-
-
 def test_the_restated_draw_stays_inside_the_unit_interval_on_a_site_of_its_own():
     u, g = gumbel_restated(0x1234_5678_9ABC_DEF, 3, 5, 64, 1000)
     assert (u > 0).all() and (u < 1).all() and np.isfinite(g).all()
@@ -84,7 +68,7 @@ def test_the_restated_draw_stays_inside_the_unit_interval_on_a_site_of_its_own()
     assert abs(g.mean() - np.euler_gamma) < 5 * np.sqrt(np.pi ** 2 / 6 / g.size)      # Gumbel(0, 1): mean = Euler's gamma
     # the header and the binding name the same site, and no dropout site (0 = the embedding, l + 1 = layer l) can be it
     m = re.search(r"#define VMLMF_SITE_SAMPLE (0x[0-9A-Fa-f]+)", open(HEADER).read())
-    assert m and int(m.group(1), 16) == _lib.SITE_SAMPLE
+    assert m and int(m.group(1), 16) == _lib.SITE_SAMPLE == SITE_SAMPLE
     assert _lib.SITE_SAMPLE > 1 << 16
     # a different step, row, seed or offset is a different stream of words
     for args in ((0x1234_5678_9ABC_DEF, 3, 6), (0x1234_5678_9ABC_DEF, 4, 5), (7, 3, 5)):

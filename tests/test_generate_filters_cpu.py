@@ -1,117 +1,22 @@
 """Top-k and nucleus (top-p) sampling (Model.generate(top_k, top_p), C ABI vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered): what
 can be checked without a GPU - the new entry points' host-side refusals, the workspace size, the Python-level argument checks - and
-the fp64 numpy oracle of a filtered choice that the GPU tests (test_gpu_generate_filters.py) hold the kernels to, checked on itself.
+the fp64 numpy oracle of a filtered choice (oracle/vmlmf_decode_oracle.py) that the GPU tests (test_gpu_generate_filters.py) hold the
+kernels to, checked on itself.
 
 The oracle.  The filters act on the tempered scores z = scores / tau under one total order (larger z first, equal z to the lower
 index): top_k keeps the first k tokens; top_p keeps, of those, the token at sorted position j iff the mass of the tokens before it -
 exp(z - z_max) over the set top-k kept, normalised by its own sum - is < p.  fp32 scores cannot order near-equal tokens, so the oracle
 returns two sets per row: `lo`, the tokens kept under any admissible rounding, and `hi`, the tokens possibly kept (filtered_sets)."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-from test_generate_cpu import gumbel_restated
 from vmlmf_amd import _lib
-
-# the kernel holds a token's mass in fixed point with 40 fractional bits (the row's largest token weighs 2^40): a rounding of at most
-# 2^-41 per token against a sum of at least 2^40 - the issue's V 2^-31 term, adjusted to this format
-MASS_BITS = 40
-
-
-def nucleus_eps(p, margin, V):
-    """How far a cumulative mass may be off: the score margin carried into the probabilities, and the fixed-point rounding."""
-    return p * (np.exp(2 * margin) - 1) + V * 2.0 ** -MASS_BITS
-
-
-def filtered_sets(z, top_k, top_p, margin=0.0, eps=0.0):
-    """z (V) fp64 tempered scores -> (lo, hi) boolean masks over the vocabulary.  margin = eps = 0: the exact kept set, twice.
-    top_k None / 0 / >= V and top_p None / 1.0: off."""
-    V = z.shape[0]
-    order = np.lexsort((np.arange(V), -z))            # larger z first, equal z to the lower index
-    zs = z[order]
-    k = V if not top_k or top_k >= V else int(top_k)
-    lo = np.ones(V, bool)
-    hi = np.ones(V, bool)
-    if k < V and margin == 0.0:
-        lo = np.zeros(V, bool)
-        lo[order[:k]] = True                          # the first k of the order: equal scores are told apart by their index
-        hi = lo.copy()
-    elif k < V:
-        lo = z > zs[k] + margin                       # above the (k+1)-th score by more than the margin
-        hi = z >= zs[k - 1] - margin                  # not below the k-th score by more than the margin
-    if top_p is not None and top_p < 1.0:
-        mass = np.exp(zs[:k] - zs[0])
-        mass /= mass.sum()
-        before = np.concatenate([[0.0], np.cumsum(mass)[:-1]])          # mass of the tokens before sorted position j < k
-        # a token beyond position k can only enter in the place of the last one top-k kept (a score within the margin of it)
-        before_all = np.concatenate([before, np.full(V - k, before[-1])])
-        b = np.empty(V)
-        b[order] = before_all
-        lo &= b < top_p - eps
-        hi &= b < top_p + eps
-    lo[order[0]] = True                               # the first token is always kept
-    hi |= lo
-    return lo, hi
-
-
-def judge(z, G, lo, hi, token, kept, margin, what):
-    """The rule a filtered GPU choice passes by.  z, G (V) fp64; returns whether the row is unambiguous (argmax over lo == over hi)."""
-    zg = z + G
-    best_lo = np.flatnonzero(lo)[np.argmax(zg[lo])]
-    best_hi = np.flatnonzero(hi)[np.argmax(zg[hi])]
-    assert hi[token], (what, "token outside hi", token)
-    assert zg[token] >= zg[best_lo] - margin, (what, "a kept token beats it", token, best_lo, zg[token], zg[best_lo])
-    if kept is not None:
-        assert lo.sum() <= kept <= hi.sum(), (what, "kept", kept, lo.sum(), hi.sum())
-    if best_lo == best_hi:
-        assert token == best_lo or abs(zg[token] - zg[best_lo]) <= margin, (what, token, best_lo)
-    return best_lo == best_hi
-
-
-def ambiguous_share(z, G, k, p, margin):
-    """Share of the rows of z (R, V) whose argmax of z + G differs between lo and hi: a property of the oracle's sets alone."""
-    n = 0
-    for zr, gr in zip(z, G):
-        lo, hi = filtered_sets(zr, k, p, margin, nucleus_eps(p or 1.0, margin, zr.shape[0]))
-        zg = zr + gr
-        n += np.flatnonzero(lo)[np.argmax(zg[lo])] != np.flatnonzero(hi)[np.argmax(zg[hi])]
-    return n / z.shape[0]
-
+from vmlmf_decode_oracle import LDS_ROW, SETTINGS, SHAPES, TAUS, ambiguous_share, case_reference, filtered_sets, nucleus_eps, setting
 
 # ---- the kernel-level cases of the GPU tests: seeded on the CPU, so the condition on the oracle's sets is checked here ----
-LDS_ROW = 12288                                       # the longest row whose keys the choice kernel holds in LDS (SF_LDS_V)
-SHAPES = [(3, 32, 97), (19, 40, 33), (40, 700, 1000), (1, 650, 10000), (2, 16, LDS_ROW + 5)]
-SETTINGS = ["k10", "p0.9", "kp"]
-TAUS = [0.7, 1.0]
-SEED, STEP = 0x5EED_F117, 3
-
-
-def setting(name, V):
-    return {"k10": (10, None), "p0.9": (None, 0.9), "kp": (50 if V >= 100 else V // 2, 0.9)}[name]
-
-
-@functools.lru_cache(maxsize=None)
-def case_inputs(B, H, V):
-    """h (B, H), w (V, H) scaled as the unfiltered tests' (0.1), bias (V), embed (V, H): CPU tensors from a seeded generator."""
-    g = torch.Generator().manual_seed(1000 * B + V)
-    h = torch.randn(B, H, generator=g)
-    w = torch.randn(V, H, generator=g) * 0.1
-    b = torch.randn(V, generator=g)
-    e = torch.randn(V, H, generator=g)
-    return h, w, b, e
-
-
-@functools.lru_cache(maxsize=None)
-def case_reference(B, H, V):
-    """fp64 scores (B, V) and the sampler's noise G (B, V) at (SEED, offset 0, STEP)."""
-    h, w, b, _ = case_inputs(B, H, V)
-    scores = (h.double() @ w.double().t() + b.double()).numpy()
-    return scores, gumbel_restated(SEED, 0, STEP, B, V)[1]
-
-
 @pytest.mark.parametrize("tau", TAUS)
 @pytest.mark.parametrize("name", SETTINGS)
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))

@@ -1,16 +1,15 @@
 """Model.beam_search and its three launches (vmlmf_beam_step / _gather / _backtrack, csrc/vmlmf_beam.hip) against the fp64 oracle of
-tests/test_beam_cpu.py: a step passes when lo <= chosen <= hi and |chosen| = W (step_sets), and where the oracle is clear (lo == hi)
+oracle/vmlmf_decode_oracle.py: a step passes when lo <= chosen <= hi and |chosen| = W (step_sets), and where the oracle is clear (lo == hi)
 the chosen set is the oracle's exactly.  The model-level tests are teacher-forced: the oracle's literal layers run over the GPU's own
 live hypotheses, so every step is judged on the scores it had in front of it."""
 import numpy as np
 import pytest
 import torch
 
-import test_beam_cpu as C
-from test_gpu_generate import LP_TOL, MARGIN, _check_choices, _oracle_scores, _prompt, _teacher_forced
+import vmlmf_decode_oracle as C
+from lm_util import DEV, LP_TOL, MARGIN, _check_choices, _oracle_scores, _prompt, _teacher_forced, _tied_row, beam_model, cpu_prompt
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 EOS = C.EOS_KERNEL
 
 
@@ -111,7 +110,6 @@ def test_one_beam_is_greedy():
 
 # ---- 3. ties go to the lower flat index ----
 def test_ties_go_to_the_lower_flat_index():
-    from test_gpu_generate_filters import _tied_row
     from vmlmf_amd import lm_beam_step
     h, w, bias = _tied_row()
     z = (w.double() @ h.double()).numpy()
@@ -219,10 +217,10 @@ def _history(m, prompt, W, steps, eos):
 
 @pytest.mark.parametrize("kind,B,W,seed", C.MODEL_CASES)
 def test_beam_search_teacher_forced(kind, B, W, seed):
-    m = C.beam_model(kind).to(DEV)
+    m = beam_model(kind).to(DEV)
     eos, steps, V = C.MODEL_EOS, C.MODEL_STEPS, 97
     prompt = _prompt(B, seed=seed)
-    assert torch.equal(prompt.cpu(), C.cpu_prompt(B, seed=seed))
+    assert torch.equal(prompt.cpu(), cpu_prompt(B, seed=seed))
     tokens, scores, lengths, states = m.beam_search(prompt, steps, beams=W, eos=eos)
     assert tokens.shape == (steps, B, W) and tokens.dtype == torch.int64
     assert scores.shape == (B, W) and scores.dtype == torch.float32 and lengths.shape == (B, W) and lengths.dtype == torch.int32
@@ -270,7 +268,7 @@ def test_beam_search_teacher_forced(kind, B, W, seed):
 
 # ---- 7. one beam against generate, the length penalty, determinism, the captured chunk ----
 def test_one_beam_reproduces_greedy_generate():
-    m = C.beam_model("plain").to(DEV)
+    m = beam_model("plain").to(DEV)
     prompt = _prompt(3, seed=13)
     m.train()
     cpu_rng, gpu_rng = torch.get_rng_state(), torch.cuda.get_rng_state()
@@ -292,7 +290,7 @@ def test_one_beam_reproduces_greedy_generate():
 
 
 def test_length_penalty_determinism_and_the_captured_chunk():
-    m = C.beam_model("plain").to(DEV)
+    m = beam_model("plain").to(DEV)
     prompt = _prompt(3, seed=13)
     eos, W = C.MODEL_EOS, 4
     base = m.beam_search(prompt, 12, beams=W, eos=eos)
@@ -321,7 +319,7 @@ def test_length_penalty_determinism_and_the_captured_chunk():
 
 
 def test_cpu_tensors_raise():
-    m = C.beam_model("plain")
+    m = beam_model("plain")
     with pytest.raises(RuntimeError, match="cuda"):
         m.beam_search(torch.zeros((3, 2), dtype=torch.int64), 4)
 

@@ -1,12 +1,11 @@
 """Stopping and token controls on the GPU: vmlmf_decode_choose (csrc/vmlmf_decode.hip, libvmlmf_decode.so) through
-decoding.lm_sample(controls=...), Model.generate and DecodeGraph, against the fp64 oracle of test_decode_controls_cpu.py
+decoding.lm_sample(controls=...), Model.generate and DecodeGraph, against the fp64 oracle of oracle/vmlmf_decode_oracle.py
 (controlled_scores: repetition penalty, logit bias and bans, eos held back below the minimum length) and, for the choice on those
-scores, the oracle of the filters (test_generate_filters_cpu.filtered_sets / judge).
+scores, the oracle of the filters (filtered_sets / judge).
 
 A token passes as a filtered token does (test_gpu_generate_filters.py), on the CONTROLLED tempered scores z = c / tau and with the sets
 stripped of the tokens at -inf: those are never chosen and never counted in `kept`.  The margin on z is the filter tests' margin times
 max(theta, 1 / theta): what the penalty can multiply an fp32 rounding of the raw score by."""
-import functools
 import subprocess
 import sys
 
@@ -14,33 +13,21 @@ import numpy as np
 import pytest
 import torch
 
-import test_decode_controls_cpu as K
-import test_generate_filters_cpu as C
-from test_generate_cpu import gumbel_restated
-from test_gpu_generate import LP_TOL, MARGIN, _prompt, _small, _teacher_forced
+import vmlmf_decode_oracle as C
+from lm_util import DEV, LP_TOL, MARGIN, _on_device, _prompt, _small, _snap, _teacher_forced
+from vmlmf_decode_oracle import gumbel_restated
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-KERNEL_CASES = [(shape, name, tau) for shape in C.SHAPES for name in K.SETTINGS for tau in C.TAUS]
+KERNEL_CASES = [(shape, name, tau) for shape in C.SHAPES for name in C.CONTROL_SETTINGS for tau in C.TAUS]
 CASE_IDS = ["x".join(map(str, s)) + f"-{n}-{t}" for s, n, t in KERNEL_CASES]
-
-
-def _snap(seed=C.SEED):
-    from vmlmf_amd import dropout_advance, dropout_state
-    return dropout_advance(dropout_state(DEV, seed))
-
-
-@functools.lru_cache(maxsize=None)
-def _on_device(B, H, V):
-    return tuple(t.to(DEV) for t in C.case_inputs(B, H, V))
 
 
 def _case_controls(shape, length=None, finished=None):
     """A fresh DecodeControls of a kernel-level case (their state moves with every launch)."""
     from vmlmf_amd import DecodeControls
     B, _, V = shape
-    seen, lb = K.case_controls(*shape)
-    c = DecodeControls(B, V, DEV, eos=K.EOS, min_length=K.MIN_LENGTH, repetition_penalty=K.THETA, logit_bias=torch.from_numpy(lb))
+    seen, lb = C.case_controls(*shape)
+    c = DecodeControls(B, V, DEV, eos=C.EOS, min_length=C.MIN_LENGTH, repetition_penalty=C.THETA, logit_bias=torch.from_numpy(lb))
     c.seen.copy_(torch.from_numpy(seen.astype(np.uint8)))
     if length is not None:
         c.length.copy_(torch.from_numpy(np.asarray(length, dtype=np.int32)))
@@ -71,10 +58,10 @@ def test_controlled_lm_sample_against_the_oracle(shape, name, tau):
     from vmlmf_amd import lm_sample
     B, H, V = shape
     h, w, b, e = _on_device(B, H, V)
-    k, p = K.setting(name, V)
+    k, p = C.control_setting(name, V)
     tok, lp, xn, kept = lm_sample(h, w, b, tau, _snap(), C.STEP, embed=e, top_k=k, top_p=p, return_kept=True, controls=_case_controls(shape))
-    scores, c, G = K.case_controlled(B, H, V)
-    margin = K.z_margin(tau)
+    scores, c, G = C.case_controlled(B, H, V)
+    margin = C.z_margin(tau)
     tok_c, kept_c = tok.cpu().numpy(), kept.cpu().numpy()
     clear = 0
     for r in range(B):
@@ -120,26 +107,26 @@ def test_the_state_follows_the_tokens_and_finished_rows_are_padding(shape, tau, 
     from vmlmf_amd import lm_sample
     B, H, V = shape
     h, w, b, e = _on_device(B, H, V)
-    k, p = K.setting(name, V)
+    k, p = C.control_setting(name, V)
     rng = np.random.Generator(np.random.PCG64(B))
     length = rng.integers(0, 3, B).astype(np.int32)                     # below, at and past min_length = 1
     finished = (rng.random(B) < 0.3).astype(np.int32)
     ctl = _case_controls(shape, length, finished)
     # make eos every free row's choice by far, so that rows finish in this launch
-    ctl.logit_bias[K.EOS] = 30.0
+    ctl.logit_bias[C.EOS] = 30.0
     seen0, _, _ = _state(ctl)
     tok, lp, xn, kept = lm_sample(h, w, b, tau, _snap(), 1, embed=e, top_k=k, top_p=p, return_kept=True, controls=ctl)
     t = tok.cpu().numpy()
     seen1, length1, fin1 = _state(ctl)
-    want = K.next_state(seen0, length, finished, t, K.EOS)
+    want = C.next_state(seen0, length, finished, t, C.EOS)
     assert np.array_equal(seen1, want[0]) and np.array_equal(length1, want[1]) and np.array_equal(fin1, want[2])
     f = torch.from_numpy(finished.astype(bool)).to(DEV)
     assert f.any() and (~f).any()
-    assert (tok[f] == K.EOS).all() and (kept[f] == 0).all() and torch.equal(xn[f], e[K.EOS].expand(int(f.sum()), -1))
+    assert (tok[f] == C.EOS).all() and (kept[f] == 0).all() and torch.equal(xn[f], e[C.EOS].expand(int(f.sum()), -1))
     assert torch.equal(lp[f], torch.zeros_like(lp[f])) and not torch.signbit(lp[f]).any()           # 0.0 exactly
     live = ~finished.astype(bool)
-    assert not (t[live & (length < K.MIN_LENGTH)] == K.EOS).any()       # held back below the minimum length ...
-    assert (t[live & (length >= K.MIN_LENGTH)] == K.EOS).any()          # ... free at it: rows finished here
+    assert not (t[live & (length < C.MIN_LENGTH)] == C.EOS).any()       # held back below the minimum length ...
+    assert (t[live & (length >= C.MIN_LENGTH)] == C.EOS).any()          # ... free at it: rows finished here
     assert (kept[~f] >= 1).all() and (lp[~f] < 0).all() and torch.equal(xn, e[tok])
 
 
@@ -209,8 +196,8 @@ def test_token_frequencies_follow_the_renormalised_softmax_of_the_controlled_sco
     lb = rng.standard_normal(97).astype(np.float32)
     lb[rng.random(97) < 0.2] = -np.inf
     theta = 1.5
-    z = K.controlled_scores(x, seen, theta, lb, None, 0, 0)
-    lo, hi = _sets(z, kw.get("top_k"), kw.get("top_p"), K.z_margin(1.0, theta))
+    z = C.controlled_scores(x, seen, theta, lb, None, 0, 0)
+    lo, hi = _sets(z, kw.get("top_k"), kw.get("top_p"), C.z_margin(1.0, theta))
     assert np.array_equal(lo, hi) and 4 <= lo.sum() <= 90                  # the boundary is unambiguous
     N = 4096
     ctl = DecodeControls(N, 97, DEV, repetition_penalty=theta, logit_bias=torch.from_numpy(lb))
@@ -253,7 +240,7 @@ def test_generate_with_controls_against_the_oracle(kind, B):
     clear = live = 0
     for j in range(steps):
         G = gumbel_restated(seed, 0, j, B, V)[1]
-        c = K.controlled_scores(scores[j], seen, theta, lbn, eos, min_length, length)
+        c = C.controlled_scores(scores[j], seen, theta, lbn, eos, min_length, length)
         lsm = torch.log_softmax(torch.from_numpy(scores[j]), -1).numpy()
         for r in range(B):
             if finished[r]:
@@ -264,7 +251,7 @@ def test_generate_with_controls_against_the_oracle(kind, B):
             clear += C.judge(z, G[r], lo, hi, int(t[j, r]), None, margin, f"{kind} B {B} step {j} row {r}")
             live += 1
             assert abs(lp[j, r] - lsm[r, t[j, r]]) <= LP_TOL, (j, r, lp[j, r], lsm[r, t[j, r]])
-        seen, length, finished = K.next_state(seen, length, finished, t[j], eos)
+        seen, length, finished = C.next_state(seen, length, finished, t[j], eos)
     print(f"{kind} B {B}: clear {clear} of {live} live choices; lengths {length.tolist()}")
     assert clear >= 0.9 * live
     assert not (t == banned).any()
@@ -335,7 +322,7 @@ def test_the_same_bits_three_times_over(shape, name, tau):
     from vmlmf_amd import lm_sample
     B, H, V = shape
     h, w, b, e = _on_device(B, H, V)
-    k, p = K.setting(name, V)
+    k, p = C.control_setting(name, V)
     snap = _snap()
     runs = []
     for _ in range(3):
@@ -348,7 +335,7 @@ def test_the_same_bits_three_times_over(shape, name, tau):
 def test_a_plain_generate_never_opens_the_library():
     code = ("import sys; sys.path[:0] = %r\n"
             "import torch, vmlmf_amd\nfrom vmlmf_amd import _decode\n"
-            "from test_gpu_generate import _small, _prompt\n"
+            "from lm_util import _small, _prompt\n"
             "m = _small('plain')\n"
             "m.generate(_prompt(3), 4, temperature=0.8, seed=1, top_k=5)\nm.generate(_prompt(3), 4, temperature=0.0, chunk=2)\n"
             "torch.cuda.synchronize()\n"

@@ -8,69 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-import vmlmf_oracle as O
-from test_generate_cpu import gumbel_restated
+from lm_util import DEV, LP_TOL, MARGIN, _check_choices, _prompt, _small, _teacher_forced
+from vmlmf_decode_oracle import gumbel_restated
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-MARGIN = 2e-3          # |score| differences fp32 cannot order after ~30 recurrent steps (scores are O(1))
-LP_TOL = 2e-4          # log-probabilities against the oracle's log-softmax
-
-
-def _small(kind):
-    from vmlmf_amd import Model
-    torch.manual_seed({"plain": 1, "group": 2, "wide": 3, "wide300": 4}[kind])
-    if kind == "plain":
-        m = Model(97, 32, 2, 0.0, 0.3, w_rank=8, u_ranks=[8], lstm_type="vmlmf")
-    elif kind == "group":
-        m = Model.with_group_layers(97, 32, 2, 0.0, 0.3, w_rank=8, u_ranks=[8, 8])
-    elif kind == "wide":   # padded u_rank 48 > 32: the step-wise wide-rank layers
-        m = Model(97, 64, 2, 0.0, 0.2, w_rank=40, u_ranks=[48], lstm_type="vmlmf")
-    else:                  # the LM default's hidden rank, u_ranks = 300
-        m = Model(97, 320, 2, 0.0, 0.05, w_rank=32, u_ranks=[300], lstm_type="vmlmf")
-    return m.to(DEV)
-
-
-def _oracle_scores(m, tokens):
-    """fp64 literal forward of `m` over tokens (T, B) from zero states: (scores (T, B, V), [(hT, cT)])."""
-    sd = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
-    variant = O.V4 if m.lstm_type == "vmgroup" else O.V3
-    h = sd["embed.w"][tokens.cpu()]
-    B = tokens.shape[1]
-    states = []
-    for i in range(len(m.rnns)):
-        P = {k.split(".", 2)[2]: v for k, v in sd.items() if k.startswith(f"rnns.{i}.")}
-        H = m.rnns[i].hidden_size
-        z = torch.zeros(B, H, dtype=torch.float64)
-        h, hT, cT = O.literal_sequence(variant, P, h, z, z.clone(), g=2, time_major=True, v4_scratch_rows=B)
-        states.append((hT, cT))
-    scores = torch.addmm(sd["fc.b"], h.reshape(-1, h.shape[2]), sd["fc.w"].t()).view(h.shape[0], B, -1)
-    return scores, states
-
-
-def _check_choices(z, tokens, margin, what):
-    """z (steps, B, V) fp64 criterion; tokens (steps, B): argmax, or within `margin` of it."""
-    z = z.numpy()
-    t = tokens.cpu().numpy()
-    best = z.max(-1)
-    picked = np.take_along_axis(z, t[..., None], -1)[..., 0]
-    exact = (t == z.argmax(-1))
-    assert (best - picked <= margin).all(), (what, np.argwhere(best - picked > margin)[:5])
-    assert exact.mean() > 0.9, (what, exact.mean())
-
-
-def _prompt(B, T0=5, V=97, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(0, V, (T0, B), generator=g).to(DEV)
-
-
-def _teacher_forced(m, prompt, tokens):
-    T0 = prompt.shape[0]
-    seq = torch.cat([prompt.cpu(), tokens.cpu()])
-    scores, states = _oracle_scores(m, seq)
-    return scores[T0 - 1:T0 - 1 + tokens.shape[0]], states
-
-
 @pytest.mark.parametrize("kind", ["plain", "group", "wide", "wide300"])
 def test_greedy_tokens_and_logprobs_against_the_oracle(kind):
     m = _small(kind)

@@ -1,44 +1,20 @@
 """Top-k and nucleus (top-p) sampling on the GPU: vmlmf_lm_sample_filtered / vmlmf_lm_choose_filtered (csrc/vmlmf_sample.hip) through
-decoding.lm_sample, Model.generate and DecodeGraph, against the fp64 oracle of test_generate_filters_cpu.py.
+decoding.lm_sample, Model.generate and DecodeGraph, against the fp64 oracle of oracle/vmlmf_decode_oracle.py.
 
 A filtered token passes when it lies in the oracle's `hi` set (the tokens possibly kept), its z + G is at least the best of the `lo`
 set (the tokens certainly kept) minus the margin, and lo <= kept <= hi in size; where the argmax of z + G over lo and over hi is one
-token, the GPU's token is that one, or within the margin of it (test_generate_filters_cpu.judge)."""
+token, the GPU's token is that one, or within the margin of it (vmlmf_decode_oracle.judge)."""
 import ctypes
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-import test_generate_filters_cpu as C
-from test_generate_cpu import gumbel_restated
-from test_gpu_generate import LP_TOL, MARGIN, _prompt, _teacher_forced
+import vmlmf_decode_oracle as C
+from lm_util import DEV, LP_TOL, MARGIN, _on_device, _prompt, _small, _snap, _teacher_forced, _tied_row
+from vmlmf_decode_oracle import gumbel_restated
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _snap(seed=C.SEED):
-    from vmlmf_amd import dropout_advance, dropout_state
-    return dropout_advance(dropout_state(DEV, seed))
-
-
-def _small(kind):
-    from vmlmf_amd import Model
-    torch.manual_seed({"plain": 1, "group": 2}[kind])
-    if kind == "plain":
-        m = Model(97, 32, 2, 0.0, 0.3, w_rank=8, u_ranks=[8], lstm_type="vmlmf")
-    else:
-        m = Model.with_group_layers(97, 32, 2, 0.0, 0.3, w_rank=8, u_ranks=[8, 8])
-    return m.to(DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _on_device(B, H, V):
-    return tuple(t.to(DEV) for t in C.case_inputs(B, H, V))
-
-
 # ---- 1. lm_sample alone against the oracle, both forms ----
 @pytest.mark.parametrize("form", ["fused", "gemm"])
 @pytest.mark.parametrize("tau", C.TAUS)
@@ -128,19 +104,6 @@ def test_one_token_kept_is_greedy(form):
 
 
 # ---- 4. ties at the boundary go to the lower index ----
-def _tied_row():
-    """h (16), w (97, 16), bias (97) whose scores are exact in fp32 in any order of summation (small dyadic numbers): token 40 scores
-    2.5, tokens 5, 20 and 60 carry identical rows and the second-highest score 2.0, every other token stays below 1."""
-    g = torch.Generator().manual_seed(4)
-    h = torch.randint(0, 2, (16,), generator=g).float() * 2 - 1            # +-1
-    w = torch.randint(-8, 9, (97, 16), generator=g).float() / 128           # |score| <= 1
-    bias = torch.zeros(97)
-    for v in (5, 20, 60):
-        w[v] = h / 8
-    w[40] = h * 5 / 32
-    return h, w, bias
-
-
 @pytest.mark.parametrize("form", ["fused", "gemm"])
 def test_ties_at_the_boundary_go_to_the_lower_index(form):
     from vmlmf_amd import lm_sample

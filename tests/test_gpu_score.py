@@ -1,6 +1,6 @@
 """Model.score, lm_score and the vmlmf_score_rows launch (csrc/vmlmf_score.hip, libvmlmf_score.so) on the GPU: the kernel against the
-numpy oracle of test_score_cpu.py on the very fp32 scores it read (ranks and top tokens EQUAL, log-probabilities within 1e-4 of fp64),
-bit for bit against the sampler's greedy choice, and Model.score against the fp64 teacher-forced oracle of test_gpu_generate.py,
+numpy oracle of oracle/vmlmf_decode_oracle.py on the very fp32 scores it read (ranks and top tokens EQUAL, log-probabilities within 1e-4 of fp64),
+bit for bit against the sampler's greedy choice, and Model.score against the fp64 teacher-forced oracle of lm_util.py,
 against Model.generate and Model.beam_search, and against stock ops."""
 import ctypes
 import functools
@@ -9,12 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-import test_beam_cpu as BC
-from test_gpu_generate import LP_TOL, MARGIN, _oracle_scores, _prompt, _small, _teacher_forced
-from test_score_cpu import score_oracle
+from lm_util import DEV, LP_TOL, MARGIN, _oracle_scores, _prompt, _small, _teacher_forced, beam_model
+from vmlmf_decode_oracle import MODEL_EOS, score_oracle
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
 KERNEL_TOL = 1e-4      # fp32 log-probabilities against fp64 on the same scores: the figure test_gpu_generate.py holds lm_sample to
 
 
@@ -260,8 +258,8 @@ def test_greedy_generate_is_scored_as_it_reported():
 
 
 def test_beam_search_scores_are_the_sums_of_the_scored_tokens():
-    m = BC.beam_model("plain").to(DEV)
-    eos, steps, W, Bb = BC.MODEL_EOS, 8, 3, 2
+    m = beam_model("plain").to(DEV)
+    eos, steps, W, Bb = MODEL_EOS, 8, 3, 2
     prompt = _prompt(Bb, seed=3)
     tokens, scores, lengths, _ = m.beam_search(prompt, steps, beams=W, eos=eos)
     assert 0 < (lengths < steps).sum().item()                          # some hypothesis finished: its padding must not count

@@ -1,45 +1,20 @@
 """Model.score and lm_score (C ABI vmlmf_score_rows in libvmlmf_score.so, include/vmlmf_score.h): what can be checked without a GPU -
-the numpy oracle that the GPU tests (test_gpu_score.py) hold the kernel to, checked on itself; every refusal, in Python and at the C
-ABI; the library, its binding, its lazy load and its place in the Makefile.
+the numpy oracle (oracle/vmlmf_decode_oracle.py) that the GPU tests (test_gpu_score.py) hold the kernel to, checked on itself; every
+refusal, in Python and at the C ABI.
 
 The contract, per row, on x = bias + scores in fp32: the tokens' ORDER is larger x first, equal x to the lower index;
 logprob = x[y] - logsumexp(x); rank = how many tokens are ahead of y in the order; the top tokens are the order's first `top`."""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+from vmlmf_decode_oracle import score_oracle
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def score_oracle(scores_f32, bias_f32, targets, top):
-    """scores (R, V) fp32, bias (V) fp32 or None, targets (R) integers (< 0: no target) or None, top in [0, V].  x is formed by the fp32
-    add, the order by np.lexsort on (x descending, index ascending), the log-probabilities in fp64 from x.  Returns (logprob (R) f64,
-    rank (R) int64, top_tokens (R, top) int64, top_logprob (R, top) f64, order (R, V)); a row without a target has (0.0, -1)."""
-    s = np.asarray(scores_f32, dtype=np.float32)
-    x = s + (np.float32(0) if bias_f32 is None else np.asarray(bias_f32, dtype=np.float32)[None, :])
-    assert x.dtype == np.float32
-    R, V = x.shape
-    y = np.full(R, -1, dtype=np.int64) if targets is None else np.asarray(targets, dtype=np.int64)
-    x64 = x.astype(np.float64)
-    m = x64.max(1)
-    lse = m + np.log(np.exp(x64 - m[:, None]).sum(1))
-    order = np.stack([np.lexsort((np.arange(V), -x[r])) for r in range(R)])
-    place = np.empty_like(order)
-    np.put_along_axis(place, order, np.broadcast_to(np.arange(V), (R, V)), 1)      # place[r, v]: how many tokens are ahead of v
-    has = y >= 0
-    yc = np.where(has, y, 0)
-    rows = np.arange(R)
-    logprob = np.where(has, x64[rows, yc] - lse, 0.0)
-    rank = np.where(has, place[rows, yc], -1)
-    top_tokens = order[:, :top].astype(np.int64)
-    top_logprob = np.take_along_axis(x64, top_tokens, 1) - lse[:, None]
-    return logprob, rank, top_tokens, top_logprob, order
 
 
 # ---- the oracle on itself ----
@@ -131,28 +106,12 @@ def test_lm_score_refuses():
 
 
 # ---- the library and its binding ----
-def declared_functions():
-    text = open(os.path.join(ROOT, "include", "vmlmf_score.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", text)))
 
-
-def test_every_declared_function_is_exported_and_bound():
-    from vmlmf_amd import _beam, _decode, _lib, _score
-    decl = declared_functions()
-    assert decl == ["vmlmf_score_abi_version", "vmlmf_score_last_error", "vmlmf_score_rows"]
-    assert sorted(_score.SYMBOLS) == decl
-    assert os.path.exists(_score.LIB_PATH), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(_score.LIB_PATH)
-    for name in decl:
-        assert hasattr(handle, name), f"missing export {name}"
+def test_max_top_is_the_headers_and_the_beam_limit():
+    """(the exports, the ABI number, the lazy load and the Makefile: test_side_libraries_cpu.py)"""
+    from vmlmf_amd import _beam, _score
     header = open(os.path.join(ROOT, "include", "vmlmf_score.h")).read()
-    assert int(re.search(r"#define VMLMF_SCORE_ABI_VERSION (\d+)", header).group(1)) == _score.ABI_VERSION == 1
-    assert _score.lib().vmlmf_score_abi_version() == _score.ABI_VERSION
     assert int(re.search(r"#define VMLMF_SCORE_MAX_TOP (\d+)", header).group(1)) == _score.MAX_TOP == _beam.MAX_BEAMS
-    assert not set(_score.SYMBOLS) & (set(_lib.SYMBOLS) | set(_beam.SYMBOLS) | set(_decode.SYMBOLS))   # the other ABIs are not touched
-    for other in (_lib.LIB_PATH, _beam.LIB_PATH, _decode.LIB_PATH):
-        assert not hasattr(ctypes.CDLL(other), "vmlmf_score_rows")                   # the kernel lives in the new library only
 
 
 def _rows(R=2, V=16, scores=1, targets=1, top=0, logprob=1, rank=1, top_tokens=1, top_logprob=1):
@@ -176,54 +135,3 @@ def test_the_entry_point_refuses_on_the_host():
     for kw, words in cases:
         rc, msg = _rows(**kw)
         assert rc == _lib.E_BADARG and words in msg and msg.startswith("vmlmf_score_rows: "), (kw, rc, msg)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _score
-    monkeypatch.setattr(_score, "_handle", None)
-    monkeypatch.setattr(_score, "LIB_PATH", str(tmp_path / "libvmlmf_score.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_score.so is missing: build it"):
-        _score.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for Model.score"):
-        _score.lib()
-    assert not _score.loaded()
-
-
-def test_the_library_is_loaded_by_the_first_scoring_call_only():
-    """A process that imports the package, opens the main library and walks generate() and score() up to their refusals of CPU tensors
-    has not opened libvmlmf_score.so."""
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import torch, vmlmf_amd\nfrom vmlmf_amd import _score, _lib\n_lib.lib()\n"
-            "m = vmlmf_amd.Model(16, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')\n"
-            "tok = torch.zeros((3, 2), dtype=torch.int64)\n"
-            "for call in (lambda: m.generate(tok, 4), lambda: m.score(tok), lambda: m.score(tok, tok, top=4, lengths=torch.tensor([1, 2])),\n"
-            "             lambda: vmlmf_amd.lm_score(torch.zeros(3, 8), torch.zeros(16, 8), None, top=2)):\n"
-            "    try:\n        call()\n        raise SystemExit('no refusal')\n"
-            "    except RuntimeError as e:\n        assert 'cuda' in str(e)\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert 'libvmlmf_hip.so' in maps and 'libvmlmf_score.so' not in maps and not _score.loaded()\n"
-            "_score.lib()\nassert 'libvmlmf_score.so' in open('/proc/self/maps').read() and _score.loaded()\n") % ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
-def test_the_makefile_builds_and_cleans_the_fourth_library():
-    csrc = os.path.join(ROOT, "vmlmf_amd", "csrc")
-    libs = ("libvmlmf_hip.so", "libvmlmf_beam.so", "libvmlmf_decode.so", "libvmlmf_score.so")
-    r = subprocess.run(["make", "-n", "-B", "-C", csrc, "all"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and all(n in r.stdout for n in libs)
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln and "vmlmf_score.o" in ln]
-    assert len(links) == 1 and "-o ../lib/libvmlmf_score.so" in links[0]                      # linked into its own library only
-    assert not any(o in links[0] for o in ("vmlmf_sample.o", "vmlmf_decode.o", "vmlmf_beam.o"))
-    r = subprocess.run(["make", "-n", "-C", csrc, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and all(n in r.stdout for n in libs) and "vmlmf_score.o" in r.stdout
-
-
-def test_the_selection_is_still_written_once():
-    """vmlmf_score.hip takes the merges, the reduction tree and the selection from vmlmf_select.h; it holds no copy of them."""
-    text = open(os.path.join(ROOT, "vmlmf_amd", "csrc", "vmlmf_score.hip")).read()
-    assert '#include "vmlmf_select.h"' in text
-    for fn in ("best_merge", "lse_merge", "radix_select", "tie_cutoff", "choose_row", "key_of", "for_quads"):
-        assert not re.search(r"__device__[^;{]*\b%s\s*\(" % fn, text), fn
-    for fn in ("choose_row", "radix_select", "tie_cutoff"):
-        assert re.search(r"\b%s\s*\(" % fn, text), fn                 # ... and calls them

@@ -13,9 +13,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
+
+from _timing import replayed_us, wall_ms
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -24,35 +25,13 @@ V, H, L = 10000, 650, 2
 
 def _replayed_us(body, n, reps):
     """us per iteration of `body`, n of them captured into one graph; best of `reps` replays, and max / min."""
-    for _ in range(3):
-        body()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(n):
-            body()
-    g.replay()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(1e3 * e0.elapsed_time(e1) / n)
-    return min(ts), round(max(ts) / min(ts), 3)
+    us, spread = replayed_us(lambda j: body(), n, reps)
+    return us, round(spread, 3)
 
 
 def _wall_ms(fn, per, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append(1e3 * (time.perf_counter() - t0) / per)
-    return min(ts), round(max(ts) / min(ts), 3)
+    ms, spread = wall_ms(fn, reps)
+    return ms / per, round(spread, 3)
 
 
 def stock_select(scores, bias, cum, embed, states, B, W):

@@ -21,34 +21,14 @@ import ctypes
 import json
 import os
 import sys
-import time
 
 import torch
+
+from _timing import replayed_us, wall_ms
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 V, H, TOP_K, TOP_P, N = 10000, 650, 40, 0.9, 50
-
-
-def replayed_us(launch, reps, n=N):
-    """us per call of launch(j) (best of `reps` replays of a graph of n calls); replayed_us.spread: max / min over the replays."""
-    for j in range(3):
-        launch(j)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for j in range(n):
-            launch(j)
-    g.replay()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(1e3 * e0.elapsed_time(e1) / n)
-    replayed_us.spread = max(ts) / min(ts)
-    return min(ts)
 
 
 def all_controls(B, dev, prompt=None):
@@ -110,15 +90,14 @@ def main():
                 _lib.check(lib.vmlmf_lm_choose_filtered(B, H, V, _ptr(scores), _ptr(bias), _ptr(embed), 1.0, TOP_K, TOP_P, _ptr(snap), j, _ptr(tok),
                                                         _ptr(lp), _ptr(xn), _ptr(kept), stream()))
             for name, fn in (("unfiltered", plain), ("filtered", filtered)):
-                rec[f"choice_{prefix}{name}_us"] = round(replayed_us(fn, a.reps), 3)
-                rec[f"choice_{prefix}{name}_spread"] = round(replayed_us.spread, 3)
+                us, spread = replayed_us(fn, N, a.reps)
+                rec[f"choice_{prefix}{name}_us"], rec[f"choice_{prefix}{name}_spread"] = round(us, 3), round(spread, 3)
         if not a.skip_controls:
             from vmlmf_amd import _decode
             for name, k, p in (("controlled", TOP_K, TOP_P), ("controlled_unfiltered", 0, 1.0)):
                 ctl = all_controls(B, dev)
-                rec[f"choice_{name}_us"] = round(replayed_us(
-                    lambda j: _decode.decode_choose(scores, bias, embed, 1.0, k, p, snap, j, ctl, tok, lp, xn, kept), a.reps), 3)
-                rec[f"choice_{name}_spread"] = round(replayed_us.spread, 3)
+                us, spread = replayed_us(lambda j: _decode.decode_choose(scores, bias, embed, 1.0, k, p, snap, j, ctl, tok, lp, xn, kept), N, a.reps)
+                rec[f"choice_{name}_us"], rec[f"choice_{name}_spread"] = round(us, 3), round(spread, 3)
                 assert not ctl.finished.any()
             rec["controlled_minus_filtered_us"] = round(rec["choice_controlled_us"] - rec["choice_filtered_us"], 3)
         K = 16
@@ -127,17 +106,10 @@ def main():
             cases.append(("controlled", dict(top_k=TOP_K, top_p=TOP_P), True))
         for name, kw, controlled in cases:
             g = DecodeGraph(m, hv, st, K, temperature=1.0, controls=all_controls(B, dev, prompt) if controlled else None, **kw)
-            ts = []
             g.replay()
-            torch.cuda.synchronize()
-            for _ in range(a.reps):
-                t0 = time.perf_counter()
-                for _ in range(4):
-                    g.graph.replay()
-                torch.cuda.synchronize()
-                ts.append((time.perf_counter() - t0) / (4 * K))
-            rec[f"graph_{name}_ms_per_token"] = round(1e3 * min(ts), 5)
-            rec[f"graph_{name}_spread"] = round(max(ts) / min(ts), 3)
+            ms, spread = wall_ms(g.graph.replay, a.reps, calls=4)
+            rec[f"graph_{name}_ms_per_token"] = round(ms / K, 5)
+            rec[f"graph_{name}_spread"] = round(spread, 3)
             del g
         line = json.dumps(rec)
         print(line, flush=True)

@@ -14,9 +14,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
+
+from _timing import replayed_us, wall_ms
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
@@ -31,43 +32,10 @@ def _model(group):
     return m.cuda().eval()
 
 
-def _timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    _timed.spread = max(ts) / min(ts)
-    return min(ts)
-
-
-def _rec(t, B, steps):
-    return {"ms_per_token": 1e3 * t / steps, "tokens_per_s": B * steps / t, "spread": round(_timed.spread, 3)}
-
-
-def sampler_us(h, w, b, e, snap, form, n=50, reps=3, **filters):
-    """us per sampler step (best of `reps` replays of a graph of n steps); sampler_us.spread: max / min over the replays."""
-    from vmlmf_amd import lm_sample
-    for _ in range(3):
-        lm_sample(h, w, b, 1.0, snap, 0, embed=e, form=form, **filters)
-    gs = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gs):
-        for j in range(n):
-            lm_sample(h, w, b, 1.0, snap, j, embed=e, form=form, **filters)
-    gs.replay()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        e0.record()
-        gs.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(1e3 * e0.elapsed_time(e1) / n)
-    sampler_us.spread = max(ts) / min(ts)
-    return min(ts)
+def _rec(timing, B, steps):
+    """A record of wall_ms()'s (ms, spread) for one pass over `steps` tokens of B rows."""
+    ms, spread = timing
+    return {"ms_per_token": ms / steps, "tokens_per_s": 1e3 * B * steps / ms, "spread": round(spread, 3)}
 
 
 def naive(m, x, states, steps):
@@ -96,7 +64,7 @@ def main():
     ap.add_argument("--models", default="plain,group")
     a = ap.parse_args()
     filters = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p)) if v is not None}
-    from vmlmf_amd import DecodeGraph, dropout_advance
+    from vmlmf_amd import DecodeGraph, dropout_advance, lm_sample
     from vmlmf_amd.decoding import _KeptImages, decode_steps
     dev = torch.device("cuda")
     rows = []
@@ -124,9 +92,10 @@ def main():
             snap = dropout_advance(m.sampler_state())
             hv = h[-1].contiguous()
             for form in ("fused", "gemm"):
-                us = sampler_us(hv, m.fc.w, m.fc.b, m.embed.w, snap, form, reps=a.reps, **filters)
+                # the sampler alone: 50 steps replayed from a graph
+                us, spread = replayed_us(lambda j: lm_sample(hv, m.fc.w, m.fc.b, 1.0, snap, j, embed=m.embed.w, form=form, **filters), 50, a.reps)
                 res["sampler_%s_us" % form] = us
-                res["sampler_%s_spread" % form] = round(sampler_us.spread, 3)
+                res["sampler_%s_spread" % form] = round(spread, 3)
                 res["sampler_%s_fc_w_GBps" % form] = 10000 * 650 * 4 / (us * 1e-6) / 1e9
             if a.sampler_only:
                 emit(res)
@@ -135,14 +104,14 @@ def main():
                 def eager():
                     with torch.no_grad(), _KeptImages(m):
                         decode_steps(m, hv, [(s0.clone(), s1.clone()) for s0, s1 in st], steps, 1.0, snap, path, **filters)
-                t = _timed(eager, a.reps)
+                t = wall_ms(eager, a.reps)
                 res["eager" if path == "layers" else "eager_stack"] = _rec(t, B, steps)
             g = DecodeGraph(m, hv, st, K, temperature=1.0, **filters)
-            t = _timed(lambda: [g.replay() for _ in range(steps // K)], a.reps)
+            t = wall_ms(lambda: [g.replay() for _ in range(steps // K)], a.reps)
             res["graph"] = dict(_rec(t, B, steps), chunk=K)
             del g
             x0 = prompt[-1]
-            t = _timed(lambda: naive(m, x0, [(s0.clone(), s1.clone()) for s0, s1 in st], steps), a.reps)
+            t = wall_ms(lambda: naive(m, x0, [(s0.clone(), s1.clone()) for s0, s1 in st], steps), a.reps)
             res["naive"] = _rec(t, B, steps)
             emit(res)
         del m

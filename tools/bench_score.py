@@ -17,50 +17,19 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
+
+from _timing import replayed_us, wall_ms
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 V, H, N, TOPS = 10000, 650, 50, (0, 8, 32)
 
 
-def replayed_us(launch, reps, n=N):
-    """us per call of launch() (best of `reps` replays of a graph of n calls); replayed_us.spread: max / min over the replays."""
-    for _ in range(3):
-        launch()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(n):
-            launch()
-    g.replay()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ts = []
-    for _ in range(reps):
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(1e3 * e0.elapsed_time(e1) / n)
-    replayed_us.spread = max(ts) / min(ts)
-    return min(ts)
-
-
-def eager_ms(call, reps, n=5):
-    """ms per call() (best of `reps` timings of n calls between synchronisations); eager_ms.spread: max / min."""
-    for _ in range(2):
-        call()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            call()
-        torch.cuda.synchronize()
-        ts.append(1e3 * (time.perf_counter() - t0) / n)
-    eager_ms.spread = max(ts) / min(ts)
-    return min(ts)
+def timed(rec, key, unit, timing, digits):
+    """rec[<key>_<unit>], rec[<key>_spread] from a timer's (best, spread)."""
+    rec[f"{key}_{unit}"], rec[f"{key}_spread"] = round(timing[0], digits), round(timing[1], 3)
 
 
 def stock(sb, y, top):
@@ -103,13 +72,10 @@ def main():
         for top in TOPS:
             toks = torch.empty((R, max(top, 1)), device=dev, dtype=torch.int64)
             tlp = torch.empty((R, max(top, 1)), device=dev)
-            rec[f"launch_top{top}_us"] = round(replayed_us(lambda: _score.score_rows(scores, bias, y, top, lp, rank, toks, tlp), a.reps), 3)
-            rec[f"launch_top{top}_spread"] = round(replayed_us.spread, 3)
-            rec[f"stock_top{top}_us"] = round(replayed_us(lambda: stock(sb, y, top), a.reps), 3)
-            rec[f"stock_top{top}_spread"] = round(replayed_us.spread, 3)
-        rec["choose_us"] = round(replayed_us(lambda: _lib.check(_lib.lib().vmlmf_lm_choose(
-            R, H, V, _ptr(scores), _ptr(bias), None, 0.0, None, 0, _ptr(tok), _ptr(lp), None, _lib.raw_stream(dev))), a.reps), 3)
-        rec["choose_spread"] = round(replayed_us.spread, 3)
+            timed(rec, f"launch_top{top}", "us", replayed_us(lambda j: _score.score_rows(scores, bias, y, top, lp, rank, toks, tlp), N, a.reps), 3)
+            timed(rec, f"stock_top{top}", "us", replayed_us(lambda j: stock(sb, y, top), N, a.reps), 3)
+        timed(rec, "choose", "us", replayed_us(lambda j: _lib.check(_lib.lib().vmlmf_lm_choose(
+            R, H, V, _ptr(scores), _ptr(bias), None, 0.0, None, 0, _ptr(tok), _ptr(lp), None, _lib.raw_stream(dev))), N, a.reps), 3)
         emit(rec)
     T, B = 35, 32
     cache_packed_parameters(m)
@@ -120,10 +86,8 @@ def main():
         with torch.no_grad():
             return stock(m(x[:-1], m.state_init(B))[0], x[1:].reshape(-1), top)
     for top in (0, 8):
-        rec[f"model_score_top{top}_ms"] = round(eager_ms(lambda: m.score(x, top=top), a.reps), 4)
-        rec[f"model_score_top{top}_spread"] = round(eager_ms.spread, 3)
-        rec[f"model_stock_top{top}_ms"] = round(eager_ms(lambda: stock_model(top), a.reps), 4)
-        rec[f"model_stock_top{top}_spread"] = round(eager_ms.spread, 3)
+        timed(rec, f"model_score_top{top}", "ms", wall_ms(lambda: m.score(x, top=top), a.reps, calls=5, warm=2), 4)
+        timed(rec, f"model_stock_top{top}", "ms", wall_ms(lambda: stock_model(top), a.reps, calls=5, warm=2), 4)
     emit(rec)
     if out:
         out.close()

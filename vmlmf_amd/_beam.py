@@ -6,14 +6,12 @@ There is no fallback: if the library is missing, or a call fails, this raises.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import torch
 
 from . import _lib
 from ._lib import ptr
 
-LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_beam.so")
 ABI_VERSION = 1
 MAX_BEAMS = 32
 MAX_TENSORS = 16
@@ -29,25 +27,9 @@ SYMBOLS = {
     "vmlmf_beam_backtrack": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
-_handle = None
-
-
-def lib():
-    """The loaded libvmlmf_beam.so.  Raises if it has not been built: there is no fallback path."""
-    global _handle
-    if _handle is None:
-        _handle = _lib.load(LIB_PATH, SYMBOLS, "vmlmf_beam_abi_version", ABI_VERSION, "stock-op fallback for the beam-search step")
-    return _handle
-
-
-def loaded():
-    """Whether this process has opened libvmlmf_beam.so."""
-    return _handle is not None
-
-
-def check(rc):
-    if rc != 0:
-        raise _lib.VmlmfError(rc, lib().vmlmf_beam_last_error().decode())
+LIBRARY = _lib.Library("libvmlmf_beam.so", SYMBOLS, "vmlmf_beam_abi_version", ABI_VERSION, "vmlmf_beam_last_error",
+                       "stock-op fallback for the beam-search step")
+lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 
 def check_beams(beams, V=None):
@@ -136,7 +118,6 @@ def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
     B, W = cum.shape
     V = scores.shape[1]
     dev = scores.device
-    handle = lib()
     ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
     H = embed.shape[1] if embed is not None else 1
     parent = torch.empty((B, W), device=dev, dtype=torch.int32)
@@ -146,10 +127,8 @@ def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
     ln = torch.empty((B, W), device=dev, dtype=torch.int32)
     src = torch.empty(B * W, device=dev, dtype=torch.int32)
     xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
-    with _lib.on_device(dev):
-        check(handle.vmlmf_beam_step(B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                                     ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket),
-                                     ptr(ws), ws.numel() * 8, _lib.raw_stream(dev)))
+    LIBRARY.call(dev, "vmlmf_beam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
+                 ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8)
     return parent, token, total, fin, ln, xn, src
 
 
@@ -173,10 +152,8 @@ def beam_gather(tensors, src_row):
     n = len(srcs)
     sp = (_vp * n)(*[t.data_ptr() for t in srcs])
     dp = (_vp * n)(*[t.data_ptr() for t in dsts])
-    dev = srcs[0].device
     rows_c = src_row.contiguous()
-    with _lib.on_device(dev):
-        check(lib().vmlmf_beam_gather(n, rows, H, ptr(rows_c), sp, dp, _lib.raw_stream(dev)))
+    LIBRARY.call(srcs[0].device, "vmlmf_beam_gather", n, rows, H, ptr(rows_c), sp, dp)
     return dsts
 
 
@@ -198,7 +175,5 @@ def beam_backtrack(parent, token, order=None):
     if steps == 0:
         return out
     p, t = parent.contiguous(), token.contiguous()
-    dev = p.device
-    with _lib.on_device(dev):
-        check(lib().vmlmf_beam_backtrack(steps, B, W, ptr(p), ptr(t), ptr(order), ptr(out), _lib.raw_stream(dev)))
+    LIBRARY.call(p.device, "vmlmf_beam_backtrack", steps, B, W, ptr(p), ptr(t), ptr(order), ptr(out))
     return out

@@ -8,14 +8,12 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 
 import torch
 
 from . import _lib
 from ._lib import ptr
 
-LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_decode.so")
 ABI_VERSION = 1
 
 
@@ -33,26 +31,9 @@ SYMBOLS = {
     "vmlmf_decode_choose": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _i, _f, _vp, _i, ctypes.POINTER(Controls), _vp, _vp, _vp, _vp, _vp]),
 }
 
-_handle = None
-
-
-def lib():
-    """The loaded libvmlmf_decode.so.  Raises if it has not been built: there is no fallback path."""
-    global _handle
-    if _handle is None:
-        _handle = _lib.load(LIB_PATH, SYMBOLS, "vmlmf_decode_abi_version", ABI_VERSION,
-                            "stock-op fallback for the controlled choice of Model.generate")
-    return _handle
-
-
-def loaded():
-    """Whether this process has opened libvmlmf_decode.so."""
-    return _handle is not None
-
-
-def check(rc):
-    if rc != 0:
-        raise _lib.VmlmfError(rc, lib().vmlmf_decode_last_error().decode())
+LIBRARY = _lib.Library("libvmlmf_decode.so", SYMBOLS, "vmlmf_decode_abi_version", ABI_VERSION, "vmlmf_decode_last_error",
+                       "stock-op fallback for the controlled choice of Model.generate")
+lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 
 def controls_on(eos=None, repetition_penalty=1.0, logit_bias=None, banned_tokens=None):
@@ -162,8 +143,6 @@ def decode_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls,
     if not isinstance(controls, DecodeControls) or (controls.B, controls.V) != (B, V) or controls.seen.device != dev:
         raise RuntimeError(f"vmlmf_amd.lm_sample: controls must be a DecodeControls for {B} rows of {V} tokens on {dev}")
     H = embed.shape[1] if embed is not None else 1
-    handle = lib()
     c = controls.struct()
-    with _lib.on_device(dev):
-        check(handle.vmlmf_decode_choose(B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
-                                         ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept), _lib.raw_stream(dev)))
+    LIBRARY.call(dev, "vmlmf_decode_choose", B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
+                 ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept))

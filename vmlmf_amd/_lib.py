@@ -261,7 +261,39 @@ def check(rc):
         raise VmlmfError(rc, lib().vmlmf_last_error().decode())
 
 
-def make_desc(variant, B, T, I, H, w_rank, u_ranks, g=1, time_major=False, training=True, dtype=0):
+class Library:
+    """A side library beside libvmlmf_hip.so (beam, decode, score: a header, an ABI version and a last-error text of its own), opened
+    and bound on first use - a process that never calls into it never maps it.  `path` may be repointed before the first use."""
+
+    def __init__(self, filename, symbols, abi_symbol, abi_version, error_symbol, no_fallback):
+        self.path = os.path.join(os.path.dirname(LIB_PATH), filename)
+        self.symbols, self.abi_symbol, self.abi_version = symbols, abi_symbol, abi_version
+        self.error_symbol, self.no_fallback = error_symbol, no_fallback
+        self._handle = None
+
+    def handle(self):
+        """The loaded library.  Raises if it has not been built: there is no fallback path."""
+        if self._handle is None:
+            self._handle = load(self.path, self.symbols, self.abi_symbol, self.abi_version, self.no_fallback)
+        return self._handle
+
+    def loaded(self):
+        """Whether this process has opened the library."""
+        return self._handle is not None
+
+    def check(self, rc):
+        if rc != 0:
+            raise VmlmfError(rc, getattr(self.handle(), self.error_symbol)().decode())
+
+    def call(self, dev, name, *args):
+        """One launch: `dev` made current, the entry point `name` called with torch's current stream on `dev` as its last argument,
+        the result checked."""
+        fn = getattr(self.handle(), name)
+        with on_device(dev):
+            self.check(fn(*args, raw_stream(dev)))
+
+
+def make_desc(variant,B, T, I, H, w_rank, u_ranks, g=1, time_major=False, training=True, dtype=0):
     d = Desc()
     d.variant, d.B, d.T, d.I, d.H, d.w_rank = variant, B, T, I, H, w_rank
     d.g = g

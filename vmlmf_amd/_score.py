@@ -7,12 +7,10 @@ There is no fallback: if the library is missing, or a call fails, this raises.
 from __future__ import annotations
 
 import ctypes
-import os
 
 from . import _lib
 from ._lib import ptr
 
-LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libvmlmf_score.so")
 ABI_VERSION = 1
 MAX_TOP = 32    # VMLMF_SCORE_MAX_TOP
 
@@ -24,25 +22,9 @@ SYMBOLS = {
     "vmlmf_score_rows": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
-_handle = None
-
-
-def lib():
-    """The loaded libvmlmf_score.so.  Raises if it has not been built: there is no fallback path."""
-    global _handle
-    if _handle is None:
-        _handle = _lib.load(LIB_PATH, SYMBOLS, "vmlmf_score_abi_version", ABI_VERSION, "stock-op fallback for Model.score")
-    return _handle
-
-
-def loaded():
-    """Whether this process has opened libvmlmf_score.so."""
-    return _handle is not None
-
-
-def check(rc):
-    if rc != 0:
-        raise _lib.VmlmfError(rc, lib().vmlmf_score_last_error().decode())
+LIBRARY = _lib.Library("libvmlmf_score.so", SYMBOLS, "vmlmf_score_abi_version", ABI_VERSION, "vmlmf_score_last_error",
+                       "stock-op fallback for Model.score")
+lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 
 def check_top(top, V, who="lm_score"):
@@ -56,8 +38,5 @@ def check_top(top, V, who="lm_score"):
 def score_rows(scores, bias, targets, top, logprob, rank, top_tokens, top_logprob):
     """The vmlmf_score_rows launch on checked, contiguous arguments: scores (R, V) without the bias; outputs are written in place."""
     R, V = scores.shape
-    dev = scores.device
-    handle = lib()
-    with _lib.on_device(dev):
-        check(handle.vmlmf_score_rows(R, V, ptr(scores), ptr(bias), ptr(targets), int(top), ptr(logprob), ptr(rank), ptr(top_tokens),
-                                      ptr(top_logprob), _lib.raw_stream(dev)))
+    LIBRARY.call(scores.device, "vmlmf_score_rows", R, V, ptr(scores), ptr(bias), ptr(targets), int(top), ptr(logprob), ptr(rank),
+                 ptr(top_tokens), ptr(top_logprob))

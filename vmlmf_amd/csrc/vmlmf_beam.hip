@@ -22,9 +22,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/vmlmf_beam.h"
+#include "vmlmf_side.h"
 
 namespace {
 
@@ -293,15 +292,7 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(int steps, int B, in
   }
 }
 
-thread_local std::string g_error;
-int fail(int code, const std::string& msg) {
-  g_error = msg;
-  return code;
-}
-int hip_tail(const char* what) {
-  const hipError_t rc = hipGetLastError();
-  return rc == hipSuccess ? 0 : fail((int)rc, std::string(what) + ": " + hipGetErrorString(rc));
-}
+using vmlmf_side::fail;   // (every call site gives the entry point's name itself)
 // 0, or why vmlmf_beam_step refuses these sizes
 int step_sizes(int B, int W, int H, int V, int eos, std::string* why) {
   if (B < 1 || H < 1 || V < 1) return *why = "B, H and V must be >= 1", VMLMF_E_BADARG;
@@ -315,10 +306,9 @@ int step_sizes(int B, int W, int H, int V, int eos, std::string* why) {
 
 }  // namespace
 
-extern "C" {
+VMLMF_SIDE_LIBRARY(vmlmf_beam, VMLMF_BEAM_ABI_VERSION)
 
-int vmlmf_beam_abi_version(void) { return VMLMF_BEAM_ABI_VERSION; }
-const char* vmlmf_beam_last_error(void) { return g_error.c_str(); }
+extern "C" {
 
 size_t vmlmf_beam_workspace_bytes(int B, int W, int V) {
   std::string why;
@@ -349,7 +339,7 @@ int vmlmf_beam_step(int B, int W, int H, int V, const float* scores, const float
   a.token = reinterpret_cast<long long*>(token), a.total = total, a.x_next = x_next, a.ticket = ticket;
   a.cand = static_cast<unsigned long long*>(workspace);
   hipLaunchKernelGGL(beam_step_kernel, dim3(B * W), dim3(BS_NT), 0, static_cast<hipStream_t>(stream), a);
-  return hip_tail("vmlmf_beam_step");
+  return vmlmf_side::launch_tail("vmlmf_beam_step");
 }
 
 int vmlmf_beam_gather(int n, int rows, int H, const int32_t* src_row, const void* const* src, void* const* dst, void* stream) {
@@ -368,7 +358,7 @@ int vmlmf_beam_gather(int n, int rows, int H, const int32_t* src_row, const void
       if (dst[i] == src[j]) return fail(VMLMF_E_BADARG, "vmlmf_beam_gather: a destination is also a source (rows would be read after they were overwritten)");
   a.src_row = src_row, a.rows = rows, a.H = H;
   hipLaunchKernelGGL(beam_gather_kernel, dim3(rows, n), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return hip_tail("vmlmf_beam_gather");
+  return vmlmf_side::launch_tail("vmlmf_beam_gather");
 }
 
 int vmlmf_beam_backtrack(int steps, int B, int W, const int32_t* parent, const int64_t* token, const int32_t* order, int64_t* out,
@@ -379,7 +369,7 @@ int vmlmf_beam_backtrack(int steps, int B, int W, const int32_t* parent, const i
   if (!parent || !token || !out) return fail(VMLMF_E_BADARG, "vmlmf_beam_backtrack: null pointer (only order may be null)");
   hipLaunchKernelGGL(beam_backtrack_kernel, dim3((B * W + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), steps, B, W, parent,
                      reinterpret_cast<const long long*>(token), order, reinterpret_cast<long long*>(out));
-  return hip_tail("vmlmf_beam_backtrack");
+  return vmlmf_side::launch_tail("vmlmf_beam_backtrack");
 }
 
 }  // extern "C"

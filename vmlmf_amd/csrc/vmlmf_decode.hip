@@ -12,10 +12,10 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/vmlmf_decode.h"
+#include "vmlmf_refusals.h"
 #include "vmlmf_select.h"
+#include "vmlmf_side.h"
 
 namespace {
 
@@ -89,18 +89,13 @@ __global__ __launch_bounds__(DC_FILTERED_NT) void decode_choose_kernel(DecodeArg
   }
 }
 
-thread_local std::string g_error;
-int fail(int code, const std::string& msg) {
-  g_error = "vmlmf_decode_choose: " + msg;
-  return code;
-}
+int fail(int code, const char* msg) { return vmlmf_side::fail(code, std::string("vmlmf_decode_choose: ") + msg); }
 
 }  // namespace
 
-extern "C" {
+VMLMF_SIDE_LIBRARY(vmlmf_decode, VMLMF_DECODE_ABI_VERSION)
 
-int vmlmf_decode_abi_version(void) { return VMLMF_DECODE_ABI_VERSION; }
-const char* vmlmf_decode_last_error(void) { return g_error.c_str(); }
+extern "C" {
 
 int vmlmf_decode_choose(int B, int H, int V, const float* scores, const float* bias, const float* embed, float inv_temperature, int top_k,
                         float top_p, const int64_t* state, int step, const vmlmf_decode_controls* c, int64_t* tokens, float* logprob,
@@ -109,14 +104,8 @@ int vmlmf_decode_choose(int B, int H, int V, const float* scores, const float* b
   if (!scores || !tokens) return fail(VMLMF_E_BADARG, "null pointer (scores, tokens)");
   if (!c) return fail(VMLMF_E_BADARG, "null controls");
   if (!c->seen || !c->finished || !c->length) return fail(VMLMF_E_BADARG, "null pointer in the controls (seen, finished and length are required)");
-  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-    return fail(VMLMF_E_BADARG, "the inverse temperature must be finite and >= 0 (0: greedy)");
-  if (inv_temperature > 0.f && !state) return fail(VMLMF_E_BADARG, "sampling needs the {seed, offset} snapshot");
-  if (x_next && !embed) return fail(VMLMF_E_BADARG, "x_next needs the embedding table");
-  if (step < 0) return fail(VMLMF_E_BADARG, "step must be >= 0");
-  if ((long long)(step + 1ll) * B > (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "2^32 positions (step * B + b) and more");
-  if (top_k < 0) return fail(VMLMF_E_BADARG, "top_k must be >= 0 (0: off)");
-  if (!(top_p > 0.f && top_p <= 1.f)) return fail(VMLMF_E_BADARG, "top_p must lie in (0, 1] (1: off)");
+  if (const int rc = sampler_refusal(fail, B, inv_temperature, state, embed, x_next, step)) return rc;
+  if (const int rc = filter_refusal(fail, top_k, top_p)) return rc;
   if (c->eos < -1 || c->eos >= V) return fail(VMLMF_E_BADARG, "eos must be a token in [0, V), or -1 for none");
   if (!(c->repetition_penalty > 0.f) || c->repetition_penalty > 3.0e38f)
     return fail(VMLMF_E_BADARG, "repetition_penalty must be finite and > 0 (1: off)");
@@ -130,8 +119,7 @@ int vmlmf_decode_choose(int B, int H, int V, const float* scores, const float* b
   a.logit_bias = c->logit_bias, a.seen = c->seen, a.finished = c->finished, a.length = c->length;
   const bool filtered = inv_temperature > 0.f && (a.top_k > 0 || top_p < 1.f);
   hipLaunchKernelGGL(decode_choose_kernel, dim3(B), dim3(filtered ? DC_FILTERED_NT : SM_CHOOSE_NT), 0, static_cast<hipStream_t>(stream), a);
-  const hipError_t rc = hipGetLastError();
-  return rc == hipSuccess ? 0 : fail((int)rc, hipGetErrorString(rc));
+  return vmlmf_side::launch_tail("vmlmf_decode_choose");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // The thin entry points of the C ABI: argument checks and one launch each (head, criterion, embedding, dropout, sampler, transpose).
 #include "vmlmf_host.h"
+#include "vmlmf_refusals.h"
 
 using namespace vmlmf_host;
 
@@ -153,20 +154,12 @@ namespace {
 // "<entry point>: <text>" (one copy of the string work for all the refusals below)
 __attribute__((noinline)) int refuse(int code, const char* name, const char* text) { return fail(code, std::string(name) + ": " + text); }
 
-// what both forms of the sampler step refuse, under the entry point's name
-int sampler_refusal(const char* name, int B, float inv_temperature, const void* state, const void* embed, const void* x_next, int step) {
-  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
-    return refuse(VMLMF_E_BADARG, name, "the inverse temperature must be finite and >= 0 (0: greedy)");
-  if (inv_temperature > 0.f && !state) return refuse(VMLMF_E_BADARG, name, "sampling needs the {seed, offset} snapshot");
-  if (x_next && !embed) return refuse(VMLMF_E_BADARG, name, "x_next needs the embedding table");
-  if (step < 0) return refuse(VMLMF_E_BADARG, name, "step must be >= 0");
-  if ((long long)(step + 1ll) * B > (1ll << 32)) return refuse(VMLMF_E_UNSUPPORTED, name, "2^32 positions (step * B + b) and more");
-  return 0;
-}
-int filter_refusal(const char* name, int top_k, float top_p) {
-  if (top_k < 0) return refuse(VMLMF_E_BADARG, name, "top_k must be >= 0 (0: off)");
-  if (!(top_p > 0.f && top_p <= 1.f)) return refuse(VMLMF_E_BADARG, name, "top_p must lie in (0, 1] (1: off)");
-  return 0;
+// what both forms of the sampler step refuse (vmlmf_refusals.h), under the entry point's name
+int sampler_and_filter_refusal(const char* name, int B, float inv_temperature, int top_k, float top_p, const void* state, const void* embed,
+                               const void* x_next, int step) {
+  const auto named = [name](int code, const char* text) { return refuse(code, name, text); };
+  if (int rc = sampler_refusal(named, B, inv_temperature, state, embed, x_next, step)) return rc;
+  return filter_refusal(named, top_k, top_p);
 }
 // the launch where no selection runs (filters off, or greedy: the argmax is always kept) writes no counts: the whole row then
 int kept_is_the_row(int B, int V, float inv_temperature, int top_k, float top_p, int32_t* kept_out, hipStream_t s) {
@@ -180,8 +173,7 @@ int lm_sample_entry(const char* name, size_t need, int B, int H, int V, const fl
                     void* stream) {
   if (B < 1 || H < 1 || V < 1) return refuse(VMLMF_E_BADARG, name, "B, H, V must be >= 1");
   if (!h || !weight || !tokens_out || !ticket || !workspace) return refuse(VMLMF_E_BADARG, name, "null pointer");
-  if (int rc = sampler_refusal(name, B, inv_temperature, state, embed, x_next, step)) return rc;
-  if (int rc = filter_refusal(name, top_k, top_p)) return rc;
+  if (int rc = sampler_and_filter_refusal(name, B, inv_temperature, top_k, top_p, state, embed, x_next, step)) return rc;
   if (workspace_bytes < need) return fail(VMLMF_E_WORKSPACE, std::string(name) + ": workspace smaller than vmlmf_" + name + "_workspace_bytes()");
   LmSampleArgs a;
   memset(&a, 0, sizeof(a));
@@ -200,8 +192,7 @@ int lm_choose_entry(const char* name, int B, int H, int V, const float* scores, 
                     float* x_next, int32_t* kept_out, void* stream) {
   if (B < 1 || V < 1 || (x_next && H < 1)) return refuse(VMLMF_E_BADARG, name, "B, V (and H with x_next) must be >= 1");
   if (!scores || !tokens_out) return refuse(VMLMF_E_BADARG, name, "null pointer");
-  if (int rc = sampler_refusal(name, B, inv_temperature, state, embed, x_next, step)) return rc;
-  if (int rc = filter_refusal(name, top_k, top_p)) return rc;
+  if (int rc = sampler_and_filter_refusal(name, B, inv_temperature, top_k, top_p, state, embed, x_next, step)) return rc;
   LmChooseArgs a;
   memset(&a, 0, sizeof(a));
   a.scores = scores, a.bias = bias, a.embed = embed, a.state = reinterpret_cast<const unsigned long long*>(state);

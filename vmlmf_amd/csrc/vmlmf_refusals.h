@@ -1,0 +1,22 @@
+// What every form of the sampler step refuses, written once for vmlmf_lm_sample / vmlmf_lm_choose and their filtered forms
+// (vmlmf_ops.hip) and for vmlmf_decode_choose (vmlmf_decode.hip).  `refuse(code, text)` is the caller's: it puts the entry point's
+// name before the text, keeps the result as its library's error and returns the code.  Host code only.
+#pragma once
+#include "../../include/vmlmf_hip.h" /* VMLMF_E_* */
+
+template <class Refuse>
+static int sampler_refusal(const Refuse& refuse, int B, float inv_temperature, const void* state, const void* embed, const void* x_next, int step) {
+  if (!(inv_temperature >= 0.f) || inv_temperature > 3.0e38f)
+    return refuse(VMLMF_E_BADARG, "the inverse temperature must be finite and >= 0 (0: greedy)");
+  if (inv_temperature > 0.f && !state) return refuse(VMLMF_E_BADARG, "sampling needs the {seed, offset} snapshot");
+  if (x_next && !embed) return refuse(VMLMF_E_BADARG, "x_next needs the embedding table");
+  if (step < 0) return refuse(VMLMF_E_BADARG, "step must be >= 0");
+  if ((long long)(step + 1ll) * B > (1ll << 32)) return refuse(VMLMF_E_UNSUPPORTED, "2^32 positions (step * B + b) and more");
+  return 0;
+}
+template <class Refuse>
+static int filter_refusal(const Refuse& refuse, int top_k, float top_p) {
+  if (top_k < 0) return refuse(VMLMF_E_BADARG, "top_k must be >= 0 (0: off)");
+  if (!(top_p > 0.f && top_p <= 1.f)) return refuse(VMLMF_E_BADARG, "top_p must lie in (0, 1] (1: off)");
+  return 0;
+}

@@ -13,10 +13,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/vmlmf_score.h"
 #include "vmlmf_select.h"
+#include "vmlmf_side.h"
 
 namespace {
 
@@ -142,18 +141,13 @@ __global__ __launch_bounds__(SM_CHOOSE_NT) void score_rows_kernel(ScoreArgs a) {
   }
 }
 
-thread_local std::string g_error;
-int fail(int code, const std::string& msg) {
-  g_error = "vmlmf_score_rows: " + msg;
-  return code;
-}
+int fail(int code, const char* msg) { return vmlmf_side::fail(code, std::string("vmlmf_score_rows: ") + msg); }
 
 }  // namespace
 
-extern "C" {
+VMLMF_SIDE_LIBRARY(vmlmf_score, VMLMF_SCORE_ABI_VERSION)
 
-int vmlmf_score_abi_version(void) { return VMLMF_SCORE_ABI_VERSION; }
-const char* vmlmf_score_last_error(void) { return g_error.c_str(); }
+extern "C" {
 
 int vmlmf_score_rows(int R, int V, const float* scores, const float* bias, const int64_t* targets, int top, float* logprob, int32_t* rank,
                      int64_t* top_tokens, float* top_logprob, void* stream) {
@@ -169,8 +163,7 @@ int vmlmf_score_rows(int R, int V, const float* scores, const float* bias, const
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (top > 0) hipLaunchKernelGGL(score_rows_kernel<true>, dim3(R), dim3(SM_CHOOSE_NT), 0, s, a);
   else hipLaunchKernelGGL(score_rows_kernel<false>, dim3(R), dim3(SM_CHOOSE_NT), 0, s, a);
-  const hipError_t rc = hipGetLastError();
-  return rc == hipSuccess ? 0 : fail((int)rc, hipGetErrorString(rc));
+  return vmlmf_side::launch_tail("vmlmf_score_rows");
 }
 
 }  // extern "C"
