@@ -88,7 +88,8 @@ typedef struct vmlmf_grads {
 } vmlmf_grads;
 
 typedef struct vmlmf_sizes {
-  size_t workspace_bytes; /* scratch, may be reused by the next call on the same stream            */
+  size_t workspace_bytes; /* scratch, may be reused by the next call on the same stream; one size for both directions: forward and
+                           * backward alike refuse a smaller buffer (VMLMF_E_WORKSPACE, nothing launched)                  */
   size_t reserve_bytes;   /* written by forward(training=1), read by backward                      */
   int32_t rows_per_wg;    /* batch rows one persistent workgroup owns                              */
   int32_t threads_per_wg; /* = groups * waves_per_group * 64                                       */
@@ -191,7 +192,9 @@ int vmlmf_seq_backward_packed(const vmlmf_desc *d, const vmlmf_params *p, const 
 int vmlmf_tune_generation(void);
 /* ABI 11: the current value of a vmlmf_tune switch.  "wride" reads 0 while the riding weight-gradient workers are off - by
  * VMLMF_WRIDE=0, by vmlmf_tune("wride", 0), or because a launch gave up a bounded wait (VMLMF_E_PROTOCOL) and the library fell back
- * to the stand-alone kernel: a benchmark reports it, so a shared GPU cannot pass for a regression. */
+ * to the stand-alone kernel: a benchmark reports it, so a shared GPU cannot pass for a regression.  "wring_launches" (read-only) counts the
+ * launches of wgrad_ring_kernel by this process: "wring" says what was asked for, this what ran (the ring falls back to the stand-alone
+ * kernel where it has no instantiation or no LDS on the device). */
 int vmlmf_tune_get(const char *key, int *value);
 
 /*

@@ -354,6 +354,7 @@ int backward_tail(const VGeo& g, const LayerPlan& pl, const Layout& L, const vml
     // large layers: operands through an LDS ring, long chunks (vmlmf_wgrad_ring.hip); -1: where it was measured faster
     const bool ring = g_wring != 0 && wgrad_ring_ok(g) && (g_wring > 0 || (g.generic && (long long)g.T * g.B >= 1024));
     int rr = ring ? launch_wgrad_ring(g, wh, device_cus(), ring_nc, s) : -3;
+    if (rr == 0) ++g_ring_launches;
     if (rr == -3) {   // not taken, or no instantiation / no LDS for it on this device: the stand-alone products, one chunking for all
       ring_nc[0] = ring_nc[1] = ring_nc[2] = 0;
       rr = launch_wgrad_h(g, wh, s);
@@ -428,8 +429,7 @@ int vmlmf_query(const vmlmf_desc* d, vmlmf_sizes* out) {
   if (rc != 0) return rc;
   const VPack P = vg_pack_layout(g, q.total);
   const Layout L = make_layout(g, P, q);
-  const long long ws = L.f_total > L.b_total ? L.f_total : L.b_total;
-  out->workspace_bytes = (size_t)ws * sizeof(float);
+  out->workspace_bytes = (size_t)L.ws_total() * sizeof(float);
   out->reserve_bytes = (size_t)L.r_total * sizeof(float);
   out->rows_per_wg = g.rb ? q.rbl : g.R;
   out->threads_per_wg = g.rb ? 256 : g.NT;
@@ -589,7 +589,8 @@ int vmlmf_seq_forward_ex(const vmlmf_desc* d, const vmlmf_params* p, const float
   }
   const VPack P = vg_pack_layout(g, q.total);
   const Layout L = make_layout(g, P, q);
-  if (workspace_bytes < (size_t)L.f_total * sizeof(float))
+  // (the size vmlmf_query reports serves either direction: a buffer short of it is refused by both, whichever needs less)
+  if (workspace_bytes < (size_t)L.ws_total() * sizeof(float))
     return fail(VMLMF_E_WORKSPACE, "workspace smaller than vmlmf_query() reported");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
@@ -705,7 +706,7 @@ int vmlmf_seq_backward_ex(const vmlmf_desc* d, const vmlmf_params* p, const floa
   if ((rc = make_drop(ex != nullptr ? ex->drop : nullptr, g, false, &drop)) != 0) return rc;
   const VPack P = vg_pack_layout(g, q.total);
   const Layout L = make_layout(g, P, q);
-  if (workspace_bytes < (size_t)L.b_total * sizeof(float))
+  if (workspace_bytes < (size_t)L.ws_total() * sizeof(float))
     return fail(VMLMF_E_WORKSPACE, "workspace smaller than vmlmf_query() reported");
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;

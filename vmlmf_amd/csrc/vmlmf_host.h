@@ -28,6 +28,7 @@ extern int g_debug_sync, g_adam_guard, g_xwave, g_wchunks, g_wmin, g_rc, g_wride
     g_rb_minB, g_rb_S, g_rb_rows, g_rec3, g_inrow, g_wring, g_direct, g_finish2, g_wf_bwd, g_pack_slim, g_finish_units, g_rbx, g_ffb;
 extern int g_wride_spin, g_tune_generation;
 extern std::atomic<int> g_wride_tripped;
+extern std::atomic<int> g_ring_launches;   // launches of wgrad_ring_kernel by this process (vmlmf_tune_get "wring_launches")
 
 // ---- profiling (bench.py): HIP event pairs around every internal launch, on the launch stream.  The slots and their names
 // (vmlmf_kernel_name, vmlmf_profile_read): the order is part of the ABI
@@ -95,6 +96,8 @@ struct Layout {
   long long f_pack, f_gx, f_qx, f_trash, f_Qtmp, f_P, f_ccar, f_zeros, f_part, f_xq, f_flag, f_xrows, f_total;
   // backward workspace : dpre | dQs | wpart | cgrad
   long long b_dpre, b_dQs, b_dqx, b_wpart, b_cgrad, b_trash, b_dHrec, b_ehterm, b_dcar, b_part, b_xq, b_flag, b_headdh, b_dux, b_wide, b_total;
+  // the ONE workspace size of a layer (vmlmf_query reports it, forward and backward both demand it)
+  long long ws_total() const { return f_total > b_total ? f_total : b_total; }
 };
 Layout make_layout(const VGeo& g, const VPack& P, const RbGeo& q);
 

@@ -27,7 +27,7 @@ static void stack_offsets(StackPlan& S, long long o) {
   for (int l = 0; l < S.L; ++l) {
     S.P[l] = vg_pack_layout(S.g[l], S.q.total, S.W.total);
     S.lay[l] = make_layout(S.g[l], S.P[l], S.q);
-    const long long per = S.lay[l].f_total > S.lay[l].b_total ? S.lay[l].f_total : S.lay[l].b_total;
+    const long long per = S.lay[l].ws_total();
     S.ws_layer[l] = o, o += align64(per);
     S.ws_dx[l] = o, o += align64(l > 0 ? (long long)S.g[0].T * S.g[0].B * S.g[l].I : 0);   // dx of layer l = dy of layer l - 1
   }
@@ -285,6 +285,7 @@ static int rbx_stack_backward(const StackPlan& S, const vmlmf_stack_layer* ly, c
     int nc[3] = {0, 0, 0};
     Scope sc(SL_WGRAD, s);   // (covers the fallback's launches too)
     const int rr = launch_wgrad_ring(S.g[l], wh, device_cus(), nc, s);
+    if (rr == 0) ++g_ring_launches;
     if (rr == -3) {   // no LDS / instantiation for the ring on this device: the per-layer path for every layer from here
       for (int k = l; k >= 0; --k)
         if ((rc = stack_tail(S, ly, k, x, ws, s)) != 0) return rc;

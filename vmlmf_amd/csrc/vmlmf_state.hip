@@ -168,6 +168,7 @@ int g_wride_spin = WRIDE_SPIN_DEFAULT;
 // stand-alone weight-gradient kernel (plan_wride) instead of failing every step; vmlmf_tune("wride", 1) re-arms the riding form.
 // (Launches already captured into a hipGraph stay what they are.)
 std::atomic<int> g_wride_tripped{0};
+std::atomic<int> g_ring_launches{0};
 
 static const char* status_text(unsigned code) {
   switch (code) {
@@ -263,6 +264,7 @@ int vmlmf_tune_get(const char* key, int* value) {
   const std::string k(key);
   const Switch* sw = find_switch(k);
   if (k == "wride") *value = (g_wride && g_wride_tripped.load() == 0) ? 1 : 0;   // 0 also after a bounded wait gave up (VMLMF_ST_WRIDE)
+  else if (k == "wring_launches") *value = g_ring_launches.load();   // read-only: how often wgrad_ring_kernel itself was launched
   else if (sw != nullptr) *value = *sw->var;
   else return fail(VMLMF_E_BADARG, "tune_get: unknown key " + k);
   return 0;

@@ -110,8 +110,8 @@ __device__ __forceinline__ void ring_run(const VGeo& g, const AtbArgs& a, const 
   }
   const int nst_i = (row1 - row0 + WR_KR - 1) / WR_KR;
   // Rows of the caller's tensors (x, y, h0) and of dpre are clamped to the last row; the rank-space buffers (qx, Q, dQ, dqx) are
-  // read up to 15 rows past theirs in the last stage of the last chunk (vmlmf_api.hip's layout keeps 16 spare rows behind each) -
-  // masked at use either way.
+  // read up to 15 rows past theirs in the last stage of the last chunk (vmlmf_api.hip's layout keeps 16 spare rows behind each, which
+  // nobody writes) - selected away at use either way (compute: the special stages).
   auto issue = [&](const int st, const int slot) __attribute__((always_inline)) {
     const int r0 = st >= nst_i ? row0 : row0 + st * WR_KR;   // (past the last stage: any rows)
     const unsigned sb = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)slot * (WR_STAGE * 4));
@@ -176,6 +176,27 @@ __device__ __forceinline__ void ring_run(const VGeo& g, const AtbArgs& a, const 
 
   auto compute = [&](const float* S, const int r0, auto special) __attribute__((always_inline)) {
     constexpr bool SP = decltype(special)::value;   // a stage with rows past the chunk's end, or rows of t = 0 without h0
+    if constexpr (SP) {
+      // One row pair at a time, not unrolled (a chunk has a stage or two of these).  A row past the chunk takes part with NEITHER operand:
+      // past T B the rank-space rows are the layout's spare rows, which nobody wrote - selected away, since 0 x NaN is NaN.
+#pragma unroll 1
+      for (int u = 0; u < 8; ++u) {
+        const int r = r0 + 2 * u + lk;
+        const bool in = r < row1, noh = r < Bnoh;
+        const float a1 = (in && !(MODE == 2 && noh)) ? S[aoff + u * 2 * WR_AW] : 0.f;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const float b1 = in ? S[boff[j] + u * 2 * ((MODE == 3 || (MODE == 1 && j == 0)) ? 32 : QS)] : 0.f;
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[j], 0, 0, 0);
+        }
+        if (MODE == 1) {
+          e_h = fmaf(a1, noh ? 0.f : S[hoff + u * 128], e_h);
+          e_x = fmaf(a1, S[xoff + u * 128], e_x);
+          e_b += a1;
+        }
+      }
+      return;
+    }
     float av[8], hv[8], xv[8], bv[8][NB];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -186,14 +207,6 @@ __device__ __forceinline__ void ring_run(const VGeo& g, const AtbArgs& a, const 
       }
 #pragma unroll
       for (int j = 0; j < NB; ++j) bv[u][j] = S[boff[j] + u * 2 * ((MODE == 3 || (MODE == 1 && j == 0)) ? 32 : QS)];
-      if constexpr (SP) {
-        const int r = r0 + 2 * u + lk;
-        if (r >= row1) av[u] = 0.f;
-        if (r < Bnoh) {
-          if (MODE == 1) hv[u] = 0.f;
-          if (MODE == 2) av[u] = 0.f;
-        }
-      }
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
