@@ -70,7 +70,8 @@ def check_controls(V, eos=None, min_length=0, repetition_penalty=1.0, logit_bias
 
 def check_bias(V, logit_bias, banned, eos, min_length):
     """ValueError for a NaN or +inf in logit_bias, and for a bias (bans included) that leaves nothing to choose: no finite token at
-    all, or - while eos is held back by min_length - none besides eos.  Reads the tensor back once."""
+    all, or - while eos is held back by min_length - none besides eos.  Reads the tensor back once.  Returns how many tokens are closed
+    (eos, while min_length holds it back, among them)."""
     if logit_bias is None:
         open_ = torch.ones(V, dtype=torch.bool)
     else:
@@ -86,6 +87,7 @@ def check_bias(V, logit_bias, banned, eos, min_length):
         open_[eos] = False
         if not bool(open_.any()):
             raise ValueError("vmlmf_amd: logit_bias / banned_tokens leave no token besides eos, which min_length holds back")
+    return V - int(open_.sum())
 
 
 class DecodeControls:

@@ -106,11 +106,7 @@ int vmlmf_decode_choose(int B, int H, int V, const float* scores, const float* b
   if (!c->seen || !c->finished || !c->length) return fail(VMLMF_E_BADARG, "null pointer in the controls (seen, finished and length are required)");
   if (const int rc = sampler_refusal(fail, B, inv_temperature, state, embed, x_next, step)) return rc;
   if (const int rc = filter_refusal(fail, top_k, top_p)) return rc;
-  if (c->eos < -1 || c->eos >= V) return fail(VMLMF_E_BADARG, "eos must be a token in [0, V), or -1 for none");
-  if (!(c->repetition_penalty > 0.f) || c->repetition_penalty > 3.0e38f)
-    return fail(VMLMF_E_BADARG, "repetition_penalty must be finite and > 0 (1: off)");
-  if (c->min_length < 0) return fail(VMLMF_E_BADARG, "min_length must be >= 0");
-  if (c->min_length > 0 && c->eos < 0) return fail(VMLMF_E_BADARG, "min_length needs eos");
+  if (const int rc = controls_refusal(fail, V, c->eos, c->repetition_penalty, c->min_length)) return rc;
   DecodeArgs a;
   a.scores = scores, a.bias = bias, a.embed = embed, a.state = reinterpret_cast<const unsigned long long*>(state);
   a.tokens = reinterpret_cast<long long*>(tokens), a.logprob = logprob, a.x_next = x_next, a.kept = kept;

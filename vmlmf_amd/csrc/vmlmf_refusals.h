@@ -1,5 +1,6 @@
 // What every form of the sampler step refuses, written once for vmlmf_lm_sample / vmlmf_lm_choose and their filtered forms
-// (vmlmf_ops.hip) and for vmlmf_decode_choose (vmlmf_decode.hip).  `refuse(code, text)` is the caller's: it puts the entry point's
+// (vmlmf_ops.hip), for vmlmf_decode_choose (vmlmf_decode.hip) and for vmlmf_history_choose (vmlmf_history.hip); what the two controlled
+// choices refuse of the controls they share is controls_refusal.  `refuse(code, text)` is the caller's: it puts the entry point's
 // name before the text, keeps the result as its library's error and returns the code.  Host code only.
 #pragma once
 #include "../../include/vmlmf_hip.h" /* VMLMF_E_* */
@@ -18,5 +19,15 @@ template <class Refuse>
 static int filter_refusal(const Refuse& refuse, int top_k, float top_p) {
   if (top_k < 0) return refuse(VMLMF_E_BADARG, "top_k must be >= 0 (0: off)");
   if (!(top_p > 0.f && top_p <= 1.f)) return refuse(VMLMF_E_BADARG, "top_p must lie in (0, 1] (1: off)");
+  return 0;
+}
+// eos, the repetition penalty and the minimum length of a controlled choice (vmlmf_decode_controls, and vmlmf_history_controls' head)
+template <class Refuse>
+static int controls_refusal(const Refuse& refuse, int V, int eos, float repetition_penalty, int min_length) {
+  if (eos < -1 || eos >= V) return refuse(VMLMF_E_BADARG, "eos must be a token in [0, V), or -1 for none");
+  if (!(repetition_penalty > 0.f) || repetition_penalty > 3.0e38f)
+    return refuse(VMLMF_E_BADARG, "repetition_penalty must be finite and > 0 (1: off)");
+  if (min_length < 0) return refuse(VMLMF_E_BADARG, "min_length must be >= 0");
+  if (min_length > 0 && eos < 0) return refuse(VMLMF_E_BADARG, "min_length needs eos");
   return 0;
 }

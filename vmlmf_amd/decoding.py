@@ -14,9 +14,10 @@ import contextlib
 
 import torch
 
-from . import _beam, _decode, _lib
+from . import _beam, _decode, _history, _lib
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._decode import DecodeControls
+from ._history import HistoryControls
 from ._lib import ptr
 from .functional import PackCache, _require_hip, _workspace, dropout_advance, sample_ticket
 from .lm import stack_layers
@@ -67,7 +68,10 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     controls: a DecodeControls (eos, min_length, repetition_penalty, logit_bias / bans and the rows' seen / finished / length state):
     the choice runs on the controlled scores in ONE launch of its own library behind the head's GEMM (vmlmf_decode_choose,
     include/vmlmf_decode.h has the contract; form "gemm" only), which updates the controls' state in place; the noise and the
-    log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf."""
+    log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf.
+    A HistoryControls (those, and no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty with the rows' hist /
+    hist_len / count / overflow state) goes to ONE launch of vmlmf_history_choose instead (include/vmlmf_history.h has the contract),
+    whatever of its controls is on: with none of the history's on, the results and the shared state are vmlmf_decode_choose's to the bit."""
     for t, what in ((h, "h"), (weight, "weight")):
         _require_hip(t, what)
     if bias is not None:
@@ -108,8 +112,9 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
     bias_p, embed_p = ptr(bias_c), ptr(embed_c)
     if controls is not None:
-        _decode.decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn,
-                              kept)
+        choose = _history.history_choose if isinstance(controls, HistoryControls) else _decode.decode_choose
+        choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn,
+               kept)
         return outs()
     if form == "gemm":
         scores = torch.mm(h2, w.t())
@@ -154,7 +159,7 @@ def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=N
     """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
     the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
     capturable (DecodeGraph).  controls: a DecodeControls - the choice is then the controlled launch behind the head's GEMM
-    (vmlmf_decode_choose), which moves the controls' state on in place."""
+    (vmlmf_decode_choose; a HistoryControls: vmlmf_history_choose), which moves the controls' state on in place."""
     toks, lps = [], []
     for j in range(steps):
         tok, lp, x = lm_sample(h, model.fc.w, model.fc.b, temperature, snap, j, embed=model.embed.w, top_k=top_k, top_p=top_p,
@@ -282,7 +287,8 @@ class DecodeGraph(_StepGraph):
     criterion's, functional.ce_ticket), so two graphs can share them, and concurrent replays would break the last-arrival count.
     top_k / top_p: the filters of Model.generate, fixed at construction.
     controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
-    length -, so replays continue one decode: finished rows stay finished, seen accumulates (the warm-up runs on a clone)."""
+    length, and a HistoryControls' hist, hist_len, count, overflow -, so replays continue one decode: finished rows stay finished, seen
+    and the history accumulate (the warm-up runs on a clone of all of them)."""
 
     def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None):
         self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
@@ -375,22 +381,33 @@ def _run(steps, chunk, eager, graph):
 
 
 def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-             eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False):
+             eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+             no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
     """Model.generate (lm.py has the contract)."""
     sample_filters(top_k, top_p)
+    hist_args = dict(no_repeat_ngram_size=no_repeat_ngram_size, banned_sequences=banned_sequences, frequency_penalty=frequency_penalty,
+                     presence_penalty=presence_penalty)
+    history = _history.history_on(**hist_args)
     ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
                     banned_tokens=banned_tokens)
     eos_c, min_c, _, banned = _decode.check_controls(model.vocab_size, **ctl_args)
     controlled = _decode.controls_on(eos, repetition_penalty, logit_bias, banned_tokens)
-    if controlled:
-        _decode.check_bias(model.vocab_size, logit_bias, banned, eos_c, min_c)
+    if controlled or history:
+        closed = _decode.check_bias(model.vocab_size, logit_bias, banned, eos_c, min_c)
+    if history:
+        T0 = prompt.shape[0] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
+        _history.check_history(model.vocab_size, prompt_length=T0, steps=int(steps), closed=closed, **hist_args)
     _check_call(model, prompt, "generate", "sampler kernel (vmlmf_lm_sample)")
     steps, temperature = int(steps), float(temperature)
     _check_chunk("generate", chunk, steps)
     B, dev = prompt.shape[1], prompt.device
     gen = model.sampler_state(seed) if temperature > 0 else None
     with _session(model, prompt, states) as (h, states):
-        controls = DecodeControls(B, model.vocab_size, dev, prompt=prompt, _checked=True, **ctl_args) if controlled else None
+        if history:     # capacity: the prompt and every step - the history never overflows
+            controls = HistoryControls(B, model.vocab_size, dev, capacity=max(prompt.shape[0] + steps, 1), prompt=prompt, _checked=True,
+                                       **hist_args, **ctl_args)
+        else:
+            controls = DecodeControls(B, model.vocab_size, dev, prompt=prompt, _checked=True, **ctl_args) if controlled else None
         if steps == 0:
             tokens, logprobs = torch.empty((0, B), dtype=torch.int64, device=dev), torch.empty((0, B), device=dev)
         else:

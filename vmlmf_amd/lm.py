@@ -348,7 +348,8 @@ class Model(nn.Module):
         return st
 
     def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-                 eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False):
+                 eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+                 no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
@@ -376,10 +377,27 @@ class Model(nn.Module):
         unprocessed log-softmax.  Decoding always runs the full `steps`: the step loop has no host synchronisation.
         return_lengths=True: (tokens, logprobs, lengths (B) int32 - tokens up to and including eos -, states).  ValueError, before any
         device work, for repetition_penalty <= 0 or not finite, min_length < 0 or without eos, eos or a banned index outside the
-        vocabulary, a logit_bias that is not (V) fp32, holds NaN or +inf (its values are read back once), or leaves nothing to choose."""
+        vocabulary, a logit_bias that is not (V) fp32, holds NaN or +inf (its values are read back once), or leaves nothing to choose.
+        History controls (all off by default; with any of no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty
+        given the choice of every step is ONE launch of a fourth library behind the head's GEMM - vmlmf_history_choose,
+        include/vmlmf_history.h -, which applies the controls above too; without them this is the call above, launch for launch, and
+        that library is never opened).  Beside a row's set of tokens the launch keeps its sequence - prompt included - and how often it
+        has GENERATED each token (the prompt is not counted; the count saturates at 65535).  Per step and row, in this order:
+        repetition_penalty as above, r; then q = (r - frequency_penalty * count) - (presence_penalty if count > 0 else 0), in fp32,
+        each operation rounded, both penalties finite and >= 0; then logit_bias and min_length as above; then the history bans, to
+        -inf: no_repeat_ngram_size = n >= 1 closes every token that would complete an n-gram the row already holds (the tokens that
+        followed an earlier occurrence of its last n - 1 tokens; n = 1: every token of the history; overlapping occurrences count -
+        the rule of Hugging Face's NoRepeatNGramLogitsProcessor); banned_sequences, a list of lists of tokens, closes a sequence's
+        last token while the row ends in the tokens before it (a sequence of one token is always closed).  Then temperature, top_k,
+        top_p and the draw as above on the same noise; logprobs stay the unprocessed log-softmax.  Bans need a vocabulary of at most
+        65536 tokens (a row's ban set is a bitmap in the workgroup's LDS); the penalties do not.  ValueError, before any device work,
+        for a negative n, a negative or non-finite penalty, an empty sequence or one with a token outside the vocabulary, more than
+        4096 sequence tokens in all, and - with a ban on - for a vocabulary that might run out of open tokens: V must exceed the tokens
+        the other controls close + the prompt's length + steps + the number of sequences + 1."""
         from . import decoding
         return decoding.generate(self, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length,
-                                 repetition_penalty, logit_bias, banned_tokens, return_lengths)
+                                 repetition_penalty, logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences,
+                                 frequency_penalty, presence_penalty)
 
     def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
         """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
