@@ -72,7 +72,7 @@ def new_step_buffers(dev, B, W, V):
     return torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
 
 
-def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None):
+def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None, controls=None, hist=None, hist_len=None):
     """One step of beam search over B batch rows of W beams (cum is (B, W)): the head's GEMM over the beams' top-layer outputs h (B W, H)
     - row b W + w is beam w of batch row b -, then ONE launch (vmlmf_beam_step, csrc/vmlmf_beam.hip) that forms every candidate's total
     cum[b, w] + log_softmax(h fc.w^T + bias)[v] in fp32, keeps the W best of each batch row under the total order (larger total first,
@@ -81,7 +81,12 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     finished: (B, W) bool or int32; length: (B, W) int32; eos: a token, or None - then no beam is finished, whatever `finished` says.
     Returns (parent (B, W) int32, token (B, W) int64, total (B, W) fp32, finished (B, W) int32, length (B, W) int32,
     x_next (B W, H) = embed[token] or None without embed, src_row (B W) int32 = b W + parent: the state row a survivor continues).
-    buffers: (ticket, workspace) of new_step_buffers() - default: the current stream's."""
+    buffers: (ticket, workspace) of new_step_buffers() - default: the current stream's.
+    controls: a BeamControls (_beamctl.py: min_length, banned_tokens, no_repeat_ngram_size, banned_sequences) - the selection is then
+    ONE launch of vmlmf_beamctl_step (csrc/vmlmf_beamctl.hip, a library of its own) in which a live beam withholds what the controls
+    close, behind ONE vmlmf_history_bans launch on the beams' histories hist (B W, capacity) / hist_len (B W) when an n-gram or a
+    sequence control is on; the totals of what is offered are the plain step's to the bit.  Two more results follow the seven: the
+    survivors' (hist, hist_len), fresh buffers - (None, None) when the controls keep no history."""
     for t, what in ((h, "h"), (weight, "weight"), (cum, "cum")):
         _require(t, what)
     if bias is not None:
@@ -108,8 +113,12 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     eos_c = -1 if eos is None else int(eos)
     if eos is not None and not 0 <= eos_c < V:
         raise ValueError(f"vmlmf_amd.lm_beam_step: eos={eos} is not a token of the vocabulary ({V})")
-    return beam_select(torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
-                       length.contiguous(), eos_c, None if embed is None else embed.contiguous(), buffers)
+    args = (torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
+            length.contiguous(), eos_c, None if embed is None else embed.contiguous())
+    if controls is not None:
+        from . import _beamctl
+        return _beamctl.beamctl_select(*args, controls, hist, hist_len, buffers)
+    return beam_select(*args, buffers)
 
 
 def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):

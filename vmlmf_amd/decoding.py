@@ -14,8 +14,9 @@ import contextlib
 
 import torch
 
-from . import _beam, _decode, _history, _lib
+from . import _beam, _beamctl, _decode, _history, _lib
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
+from ._beamctl import BeamControls
 from ._decode import DecodeControls
 from ._history import HistoryControls
 from ._lib import ptr
@@ -171,26 +172,37 @@ def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=N
     return torch.stack(toks), torch.stack(lps), h, states
 
 
-def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None):
+def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None, controls=None, hist=None, hist_len=None):
     """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
     (lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
     2 L state tensors follow their hypotheses (beam_gather), then the layers at T = 1 on the B W rows.  No host
-    synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length)."""
+    synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length).
+    controls: a BeamControls - the selection is then the controlled launch (vmlmf_beamctl_step) and, where the controls keep a history,
+    the vmlmf_history_bans launch in front of it on hist / hist_len, the beams' histories (default: controls.history(), a search that
+    starts); the survivors' (hist, hist_len) then follow the seven results."""
     parents, toks = [], []
+    if controls is None:
+        select = lambda: lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w, buffers=buffers) + (None, None)
+    else:
+        if controls.keeps_history and hist is None:
+            hist, hist_len = controls.history()
+        select = lambda: lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w, buffers=buffers,
+                                      controls=controls, hist=hist, hist_len=hist_len)
     for _ in range(steps):
-        par, tok, cum, finished, length, x, src = lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w,
-                                                               buffers=buffers)
+        par, tok, cum, finished, length, x, src, hist, hist_len = select()
         parents.append(par)
         toks.append(tok)
         flat = beam_gather([t for st in states for t in st], src)
         states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
         y, states = decode_layers(model, x.unsqueeze(0), states, "layers")
         h = y[-1]
-    return torch.stack(parents), torch.stack(toks), h, states, cum, finished, length
+    out = (torch.stack(parents), torch.stack(toks), h, states, cum, finished, length)
+    return out if controls is None or not controls.keeps_history else out + (hist, hist_len)
 
 
 # What a decode carries from step to step, as one flat list: [h, h_0, c_0, ... h_L-1, c_L-1] and, for beams, cum, finished and length
-# behind them.  The two forms below are the step loops above on such a list: carried -> (outputs, carried after the steps).
+# behind them - and behind those, under BeamControls that keep a history, the beams' hist and hist_len.  The two forms below are the
+# step loops above on such a list: carried -> (outputs, carried after the steps).
 def _pairs(flat):
     return [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
 
@@ -202,10 +214,14 @@ def _sampled(model, gen, carried, steps, temperature, layer_path, top_k, top_p, 
     return (toks, lps), [h, *(t for st in states for t in st)]
 
 
-def _beamed(model, carried, steps, eos, buffers=None):
+def _beamed(model, carried, steps, eos, buffers=None, controls=None):
+    history = []
+    if controls is not None and controls.keeps_history:
+        carried, history = carried[:-2], carried[-2:]
     h, *flat, cum, finished, length = carried
-    par, tok, h, states, cum, finished, length = beam_steps(model, h, _pairs(flat), cum, finished, length, steps, eos, buffers)
-    return (par, tok), [h, *(t for st in states for t in st), cum, finished, length]
+    par, tok, h, states, cum, finished, length, *history = beam_steps(model, h, _pairs(flat), cum, finished, length, steps, eos, buffers,
+                                                                      controls, *history)
+    return (par, tok), [h, *(t for st in states for t in st), cum, finished, length, *history]
 
 
 def _fresh_beams(B, W, dev):
@@ -316,18 +332,27 @@ class BeamGraph(_StepGraph):
     the previous replay stopped - h, states, cum, finished and length live in this object's buffers - and returns (parents, tokens),
     both (steps, B, W), for beam_backtrack.  The ticket words and the workspace of the selection are this graph's own, so
     graphs may be replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after
-    the parameters change."""
+    the parameters change.
+    controls: a BeamControls (min_length, token, n-gram and sequence bans).  Where they keep a history, hist / hist_len (default:
+    controls.history()) are carried with cum, finished and length - in this object's buffers, so a replay continues the hypotheses of
+    the last one; the captured launches set the controls' own `overflow` (the warm-up runs on a clone)."""
 
-    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None):
-        self.model, self.steps, self.eos = model, int(steps), eos
+    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None, controls=None, hist=None,
+                 hist_len=None):
+        self.model, self.steps, self.eos, self.controls = model, int(steps), eos, controls
         W = _beam.check_beams(beams, model.vocab_size)
         B = h.shape[0] // W
         fresh = _fresh_beams(B, W, h.device)
         cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), fresh))
         self.buffers = _beam.new_step_buffers(h.device, B, W, model.vocab_size)
-        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32)],
-                      lambda carried: _beamed(model, carried, self.steps, eos, self.buffers))
-        self.h, *flat, self.cum, self.finished, self.length = self.carried
+        history = []
+        if controls is not None and controls.keeps_history:
+            history = list(controls.history()) if hist is None else [hist, hist_len]
+        step = lambda carried, controls=controls: _beamed(model, carried, self.steps, eos, self.buffers, controls)
+        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32), *history], step,
+                      None if controls is None else lambda carried: step(carried, controls.clone()))
+        self.hist, self.hist_len = history and self.carried[-2:] or (None, None)
+        self.h, *flat, self.cum, self.finished, self.length = self.carried[:len(self.carried) - len(history)]
         self.states, (self.parents, self.tokens) = _pairs(flat), self.outputs
 
 
@@ -422,7 +447,8 @@ def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chun
         return tokens, logprobs, lengths, states
 
 
-def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
+def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                no_repeat_ngram_size=0, banned_sequences=None):
     """Model.beam_search (lm.py has the contract)."""
     W = _beam.check_beams(beams, model.vocab_size)
     steps, alpha = int(steps), float(length_penalty)
@@ -432,19 +458,29 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
         raise ValueError(f"vmlmf_amd: Model.beam_search: length_penalty must be >= 0, got {length_penalty}")
     if steps < 0:
         raise ValueError(f"vmlmf_amd: Model.beam_search: steps must be >= 0, got {steps}")
+    ctl_args = dict(eos=eos, min_length=min_length, banned_tokens=banned_tokens, no_repeat_ngram_size=no_repeat_ngram_size,
+                    banned_sequences=banned_sequences)
+    controlled = _beamctl.controls_on(min_length, banned_tokens, no_repeat_ngram_size, banned_sequences)
+    T0 = prompt.shape[0] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
+    if controlled:      # (without them nothing of the controls is looked at: the call is what it was)
+        _beamctl.check_beam_controls(model.vocab_size, W, prompt_length=T0, steps=steps, **ctl_args)
     _check_chunk("beam_search", chunk, steps)
     _check_call(model, prompt, "beam_search", "beam-step kernel (vmlmf_beam_step)")
     B, dev = prompt.shape[1], prompt.device
     with _session(model, prompt, states) as (h, states):
+        # capacity: the prompt and every step - the history never overflows
+        controls = BeamControls(B, W, model.vocab_size, dev, prompt=prompt, capacity=max(T0 + steps, 1), **ctl_args) if controlled else None
+        history = [] if controls is None or not controls.keeps_history else list(controls.history())
         h = h.repeat_interleave(W, 0)
         states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
         cum, finished, length = _fresh_beams(B, W, dev)
         if steps == 0:
             return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
-        (parents, toks), (_, *flat, cum, finished, length) = _run(
+        (parents, toks), carried = _run(
             steps, chunk,
-            lambda: _beamed(model, [h, *(t for st in states for t in st), cum, finished, length], steps, eos),
-            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length))
+            lambda: _beamed(model, [h, *(t for st in states for t in st), cum, finished, length, *history], steps, eos, None, controls),
+            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls, *history))
+        _, *flat, cum, finished, length = carried[:len(carried) - len(history)]
         order = None
         if alpha > 0.0:
             key = cum / length.to(torch.float32) ** alpha

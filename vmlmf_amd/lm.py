@@ -399,7 +399,8 @@ class Model(nn.Module):
                                  repetition_penalty, logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences,
                                  frequency_penalty, presence_penalty)
 
-    def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None):
+    def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                    no_repeat_ngram_size=0, banned_sequences=None):
         """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
         (steps, B, W) int64, scores (B, W) fp32, lengths (B, W) int32, states): tokens[:, b, w] is hypothesis w of row b, best first;
         its score is the fp32 sum of the untempered log-softmax (bias included) of its tokens - what nll_loss charges -; states are per
@@ -415,9 +416,21 @@ class Model(nn.Module):
         raw sums.  Decoding always runs the full `steps`: an early exit would need a host synchronisation, and the step loop has none.
         chunk=K (steps % K == 0): K steps are captured into a linear hipGraph on one stream and replayed steps / K times (BeamGraph):
         the eager call's bits.  ValueError for beams < 1, beams > 32 and beams > V; no random generator is touched; every module's
-        train / eval flag is as the caller left it afterwards."""
+        train / eval flag is as the caller left it afterwards.
+        min_length, banned_tokens, no_repeat_ngram_size, banned_sequences: generate()'s controls of the same names, per HYPOTHESIS - a
+        live beam does not offer eos before it has emitted min_length tokens (needs eos), never a banned token, never a token that
+        would repeat an n-gram of its prompt and tokens so far, never the last token of a banned sequence whose other tokens it ends
+        in.  They only close candidates: a closed candidate is not offered at all, every offered one keeps its total, so scores stay
+        the sums of plain log-probabilities; a finished beam keeps offering eos.  With any of them on the selection is the controlled
+        launch (decoding.BeamControls, vmlmf_beamctl_step) and, for the last two, one small launch in front of it that forms every
+        beam's ban set from its history (vmlmf_history_bans on B W rows); without them the call is launch for launch what it was.
+        ValueError for what generate() refuses for the same arguments, for eos among banned_tokens, and for a vocabulary in which a
+        beam might run short of candidates: V < closed + T0 + steps + len(banned_sequences) + beams."""
         from . import decoding
-        return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
+        if min_length == 0 and banned_tokens is None and no_repeat_ngram_size == 0 and banned_sequences is None:
+            return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
+        return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens,
+                                    no_repeat_ngram_size, banned_sequences)
 
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
