@@ -1,14 +1,12 @@
 """The controls of Model.beam_search (min_length, banned_tokens, no_repeat_ngram_size, banned_sequences; C ABI vmlmf_beamctl_step in
-libvmlmf_beamctl.so, include/vmlmf_beamctl.h): what can be checked without a GPU - the fifth side library against the table
-test_side_libraries_cpu.py holds the first three to; its lazy load; every refusal, in Python and at the C ABI; the workspace; the
+libvmlmf_beamctl.so, include/vmlmf_beamctl.h): what can be checked without a GPU, beside the table test_side_libraries_cpu.py holds
+every side library to - the step written once; every refusal, in Python and at the C ABI; the workspace; the
 controlled fp64 search (beam_control_cases.py) against the oracle's own; and the conditions on the reference alone that the GPU tests
 rely on."""
 import ctypes
 import inspect
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,72 +17,6 @@ import vmlmf_decode_oracle as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_beamctl_abi_version", "vmlmf_beamctl_last_error", "vmlmf_beamctl_step", "vmlmf_beamctl_workspace_bytes"]
-OTHERS = [("_lib", "libvmlmf_hip.so"), ("_beam", "libvmlmf_beam.so"), ("_decode", "libvmlmf_decode.so"), ("_score", "libvmlmf_score.so"),
-          ("_history", "libvmlmf_history.so")]
-NO_FALLBACK = "no stock-op fallback for the controlled beam-search step"
-
-
-def _binding(name):
-    import importlib
-    return importlib.import_module("vmlmf_amd." + name)
-
-
-def _path(name):
-    b = _binding(name)
-    return b.LIB_PATH if name == "_lib" else b.LIBRARY.path
-
-
-# ---- the table's properties, for the fifth library ----
-def test_every_declared_function_is_exported_and_bound():
-    from vmlmf_amd import _beamctl
-    header = open(os.path.join(ROOT, "include", "vmlmf_beamctl.h")).read()
-    declared = sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S))))
-    assert declared == sorted(_beamctl.SYMBOLS) == FUNCTIONS and all(n.startswith("vmlmf_beamctl_") for n in FUNCTIONS)
-    assert os.path.exists(_beamctl.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(_beamctl.LIBRARY.path)
-    assert all(hasattr(handle, n) for n in FUNCTIONS)
-    in_header = int(re.search(r"#define VMLMF_BEAMCTL_ABI_VERSION (\d+)", header).group(1))
-    assert (_beamctl.LIBRARY.abi_symbol, _beamctl.LIBRARY.error_symbol) == ("vmlmf_beamctl_abi_version", "vmlmf_beamctl_last_error")
-    assert in_header == _beamctl.ABI_VERSION == _beamctl.LIBRARY.abi_version == _beamctl.lib().vmlmf_beamctl_abi_version() == 1
-    assert os.path.basename(_beamctl.LIBRARY.path) == "libvmlmf_beamctl.so" and _beamctl.LIBRARY.no_fallback in NO_FALLBACK
-
-
-def test_no_symbol_is_shared_with_the_other_libraries():
-    from vmlmf_amd import _beamctl
-    mine = ctypes.CDLL(_beamctl.LIBRARY.path)
-    for name, _ in OTHERS:
-        other = _binding(name)
-        assert not set(other.SYMBOLS) & set(FUNCTIONS), name
-        theirs = ctypes.CDLL(_path(name))
-        for fn in FUNCTIONS:
-            assert not hasattr(theirs, fn), (name, fn)
-        for fn in sorted(other.SYMBOLS):
-            assert not hasattr(mine, fn), (name, fn)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _beamctl
-    monkeypatch.setattr(_beamctl.LIBRARY, "_handle", None)
-    monkeypatch.setattr(_beamctl.LIBRARY, "path", str(tmp_path / "libvmlmf_beamctl.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_beamctl.so is missing: build it"):
-        _beamctl.lib()
-    with pytest.raises(RuntimeError, match=NO_FALLBACK):
-        _beamctl.lib()
-    assert not _beamctl.loaded()
-
-
-def test_the_makefile_links_the_library_once_from_its_own_object_and_cleans_it():
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert len(links) == 6                                                                    # the main library and five beside it
-    mine = [ln for ln in links if "-o ../lib/libvmlmf_beamctl.so" in ln]
-    assert len(mine) == 1 and [ln for ln in links if "vmlmf_beamctl.o" in ln] == mine       # once, and into no other library
-    assert re.findall(r"\bvmlmf_\w+\.o\b", mine[0]) == ["vmlmf_beamctl.o"]
-    assert re.search(r"^SIDE := beam decode score history beamctl$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M)
-    r = subprocess.run(["make", "-n", "-C", CSRC, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "libvmlmf_beamctl.so" in r.stdout and "vmlmf_beamctl.o" in r.stdout
 
 
 def test_the_step_is_written_once():
@@ -103,30 +35,6 @@ def test_the_step_is_written_once():
     history = open(os.path.join(CSRC, "vmlmf_history.hip")).read()
     assert len(re.findall(r"__device__[^;{]*\bhistory_bans\s*\(", history)) == 1              # the ban sets are formed there alone
     assert "history_bans" not in open(os.path.join(CSRC, "vmlmf_beamctl.hip")).read().replace("vmlmf_history_bans", "")
-
-
-# ---- lazy loading ----
-def test_the_library_is_loaded_by_the_first_controlled_beam_step_only():
-    """beam_search with and without the new arguments, up to its refusal of CPU tensors, and BeamControls on the CPU open neither
-    libvmlmf_beamctl.so nor libvmlmf_history.so; then each opens alone."""
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import torch, vmlmf_amd\nfrom vmlmf_amd import _beamctl, _history\n"
-            "m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')\n"
-            "tok = torch.zeros((3, 2), dtype=torch.int64)\n"
-            "for kw in (dict(), dict(eos=3), dict(eos=3, min_length=2), dict(banned_tokens=[5]), dict(no_repeat_ngram_size=2),\n"
-            "           dict(banned_sequences=[[1, 2]]), dict(eos=3, min_length=2, banned_tokens=[5], no_repeat_ngram_size=3, banned_sequences=[[1, 2]])):\n"
-            "    try:\n        m.beam_search(tok, 4, **kw)\n        raise SystemExit('no refusal')\n"
-            "    except RuntimeError as e:\n        assert 'cuda' in str(e)\n"
-            "c = vmlmf_amd.BeamControls(2, 4, 97, 'cpu', prompt=tok, no_repeat_ngram_size=2, banned_sequences=[[1, 2]], banned_tokens=[5], eos=3, min_length=1)\n"
-            "assert c.history()[1].tolist() == [3] * 8\n"
-            "names = ['libvmlmf_beamctl.so', 'libvmlmf_history.so', 'libvmlmf_beam.so', 'libvmlmf_decode.so', 'libvmlmf_score.so']\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert not any(n in maps for n in names) and not _beamctl.loaded() and not _history.loaded(), maps\n"
-            "_beamctl.lib()\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert names[0] in maps and _beamctl.loaded() and not any(n in maps for n in names[1:])\n") % ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- every refusal, in Python ----

@@ -1,14 +1,13 @@
 """History controls of Model.generate (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty; C ABI
-vmlmf_history_choose / vmlmf_history_bans in libvmlmf_history.so, include/vmlmf_history.h): what can be checked without a GPU - the
-fourth side library against the table test_side_libraries_cpu.py holds the other three to; its lazy load; the two statements of the ban
-set (history_cases.py) against each other; the condition on the reference's sets that the GPU test of the choice relies on; every
+vmlmf_history_choose / vmlmf_history_bans in libvmlmf_history.so, include/vmlmf_history.h): what can be checked without a GPU, beside
+the table test_side_libraries_cpu.py holds every side library to - the two statements of the ban set (history_cases.py) against each
+other; the condition on the reference's sets that the GPU test of the choice relies on; every
 refusal, in Python and at the C ABI; the struct of the binding."""
 import ctypes
 import inspect
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,98 +18,12 @@ import vmlmf_decode_oracle as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_history_abi_version", "vmlmf_history_bans", "vmlmf_history_choose", "vmlmf_history_last_error"]
-OTHERS = [("_lib", "libvmlmf_hip.so"), ("_beam", "libvmlmf_beam.so"), ("_decode", "libvmlmf_decode.so"), ("_score", "libvmlmf_score.so")]
 
 
-def _binding(name):
-    import importlib
-    return importlib.import_module("vmlmf_amd." + name)
-
-
-def _path(name):
-    b = _binding(name)
-    return b.LIB_PATH if name == "_lib" else b.LIBRARY.path
-
-
-# ---- the table's properties, for the fourth library ----
-def test_every_declared_function_is_exported_and_bound():
+def test_the_widest_vocabulary_is_the_headers():
     from vmlmf_amd import _history
     header = open(os.path.join(ROOT, "include", "vmlmf_history.h")).read()
-    declared = sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S))))
-    assert declared == sorted(_history.SYMBOLS) == FUNCTIONS and all(n.startswith("vmlmf_history_") for n in FUNCTIONS)
-    assert os.path.exists(_history.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(_history.LIBRARY.path)
-    assert all(hasattr(handle, n) for n in FUNCTIONS)
-    in_header = int(re.search(r"#define VMLMF_HISTORY_ABI_VERSION (\d+)", header).group(1))
-    assert (_history.LIBRARY.abi_symbol, _history.LIBRARY.error_symbol) == ("vmlmf_history_abi_version", "vmlmf_history_last_error")
-    assert in_header == _history.ABI_VERSION == _history.LIBRARY.abi_version == _history.lib().vmlmf_history_abi_version() == 1
-    assert os.path.basename(_history.LIBRARY.path) == "libvmlmf_history.so"
     assert int(re.search(r"#define VMLMF_HISTORY_MAX_V (\d+)", header).group(1)) == _history.MAX_V
-
-
-def test_no_symbol_is_shared_with_the_other_libraries():
-    from vmlmf_amd import _history
-    mine = ctypes.CDLL(_history.LIBRARY.path)
-    for name, _ in OTHERS:
-        other = _binding(name)
-        assert not set(other.SYMBOLS) & set(FUNCTIONS), name
-        theirs = ctypes.CDLL(_path(name))
-        for fn in FUNCTIONS:
-            assert not hasattr(theirs, fn), (name, fn)
-        for fn in sorted(other.SYMBOLS):
-            assert not hasattr(mine, fn), (name, fn)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _history
-    monkeypatch.setattr(_history.LIBRARY, "_handle", None)
-    monkeypatch.setattr(_history.LIBRARY, "path", str(tmp_path / "libvmlmf_history.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_history.so is missing: build it"):
-        _history.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for the history controls of Model.generate"):
-        _history.lib()
-    assert not _history.loaded()
-
-
-def test_the_makefile_links_the_library_once_from_its_own_object():
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    mine = [ln for ln in links if "-o ../lib/libvmlmf_history.so" in ln]
-    assert len(mine) == 1 and [ln for ln in links if "vmlmf_history.o" in ln] == mine       # once, and not into libvmlmf_hip.so
-    assert re.findall(r"\bvmlmf_\w+\.o\b", mine[0]) == ["vmlmf_history.o"]
-    r = subprocess.run(["make", "-n", "-C", CSRC, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "libvmlmf_history.so" in r.stdout and "vmlmf_history.o" in r.stdout
-
-
-def test_the_selection_is_not_copied():
-    text = open(os.path.join(CSRC, "vmlmf_history.hip")).read()
-    assert '#include "vmlmf_select.h"' in text and re.search(r"\bpick_row\s*\(", text) and re.search(r"\bchoose_row\s*\(", text)
-    for fn in ("radix_select", "tie_cutoff", "best_merge", "lse_merge", "key_of", "choose_row", "pick_row", "for_quads"):
-        assert not re.search(r"__device__[^;{]*\b%s\s*\(" % fn, text), fn
-    assert len(re.findall(r"__device__[^;{]*\bhistory_bans\s*\(", text)) == 1             # phase 0 is written once, for both kernels
-    assert len(re.findall(r"\bhistory_bans\s*\(", text)) == 3
-
-
-# ---- lazy loading ----
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import torch, vmlmf_amd\nfrom vmlmf_amd import _history\n"
-            "m = vmlmf_amd.Model(64, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')\n"
-            "tok = torch.zeros((3, 2), dtype=torch.int64)\n"
-            "c = vmlmf_amd.HistoryControls(2, 64, 'cpu', no_repeat_ngram_size=2, banned_sequences=[[1, 2]], frequency_penalty=0.5, prompt=tok)\n"
-            "assert c.hist_len.tolist() == [3, 3] and c.count.dtype == torch.uint16\n"
-            "try:\n    m.generate(tok, 4, no_repeat_ngram_size=2)\n    raise SystemExit('no refusal')\n"
-            "except RuntimeError as e:\n    assert 'cuda' in str(e)\n"
-            "names = ['libvmlmf_history.so', 'libvmlmf_beam.so', 'libvmlmf_decode.so', 'libvmlmf_score.so']\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert not any(n in maps for n in names) and not _history.loaded(), maps\n"
-            "_history.lib()\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert names[0] in maps and _history.loaded() and not any(n in maps for n in names[1:])\n") % ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the two statements of the ban set ----
@@ -354,18 +267,12 @@ def test_the_entry_points_refuse_on_the_host():
         assert rc == bad and words in msg and msg.startswith("vmlmf_history_bans: "), (kw, rc, msg)
 
 
-def test_the_kernels_static_lds_fits_and_is_what_the_header_says():
-    """The code object's metadata: history_choose_kernel holds the selection's scratch and the bitmap of VMLMF_HISTORY_MAX_V bits in
-    static LDS, at most 64 KB; history_bans_kernel the bitmap alone."""
-    from vmlmf_amd import _history
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not all(os.path.exists(t) for t in tools):
-        pytest.skip("no LLVM binary tools beside hipcc")
+def _static_lds(library, tools):
+    """{kernel: static LDS bytes} from the metadata of a library's gfx950 code object."""
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "gfx950.co")
-        subprocess.run([tools[0], "--dump-section", ".hip_fatbin=" + fat, _history.LIBRARY.path, os.path.join(tmp, "copy.so")], check=True)
+        subprocess.run([tools[0], "--dump-section", ".hip_fatbin=" + fat, library, os.path.join(tmp, "copy.so")], check=True)
         subprocess.run([tools[1], "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co],
                        check=True)
         notes = subprocess.run([tools[2], "--notes", co], check=True, capture_output=True, text=True).stdout
@@ -373,9 +280,25 @@ def test_the_kernels_static_lds_fits_and_is_what_the_header_says():
     for block in notes.split(".args:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
         lds[name] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", block).group(1))
+    return lds
+
+
+def test_the_kernels_static_lds_fits_and_is_what_the_header_says():
+    """The code objects' metadata: history_choose_kernel holds the selection's scratch and the bitmap of VMLMF_HISTORY_MAX_V bits in
+    static LDS, at most 64 KB; history_bans_kernel the bitmap alone; libvmlmf_decode.so's one kernel, decode_choose_kernel, the scratch
+    alone."""
+    from vmlmf_amd import _decode, _history
+    llvm = "/opt/rocm/lib/llvm/bin"
+    tools = [os.path.join(llvm, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
+    if not all(os.path.exists(t) for t in tools):
+        pytest.skip("no LLVM binary tools beside hipcc")
+    lds = _static_lds(_history.LIBRARY.path, tools)
     choose = [v for k, v in lds.items() if "history_choose_kernel" in k]
     bans = [v for k, v in lds.items() if "history_bans_kernel" in k]
     assert len(lds) == 2 and len(choose) == 1 and len(bans) == 1, lds
     bitmap = _history.MAX_V // 8
     assert bans[0] == bitmap and bitmap < choose[0] <= 65536, lds
     assert choose[0] - bitmap >= 12288 * 4                                               # ... beside the keys of the longest resident row
+    decode = _static_lds(_decode.LIBRARY.path, tools)
+    assert len(decode) == 1 and "decode_choose_kernel" in list(decode)[0], decode
+    assert list(decode.values()) == [choose[0] - bitmap], (decode, lds)                  # the decode kernel carries no bitmap

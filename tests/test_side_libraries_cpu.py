@@ -1,7 +1,8 @@
-"""The decoder's side libraries - libvmlmf_beam.so, libvmlmf_decode.so, libvmlmf_score.so, each with a header, an ABI version and a
-binding of its own (vmlmf_amd/_beam.py, _decode.py, _score.py: one _lib.Library each) - held to one table: what the header declares is
-bound and exported, and by that library alone; a missing file is a clear error; a library is opened by its own first call only; the
-Makefile links each from its own object and cleans all of them; the selection is written once, in vmlmf_select.h.
+"""The decoder's side libraries - libvmlmf_beam.so, libvmlmf_decode.so, libvmlmf_score.so, libvmlmf_history.so, libvmlmf_beamctl.so, each
+with a header, an ABI version and a binding of its own (vmlmf_amd/_beam.py, _decode.py, _score.py, _history.py, _beamctl.py: one
+_lib.Library each) - held to one table: what the header declares is bound and exported, and by that library alone; a missing file is a
+clear error; a library is opened by its own first call only; the Makefile links each from its own object and cleans all of them; the
+selection is written once, in vmlmf_select.h.
 What is specific to one library (its struct, its limits, its refusals) is in that library's own test file."""
 import ctypes
 import importlib
@@ -26,6 +27,12 @@ SIDE = [
     dict(header="vmlmf_score.h", module="_score", file="libvmlmf_score.so", abi_macro="VMLMF_SCORE_ABI_VERSION", obj="vmlmf_score.o",
          functions=["vmlmf_score_abi_version", "vmlmf_score_last_error", "vmlmf_score_rows"],
          no_fallback="no stock-op fallback for Model.score"),
+    dict(header="vmlmf_history.h", module="_history", file="libvmlmf_history.so", abi_macro="VMLMF_HISTORY_ABI_VERSION", obj="vmlmf_history.o",
+         functions=["vmlmf_history_abi_version", "vmlmf_history_bans", "vmlmf_history_choose", "vmlmf_history_last_error"],
+         no_fallback="no stock-op fallback for the history controls of Model.generate"),
+    dict(header="vmlmf_beamctl.h", module="_beamctl", file="libvmlmf_beamctl.so", abi_macro="VMLMF_BEAMCTL_ABI_VERSION", obj="vmlmf_beamctl.o",
+         functions=["vmlmf_beamctl_abi_version", "vmlmf_beamctl_last_error", "vmlmf_beamctl_step", "vmlmf_beamctl_workspace_bytes"],
+         no_fallback="no stock-op fallback for the controlled beam-search step"),
 ]
 MAIN = dict(module="_lib", file="libvmlmf_hip.so", no_fallback="no CPU / PyTorch fallback for the hot path")
 IDS = [row["module"] for row in SIDE]
@@ -98,29 +105,54 @@ def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path, row):
 
 
 # ---- c. lazy loading ----
-def test_a_side_library_is_loaded_by_its_own_first_call_only():
-    """A process that imports the package, opens the main library and walks generate(), DecodeControls, score() and lm_score up to
-    their refusals of CPU tensors has opened none of the three; then each opens alone."""
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "import torch, vmlmf_amd\nfrom vmlmf_amd import _beam, _decode, _score, _lib\n_lib.lib()\n"
-            "m = vmlmf_amd.Model(16, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')\n"
-            "tok = torch.zeros((3, 2), dtype=torch.int64)\n"
-            "for call in (lambda: m.generate(tok, 4), lambda: m.generate(tok, 4, top_k=3), lambda: m.generate(tok, 4, eos=2, repetition_penalty=1.2),\n"
-            "             lambda: m.score(tok), lambda: m.score(tok, tok, top=4, lengths=torch.tensor([1, 2])),\n"
-            "             lambda: vmlmf_amd.lm_score(torch.zeros(3, 8), torch.zeros(16, 8), None, top=2)):\n"
-            "    try:\n        call()\n        raise SystemExit('no refusal')\n"
-            "    except RuntimeError as e:\n        assert 'cuda' in str(e)\n"
-            "vmlmf_amd.DecodeControls(2, 16, 'cpu', eos=3)\n"
-            "side = [(_beam, 'libvmlmf_beam.so'), (_decode, 'libvmlmf_decode.so'), (_score, 'libvmlmf_score.so')]\n"
-            "maps = open('/proc/self/maps').read()\n"
-            "assert 'libvmlmf_hip.so' in maps\n"
-            "for i, (binding, name) in enumerate(side):\n"
-            "    maps = open('/proc/self/maps').read()\n"
-            "    for later, later_name in side[i:]:\n"
-            "        assert later_name not in maps and not later.loaded(), (name, later_name)\n"
-            "    binding.lib()\n"
-            "    assert name in open('/proc/self/maps').read() and binding.loaded(), name\n") % ROOT
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+WALK = """
+import sys; sys.path.insert(0, %r)
+import torch, vmlmf_amd
+from vmlmf_amd import _beam, _beamctl, _decode, _history, _score, _lib
+_lib.lib()
+def refused(call):
+    try:
+        call()
+        raise SystemExit('no refusal')
+    except RuntimeError as e:
+        assert 'cuda' in str(e)
+tok = torch.zeros((3, 2), dtype=torch.int64)
+m = vmlmf_amd.Model(16, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
+for call in (lambda: m.generate(tok, 4), lambda: m.generate(tok, 4, top_k=3), lambda: m.generate(tok, 4, eos=2, repetition_penalty=1.2),
+             lambda: m.score(tok), lambda: m.score(tok, tok, top=4, lengths=torch.tensor([1, 2])),
+             lambda: vmlmf_amd.lm_score(torch.zeros(3, 8), torch.zeros(16, 8), None, top=2)):
+    refused(call)
+vmlmf_amd.DecodeControls(2, 16, 'cpu', eos=3)
+m = vmlmf_amd.Model(64, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
+c = vmlmf_amd.HistoryControls(2, 64, 'cpu', no_repeat_ngram_size=2, banned_sequences=[[1, 2]], frequency_penalty=0.5, prompt=tok)
+assert c.hist_len.tolist() == [3, 3] and c.count.dtype == torch.uint16
+refused(lambda: m.generate(tok, 4, no_repeat_ngram_size=2))
+m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
+for kw in (dict(), dict(eos=3), dict(eos=3, min_length=2), dict(banned_tokens=[5]), dict(no_repeat_ngram_size=2),
+           dict(banned_sequences=[[1, 2]]), dict(eos=3, min_length=2, banned_tokens=[5], no_repeat_ngram_size=3, banned_sequences=[[1, 2]])):
+    refused(lambda: m.beam_search(tok, 4, **kw))
+c = vmlmf_amd.BeamControls(2, 4, 97, 'cpu', prompt=tok, no_repeat_ngram_size=2, banned_sequences=[[1, 2]], banned_tokens=[5], eos=3, min_length=1)
+assert c.history()[1].tolist() == [3] * 8
+side = {_beam: 'libvmlmf_beam.so', _decode: 'libvmlmf_decode.so', _score: 'libvmlmf_score.so', _history: 'libvmlmf_history.so',
+        _beamctl: 'libvmlmf_beamctl.so'}
+maps = open('/proc/self/maps').read()
+assert 'libvmlmf_hip.so' in maps
+for binding, name in side.items():
+    assert name not in maps and not binding.loaded(), name
+mine = getattr(vmlmf_amd, %r)
+mine.lib()
+maps = open('/proc/self/maps').read()
+for binding, name in side.items():
+    assert (name in maps) == binding.loaded() == (binding is mine), name
+"""
+
+
+@pytest.mark.parametrize("row", SIDE, ids=IDS)
+def test_a_side_library_is_loaded_by_its_own_first_call_only(row):
+    """A process that imports the package, opens the main library and walks generate(), beam_search(), score() and lm_score - with and
+    without every control - up to their refusals of CPU tensors, and builds DecodeControls, HistoryControls and BeamControls on the CPU,
+    has opened none of the five; then the row's own opens alone."""
+    r = subprocess.run([sys.executable, "-c", WALK % (ROOT, row["module"])], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
 
 
@@ -131,6 +163,8 @@ def test_the_makefile_builds_and_cleans_every_library():
     r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and all(n in r.stdout for n in libs)
     links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
+    assert len(links) == 1 + len(SIDE) == 6                                                   # the main library and five beside it
+    assert re.search(r"^SIDE := beam decode score history beamctl$", open(os.path.join(CSRC, "Makefile")).read(), flags=re.M)
     main = [ln for ln in links if "-o ../lib/libvmlmf_hip.so" in ln]
     assert len(main) == 1 and "vmlmf_sample.o" in main[0] and not any(o in main[0] for o in objs)   # not linked into the main library
     for row in SIDE:
@@ -143,16 +177,23 @@ def test_the_makefile_builds_and_cleans_every_library():
 
 # ---- e. the selection is written once ----
 def test_the_selection_is_written_once():
-    """The sampler, the controlled choice and the scoring take the merges, the reduction tree and the selection from one header;
+    """The sampler, the controlled choices and the scoring take the merges, the reduction tree and the selection from one header;
     none of them holds a copy."""
     header = open(os.path.join(CSRC, "vmlmf_select.h")).read()
     for fn in ("best_merge", "lse_merge", "gumbel_of", "sample_key", "key_of", "z_of", "tempered", "radix_select", "tie_cutoff", "pick_row"):
         assert re.search(r"\b%s\s*\(" % fn, header), fn
-    for name in ("vmlmf_sample.hip", "vmlmf_decode.hip", "vmlmf_score.hip"):
+    for name in ("vmlmf_sample.hip", "vmlmf_decode.hip", "vmlmf_score.hip", "vmlmf_history.hip"):
         text = open(os.path.join(CSRC, name)).read()
         assert '#include "vmlmf_select.h"' in text
-        for fn in ("radix_select", "tie_cutoff", "best_merge", "lse_merge", "key_of", "choose_row", "for_quads"):
+        for fn in ("radix_select", "tie_cutoff", "best_merge", "lse_merge", "key_of", "choose_row", "pick_row", "for_quads"):
             assert not re.search(r"__device__[^;{]*\b%s\s*\(" % fn, text), (name, fn)
     text = open(os.path.join(CSRC, "vmlmf_score.hip")).read()
     for fn in ("choose_row", "radix_select", "tie_cutoff"):
         assert re.search(r"\b%s\s*\(" % fn, text), fn                 # ... and the scoring calls them
+
+
+def test_the_history_choice_takes_the_selection_and_writes_phase_0_once():
+    text = open(os.path.join(CSRC, "vmlmf_history.hip")).read()
+    assert re.search(r"\bpick_row\s*\(", text) and re.search(r"\bchoose_row\s*\(", text)
+    assert len(re.findall(r"__device__[^;{]*\bhistory_bans\s*\(", text)) == 1             # phase 0 is written once, for both kernels
+    assert len(re.findall(r"\bhistory_bans\s*\(", text)) == 3

@@ -100,27 +100,17 @@ class BeamControls:
         if prompt is not None and not (isinstance(prompt, torch.Tensor) and prompt.dtype == torch.int64 and prompt.dim() == 2
                                        and prompt.shape[1] == B):
             raise ValueError(f"vmlmf_amd: BeamControls takes a (T0, {B}) int64 prompt")
-        T0 = int(prompt.shape[0]) if prompt is not None else 0
-        capacity = T0 + 1024 if capacity is None else int(capacity)
-        if capacity < max(T0, 1):
-            raise ValueError(f"vmlmf_amd: BeamControls: capacity={capacity} must be >= 1 and hold the prompt ({T0} tokens)")
+        capacity = _history.check_capacity("BeamControls", capacity, int(prompt.shape[0]) if prompt is not None else 0)
         self.B, self.W, self.V, self.device, self.capacity = B, W, V, torch.device(device), capacity
         self.keeps_history = self.no_repeat_ngram_size > 0 or bool(self.sequences)
         dev = self.device
         self.closed = pack_words(self.banned, V).to(dev) if self.banned else None
         self.overflow = torch.zeros(B, dtype=torch.int32, device=dev)
-        offsets = [0]
-        for s in self.sequences:
-            offsets.append(offsets[-1] + len(s))
-        flat = [t for s in self.sequences for t in s]
-        self.seq_tokens = torch.tensor(flat, dtype=torch.int32).to(dev) if flat else None
-        self.seq_offsets = torch.tensor(offsets, dtype=torch.int32).to(dev) if flat else None
+        self.seq_tokens, self.seq_offsets = _history.flat_sequences(self.sequences, dev)
         self._hist0 = None
         if self.keeps_history:
-            hist = torch.zeros((B, capacity), dtype=torch.int32, device=dev)
-            if T0 > 0:
-                hist[:, :T0] = prompt.to(dev).t().clamp(0, V - 1).to(torch.int32)
-            self._hist0 = (hist.repeat_interleave(W, 0).contiguous(), torch.full((B * W,), T0, dtype=torch.int32, device=dev))
+            hist, hist_len = _history.prompt_history(prompt, B, V, capacity, dev)
+            self._hist0 = (hist.repeat_interleave(W, 0).contiguous(), hist_len.repeat_interleave(W, 0))
 
     def history(self):
         """(hist (B W, capacity) int32, hist_len (B W) int32) of a search that starts: the prompt, repeated for the W beams of a batch
@@ -139,13 +129,7 @@ class BeamControls:
     def beam_bans(self, hist, hist_len):
         """Every beam's own ban set for its next token, (B W, ceil(V / 32)) int32 words: ONE vmlmf_history_bans launch on the B W rows
         of hist / hist_len (libvmlmf_history.so - opened here, on the first call)."""
-        rows, dev = self.B * self.W, hist.device
-        out = torch.empty((rows, (self.V + 31) // 32), dtype=torch.int32, device=dev)
-        c = _history.Controls(1.0, -1, 0, 0, None, None, None, None, self.no_repeat_ngram_size, 0.0, 0.0, 0, hist.data_ptr(),
-                              hist_len.data_ptr(), self.capacity, 0, None, None, None if self.seq_tokens is None else self.seq_tokens.data_ptr(),
-                              None if self.seq_offsets is None else self.seq_offsets.data_ptr(), len(self.sequences), 0)
-        _history.LIBRARY.call(dev, "vmlmf_history_bans", rows, self.V, ctypes.byref(c), ptr(out))
-        return out
+        return _history.launch_bans(hist, hist_len, self.capacity, self.no_repeat_ngram_size, self.seq_tokens, self.seq_offsets, self.V)
 
 
 def beamctl_select(scores, bias, cum, finished, length, eos, embed, controls, hist=None, hist_len=None, buffers=None):
@@ -179,9 +163,8 @@ def beamctl_select(scores, bias, cum, finished, length, eos, embed, controls, hi
     ln = torch.empty((B, W), device=dev, dtype=torch.int32)
     src = torch.empty(B * W, device=dev, dtype=torch.int32)
     xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
-    p = lambda t: None if t is None else t.data_ptr()
-    c = Controls(controls.min_length, cap, p(controls.closed), p(bans), p(hist), p(hist_len), p(hist_out), p(len_out),
-                 p(controls.overflow) if hist is not None else None)
+    c = Controls(controls.min_length, cap, ptr(controls.closed), ptr(bans), ptr(hist), ptr(hist_len), ptr(hist_out), ptr(len_out),
+                 ptr(controls.overflow) if hist is not None else None)
     LIBRARY.call(dev, "vmlmf_beamctl_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
                  ctypes.byref(c), ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws),
                  ws.numel() * 8)

@@ -125,26 +125,39 @@ class DecodeControls:
         self.finished = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.length = torch.zeros(B, dtype=torch.int32, device=self.device)
 
+    STATE = ("seen", "finished", "length")                                  # the buffers a launch moves on: what clone() copies
+    LIBRARY, ENTRY, STRUCT = LIBRARY, "vmlmf_decode_choose", Controls       # where decode_choose goes with these controls
+
     def clone(self):
-        """The same controls on a copy of the state (a DecodeGraph's warm-up runs on one)."""
-        c = object.__new__(DecodeControls)
+        """The same controls on a copy of ALL the state (a DecodeGraph's warm-up runs on one)."""
+        c = object.__new__(type(self))
         c.__dict__.update(self.__dict__)
-        c.seen, c.finished, c.length = self.seen.clone(), self.finished.clone(), self.length.clone()
+        for name in self.STATE:
+            setattr(c, name, getattr(self, name).clone())
         return c
 
-    def struct(self):
-        """The host struct vmlmf_decode_choose reads (its pointers are this object's buffers)."""
-        return Controls(self.repetition_penalty, self.eos, self.min_length, 0, None if self.logit_bias is None else self.logit_bias.data_ptr(),
-                        self.seen.data_ptr(), self.finished.data_ptr(), self.length.data_ptr())
+    def values(self):       # STRUCT's fields by name; the pointers are this object's buffers
+        return dict(repetition_penalty=self.repetition_penalty, eos=self.eos, min_length=self.min_length, logit_bias=ptr(self.logit_bias),
+                    seen=ptr(self.seen), finished=ptr(self.finished), length=ptr(self.length))
+
+    def struct(self):       # the host struct ENTRY reads
+        return self.STRUCT(**self.values())
 
 
-def decode_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls, tokens, logp, xn, kept):
-    """The vmlmf_decode_choose launch on checked, contiguous arguments: scores (B, V) without the bias; outputs are written in place."""
+def check_launch(controls, kind, B, V, dev, what):
+    """RuntimeError unless `controls` is a `kind` for B rows of V tokens on dev - and the history, where it keeps one, (B, capacity)."""
+    if not isinstance(controls, kind) or (controls.B, controls.V) != (B, V) or controls.seen.device != dev:
+        raise RuntimeError(f"vmlmf_amd.{what}: controls must be a {kind.__name__} for {B} rows of {V} tokens on {dev}")
+    if "hist" in controls.STATE and (tuple(controls.hist.shape) != (B, controls.capacity) or not controls.hist.is_contiguous()):
+        raise RuntimeError(f"vmlmf_amd.{what}: controls.hist must be a contiguous ({B}, capacity = {controls.capacity}) tensor")
+
+
+def decode_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls, tokens, logp, xn, kept, kind=DecodeControls):
+    """The launch of the controls' ENTRY on checked, contiguous arguments: scores (B, V) without the bias; outputs are written in place."""
     B, V = scores.shape
     dev = scores.device
-    if not isinstance(controls, DecodeControls) or (controls.B, controls.V) != (B, V) or controls.seen.device != dev:
-        raise RuntimeError(f"vmlmf_amd.lm_sample: controls must be a DecodeControls for {B} rows of {V} tokens on {dev}")
+    check_launch(controls, kind, B, V, dev, "lm_sample")
     H = embed.shape[1] if embed is not None else 1
     c = controls.struct()
-    LIBRARY.call(dev, "vmlmf_decode_choose", B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
-                 ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept))
+    controls.LIBRARY.call(dev, controls.ENTRY, B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
+                          ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept))

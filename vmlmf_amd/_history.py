@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _decode, _lib
 from ._decode import DecodeControls
 from ._lib import ptr
 
@@ -23,12 +23,11 @@ MAX_SEQUENCE_TOKENS = 4096   # the tokens of all banned sequences together: ever
 
 class Controls(ctypes.Structure):
     """struct vmlmf_history_controls: struct vmlmf_decode_controls, then the history's fields"""
-    _fields_ = [("repetition_penalty", ctypes.c_float), ("eos", ctypes.c_int32), ("min_length", ctypes.c_int32), ("pad", ctypes.c_int32),
-                ("logit_bias", ctypes.c_void_p), ("seen", ctypes.c_void_p), ("finished", ctypes.c_void_p), ("length", ctypes.c_void_p),
-                ("no_repeat_ngram_size", ctypes.c_int32), ("frequency_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float),
-                ("pad1", ctypes.c_int32), ("hist", ctypes.c_void_p), ("hist_len", ctypes.c_void_p), ("hist_capacity", ctypes.c_int32),
-                ("pad2", ctypes.c_int32), ("count", ctypes.c_void_p), ("overflow", ctypes.c_void_p), ("seq_tokens", ctypes.c_void_p),
-                ("seq_offsets", ctypes.c_void_p), ("n_sequences", ctypes.c_int32), ("pad3", ctypes.c_int32)]
+    _fields_ = _decode.Controls._fields_ + [
+        ("no_repeat_ngram_size", ctypes.c_int32), ("frequency_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float),
+        ("pad1", ctypes.c_int32), ("hist", ctypes.c_void_p), ("hist_len", ctypes.c_void_p), ("hist_capacity", ctypes.c_int32),
+        ("pad2", ctypes.c_int32), ("count", ctypes.c_void_p), ("overflow", ctypes.c_void_p), ("seq_tokens", ctypes.c_void_p),
+        ("seq_offsets", ctypes.c_void_p), ("n_sequences", ctypes.c_int32), ("pad3", ctypes.c_int32)]
 
 
 # every symbol include/vmlmf_history.h declares: (restype, argtypes)
@@ -98,6 +97,31 @@ def check_history(V, no_repeat_ngram_size=0, banned_sequences=None, frequency_pe
     return n, seqs, pen[0], pen[1]
 
 
+def check_capacity(who, capacity, T0):
+    """For HistoryControls and BeamControls (`who`): `capacity`, default the prompt's T0 tokens and 1024; ValueError unless it holds them."""
+    capacity = T0 + 1024 if capacity is None else int(capacity)
+    if capacity < max(T0, 1):
+        raise ValueError(f"vmlmf_amd: {who}: capacity={capacity} must be >= 1 and hold the prompt ({T0} tokens)")
+    return capacity
+
+
+def prompt_history(prompt, B, V, capacity, dev):
+    """(hist (B, capacity) int32, hist_len (B) int32) on dev that hold the (T0, B) prompt (None: empty), its tokens clamped into [0, V)."""
+    T0 = 0 if prompt is None else int(prompt.shape[0])
+    hist = torch.zeros((B, capacity), dtype=torch.int32, device=dev)
+    if T0 > 0:
+        hist[:, :T0] = prompt.to(dev).t().clamp(0, V - 1).to(torch.int32)
+    return hist, torch.full((B,), T0, dtype=torch.int32, device=dev)
+
+
+def flat_sequences(sequences, dev):
+    """(seq_tokens, seq_offsets) int32 on dev: the sequences end to end, and where each starts and the last ends; (None, None) for none."""
+    if not sequences:
+        return None, None
+    offsets = torch.tensor([0] + [len(s) for s in sequences]).cumsum(0).to(torch.int32)
+    return torch.tensor([t for s in sequences for t in s], dtype=torch.int32).to(dev), offsets.to(dev)
+
+
 class HistoryControls(DecodeControls):
     """DecodeControls, and the controls that need a row's sequence of tokens (include/vmlmf_history.h):
       no_repeat_ngram_size   n >= 1: no n-gram of a row's tokens - prompt included - comes twice (n = 1: no token does)
@@ -116,74 +140,46 @@ class HistoryControls(DecodeControls):
     def __init__(self, B, V, device, no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0,
                  capacity=None, prompt=None, _checked=False, **decode_controls):
         T0 = int(prompt.shape[0]) if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
-        if capacity is None:
-            capacity = T0 + 1024
-        capacity = int(capacity)
-        if capacity < max(T0, 1):
-            raise ValueError(f"vmlmf_amd: HistoryControls: capacity={capacity} must be >= 1 and hold the prompt ({T0} tokens)")
+        self.capacity = check_capacity("HistoryControls", capacity, T0)
         super().__init__(B, V, device, prompt=prompt, _checked=_checked, **decode_controls)
         self.no_repeat_ngram_size, self.sequences, self.frequency_penalty, self.presence_penalty = check_history(
             int(V), no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty)
-        self.capacity = capacity
-        dev = self.device
-        self.hist = torch.zeros((self.B, capacity), dtype=torch.int32, device=dev)
-        if T0 > 0:
-            self.hist[:, :T0] = prompt.to(dev).t().clamp(0, self.V - 1).to(torch.int32)
-        self.hist_len = torch.full((self.B,), T0, dtype=torch.int32, device=dev)
-        self.count = torch.zeros((self.B, self.V), dtype=torch.int16, device=dev).view(torch.uint16)
-        self.overflow = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        offsets = [0]
-        for s in self.sequences:
-            offsets.append(offsets[-1] + len(s))
-        flat = [t for s in self.sequences for t in s]
-        self.seq_tokens = torch.tensor(flat, dtype=torch.int32).to(dev) if flat else None
-        self.seq_offsets = torch.tensor(offsets, dtype=torch.int32).to(dev) if flat else None
+        self.hist, self.hist_len = prompt_history(prompt, self.B, self.V, self.capacity, self.device)
+        self.count = torch.zeros((self.B, self.V), dtype=torch.int16, device=self.device).view(torch.uint16)
+        self.overflow = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.seq_tokens, self.seq_offsets = flat_sequences(self.sequences, self.device)
 
-    STATE = ("seen", "finished", "length", "hist", "hist_len", "count", "overflow")
+    STATE = DecodeControls.STATE + ("hist", "hist_len", "count", "overflow")
+    LIBRARY, ENTRY, STRUCT = LIBRARY, "vmlmf_history_choose", Controls
 
-    def clone(self):
-        """The same controls on a copy of ALL the state (a DecodeGraph's warm-up runs on one)."""
-        c = object.__new__(type(self))
-        c.__dict__.update(self.__dict__)
-        for name in self.STATE:
-            setattr(c, name, getattr(self, name).clone())
-        return c
-
-    def struct(self):
-        """The host struct vmlmf_history_choose and vmlmf_history_bans read (its pointers are this object's buffers)."""
-        p = lambda t: None if t is None else t.data_ptr()
-        return Controls(self.repetition_penalty, self.eos, self.min_length, 0, p(self.logit_bias), p(self.seen), p(self.finished),
-                        p(self.length), self.no_repeat_ngram_size, self.frequency_penalty, self.presence_penalty, 0, p(self.hist),
-                        p(self.hist_len), self.capacity, 0, p(self.count), p(self.overflow), p(self.seq_tokens), p(self.seq_offsets),
-                        len(self.sequences), 0)
+    def values(self):
+        return dict(super().values(), no_repeat_ngram_size=self.no_repeat_ngram_size, frequency_penalty=self.frequency_penalty,
+                    presence_penalty=self.presence_penalty, hist=ptr(self.hist), hist_len=ptr(self.hist_len), hist_capacity=self.capacity,
+                    count=ptr(self.count), overflow=ptr(self.overflow), seq_tokens=ptr(self.seq_tokens),
+                    seq_offsets=ptr(self.seq_offsets), n_sequences=len(self.sequences))
 
 
-def _check(controls, B, V, dev, what):
-    if not isinstance(controls, HistoryControls) or (controls.B, controls.V) != (B, V) or controls.seen.device != dev:
-        raise RuntimeError(f"vmlmf_amd.{what}: controls must be a HistoryControls for {B} rows of {V} tokens on {dev}")
-    if tuple(controls.hist.shape) != (B, controls.capacity) or not controls.hist.is_contiguous():
-        raise RuntimeError(f"vmlmf_amd.{what}: controls.hist must be a contiguous ({B}, capacity = {controls.capacity}) tensor")
+def history_choose(*args):      # decode_choose where only a HistoryControls will do: the vmlmf_history_choose launch
+    _decode.decode_choose(*args, kind=HistoryControls)
 
 
-def history_choose(scores, bias, embed, inv, top_k, top_p, state, step, controls, tokens, logp, xn, kept):
-    """The vmlmf_history_choose launch on checked, contiguous arguments: scores (B, V) without the bias; outputs are written in place."""
-    B, V = scores.shape
-    dev = scores.device
-    _check(controls, B, V, dev, "lm_sample")
-    H = embed.shape[1] if embed is not None else 1
-    c = controls.struct()
-    LIBRARY.call(dev, "vmlmf_history_choose", B, H, V, ptr(scores), ptr(bias), ptr(embed), inv, top_k, top_p, ptr(state), int(step),
-                 ctypes.byref(c), ptr(tokens), ptr(logp), ptr(xn), ptr(kept))
+def launch_bans(hist, hist_len, capacity, n, seq_tokens, seq_offsets, V, eos=-1, finished=None):
+    """ONE vmlmf_history_bans launch on given buffers - hist (R, capacity), hist_len (R), n = no_repeat_ngram_size, flat_sequences' two -:
+    (R, ceil(V / 32)) int32 words, bit v & 31 of word v >> 5 set when v is banned; with eos and finished (R), a finished row's are zero."""
+    R, dev = hist_len.numel(), hist.device
+    out = torch.empty((R, (V + 31) // 32), dtype=torch.int32, device=dev)
+    c = Controls(repetition_penalty=1.0, eos=eos, finished=ptr(finished), no_repeat_ngram_size=n, hist=ptr(hist), hist_len=ptr(hist_len),
+                 hist_capacity=capacity, seq_tokens=ptr(seq_tokens), seq_offsets=ptr(seq_offsets),
+                 n_sequences=0 if seq_offsets is None else seq_offsets.numel() - 1)
+    LIBRARY.call(dev, "vmlmf_history_bans", R, V, ctypes.byref(c), ptr(out))
+    return out
 
 
 def history_bans(controls):
-    """The ban sets of the rows' NEXT choice (step 5 of the contract; vmlmf_history_bans, one launch): (B, ceil(V / 32)) int32 words,
-    bit v & 31 of word v >> 5 set when v is banned - a finished row's are zero.  Nothing is chosen, no state moves."""
+    """The ban sets of the rows' NEXT choice (step 5 of the contract): launch_bans on the controls' own buffers.  No state moves."""
     B, V, dev = controls.B, controls.V, controls.seen.device
     if dev.type != "cuda":
         raise RuntimeError("vmlmf_amd.history_bans runs on the HIP kernel only: the controls must live on 'cuda' (no CPU fallback)")
-    _check(controls, B, V, dev, "history_bans")
-    out = torch.empty((B, (V + 31) // 32), dtype=torch.int32, device=dev)
-    c = controls.struct()
-    LIBRARY.call(dev, "vmlmf_history_bans", B, V, ctypes.byref(c), ptr(out))
-    return out
+    _decode.check_launch(controls, HistoryControls, B, V, dev, "history_bans")
+    return launch_bans(controls.hist, controls.hist_len, controls.capacity, controls.no_repeat_ngram_size, controls.seq_tokens,
+                       controls.seq_offsets, V, controls.eos, controls.finished)

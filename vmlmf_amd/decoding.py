@@ -113,9 +113,8 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
     bias_p, embed_p = ptr(bias_c), ptr(embed_c)
     if controls is not None:
-        choose = _history.history_choose if isinstance(controls, HistoryControls) else _decode.decode_choose
-        choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp, xn,
-               kept)
+        _decode.decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp,
+                              xn, kept)      # (the controls' class has the library and the entry point)
         return outs()
     if form == "gemm":
         scores = torch.mm(h2, w.t())
@@ -214,14 +213,21 @@ def _sampled(model, gen, carried, steps, temperature, layer_path, top_k, top_p, 
     return (toks, lps), [h, *(t for st in states for t in st)]
 
 
+def _join_beams(h, states, cum, finished, length, history):
+    return [h, *(t for st in states for t in st), cum, finished, length, *history]
+
+
+def _split_beams(carried, controls):        # _join_beams' arguments back; history is [hist, hist_len] where the controls keep one
+    history = list(carried[-2:]) if controls is not None and controls.keeps_history else []
+    h, *flat, cum, finished, length = carried[:len(carried) - len(history)]
+    return h, _pairs(flat), cum, finished, length, history
+
+
 def _beamed(model, carried, steps, eos, buffers=None, controls=None):
-    history = []
-    if controls is not None and controls.keeps_history:
-        carried, history = carried[:-2], carried[-2:]
-    h, *flat, cum, finished, length = carried
-    par, tok, h, states, cum, finished, length, *history = beam_steps(model, h, _pairs(flat), cum, finished, length, steps, eos, buffers,
-                                                                      controls, *history)
-    return (par, tok), [h, *(t for st in states for t in st), cum, finished, length, *history]
+    h, states, cum, finished, length, history = _split_beams(carried, controls)
+    par, tok, h, states, cum, finished, length, *history = beam_steps(model, h, states, cum, finished, length, steps, eos, buffers, controls,
+                                                                      *history)
+    return (par, tok), _join_beams(h, states, cum, finished, length, history)
 
 
 def _fresh_beams(B, W, dev):
@@ -349,11 +355,11 @@ class BeamGraph(_StepGraph):
         if controls is not None and controls.keeps_history:
             history = list(controls.history()) if hist is None else [hist, hist_len]
         step = lambda carried, controls=controls: _beamed(model, carried, self.steps, eos, self.buffers, controls)
-        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32), *history], step,
+        self._capture(model, _join_beams(h, states, cum, finished.to(torch.int32), length.to(torch.int32), history), step,
                       None if controls is None else lambda carried: step(carried, controls.clone()))
-        self.hist, self.hist_len = history and self.carried[-2:] or (None, None)
-        self.h, *flat, self.cum, self.finished, self.length = self.carried[:len(self.carried) - len(history)]
-        self.states, (self.parents, self.tokens) = _pairs(flat), self.outputs
+        self.h, self.states, self.cum, self.finished, self.length, history = _split_beams(self.carried, controls)
+        self.hist, self.hist_len = history or (None, None)
+        self.parents, self.tokens = self.outputs
 
 
 # ---- one call: the checks, the prompt, the steps -----------------------------------------------------------------------------------
@@ -478,15 +484,15 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
             return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
         (parents, toks), carried = _run(
             steps, chunk,
-            lambda: _beamed(model, [h, *(t for st in states for t in st), cum, finished, length, *history], steps, eos, None, controls),
+            lambda: _beamed(model, _join_beams(h, states, cum, finished, length, history), steps, eos, None, controls),
             lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls, *history))
-        _, *flat, cum, finished, length = carried[:len(carried) - len(history)]
+        _, states, cum, finished, length, _ = _split_beams(carried, controls)
         order = None
         if alpha > 0.0:
             key = cum / length.to(torch.float32) ** alpha
             order = torch.sort(key, dim=1, descending=True, stable=True).indices
             cum, length = cum.gather(1, order), length.gather(1, order)
             rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
-            flat = beam_gather(flat, rows)
+            states = _pairs(beam_gather([t for st in states for t in st], rows))
             order = order.to(torch.int32)
-        return beam_backtrack(parents, toks, order), cum, length, _pairs(flat)
+        return beam_backtrack(parents, toks, order), cum, length, states
