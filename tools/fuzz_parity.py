@@ -1,7 +1,10 @@
 """Randomised parity sweep of the sequence entry point against the fp64 literal oracle (tests/hip_util.py's run_hip /
 run_literal / compare_all at the tolerances of the test suite): shapes, ranks, variants, optional initial states and upstream
 gradients drawn at random from a seed.  Prints every case that fails or that the library refuses, and a summary line.
-    python tools/fuzz_parity.py [cases] [seed] [seq|stack|rb|big|wide]
+    python tools/fuzz_parity.py [cases] [seed] [seq|stack|rb|big|wide] [hot]
+hot (modes seq, rb, stack): the same draws with their values in the saturated-gate regime of tests/hot_cases.py (biases at sigma 5, or
+40 for one case in four; docs/design/value_regimes.md); a case on which the fp32 literal oracle itself uses more than a third of the
+tolerance is drawn again and counted, and more than one redraw per ten cases fails the run
 wide: layers at wide ranks (padded w_rank > 32 or padded hidden rank summed over groups > 128) inside the envelope the library
 documents for them (include/vmlmf_hip.h): the step-wise path, fp32, w_rank <= input_size, u_rank <= hidden_size / g, padded ranks
 <= 1024; mostly ranks 33 - 320, sometimes up to the cap
@@ -19,53 +22,19 @@ import vmlmf_oracle as O
 from hip_util import run_hip, run_literal, compare_all, ORDER, ranks_of, assert_out, assert_grad
 from vmlmf_amd import functional as F
 
+import fuzz_draw as D
+
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-rng = np.random.Generator(np.random.PCG64(SEED))
-VARIANTS = [O.V1, O.V2, O.V3, O.V4, O.V5, O.V6]
 MODE = sys.argv[3] if len(sys.argv) > 3 else "seq"
+HOT = len(sys.argv) > 4 and sys.argv[4] == "hot"
+if len(sys.argv) > 4 and not (HOT and MODE in D.HOT_MODES):
+    sys.exit("usage: fuzz_parity.py [cases] [seed] [seq|stack|rb|big|wide] [hot]   (hot: seq, rb and stack only)")
+rng = D.init(SEED, MODE)        # the draws (tools/fuzz_draw.py) and draw_wide below share this stream
+VARIANTS, pick, draw, draw_stack = D.VARIANTS, D.pick, D.draw, D.draw_stack
 if MODE == "rb":                      # the row-block MFMA kernels wherever an instantiation exists (vmlmf_tune "rb"), else the default choice
     from vmlmf_amd import _lib
     _lib.tune("rb", 1)
-
-
-def pick(lo, hi, small=0.5):
-    """mostly small values, sometimes up to hi"""
-    if rng.random() < small:
-        return int(rng.integers(lo, min(hi, lo + 12) + 1))
-    return int(rng.integers(lo, hi + 1))
-
-
-def draw():
-    v = VARIANTS[int(rng.integers(0, len(VARIANTS)))]
-    group = v in (O.V2, O.V4, O.V6)
-    H = pick(2, 300, 0.3)
-    if group and H % 2:
-        H += 1
-    novm = v in (O.V5, O.V6)
-    lm = v in (O.V3, O.V4)            # the LM layers need input_size == hidden_size (vmlmf_lm.py:243)
-    if lm:
-        H = min(H, 160)
-    I = H if lm else pick(2, 150 if novm else min(H, 150), 0.4)   # (I = 1: the reference's own squeeze() breaks the literal oracle)
-    rw = pick(1, 32, 0.3)             # narrow ranks (padded <= 32 / hidden <= 128 summed): every kernel family; wider: MODE "wide"
-    ru = [pick(1, 32, 0.3), pick(1, 32, 0.3)] if group else pick(1, 32, 0.3)
-    B, T = pick(1, 200, 0.4), pick(1, 40, 0.4)
-    if MODE == "big":
-        B, T = int(rng.integers(64, 1101)), int(rng.integers(16, 201))
-        H = int(rng.integers(32, 701)) + (0 if not group else 0)
-        if group and H % 2:
-            H += 1
-        if lm:
-            H = min(H, 660)
-            I = H
-        else:
-            I = int(rng.integers(2, (150 if novm else min(H, 150)) + 1))
-        while B * T * H > 24_000_000:      # keeps the float64 oracle of a case within seconds
-            T = max(8, T // 2)
-    if v == O.V4 and B == 1:
-        B = 2                         # (B = 1: the reference's squeeze() in vmlmf_lm.py:257 drops the batch dimension and the layer raises)
-    return dict(v=v, B=B, T=T, I=I, H=H, rw=rw, ru=ru, states=bool(rng.random() < 0.5), tm=bool(rng.random() < 0.3),
-                dy=bool(rng.random() < 0.8), dh=bool(rng.random() < 0.5), dc=bool(rng.random() < 0.4), seed=int(rng.integers(0, 2**31)))
 
 
 def pad8(r):
@@ -118,7 +87,12 @@ def draw_wide():
                     seed=int(rng.integers(0, 2**31)), scale=scale)
 
 
-def run(c):
+def run(c, vals=None):
+    if vals is not None:              # hot: the values came with the draw (fuzz_draw.draw_hot)
+        got = run_hip(c["v"], *vals, time_major=c["tm"])
+        ref = run_literal(c["v"], *vals, time_major=c["tm"])
+        compare_all(got, ref, "fuzz")
+        return
     r = np.random.Generator(np.random.PCG64(c["seed"]))
     P = O.make_params(c["v"], c["I"], c["H"], c["rw"], c["ru"], seed=c["seed"] % 1000, scale=c.get("scale", 0.1))
     shp = (c["T"], c["B"], c["I"]) if c["tm"] else (c["B"], c["T"], c["I"])
@@ -142,18 +116,22 @@ class NotCovered(Exception):
     pass
 
 
-def run_stack(c):
+def run_stack(c, vals=None):
     """L like layers: vmlmf_stack on the GPU, the literal layers chained on the CPU (float64)."""
     r = np.random.Generator(np.random.PCG64(c["seed"]))
     v, L, B, T, I, H = c["v"], c["L"], c["B"], c["T"], c["I"], c["H"]
     Hs = c.get("Hs") or [H] * L          # (round 6: the layers of a stack may differ in hidden size; no initial states then)
-    Ps = [O.make_params(v, I if l == 0 else Hs[l - 1], Hs[l], c["rw"], c["ru"], seed=c["seed"] % 1000 + l) for l in range(L)]
-    shp = (T, B, I) if c["tm"] else (B, T, I)
-    x = r.standard_normal(shp).astype(np.float32)
-    dy = r.standard_normal(shp[:2] + (Hs[-1],)).astype(np.float32)
-    st = None
-    if c["states"] and len(set(Hs)) == 1:
-        st = [(0.5 * r.standard_normal((L, B, H))).astype(np.float32) for _ in range(2)]
+    if vals is not None:              # hot: the values came with the draw (fuzz_draw.draw_hot), every layer's in the regime
+        Ps, x, h0s, c0s, dy, dhT_hot = vals[:6]
+        st = None if h0s is None else [np.stack(h0s), np.stack(c0s)]
+    else:
+        Ps = [O.make_params(v, I if l == 0 else Hs[l - 1], Hs[l], c["rw"], c["ru"], seed=c["seed"] % 1000 + l) for l in range(L)]
+        shp = (T, B, I) if c["tm"] else (B, T, I)
+        x = r.standard_normal(shp).astype(np.float32)
+        dy = r.standard_normal(shp[:2] + (Hs[-1],)).astype(np.float32)
+        st = None
+        if c["states"] and len(set(Hs)) == 1:
+            st = [(0.5 * r.standard_normal((L, B, H))).astype(np.float32) for _ in range(2)]
     names = ORDER[v]
     rw, ru, g = ranks_of(v, Ps[0])
     params = [[torch.tensor(np.asarray(P[k]), device="cuda").requires_grad_(True) for k in names] for P in Ps]
@@ -165,7 +143,7 @@ def run_stack(c):
     if out is None:
         raise NotCovered()
     y, hTs, cTs = out[:3]
-    dhT = [r.standard_normal((B, Hs[l])).astype(np.float32) for l in range(L)]
+    dhT = dhT_hot if vals is not None else [r.standard_normal((B, Hs[l])).astype(np.float32) for l in range(L)]
     loss = (y * torch.tensor(dy, device="cuda")).sum()
     for l in range(L):
         loss = loss + (hTs[l] * torch.tensor(dhT[l], device="cuda")).sum()
@@ -198,38 +176,20 @@ def run_stack(c):
             assert_grad(p.grad.cpu().numpy(), Pt[l][k].grad.numpy(), f"stack.G[{l}].{k}")
 
 
-def draw_stack():
-    c = draw()
-    while c["v"] == O.V4:             # (the flat V4 layout is not on the wavefront kernels)
-        c = draw()
-    c["L"] = int(rng.integers(2, 5))
-    c["H"] = min(c["H"], 256)
-    if c["v"] in (O.V2, O.V6) and c["H"] % 2:
-        c["H"] += 1
-    if c["v"] == O.V3:
-        c["I"] = c["H"]
-    elif c["v"] == O.V5 or c["v"] == O.V6:
-        pass
-    else:
-        c["I"] = min(c["I"], c["H"])
-    c["B"], c["T"] = min(c["B"], 128), min(c["T"], 30)
-    if c["v"] in (O.V1, O.V5) and rng.random() < 0.35:      # growing hidden sizes (a VMLMF cell needs input_size <= hidden_size)
-        hs = sorted(int(min(256, max(c["I"] if c["v"] == O.V1 else 2, pick(2, 256, 0.2)))) for _ in range(c["L"]))
-        c["Hs"], c["H"] = hs, hs[0]
-        if c["v"] == O.V1:
-            c["I"] = min(c["I"], hs[0])
-    return c
-
-
-ok = refused = failed = uncovered = 0
+ok = refused = failed = uncovered = redrawn = 0
 t0 = time.time()
 for n in range(N):
-    c = draw_stack() if MODE == "stack" else (draw_wide() if MODE == "wide" else draw())
+    vals = None
+    if HOT:
+        c, vals, again = D.draw_hot()
+        redrawn += again
+    else:
+        c = draw_stack() if MODE == "stack" else (draw_wide() if MODE == "wide" else draw())
     try:
         if MODE == "stack":
-            run_stack(c)
+            run_stack(c, vals)
         else:
-            run(c)
+            run(c, vals)
         ok += 1
     except NotCovered:
         uncovered += 1
@@ -250,6 +210,12 @@ for n in range(N):
     except Exception as e:      # noqa: BLE001
         failed += 1
         print("EXC", c, traceback.format_exc()[-600:], flush=True)
-print(f"fuzz {MODE} seed {SEED}: {N} cases, {ok} ok, {refused} refused by the library, {uncovered} not covered by the wavefront "
-      f"launches, {failed} FAILED, {time.time() - t0:.0f} s")
+summary = (f"fuzz {MODE}{' hot' if HOT else ''} seed {SEED}: {N} cases, {ok} ok, {refused} refused by the library, {uncovered} not covered by "
+           f"the wavefront launches, {failed} FAILED, {time.time() - t0:.0f} s")
+if HOT:
+    summary += f", {redrawn} redrawn (fp32 oracle)"
+    if redrawn > D.REDRAW_CAP * N:
+        print(f"more than {D.REDRAW_CAP:.0%} of the cases had to be drawn again: the regime is not one plain fp32 can be held to", flush=True)
+        failed += 1
+print(summary)
 sys.exit(1 if failed else 0)
