@@ -1,6 +1,7 @@
 // What every form of the sampler step refuses, written once for vmlmf_lm_sample / vmlmf_lm_choose and their filtered forms
-// (vmlmf_ops.hip), for vmlmf_decode_choose (vmlmf_decode.hip) and for vmlmf_history_choose (vmlmf_history.hip); what the two controlled
-// choices refuse of the controls they share is controls_refusal.  `refuse(code, text)` is the caller's: it puts the entry point's
+// (vmlmf_ops.hip), for vmlmf_decode_choose (vmlmf_decode.hip), for vmlmf_history_choose (vmlmf_history.hip) and for
+// vmlmf_truncate_choose (vmlmf_truncate.hip); what the controlled choices refuse of the controls they share is controls_refusal, what
+// the truncated choice refuses of its four samplers truncation_refusal.  `refuse(code, text)` is the caller's: it puts the entry point's
 // name before the text, keeps the result as its library's error and returns the code.  Host code only.
 #pragma once
 #include "../../include/vmlmf_hip.h" /* VMLMF_E_* */
@@ -29,5 +30,14 @@ static int controls_refusal(const Refuse& refuse, int V, int eos, float repetiti
     return refuse(VMLMF_E_BADARG, "repetition_penalty must be finite and > 0 (1: off)");
   if (min_length < 0) return refuse(VMLMF_E_BADARG, "min_length must be >= 0");
   if (min_length > 0 && eos < 0) return refuse(VMLMF_E_BADARG, "min_length needs eos");
+  return 0;
+}
+// the four truncation samplers of vmlmf_truncate_choose (vmlmf_truncation: min_p, typical_p, epsilon_cutoff, eta_cutoff)
+template <class Refuse>
+static int truncation_refusal(const Refuse& refuse, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff) {
+  if (!(min_p >= 0.f && min_p <= 1.f)) return refuse(VMLMF_E_BADARG, "min_p must lie in [0, 1] (0: off)");
+  if (!(typical_p > 0.f && typical_p <= 1.f)) return refuse(VMLMF_E_BADARG, "typical_p must lie in (0, 1] (1: off)");
+  if (!(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f)) return refuse(VMLMF_E_BADARG, "epsilon_cutoff must lie in [0, 1) (0: off)");
+  if (!(eta_cutoff >= 0.f && eta_cutoff < 1.f)) return refuse(VMLMF_E_BADARG, "eta_cutoff must lie in [0, 1) (0: off)");
   return 0;
 }

@@ -14,12 +14,13 @@ import contextlib
 
 import torch
 
-from . import _beam, _beamctl, _decode, _history, _lib
+from . import _beam, _beamctl, _decode, _history, _lib, _truncate
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._beamctl import BeamControls
 from ._decode import DecodeControls
 from ._history import HistoryControls
 from ._lib import ptr
+from ._truncate import Truncation
 from .functional import PackCache, _require_hip, _workspace, dropout_advance, sample_ticket
 from .lm import stack_layers
 
@@ -51,7 +52,7 @@ def sample_filters(top_k, top_p, V=None):
 
 
 def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form=None, top_k=None, top_p=None, return_kept=False,
-              controls=None):
+              controls=None, truncation=None):
     """The next token of every row of h (B, H) - the top layer's output - under Linear(weight (V, H), bias (V)), in ONE launch that
     never writes the (B, V) scores.  temperature 0: greedy (argmax, ties to the lowest index); tau > 0: a draw from softmax(scores / tau)
     by Gumbel-max, its noise from Philox4x32-10 at (state = a {seed, offset} snapshot of dropout_advance(), position step * B + b,
@@ -72,7 +73,13 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     log-probabilities stay those of the plain call, a finished row gives (eos, 0.0, kept 0), kept never counts a token at -inf.
     A HistoryControls (those, and no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty with the rows' hist /
     hist_len / count / overflow state) goes to ONE launch of vmlmf_history_choose instead (include/vmlmf_history.h has the contract),
-    whatever of its controls is on: with none of the history's on, the results and the shared state are vmlmf_decode_choose's to the bit."""
+    whatever of its controls is on: with none of the history's on, the results and the shared state are vmlmf_decode_choose's to the bit.
+    truncation: a Truncation (min_p, typical_p, epsilon_cutoff, eta_cutoff).  With one of them on and temperature > 0 the choice is
+    ONE launch of a library of its own behind the head's GEMM (vmlmf_truncate_choose, include/vmlmf_truncate.h has the contract; form
+    "gemm" only), which runs top_k and top_p too and, under a DecodeControls, chooses on the controlled scores and moves their state on
+    as vmlmf_decode_choose does; the noise and the log-probabilities stay those of the plain call, kept counts the survivors.  Greedy
+    decoding ignores it, and None or a Truncation with nothing on is the call above, launch for launch.  ValueError with form="fused"
+    and with a HistoryControls."""
     for t, what in ((h, "h"), (weight, "weight")):
         _require_hip(t, what)
     if bias is not None:
@@ -93,6 +100,14 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
         raise RuntimeError(f"vmlmf_amd.lm_sample: h {tuple(h.shape)}, weight {tuple(weight.shape)}, bias / embed must be (V) / (V, H)")
     k, p = sample_filters(top_k, top_p, V)
     filtered = inv > 0.0 and (k > 0 or p < 1.0)      # greedy: the argmax is always kept, the existing kernels run
+    if truncation is not None and not isinstance(truncation, Truncation):
+        raise ValueError(f"vmlmf_amd.lm_sample: truncation must be a vmlmf_amd.Truncation or None, got {type(truncation).__name__}")
+    truncated = truncation is not None and truncation.on
+    if truncated and form not in (None, "gemm"):
+        raise ValueError(f"vmlmf_amd.lm_sample: the truncation samplers have no fused-head form (form must be 'gemm' or None, got {form!r})")
+    if truncated and isinstance(controls, HistoryControls):
+        raise ValueError(_truncate.HISTORY_REFUSAL)
+    truncated = truncated and inv > 0.0
     dev = h2.device
     lib = _lib.lib()
     tokens = torch.empty(B, device=dev, dtype=torch.int64)
@@ -100,7 +115,7 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     xn = torch.empty((B, H), device=dev, dtype=torch.float32) if embed is not None else None
     if not return_kept:
         kept = None
-    elif filtered or controls is not None:
+    elif filtered or truncated or controls is not None:
         kept = torch.empty(B, device=dev, dtype=torch.int32)
     else:
         kept = torch.full((B,), V, device=dev, dtype=torch.int32)
@@ -112,6 +127,9 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     state_p = None if inv == 0.0 else ptr(state)
     bias_c, embed_c = None if bias is None else bias.contiguous(), None if embed is None else embed.contiguous()
     bias_p, embed_p = ptr(bias_c), ptr(embed_c)
+    if truncated:
+        _truncate.truncate_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, truncation, state, step, controls, tokens, logp, xn, kept)
+        return outs()
     if controls is not None:
         _decode.decode_choose(torch.mm(h2, w.t()), bias_c, embed_c, inv, k, p, None if inv == 0.0 else state, step, controls, tokens, logp,
                               xn, kept)      # (the controls' class has the library and the entry point)
@@ -155,15 +173,18 @@ def decode_layers(model, x, states, layer_path):
     return x, states
 
 
-def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None, controls=None):
+def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=None, top_p=None, controls=None, min_p=None, typical_p=None,
+                 epsilon_cutoff=None, eta_cutoff=None):
     """`steps` tokens from the top layer's output h (B, H): per step one vmlmf_lm_sample launch (head, choice, log-probability and
     the next input row; with top_k / top_p its filtered form), then the layers at T = 1 on that row.  No host synchronisation:
     capturable (DecodeGraph).  controls: a DecodeControls - the choice is then the controlled launch behind the head's GEMM
-    (vmlmf_decode_choose; a HistoryControls: vmlmf_history_choose), which moves the controls' state on in place."""
+    (vmlmf_decode_choose; a HistoryControls: vmlmf_history_choose), which moves the controls' state on in place.  min_p, typical_p,
+    epsilon_cutoff, eta_cutoff: the truncation samplers of Model.generate - with one of them on the choice is vmlmf_truncate_choose."""
     toks, lps = [], []
+    trunc = _truncate.truncation(min_p, typical_p, epsilon_cutoff, eta_cutoff, isinstance(controls, HistoryControls))
     for j in range(steps):
         tok, lp, x = lm_sample(h, model.fc.w, model.fc.b, temperature, snap, j, embed=model.embed.w, top_k=top_k, top_p=top_p,
-                               controls=controls)
+                               controls=controls, truncation=trunc)
         toks.append(tok)
         lps.append(lp)
         y, states = decode_layers(model, x.unsqueeze(0), states, layer_path)
@@ -206,10 +227,11 @@ def _pairs(flat):
     return [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
 
 
-def _sampled(model, gen, carried, steps, temperature, layer_path, top_k, top_p, controls):
+def _sampled(model, gen, carried, steps, temperature, layer_path, top_k, top_p, controls, **truncation):
     """decode_steps, the generator `gen` (None: greedy) snapshotted and advanced in front."""
     snap = dropout_advance(gen) if gen is not None else None
-    toks, lps, h, states = decode_steps(model, carried[0], _pairs(carried[1:]), steps, temperature, snap, layer_path, top_k, top_p, controls)
+    toks, lps, h, states = decode_steps(model, carried[0], _pairs(carried[1:]), steps, temperature, snap, layer_path, top_k, top_p, controls,
+                                        **truncation)
     return (toks, lps), [h, *(t for st in states for t in st)]
 
 
@@ -310,16 +332,20 @@ class DecodeGraph(_StepGraph):
     top_k / top_p: the filters of Model.generate, fixed at construction.
     controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
     length, and a HistoryControls' hist, hist_len, count, overflow -, so replays continue one decode: finished rows stay finished, seen
-    and the history accumulate (the warm-up runs on a clone of all of them)."""
+    and the history accumulate (the warm-up runs on a clone of all of them).
+    min_p, typical_p, epsilon_cutoff, eta_cutoff: the truncation samplers of Model.generate, fixed at construction."""
 
-    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None):
+    def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None, min_p=None,
+                 typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         self.model, self.steps, self.temperature, self.layer_path = model, int(steps), float(temperature), layer_path
         sample_filters(top_k, top_p)
         self.top_k, self.top_p, self.controls = top_k, top_p, controls
+        self.truncation = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        _truncate.truncation(**self.truncation, history=isinstance(controls, HistoryControls))
         self.gen = model.sampler_state() if self.temperature > 0 else None
 
         def step(carried, controls=controls):
-            return _sampled(model, self.gen, carried, self.steps, self.temperature, layer_path, top_k, top_p, controls)
+            return _sampled(model, self.gen, carried, self.steps, self.temperature, layer_path, top_k, top_p, controls, **self.truncation)
 
         def warm_up(carried):           # on a clone of the controls; the generator is put back
             saved = None if self.gen is None else self.gen.clone()
@@ -411,14 +437,17 @@ def _run(steps, chunk, eager, graph):
     return tuple(torch.cat(o) for o in zip(*outs)), [t.clone() for t in g.carried]
 
 
-def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-             eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
-             no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
-    """Model.generate (lm.py has the contract)."""
+def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+              eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+              no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0, min_p=None, typical_p=None,
+              epsilon_cutoff=None, eta_cutoff=None):
+    """Model.generate with every argument (lm.py has the contract)."""
     sample_filters(top_k, top_p)
+    trunc_args = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
     hist_args = dict(no_repeat_ngram_size=no_repeat_ngram_size, banned_sequences=banned_sequences, frequency_penalty=frequency_penalty,
                      presence_penalty=presence_penalty)
     history = _history.history_on(**hist_args)
+    _truncate.truncation(**trunc_args, history=history)
     ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
                     banned_tokens=banned_tokens)
     eos_c, min_c, _, banned = _decode.check_controls(model.vocab_size, **ctl_args)
@@ -444,13 +473,26 @@ def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chun
         else:
             (tokens, logprobs), (_, *flat) = _run(
                 steps, chunk,
-                lambda: _sampled(model, gen, [h, *(t for st in states for t in st)], steps, temperature, layer_path, top_k, top_p, controls),
-                lambda: DecodeGraph(model, h, states, int(chunk), temperature, layer_path, top_k, top_p, controls))
+                lambda: _sampled(model, gen, [h, *(t for st in states for t in st)], steps, temperature, layer_path, top_k, top_p, controls,
+                                 **trunc_args),
+                lambda: DecodeGraph(model, h, states, int(chunk), temperature, layer_path, top_k, top_p, controls, **trunc_args))
             states = _pairs(flat)
         if not return_lengths:
             return tokens, logprobs, states
         lengths = controls.length.clone() if controls is not None else torch.full((B,), steps, dtype=torch.int32, device=dev)
         return tokens, logprobs, lengths, states
+
+
+def _generate_plain(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+                    eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+                    no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
+    """Model.generate (lm.py has the contract).  The truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff - are further
+    keyword-only arguments (_truncate.keywords)."""
+    return _generate(model, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length, repetition_penalty,
+                     logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty)
+
+
+generate = _truncate.keywords(_generate_plain, _generate)
 
 
 def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, _truncate
 from .functional import vmlmf_sequence
 
 
@@ -347,9 +347,9 @@ class Model(nn.Module):
             st = self._sample_state = dropout_state(dev, seed)
         return st
 
-    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-                 eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
-                 no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
+    def _generate_plain(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+                        eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+                        no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
@@ -393,11 +393,33 @@ class Model(nn.Module):
         65536 tokens (a row's ban set is a bitmap in the workgroup's LDS); the penalties do not.  ValueError, before any device work,
         for a negative n, a negative or non-finite penalty, an empty sequence or one with a token outside the vocabulary, more than
         4096 sequence tokens in all, and - with a ban on - for a vocabulary that might run out of open tokens: V must exceed the tokens
-        the other controls close + the prompt's length + steps + the number of sequences + 1."""
+        the other controls close + the prompt's length + steps + the number of sequences + 1.
+        Truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff: four further KEYWORD-ONLY arguments behind the ones above
+        (taken by _truncate.keywords around this function, so inspect.signature lists the parameters up to presence_penalty only) -
+        (all off by default: None, and min_p = 0, typical_p = 1.0, a cutoff of 0; with any of them on the choice
+        of every step is ONE launch of a library of its own behind the head's GEMM - vmlmf_truncate_choose,
+        include/vmlmf_truncate.h - which runs top_k and top_p too; without them this is the call above, launch for launch, and that
+        library is never opened).  They act on the tempered score z = c / tau - c the raw score, or the controlled score when eos,
+        repetition_penalty, logit_bias or banned_tokens are on -, in Hugging Face's order behind temperature, top_k and top_p, each on
+        the distribution renormalised over the survivors of the stages before it, each keeping at least its own first token, a token
+        at -inf never kept: min_p = a in (0, 1] keeps the tokens with p >= a p_max (every tie in); typical_p = m in (0, 1) orders
+        the survivors by |-log p - entropy|, smaller first, equal ones to the lower index, and keeps the shortest prefix whose mass
+        reaches m (locally typical sampling, Meister et al.; the band need not hold the most probable token); epsilon_cutoff keeps
+        the tokens with p >= epsilon, eta_cutoff those with p >= min(eta, sqrt(eta) exp(-entropy)) (Hewitt et al.), both always the
+        most probable survivor.  The draw is the argmax over the kept set on the noise of the untruncated call; logprobs stay the
+        unprocessed log-softmax; greedy decoding accepts them and is unchanged.  The choice is exact and repeats bit for bit.
+        ValueError, before any device work, for a value outside those ranges and for any of them together with the history controls
+        (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty): that composition is out of scope."""
         from . import decoding
         return decoding.generate(self, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length,
                                  repetition_penalty, logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences,
                                  frequency_penalty, presence_penalty)
+
+    def _generate_truncated(self, *args, **kw):
+        from . import decoding
+        return decoding.generate(self, *args, **kw)
+
+    generate = _truncate.keywords(_generate_plain, _generate_truncated)
 
     def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
                     no_repeat_ngram_size=0, banned_sequences=None):
