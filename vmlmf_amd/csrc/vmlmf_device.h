@@ -137,6 +137,58 @@ __device__ __forceinline__ float fast_tanh(float x) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.8853900817779268f * x));
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The LSTM cell's pointwise step, written once for the recurrent kernel families that call it: rec_fwd / rec_bwd, rec3, rec4,
+// wave, rbx and the forward of the step-wise path.  Two places keep their own text, and a change here does NOT reach them: the
+// row-block kernels of vmlmf_rb.inc (forward and backward: the same association spelled out) and gates_bwd_finish of
+// vmlmf_generic.hip (it associates differently).  The association of every product is part of the contract:
+// tests/test_gpu_inrow.py holds the headline layer's backward forms to the same bits.
+// ---------------------------------------------------------------------------------------------------
+struct CellFwd {
+  float4 gates;   // (i, f, o, g)
+  float c, h;
+};
+// forward: the gates from the four pre-activations, c_t from c_{t-1}, h_t
+__device__ __forceinline__ CellFwd cell_fwd(float pi, float pf, float po, float pg, float cprev) {
+  const float ig = fast_sigmoid(pi), fg = fast_sigmoid(pf), og = fast_sigmoid(po), ng = fast_tanh(pg);
+  const float c = fmaf(fg, cprev, ig * ng);
+  return CellFwd{make_float4(ig, fg, og, ng), c, og * fast_tanh(c)};
+}
+// backward, first half: everything of a step's gate derivatives that does not depend on dh_t - from the step's gates, c_t and
+// c_{t-1}.  The kernels with a dependent chain to shorten form these one half-step early (their prepare()).
+struct CellBwdFactors {
+  float A, F0, F1, F2, F3, fg;
+};
+__device__ __forceinline__ CellBwdFactors cell_bwd_factors(float4 gates, float c, float cprev) {
+  const float ig = gates.x, fg = gates.y, og = gates.z, ng = gates.w;
+  const float tc = fast_tanh(c);
+  CellBwdFactors f;
+  f.A = og * (1.f - tc * tc);
+  f.F0 = ng * ig * (1.f - ig);
+  f.F1 = cprev * fg * (1.f - fg);
+  f.F2 = tc * og * (1.f - og);
+  f.F3 = ig * (1.f - ng * ng);
+  f.fg = fg;
+  return f;
+}
+// backward, second half: dpre (i, f, o, g) of the step from dh_t; dcs: dL/dc carried from step t+1 in, to step t-1 out
+__device__ __forceinline__ float4 cell_bwd_step(const CellBwdFactors& f, float dh, float& dcs) {
+  const float dct = fmaf(dh, f.A, dcs);
+  const float4 dp = make_float4(dct * f.F0, dct * f.F1, dh * f.F2, dct * f.F3);
+  dcs = dct * f.fg;
+  return dp;
+}
+// dpre . (e0 .. e3): the diagonal part of dh_{t-1} (and rbx's x-side twin).  Two spellings, each family keeps its own:
+// explicit fused multiply-adds for rec3_bwd_kernel and rec4_bwd_kernel, which share one recurrence and must round it alike
+// whatever the compiler contracts in either (tests/test_gpu_inrow.py) ...
+__device__ __forceinline__ float cell_ehterm_fma(float4 dp, float e0, float e1, float e2, float e3) {
+  return fmaf(dp.x, e0, dp.y * e1) + fmaf(dp.z, e2, dp.w * e3);
+}
+// ... and the plain form, contracted as the compiler sees fit
+__device__ __forceinline__ float cell_ehterm(float4 dp, float e0, float e1, float e2, float e3) {
+  return (dp.x * e0 + dp.y * e1) + (dp.z * e2 + dp.w * e3);
+}
+
 // Select between two addresses WITHOUT letting the compiler turn it into two branch-guarded memory ops
 // (a memory op under a branch wrecks the counted s_waitcnt vmcnt(N) of the software-pipelined loops).
 // The pointer stays in the GLOBAL address space: a generic pointer would become flat_load/flat_store,

@@ -59,12 +59,9 @@ __device__ __forceinline__ FwdIn gates_fwd_load(const VGeo& g, const StepF& a, i
 __device__ __forceinline__ void gates_fwd_finish(const VGeo& g, const StepF& a, int b, int slot, const FwdIn& v, float4 p4) {
   const int t = a.t, NT = g.NT, H = g.H, n = v.n;
   const size_t so = (size_t)b * NT + slot;
-  const float ig = fast_sigmoid(v.gx4.x + p4.x + v.hp * v.e0);
-  const float fg = fast_sigmoid(v.gx4.y + p4.y + v.hp * v.e1);
-  const float og = fast_sigmoid(v.gx4.z + p4.z + v.hp * v.e2);
-  const float ng = fast_tanh(v.gx4.w + p4.w + v.hp * v.e3);
-  const float c = fmaf(fg, v.cp, ig * ng);
-  const float h = og * fast_tanh(c);
+  const CellFwd cell = cell_fwd(v.gx4.x + p4.x + v.hp * v.e0, v.gx4.y + p4.y + v.hp * v.e1, v.gx4.z + p4.z + v.hp * v.e2,
+                                v.gx4.w + p4.w + v.hp * v.e3, v.cp);
+  const float c = cell.c, h = cell.h;
   a.ccar[so] = c;
   if (v.valid) {
     a.y[(size_t)t * g.syT + (size_t)b * g.syB + n] = h;
@@ -75,7 +72,7 @@ __device__ __forceinline__ void gates_fwd_finish(const VGeo& g, const StepF& a, 
   }
   if (a.gates != nullptr) {
     const size_t sstride = (size_t)g.Bp * NT;
-    st4(a.gates + ((size_t)t * sstride + so) * 4, make_float4(ig, fg, og, ng));
+    st4(a.gates + ((size_t)t * sstride + so) * 4, cell.gates);
     if (t == 0) a.cs[so] = v.cp;
     a.cs[(size_t)(t + 1) * sstride + so] = c;
   }
@@ -118,6 +115,7 @@ __device__ __forceinline__ void gates_bwd_finish(const VGeo& g, const StepB& a, 
     dh += dhrec;
     if (a.dy != nullptr) dh += v.dy;
   }
+  // (the one site not on cell_bwd_factors / cell_bwd_step of vmlmf_device.h: its products associate differently - moving it changes its last bits)
   const float ig = v.g4.x, fg = v.g4.y, og = v.g4.z, ng = v.g4.w;
   const float tc = fast_tanh(v.ccur);
   const float dct = fmaf(dh * og, 1.f - tc * tc, v.dcar);
@@ -126,7 +124,7 @@ __device__ __forceinline__ void gates_bwd_finish(const VGeo& g, const StepB& a, 
   if (!valid) dp0 = dp1 = dp2 = dp3 = 0.f;
   a.dcar[so] = dct * fg;
   st4(a.dpre + ((size_t)t * sstride + so) * 4, make_float4(dp0, dp1, dp2, dp3));
-  a.ehterm[so] = (dp0 * eh.x + dp1 * eh.y) + (dp2 * eh.z + dp3 * eh.w);
+  a.ehterm[so] = cell_ehterm(make_float4(dp0, dp1, dp2, dp3), eh.x, eh.y, eh.z, eh.w);
 }
 
 __device__ __forceinline__ void gates_bwd_one(const VGeo& g, const StepB& a, int b, int slot, bool valid, int n,

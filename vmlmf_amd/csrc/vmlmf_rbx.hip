@@ -308,11 +308,9 @@ __global__ void __launch_bounds__(256) rbx_fwd_kernel(VGeo g, RbGeo q, RbxFwdArg
       }
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      const float ig = fast_sigmoid(acc[0][reg]), fg = fast_sigmoid(acc[1][reg]), og = fast_sigmoid(acc[2][reg]);
-      const float ng = fast_tanh(acc[3][reg]);
-      cst[reg] = fmaf(fg, cst[reg], ig * ng);
-      h[reg] = og * fast_tanh(cst[reg]);
-      pg[0][reg] = ig, pg[1][reg] = fg, pg[2][reg] = og, pg[3][reg] = ng;
+      const CellFwd cell = cell_fwd(acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg], cst[reg]);
+      cst[reg] = cell.c, h[reg] = cell.h;
+      pg[0][reg] = cell.gates.x, pg[1][reg] = cell.gates.y, pg[2][reg] = cell.gates.z, pg[3][reg] = cell.gates.w;
     }
   }
   store_tape(T - 1);
@@ -498,17 +496,14 @@ __global__ void __launch_bounds__(256) rbx_bwd_kernel(VGeo g, RbGeo q, RbxBwdArg
     f32x4v dp[4], ehterm, exterm;
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
-      const float ig = gt[reg][0], fg = gt[reg][1], og = gt[reg][2], ng = gt[reg][3];
-      const float tc = fast_tanh(ccur[reg]);
       const float dh = (rok ? dyv[reg] : 0.f) + dhrec[reg];
-      const float dct = fmaf(dh, og * (1.f - tc * tc), dcs[reg]);
-      dp[0][reg] = dct * (ng * ig * (1.f - ig));
-      dp[1][reg] = dct * (cp[reg] * fg * (1.f - fg));
-      dp[2][reg] = dh * (tc * og * (1.f - og));
-      dp[3][reg] = dct * (ig * (1.f - ng * ng));
-      dcs[reg] = dct * fg;
-      ehterm[reg] = (dp[0][reg] * eh[0][reg] + dp[1][reg] * eh[1][reg]) + (dp[2][reg] * eh[2][reg] + dp[3][reg] * eh[3][reg]);
-      exterm[reg] = (dp[0][reg] * exr[0][reg] + dp[1][reg] * exr[1][reg]) + (dp[2][reg] * exr[2][reg] + dp[3][reg] * exr[3][reg]);
+      const CellBwdFactors f = cell_bwd_factors(make_float4(gt[reg][0], gt[reg][1], gt[reg][2], gt[reg][3]), ccur[reg], cp[reg]);
+      float dc = dcs[reg];
+      const float4 d = cell_bwd_step(f, dh, dc);
+      dcs[reg] = dc;
+      dp[0][reg] = d.x, dp[1][reg] = d.y, dp[2][reg] = d.z, dp[3][reg] = d.w;
+      ehterm[reg] = cell_ehterm(d, eh[0][reg], eh[1][reg], eh[2][reg], eh[3][reg]);
+      exterm[reg] = cell_ehterm(d, exr[0][reg], exr[1][reg], exr[2][reg], exr[3][reg]);
     }
     ccur = cp;
     f32x4v qa[NJ][NP], qxa[NPX];

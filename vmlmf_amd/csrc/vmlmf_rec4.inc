@@ -313,16 +313,10 @@ __global__ void __launch_bounds__(512) rec4_bwd_kernel(VGeo g, BwdArgs a) {
     cprvn = tcp[lo];
     dyvn = tdy[lo];
   };
-  float fA, fF0, fF1, fF2, fF3, ffg, fdy;
+  CellBwdFactors fac;
+  float fdy;
   auto prepare = [&]() {   // the factors of a step's gate derivatives that do not depend on dh
-    const float ig = g4n.x, fg = g4n.y, og = g4n.z, ng = g4n.w;
-    const float tc = fast_tanh(ccur);
-    fA = og * (1.f - tc * tc);
-    fF0 = ng * ig * (1.f - ig);
-    fF1 = cprvn * fg * (1.f - fg);
-    fF2 = tc * og * (1.f - og);
-    fF3 = ig * (1.f - ng * ng);
-    ffg = fg;
+    fac = cell_bwd_factors(g4n, ccur, cprvn);
     fdy = (valid && has_dy) ? dyvn : 0.f;
     ccur = cprvn;
   };
@@ -332,23 +326,18 @@ __global__ void __launch_bounds__(512) rec4_bwd_kernel(VGeo g, BwdArgs a) {
   for (int t = T - 1; t >= 0; --t) {
     const int buf = t & (R4_NO - 1);
     fetch_tape(t - 1);
-    const float dh = fdy + dhrec;
-    const float dct = fmaf(dh, fA, dcs);
-    const float dp0 = dct * fF0, dp1 = dct * fF1, dp2 = dh * fF2, dp3 = dct * fF3;
-    dcs = dct * ffg;
-    st4(outs + (size_t)buf * NT * 4 + (size_t)utid * 4, make_float4(dp0, dp1, dp2, dp3));
-    // (explicit fused multiply-adds: left to the compiler's contraction the two kernels that share this recurrence could round it
-    //  differently - tests/test_gpu_inrow.py holds them to the same bits)
-    const float ehterm = fmaf(dp0, eh[0], dp1 * eh[1]) + fmaf(dp2, eh[2], dp3 * eh[3]);
+    const float4 dp = cell_bwd_step(fac, fdy + dhrec, dcs);
+    st4(outs + (size_t)buf * NT * 4 + (size_t)utid * 4, dp);
+    const float ehterm = cell_ehterm_fma(dp, eh[0], eh[1], eh[2], eh[3]);   // (explicit fused multiply-adds: see there)
     f32x2 z2[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) z2[j] = splat2(dp0) * vz[0][j];
+    for (int j = 0; j < 8; ++j) z2[j] = splat2(dp.x) * vz[0][j];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp1), vz[1][j], z2[j]);
+    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp.y), vz[1][j], z2[j]);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp2), vz[2][j], z2[j]);
+    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp.z), vz[2][j], z2[j]);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp3), vz[3][j], z2[j]);
+    for (int j = 0; j < 8; ++j) z2[j] = pk_fma(splat2(dp.w), vz[3][j], z2[j]);
     float z[16];
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[2 * j] = z2[j].x, z[2 * j + 1] = z2[j].y;

@@ -368,18 +368,12 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_bwd_kernel(VGeo g, BwdArgs 
       dyvn[r] = tdy[lo];
     }
   };
-  float fA[R], fF0[R], fF1[R], fF2[R], fF3[R], ffg[R], fdy[R];
+  CellBwdFactors fac[R];
+  float fdy[R];
   auto prepare = [&]() {   // from the fetched tape and c of the step (ccur): the dh-independent factors
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const float ig = g4n[r].x, fg = g4n[r].y, og = g4n[r].z, ng = g4n[r].w;
-      const float tc = fast_tanh(ccur[r]);
-      fA[r] = og * (1.f - tc * tc);
-      fF0[r] = ng * ig * (1.f - ig);
-      fF1[r] = cprvn[r] * fg * (1.f - fg);
-      fF2[r] = tc * og * (1.f - og);
-      fF3[r] = ig * (1.f - ng * ng);
-      ffg[r] = fg;
+      fac[r] = cell_bwd_factors(g4n[r], ccur[r], cprvn[r]);
       fdy[r] = (ok[r] && has_dy) ? dyvn[r] : 0.f;
       ccur[r] = cprvn[r];   // c of the step before
     }
@@ -393,15 +387,10 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_bwd_kernel(VGeo g, BwdArgs 
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const float dh = fdy[r] + dhrec[r];
-      const float dct = fmaf(dh, fA[r], dcs[r]);
-      float dp[4];
-      dp[0] = dct * fF0[r];
-      dp[1] = dct * fF1[r];
-      dp[2] = dh * fF2[r];
-      dp[3] = dct * fF3[r];
-      dcs[r] = dct * ffg[r];
-      st4(ot + ((size_t)r * NT + tid) * 4, make_float4(dp[0], dp[1], dp[2], dp[3]));
-      ehterm[r] = (dp[0] * eh[0] + dp[1] * eh[1]) + (dp[2] * eh[2] + dp[3] * eh[3]);
+      const float4 d = cell_bwd_step(fac[r], dh, dcs[r]);
+      float dp[4] = {d.x, d.y, d.z, d.w};
+      st4(ot + ((size_t)r * NT + tid) * 4, d);
+      ehterm[r] = cell_ehterm(d, eh[0], eh[1], eh[2], eh[3]);
       // rank-space reduce of dpre
       asm volatile("s_nop 1" : "+v"(dp[0]), "+v"(dp[1]), "+v"(dp[2]), "+v"(dp[3]));   // one DPP fence for the four
 #pragma unroll

@@ -724,10 +724,9 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
         p23b = pk_fma(splat2(qb.w), ve23[4 * cc + 3], p23b);
       }
       const f32x2 pre01 = p01a + p01b, pre23 = p23a + p23b;
-      const float ig = fast_sigmoid(pre01.x), fg = fast_sigmoid(pre01.y), og = fast_sigmoid(pre23.x), ng = fast_tanh(pre23.y);
-      c[r] = fmaf(fg, c[r], ig * ng);
-      h[r] = og * fast_tanh(c[r]);
-      st4(ot + ((size_t)r * NT + tid) * 4, make_float4(ig, fg, og, ng));
+      const CellFwd cell = cell_fwd(pre01.x, pre01.y, pre23.x, pre23.y, c[r]);
+      c[r] = cell.c, h[r] = cell.h;
+      st4(ot + ((size_t)r * NT + tid) * 4, cell.gates);
       *reinterpret_cast<float2*>(ot + (size_t)R * NT * 4 + ((size_t)r * NT + tid) * 2) = make_float2(c[r], h[r]);
     }
   }

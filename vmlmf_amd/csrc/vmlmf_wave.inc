@@ -502,11 +502,10 @@ __global__ void __launch_bounds__(2 * MAXT + 128) wf_fwd_kernel(VGeo g, WfFwdArg
       p23b = pk_fma(splat2(qw), ve23[4 * cc + 3], p23b);
     }
     const f32x2 pre01 = p01a + p01b, pre23 = p23a + p23b;
-    const float ig = fast_sigmoid(pre01.x), fg = fast_sigmoid(pre01.y), og = fast_sigmoid(pre23.x), ng = fast_tanh(pre23.y);
-    c = fmaf(fg, c, ig * ng);
-    h = og * fast_tanh(c);
+    const CellFwd cell = cell_fwd(pre01.x, pre01.y, pre23.x, pre23.y, c);
+    c = cell.c, h = cell.h;
     float* ot = outs + (size_t)buf * NT * 8;
-    st4(ot + (size_t)tid * 4, make_float4(ig, fg, og, ng));
+    st4(ot + (size_t)tid * 4, cell.gates);
     *reinterpret_cast<float2*>(ot + (size_t)NT * 4 + (size_t)tid * 2) = make_float2(c, h);
   }
   wf_barrier();   // b(T): last out-stage published
@@ -911,16 +910,10 @@ __global__ void __launch_bounds__(2 * MAXT + 128) wf_bwd_kernel(VGeo g, WfBwdArg
     dyvn = tdy[lo];
     if constexpr (G == 1) dyvn *= tfac[lo];
   };
-  float fA, fF0, fF1, fF2, fF3, ffg, fdy;
+  CellBwdFactors fac;
+  float fdy;
   auto prepare = [&]() {   // the dh-independent factors of the step whose tape was fetched (see rec_bwd_kernel)
-    const float ig = g4n.x, fg = g4n.y, og = g4n.z, ng = g4n.w;
-    const float tc = fast_tanh(ccur);
-    fA = og * (1.f - tc * tc);
-    fF0 = ng * ig * (1.f - ig);
-    fF1 = cprvn * fg * (1.f - fg);
-    fF2 = tc * og * (1.f - og);
-    fF3 = ig * (1.f - ng * ng);
-    ffg = fg;
+    fac = cell_bwd_factors(g4n, ccur, cprvn);
     fdy = (ok && has_dy) ? dyvn : 0.f;
     ccur = cprvn;
   };
@@ -929,15 +922,10 @@ __global__ void __launch_bounds__(2 * MAXT + 128) wf_bwd_kernel(VGeo g, WfBwdArg
   for (int t = T - 1; t >= 0; --t) {
     const int buf = t & 1;
     const float dh = fdy + dhrec;
-    const float dct = fmaf(dh, fA, dcs);
-    float dp[4];
-    dp[0] = dct * fF0;
-    dp[1] = dct * fF1;
-    dp[2] = dh * fF2;
-    dp[3] = dct * fF3;
-    dcs = dct * ffg;
-    st4(outs + ((size_t)buf * NT + tid) * 4, make_float4(dp[0], dp[1], dp[2], dp[3]));
-    const float ehterm = (dp[0] * eh[0] + dp[1] * eh[1]) + (dp[2] * eh[2] + dp[3] * eh[3]);
+    const float4 d = cell_bwd_step(fac, dh, dcs);
+    float dp[4] = {d.x, d.y, d.z, d.w};
+    st4(outs + ((size_t)buf * NT + tid) * 4, d);
+    const float ehterm = cell_ehterm(d, eh[0], eh[1], eh[2], eh[3]);
     wf_reduce4<K>(dp, vr, part + (buf * NW + wave) * KQ, lane);
     wf_barrier();   // b(t)
     fetch_tape(t - 1);   // landed since the previous barrier (t = 0: reads a valid, unused ring slot)
