@@ -72,7 +72,8 @@ def new_step_buffers(dev, B, W, V):
     return torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
 
 
-def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None, controls=None, hist=None, hist_len=None):
+def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None, controls=None, hist=None, hist_len=None,
+                 beam_state=None):
     """One step of beam search over B batch rows of W beams (cum is (B, W)): the head's GEMM over the beams' top-layer outputs h (B W, H)
     - row b W + w is beam w of batch row b -, then ONE launch (vmlmf_beam_step, csrc/vmlmf_beam.hip) that forms every candidate's total
     cum[b, w] + log_softmax(h fc.w^T + bias)[v] in fp32, keeps the W best of each batch row under the total order (larger total first,
@@ -86,7 +87,10 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     ONE launch of vmlmf_beamctl_step (csrc/vmlmf_beamctl.hip, a library of its own) in which a live beam withholds what the controls
     close, behind ONE vmlmf_history_bans launch on the beams' histories hist (B W, capacity) / hist_len (B W) when an n-gram or a
     sequence control is on; the totals of what is offered are the plain step's to the bit.  Two more results follow the seven: the
-    survivors' (hist, hist_len), fresh buffers - (None, None) when the controls keep no history."""
+    survivors' (hist, hist_len), fresh buffers - (None, None) when the controls keep no history.
+    controls: an AutomatonBeamControls (_automaton.py: a TokenAutomaton, min_length, banned_tokens) - the selection is ONE launch of
+    vmlmf_automaton_beam_step (csrc/vmlmf_automaton.hip) on beam_state (B W) int32, the beams' states (default: controls.start()); one
+    more result follows the seven: the survivors' states, a fresh buffer."""
     for t, what in ((h, "h"), (weight, "weight"), (cum, "cum")):
         _require(t, what)
     if bias is not None:
@@ -116,7 +120,9 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     args = (torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
             length.contiguous(), eos_c, None if embed is None else embed.contiguous())
     if controls is not None:
-        from . import _beamctl
+        from . import _automaton, _beamctl
+        if isinstance(controls, _automaton.AutomatonBeamControls):
+            return _automaton.automaton_select(*args, controls, beam_state, buffers)
         return _beamctl.beamctl_select(*args, controls, hist, hist_len, buffers)
     return beam_select(*args, buffers)
 

@@ -94,19 +94,24 @@ def truncation(min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
 KEYWORDS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
 
 
-def keywords(plain, truncated, name="generate"):
-    """`plain` - a generate() as it stood before the truncation samplers - taking the four samplers as further KEYWORD-ONLY arguments:
-    with none of them given the call is `plain` itself; otherwise `truncated(*args, **kw, min_p=..., typical_p=..., epsilon_cutoff=...,
-    eta_cutoff=...)`.  The result carries plain's docstring and, for inspect.signature, plain's parameters: the four keywords come behind
-    them (tests/test_history_controls_cpu.py holds generate's parameter list to what it was)."""
+def further_keywords(plain, extended, names, name):
+    """`plain` - a method as its signature is pinned - taking `names` as further KEYWORD-ONLY arguments, all None by default: with none
+    of them given the call is `plain` itself; otherwise `extended(*args, **kw)` with those that were.  The result carries plain's
+    docstring and, for inspect.signature, plain's parameters: the further keywords come behind them (tests/test_history_controls_cpu.py
+    and tests/test_beam_controls_cpu.py hold generate's and beam_search's parameter lists to what they were)."""
     @functools.wraps(plain)
-    def call(*args, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **kw):
-        if min_p is None and typical_p is None and epsilon_cutoff is None and eta_cutoff is None:
-            return plain(*args, **kw)
-        return truncated(*args, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **kw)
+    def call(*args, **kw):
+        if all(kw.get(k) is None for k in names):
+            return plain(*args, **{k: v for k, v in kw.items() if k not in names})
+        return extended(*args, **kw)
     call.__name__ = name
     call.__qualname__ = plain.__qualname__.rsplit(".", 1)[0] + "." + name if "." in plain.__qualname__ else name
     return call
+
+
+def keywords(plain, truncated, name="generate"):
+    """further_keywords for the four truncation samplers: min_p, typical_p, epsilon_cutoff, eta_cutoff."""
+    return further_keywords(plain, truncated, KEYWORDS, name)
 
 
 def truncate_choose(scores, bias, embed, inv, top_k, top_p, trunc, state, step, controls, tokens, logp, xn, kept):

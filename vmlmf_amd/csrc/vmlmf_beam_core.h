@@ -1,5 +1,6 @@
 // The beam step's selection, written once for libvmlmf_beam.so (vmlmf_beam.hip: every candidate is offered) and libvmlmf_beamctl.so
-// (vmlmf_beamctl.hip: closed tokens, per-beam ban sets, a minimum length, the beams' histories): the candidate key, the workgroup
+// (vmlmf_beamctl.hip: closed tokens, per-beam ban sets, a minimum length, the beams' histories) and libvmlmf_automaton.so
+// (vmlmf_automaton.hip: closed tokens, a minimum length, a token automaton's state per beam): the candidate key, the workgroup
 // maximum, the scratch, the step's kernel - templated on an OFFER POLICY, decided with `if constexpr`, so the plain instantiation is the
 // code it was before the policy existed - and the host's refusals of sizes and pointers.
 // A policy P has  static constexpr bool controlled;  and, where controlled,
@@ -7,6 +8,8 @@
 //                                it loads (the beam's length) is not waited for between the passes
 //   bool keeps_history()         uniform over the launch
 //   hist / hist_len / hist_out / hist_len_out / overflow / cap    the histories the last workgroup of a batch row copies
+// (a policy without keeps_history() keeps none), and, where it moves a state of its own on with the survivors,
+//   survivor(slot, parent's row, parent finished, token, has a candidate)    called by the thread that writes the slot's outputs
 // Selection: a workgroup per BEAM, a ticket per batch row.  A survivor of the row is among its own beam's first W candidates, so each
 // workgroup forms those (W rounds of a workgroup-wide argmax over the threads' own best candidates; after a round only the thread
 // that held the winner looks for its next one, strictly after the winner in the order - the winners wait in LDS, a global store per
@@ -27,6 +30,7 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
 
 #include "../../include/vmlmf_beam.h"
 
@@ -55,6 +59,16 @@ struct OfferAll {
   struct Row {};
   __device__ __forceinline__ Row row(int) const { return Row{}; }
 };
+
+// what a policy declares beyond `controlled`, found at compile time: the plain and the controlled policy are asked nothing new
+template <class P, class = void>
+struct keeps_histories : std::false_type {};
+template <class P>
+struct keeps_histories<P, std::void_t<decltype(&P::keeps_history)>> : std::true_type {};
+template <class P, class = void>
+struct moves_states : std::false_type {};
+template <class P>
+struct moves_states<P, std::void_t<decltype(&P::survivor)>> : std::true_type {};
 
 typedef unsigned long long u64;
 // A candidate as ONE 64-bit key whose unsigned order is the order of the search: the order-preserving image of the total in the high
@@ -267,7 +281,8 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(BeamStepArgs a, P p) {
     a.finished_out[slot] = (pdone || (a.eos >= 0 && tok == a.eos)) ? 1 : 0;
     a.length_out[slot] = a.length[prow] + (pdone ? 0 : 1);
     a.src_row[slot] = prow;
-    if constexpr (P::controlled) {
+    if constexpr (moves_states<P>::value) p.survivor(slot, prow, pdone, tok, ok);
+    if constexpr (keeps_histories<P>::value) {
       // the survivor's history: where it comes from and how long it is, left in LDS (the totals' room, free since the rounds) for the
       // copy below; the token behind it and the lengths are this thread's own stores
       if (p.keeps_history()) {
@@ -305,7 +320,7 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(BeamStepArgs a, P p) {
         if (e0 + BS_NT * j < n) xo[e0 + BS_NT * j] = x[j];
     }
   }
-  if constexpr (P::controlled) {
+  if constexpr (keeps_histories<P>::value) {
     if (p.keeps_history()) {   // (uniform)
       __syncthreads();
       const int* meta = reinterpret_cast<const int*>(S.vals);

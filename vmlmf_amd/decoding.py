@@ -14,7 +14,8 @@ import contextlib
 
 import torch
 
-from . import _beam, _beamctl, _decode, _history, _lib, _truncate
+from . import _automaton, _beam, _beamctl, _decode, _history, _lib, _truncate
+from ._automaton import AutomatonBeamControls, AutomatonControls, TokenAutomaton  # noqa: F401
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._beamctl import BeamControls
 from ._decode import DecodeControls
@@ -79,7 +80,10 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     "gemm" only), which runs top_k and top_p too and, under a DecodeControls, chooses on the controlled scores and moves their state on
     as vmlmf_decode_choose does; the noise and the log-probabilities stay those of the plain call, kept counts the survivors.  Greedy
     decoding ignores it, and None or a Truncation with nothing on is the call above, launch for launch.  ValueError with form="fused"
-    and with a HistoryControls."""
+    and with a HistoryControls.
+    An AutomatonControls (a DecodeControls, a TokenAutomaton and the rows' row_state / dead) goes to ONE launch of
+    vmlmf_automaton_choose (include/vmlmf_automaton.h has the contract): a row's state closes the tokens its table row does not offer
+    and moves on with the chosen token.  ValueError together with a truncation that is on."""
     for t, what in ((h, "h"), (weight, "weight")):
         _require_hip(t, what)
     if bias is not None:
@@ -107,6 +111,8 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
         raise ValueError(f"vmlmf_amd.lm_sample: the truncation samplers have no fused-head form (form must be 'gemm' or None, got {form!r})")
     if truncated and isinstance(controls, HistoryControls):
         raise ValueError(_truncate.HISTORY_REFUSAL)
+    if truncated and isinstance(controls, AutomatonControls):
+        raise ValueError(_automaton.GENERATE_REFUSAL.format(what="min_p / typical_p / epsilon_cutoff / eta_cutoff"))
     truncated = truncated and inv > 0.0
     dev = h2.device
     lib = _lib.lib()
@@ -192,37 +198,36 @@ def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=N
     return torch.stack(toks), torch.stack(lps), h, states
 
 
-def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None, controls=None, hist=None, hist_len=None):
+def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None, controls=None, hist=None, hist_len=None, beam_state=None):
     """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
     (lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
     2 L state tensors follow their hypotheses (beam_gather), then the layers at T = 1 on the B W rows.  No host
     synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length).
     controls: a BeamControls - the selection is then the controlled launch (vmlmf_beamctl_step) and, where the controls keep a history,
     the vmlmf_history_bans launch in front of it on hist / hist_len, the beams' histories (default: controls.history(), a search that
-    starts); the survivors' (hist, hist_len) then follow the seven results."""
+    starts); the survivors' (hist, hist_len) then follow the seven results.  An AutomatonBeamControls: the selection is
+    vmlmf_automaton_beam_step on beam_state (B W) int32, the beams' states (default: controls.start()); the survivors' states follow the
+    seven results."""
     parents, toks = [], []
-    if controls is None:
-        select = lambda: lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w, buffers=buffers) + (None, None)
-    else:
-        if controls.keeps_history and hist is None:
-            hist, hist_len = controls.history()
-        select = lambda: lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w, buffers=buffers,
-                                      controls=controls, hist=hist, hist_len=hist_len)
+    # what the controls carry from step to step behind cum, finished and length (lm_beam_step takes it by these names)
+    names = _beam_extras(controls)
+    extra = _beam_start(controls, hist, hist_len, beam_state)
     for _ in range(steps):
-        par, tok, cum, finished, length, x, src, hist, hist_len = select()
+        par, tok, cum, finished, length, x, src, *rest = lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w,
+                                                                      buffers=buffers, controls=controls, **dict(zip(names, extra)))
+        extra = rest[:len(names)]
         parents.append(par)
         toks.append(tok)
         flat = beam_gather([t for st in states for t in st], src)
         states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
         y, states = decode_layers(model, x.unsqueeze(0), states, "layers")
         h = y[-1]
-    out = (torch.stack(parents), torch.stack(toks), h, states, cum, finished, length)
-    return out if controls is None or not controls.keeps_history else out + (hist, hist_len)
+    return (torch.stack(parents), torch.stack(toks), h, states, cum, finished, length, *extra)
 
 
 # What a decode carries from step to step, as one flat list: [h, h_0, c_0, ... h_L-1, c_L-1] and, for beams, cum, finished and length
-# behind them - and behind those, under BeamControls that keep a history, the beams' hist and hist_len.  The two forms below are the
-# step loops above on such a list: carried -> (outputs, carried after the steps).
+# behind them - and behind those, under BeamControls that keep a history, the beams' hist and hist_len; under AutomatonBeamControls, the
+# beams' states.  The two forms below are the step loops above on such a list: carried -> (outputs, carried after the steps).
 def _pairs(flat):
     return [(flat[i], flat[i + 1]) for i in range(0, len(flat), 2)]
 
@@ -239,8 +244,23 @@ def _join_beams(h, states, cum, finished, length, history):
     return [h, *(t for st in states for t in st), cum, finished, length, *history]
 
 
-def _split_beams(carried, controls):        # _join_beams' arguments back; history is [hist, hist_len] where the controls keep one
-    history = list(carried[-2:]) if controls is not None and controls.keeps_history else []
+def _beam_extras(controls):                 # the names of what the controls carry behind cum, finished and length (beam_steps' keywords)
+    if isinstance(controls, AutomatonBeamControls):
+        return ("beam_state",)
+    return ("hist", "hist_len") if controls is not None and controls.keeps_history else ()
+
+
+def _beam_start(controls, hist=None, hist_len=None, beam_state=None):      # those tensors: the given ones, or a search that starts
+    if isinstance(controls, AutomatonBeamControls):
+        return [controls.start() if beam_state is None else beam_state]
+    if controls is not None and controls.keeps_history:
+        return list(controls.history()) if hist is None else [hist, hist_len]
+    return []
+
+
+def _split_beams(carried, controls):        # _join_beams' arguments back; history: [hist, hist_len] / [beam_state] where the controls carry them
+    n = len(_beam_extras(controls))
+    history = list(carried[-n:]) if n else []
     h, *flat, cum, finished, length = carried[:len(carried) - len(history)]
     return h, _pairs(flat), cum, finished, length, history
 
@@ -248,7 +268,7 @@ def _split_beams(carried, controls):        # _join_beams' arguments back; histo
 def _beamed(model, carried, steps, eos, buffers=None, controls=None):
     h, states, cum, finished, length, history = _split_beams(carried, controls)
     par, tok, h, states, cum, finished, length, *history = beam_steps(model, h, states, cum, finished, length, steps, eos, buffers, controls,
-                                                                      *history)
+                                                                      **dict(zip(_beam_extras(controls), history)))
     return (par, tok), _join_beams(h, states, cum, finished, length, history)
 
 
@@ -332,7 +352,8 @@ class DecodeGraph(_StepGraph):
     top_k / top_p: the filters of Model.generate, fixed at construction.
     controls: a DecodeControls (eos, bans, repetition penalty ...).  The captured launches read and write ITS buffers - seen, finished,
     length, and a HistoryControls' hist, hist_len, count, overflow -, so replays continue one decode: finished rows stay finished, seen
-    and the history accumulate (the warm-up runs on a clone of all of them).
+    and the history accumulate (the warm-up runs on a clone of all of them).  An AutomatonControls' row_state and dead are among them:
+    a replay continues the rows' walk through the automaton.
     min_p, typical_p, epsilon_cutoff, eta_cutoff: the truncation samplers of Model.generate, fixed at construction."""
 
     def __init__(self, model, h, states, steps, temperature=1.0, layer_path="layers", top_k=None, top_p=None, controls=None, min_p=None,
@@ -367,24 +388,24 @@ class BeamGraph(_StepGraph):
     the parameters change.
     controls: a BeamControls (min_length, token, n-gram and sequence bans).  Where they keep a history, hist / hist_len (default:
     controls.history()) are carried with cum, finished and length - in this object's buffers, so a replay continues the hypotheses of
-    the last one; the captured launches set the controls' own `overflow` (the warm-up runs on a clone)."""
+    the last one; the captured launches set the controls' own `overflow` (the warm-up runs on a clone).  An AutomatonBeamControls:
+    beam_state (default: controls.start()) is carried in the same way - a replay continues the states of the last one."""
 
     def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None, controls=None, hist=None,
-                 hist_len=None):
+                 hist_len=None, beam_state=None):
         self.model, self.steps, self.eos, self.controls = model, int(steps), eos, controls
         W = _beam.check_beams(beams, model.vocab_size)
         B = h.shape[0] // W
         fresh = _fresh_beams(B, W, h.device)
         cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), fresh))
         self.buffers = _beam.new_step_buffers(h.device, B, W, model.vocab_size)
-        history = []
-        if controls is not None and controls.keeps_history:
-            history = list(controls.history()) if hist is None else [hist, hist_len]
+        history = _beam_start(controls, hist, hist_len, beam_state)
         step = lambda carried, controls=controls: _beamed(model, carried, self.steps, eos, self.buffers, controls)
         self._capture(model, _join_beams(h, states, cum, finished.to(torch.int32), length.to(torch.int32), history), step,
                       None if controls is None else lambda carried: step(carried, controls.clone()))
         self.h, self.states, self.cum, self.finished, self.length, history = _split_beams(self.carried, controls)
-        self.hist, self.hist_len = history or (None, None)
+        self.hist, self.hist_len = history if len(history) == 2 else (None, None)
+        self.beam_state = history[0] if len(history) == 1 else None
         self.parents, self.tokens = self.outputs
 
 
@@ -440,20 +461,31 @@ def _run(steps, chunk, eager, graph):
 def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
               eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
               no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0, min_p=None, typical_p=None,
-              epsilon_cutoff=None, eta_cutoff=None):
+              epsilon_cutoff=None, eta_cutoff=None, automaton=None, automaton_state=None):
     """Model.generate with every argument (lm.py has the contract)."""
     sample_filters(top_k, top_p)
     trunc_args = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
     hist_args = dict(no_repeat_ngram_size=no_repeat_ngram_size, banned_sequences=banned_sequences, frequency_penalty=frequency_penalty,
                      presence_penalty=presence_penalty)
     history = _history.history_on(**hist_args)
-    _truncate.truncation(**trunc_args, history=history)
+    trunc = _truncate.truncation(**trunc_args, history=history)
+    if automaton is None and automaton_state is not None:
+        raise ValueError("vmlmf_amd: automaton_state needs automaton")
+    if automaton is not None and history:
+        raise ValueError(_automaton.GENERATE_REFUSAL.format(
+            what="the history controls (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty)"))
+    if automaton is not None and trunc is not None:
+        raise ValueError(_automaton.GENERATE_REFUSAL.format(what="the truncation samplers (min_p, typical_p, epsilon_cutoff, eta_cutoff)"))
     ctl_args = dict(eos=eos, min_length=min_length, repetition_penalty=repetition_penalty, logit_bias=logit_bias,
                     banned_tokens=banned_tokens)
     eos_c, min_c, _, banned = _decode.check_controls(model.vocab_size, **ctl_args)
     controlled = _decode.controls_on(eos, repetition_penalty, logit_bias, banned_tokens)
-    if controlled or history:
+    if controlled or history or automaton is not None:
         closed = _decode.check_bias(model.vocab_size, logit_bias, banned, eos_c, min_c)
+    if automaton is not None:
+        rows = prompt.shape[1] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
+        start = _automaton.check_automaton(automaton, model.vocab_size, rows, automaton_state)
+        automaton.check_reachable(start, _automaton.closed_tokens(model.vocab_size, logit_bias, banned), eos_c, min_c)
     if history:
         T0 = prompt.shape[0] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
         _history.check_history(model.vocab_size, prompt_length=T0, steps=int(steps), closed=closed, **hist_args)
@@ -463,7 +495,9 @@ def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chu
     B, dev = prompt.shape[1], prompt.device
     gen = model.sampler_state(seed) if temperature > 0 else None
     with _session(model, prompt, states) as (h, states):
-        if history:     # capacity: the prompt and every step - the history never overflows
+        if automaton is not None:
+            controls = AutomatonControls(B, model.vocab_size, dev, automaton, automaton_state, prompt=prompt, _checked=True, **ctl_args)
+        elif history:   # capacity: the prompt and every step - the history never overflows
             controls = HistoryControls(B, model.vocab_size, dev, capacity=max(prompt.shape[0] + steps, 1), prompt=prompt, _checked=True,
                                        **hist_args, **ctl_args)
         else:
@@ -486,18 +520,18 @@ def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chu
 def _generate_plain(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
                     eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
                     no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
-    """Model.generate (lm.py has the contract).  The truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff - are further
-    keyword-only arguments (_truncate.keywords)."""
+    """Model.generate (lm.py has the contract).  The truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff - and automaton,
+    automaton_state are further keyword-only arguments (_truncate.further_keywords)."""
     return _generate(model, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length, repetition_penalty,
                      logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty)
 
 
-generate = _truncate.keywords(_generate_plain, _generate)
+generate = _truncate.further_keywords(_generate_plain, _generate, _truncate.KEYWORDS + _automaton.KEYWORDS, "generate")
 
 
-def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
-                no_repeat_ngram_size=0, banned_sequences=None):
-    """Model.beam_search (lm.py has the contract)."""
+def _beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                 no_repeat_ngram_size=0, banned_sequences=None, automaton=None, automaton_state=None):
+    """Model.beam_search with every argument (lm.py has the contract)."""
     W = _beam.check_beams(beams, model.vocab_size)
     steps, alpha = int(steps), float(length_penalty)
     if eos is not None and not 0 <= int(eos) < model.vocab_size:
@@ -510,6 +544,16 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
                     banned_sequences=banned_sequences)
     controlled = _beamctl.controls_on(min_length, banned_tokens, no_repeat_ngram_size, banned_sequences)
     T0 = prompt.shape[0] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
+    if automaton is None and automaton_state is not None:
+        raise ValueError("vmlmf_amd: automaton_state needs automaton")
+    if automaton is not None:
+        if no_repeat_ngram_size != 0 or banned_sequences is not None:
+            raise ValueError(_automaton.BEAM_REFUSAL.format(what="no_repeat_ngram_size / banned_sequences"))
+        controlled = False
+        eos_c, min_c, banned, _, _ = _beamctl.check_beam_controls(model.vocab_size, 1, eos, min_length, banned_tokens)
+        rows = prompt.shape[1] if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 else 0
+        start = _automaton.check_automaton(automaton, model.vocab_size, rows, automaton_state)
+        automaton.check_reachable(start, _automaton.closed_tokens(model.vocab_size, None, banned), eos_c, min_c)
     if controlled:      # (without them nothing of the controls is looked at: the call is what it was)
         _beamctl.check_beam_controls(model.vocab_size, W, prompt_length=T0, steps=steps, **ctl_args)
     _check_chunk("beam_search", chunk, steps)
@@ -518,7 +562,10 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
     with _session(model, prompt, states) as (h, states):
         # capacity: the prompt and every step - the history never overflows
         controls = BeamControls(B, W, model.vocab_size, dev, prompt=prompt, capacity=max(T0 + steps, 1), **ctl_args) if controlled else None
-        history = [] if controls is None or not controls.keeps_history else list(controls.history())
+        if automaton is not None:
+            controls = AutomatonBeamControls(B, W, model.vocab_size, dev, automaton, automaton_state, eos=eos, min_length=min_length,
+                                             banned_tokens=banned_tokens, _checked=True)
+        history = _beam_start(controls)
         h = h.repeat_interleave(W, 0)
         states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
         cum, finished, length = _fresh_beams(B, W, dev)
@@ -527,7 +574,8 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
         (parents, toks), carried = _run(
             steps, chunk,
             lambda: _beamed(model, _join_beams(h, states, cum, finished, length, history), steps, eos, None, controls),
-            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls, *history))
+            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls,
+                              **dict(zip(_beam_extras(controls), history))))
         _, states, cum, finished, length, _ = _split_beams(carried, controls)
         order = None
         if alpha > 0.0:
@@ -538,3 +586,14 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
             states = _pairs(beam_gather([t for st in states for t in st], rows))
             order = order.to(torch.int32)
         return beam_backtrack(parents, toks, order), cum, length, states
+
+
+def _beam_search_plain(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                       no_repeat_ngram_size=0, banned_sequences=None):
+    """Model.beam_search (lm.py has the contract).  automaton and automaton_state are further keyword-only arguments
+    (_truncate.further_keywords)."""
+    return _beam_search(model, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens, no_repeat_ngram_size,
+                        banned_sequences)
+
+
+beam_search = _truncate.further_keywords(_beam_search_plain, _beam_search, _automaton.KEYWORDS, "beam_search")

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import _lib, _truncate
+from . import _automaton, _lib, _truncate
 from .functional import vmlmf_sequence
 
 
@@ -409,20 +409,34 @@ class Model(nn.Module):
         most probable survivor.  The draw is the argmax over the kept set on the noise of the untruncated call; logprobs stay the
         unprocessed log-softmax; greedy decoding accepts them and is unchanged.  The choice is exact and repeats bit for bit.
         ValueError, before any device work, for a value outside those ranges and for any of them together with the history controls
-        (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty): that composition is out of scope."""
+        (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty): that composition is out of scope.
+        Token automaton - automaton, automaton_state: two further KEYWORD-ONLY arguments, taken by the same wrapper (off by default:
+        None; with automaton= the choice of every step is ONE launch of a library of its own behind the head's GEMM -
+        vmlmf_automaton_choose, include/vmlmf_automaton.h -; without it this is the call above, launch for launch, and that library is
+        never opened).  automaton: a vmlmf_amd.TokenAutomaton over the vocabulary - a dense table next (S, V) on the device, next[s][v]
+        >= 0: in state s token v is open and leads to that state; forced, one_of, template and avoiding build the usual ones.  Every row
+        carries one state; per step, behind logit_bias and min_length, the tokens the row's state does not offer go to -inf, and the
+        state moves on with the chosen token.  automaton_state: (B) int32 start states, default automaton.start for every row - the
+        prompt is NOT consumed: pass automaton.advance(prompt) where it should be.  It composes with temperature, top_k, top_p, eos,
+        min_length, repetition_penalty, logit_bias, banned_tokens, return_lengths and chunk; the noise is the plain call's and logprobs
+        stay the unprocessed log-softmax.  ValueError, before any device work, for an automaton over another vocabulary, an
+        automaton_state of another shape or dtype or with a state outside [0, S), a state that can be reached from the start states (not
+        through eos, when eos is given) and has no token left that banned_tokens and -inf biases leave open - with min_length > 0: none
+        besides eos -, and for the automaton together with a history control or a truncation sampler: those compositions are out of
+        scope."""
         from . import decoding
         return decoding.generate(self, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length,
                                  repetition_penalty, logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences,
                                  frequency_penalty, presence_penalty)
 
-    def _generate_truncated(self, *args, **kw):
+    def _generate_extended(self, *args, **kw):
         from . import decoding
         return decoding.generate(self, *args, **kw)
 
-    generate = _truncate.keywords(_generate_plain, _generate_truncated)
+    generate = _truncate.further_keywords(_generate_plain, _generate_extended, _truncate.KEYWORDS + _automaton.KEYWORDS, "generate")
 
-    def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
-                    no_repeat_ngram_size=0, banned_sequences=None):
+    def _beam_search_plain(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0,
+                           banned_tokens=None, no_repeat_ngram_size=0, banned_sequences=None):
         """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
         (steps, B, W) int64, scores (B, W) fp32, lengths (B, W) int32, states): tokens[:, b, w] is hypothesis w of row b, best first;
         its score is the fp32 sum of the untempered log-softmax (bias included) of its tokens - what nll_loss charges -; states are per
@@ -447,12 +461,27 @@ class Model(nn.Module):
         launch (decoding.BeamControls, vmlmf_beamctl_step) and, for the last two, one small launch in front of it that forms every
         beam's ban set from its history (vmlmf_history_bans on B W rows); without them the call is launch for launch what it was.
         ValueError for what generate() refuses for the same arguments, for eos among banned_tokens, and for a vocabulary in which a
-        beam might run short of candidates: V < closed + T0 + steps + len(banned_sequences) + beams."""
+        beam might run short of candidates: V < closed + T0 + steps + len(banned_sequences) + beams.
+        automaton, automaton_state: two further KEYWORD-ONLY arguments (taken by _truncate.further_keywords around this function, so
+        inspect.signature lists the parameters up to banned_sequences only) - generate()'s of the same names, per HYPOTHESIS: every beam
+        carries a state of the vmlmf_amd.TokenAutomaton, a live beam offers only what its state's table row opens, a survivor's state is
+        its parent's moved on by its token (a finished parent's: unchanged).  The selection is then ONE launch of
+        vmlmf_automaton_beam_step (include/vmlmf_automaton.h: the same kernel under a third offer policy); the beams' states travel with
+        cum, finished and length, through chunk= too.  It composes with eos, min_length, banned_tokens, length_penalty and chunk;
+        ValueError together with no_repeat_ngram_size or banned_sequences, and for what generate() refuses of the automaton.  A
+        constraint that admits fewer than `beams` sequences leaves the surplus hypotheses at score -inf: they repeat admitted ones,
+        continued from the beams that start at -inf.  Without automaton= the call is launch for launch what it was."""
         from . import decoding
         if min_length == 0 and banned_tokens is None and no_repeat_ngram_size == 0 and banned_sequences is None:
             return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
         return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens,
                                     no_repeat_ngram_size, banned_sequences)
+
+    def _beam_search_extended(self, *args, **kw):
+        from . import decoding
+        return decoding.beam_search(self, *args, **kw)
+
+    beam_search = _truncate.further_keywords(_beam_search_plain, _beam_search_extended, _automaton.KEYWORDS, "beam_search")
 
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
