@@ -1,14 +1,12 @@
 """Decoding under a token automaton (vmlmf_amd.TokenAutomaton, automaton= of Model.generate and Model.beam_search;
 libvmlmf_automaton.so, include/vmlmf_automaton.h): what can be checked without a GPU - every constructor's table by brute force, the
 rule of `avoiding` against history_cases.ban_set, advance, every refusal of the Python layer and of the C ABI, the reachability check,
-the pinned signatures, the library's row of the side-library table, the Makefile's target and the lazy load."""
+what is the library's own of its build (the kernels are instantiated, not copied).  (Its exports, build rule and lazy load: its row of
+test_side_libraries_cpu.py; the signatures: test_generate_cpu.py.)"""
 import ctypes
-import inspect
 import itertools
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -224,100 +222,13 @@ def test_the_controls_own_and_clone_their_state():
         AutomatonBeamControls(2, 33, V, "cpu", a)
 
 
-def test_the_signatures_are_unchanged_and_the_new_names_are_keywords():
+def test_the_beam_steps_workspace_is_the_plain_steps():
+    from vmlmf_amd import _automaton, _beam, decoding
     import vmlmf_amd
-    from vmlmf_amd import Model, decoding
-    gen = ["self", "prompt", "steps", "states", "temperature", "seed", "chunk", "layer_path", "top_k", "top_p", "eos", "min_length",
-           "repetition_penalty", "logit_bias", "banned_tokens", "return_lengths", "no_repeat_ngram_size", "banned_sequences",
-           "frequency_penalty", "presence_penalty"]
-    beam = ["self", "prompt", "steps", "beams", "states", "eos", "length_penalty", "chunk", "min_length", "banned_tokens",
-            "no_repeat_ngram_size", "banned_sequences"]
-    assert list(inspect.signature(Model.generate).parameters) == gen and list(inspect.signature(Model.beam_search).parameters) == beam
-    assert list(inspect.signature(decoding.generate).parameters) == ["model"] + gen[1:]
-    assert list(inspect.signature(decoding.beam_search).parameters) == ["model"] + beam[1:]
-    assert (Model.generate.__name__, Model.beam_search.__name__) == ("generate", "beam_search") and "automaton" in Model.beam_search.__doc__
-    m, tok = _model(), torch.zeros((3, 2), dtype=torch.int64)
-    a = TA().forced(V, [1])
-    for call in (m.generate, m.beam_search):
-        with pytest.raises(RuntimeError, match="cuda"):                      # accepted as keywords ...
-            call(tok, 4, automaton=a, automaton_state=None)
-        with pytest.raises(RuntimeError, match="cuda"):                      # ... and None is "not given": the call it was
-            call(tok, 4, automaton=None, automaton_state=None)
-        with pytest.raises(TypeError):
-            call(tok, 4, automatons=a)
-    with pytest.raises(TypeError):
-        m.generate(tok, 4, None, 1.0, None, None, "layers", None, None, None, 0, 1.0, None, None, False, 0, None, 0.0, 0.0, a)   # keyword-only
+    assert _automaton.lib().vmlmf_automaton_workspace_bytes(3, 4, 97) == _beam.lib().vmlmf_beam_workspace_bytes(3, 4, 97) == 3 * 4 * 4 * 8
+    assert _automaton.lib().vmlmf_automaton_workspace_bytes(3, 33, 97) == 0
     for name in ("TokenAutomaton", "AutomatonControls", "AutomatonBeamControls"):
         assert name in vmlmf_amd.__all__ and getattr(vmlmf_amd, name) is getattr(decoding, name)
-    from vmlmf_amd import _truncate                                         # the wrapper is written once
-    assert _truncate.keywords.__doc__ and "further_keywords" in inspect.getsource(_truncate.keywords)
-
-
-# ---- the library's row of the side-library table ----
-ROW = dict(header="vmlmf_automaton.h", file="libvmlmf_automaton.so", abi_macro="VMLMF_AUTOMATON_ABI_VERSION", obj="vmlmf_automaton.o",
-           functions=["vmlmf_automaton_abi_version", "vmlmf_automaton_beam_step", "vmlmf_automaton_choose", "vmlmf_automaton_last_error",
-                      "vmlmf_automaton_workspace_bytes"],
-           no_fallback="no stock-op fallback for decoding under a token automaton")
-SIDE_FILES = ["libvmlmf_beam.so", "libvmlmf_beamctl.so", "libvmlmf_decode.so", "libvmlmf_history.so", "libvmlmf_score.so",
-              "libvmlmf_truncate.so"]
-
-
-def test_every_declared_function_is_exported_and_bound():
-    from vmlmf_amd import _automaton as b, _beam, _beamctl, _decode, _history, _lib, _score, _truncate
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", ROW["header"])).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(b.SYMBOLS) == ROW["functions"] and all(n.startswith("vmlmf_automaton_") for n in declared)
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    assert all(hasattr(handle, name) for name in ROW["functions"])
-    header = open(os.path.join(ROOT, "include", ROW["header"])).read()
-    in_header = int(re.search(r"#define %s (\d+)" % ROW["abi_macro"], header).group(1))
-    assert b.LIBRARY.abi_symbol == "vmlmf_automaton_abi_version" and b.LIBRARY.error_symbol == "vmlmf_automaton_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_automaton_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == ROW["file"] and b.LIBRARY.no_fallback in ROW["no_fallback"]
-    for other in (_beam, _beamctl, _decode, _history, _score, _truncate):     # disjoint from every other library
-        assert not set(other.SYMBOLS) & set(b.SYMBOLS)
-        theirs = ctypes.CDLL(other.LIBRARY.path)
-        assert not any(hasattr(theirs, n) for n in b.SYMBOLS) and not any(hasattr(handle, n) for n in other.SYMBOLS)
-    main = ctypes.CDLL(_lib.LIB_PATH)
-    assert not any(hasattr(main, n) for n in b.SYMBOLS) and not any(hasattr(handle, n) for n in ("vmlmf_lm_choose", "vmlmf_abi_version"))
-    assert b.lib().vmlmf_automaton_workspace_bytes(3, 4, 97) == _beam.lib().vmlmf_beam_workspace_bytes(3, 4, 97) == 3 * 4 * 4 * 8
-    assert b.lib().vmlmf_automaton_workspace_bytes(3, 33, 97) == 0
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _automaton as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / ROW["file"]))
-    with pytest.raises(RuntimeError, match=ROW["file"] + " is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match=ROW["no_fallback"]):
-        b.lib()
-    assert not b.loaded()
-
-
-def test_the_makefile_links_the_library_in_a_target_of_its_own():
-    run = lambda *a: subprocess.run(["make", "-n", *a], capture_output=True, text=True, timeout=120)
-    r = run("-B", "-C", CSRC, "all")
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert r.returncode == 0 and len(links) == 6 and "automaton" not in r.stdout               # `all` is what it was
-    r = run("-B", "-C", CSRC, "extra")
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert r.returncode == 0 and len(links) == 1 and "truncate" in links[0] and "automaton" not in r.stdout   # ... and so is `extra`
-    r = run("-B", "-C", CSRC, "automaton")
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert r.returncode == 0 and len(links) == 1 and "-o ../lib/" + ROW["file"] in links[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links[0]) == [ROW["obj"]]                           # from its own object alone
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    deps = re.search(r"^vmlmf_automaton\.o:(.*)$", text, flags=re.M).group(1).split()
-    for h in ("vmlmf_side.h", "vmlmf_refusals.h", "vmlmf_select.h", "vmlmf_controlled.h", "vmlmf_beam_core.h", "vmlmf_dropout.h",
-              "../../include/vmlmf_beam.h", "../../include/vmlmf_decode.h", "../../include/vmlmf_automaton.h"):
-        assert h in deps, h
-    assert "automaton" in re.search(r"^\.PHONY:(.*)$", text, flags=re.M).group(1).split()
-    r = run("-C", CSRC, "clean")
-    assert r.returncode == 0 and ROW["file"] in r.stdout and ROW["obj"] in r.stdout
-    assert '"all", "extra", "automaton"' in open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    assert "make -C vmlmf_amd/csrc -j8 all extra automaton" in open(os.path.join(ROOT, "README.md")).read()
 
 
 def test_the_kernels_are_instantiated_not_copied():
@@ -334,59 +245,6 @@ def test_the_kernels_are_instantiated_not_copied():
     assert len(re.findall(r"__global__", text)) == 1 and "asm" not in text.replace("disassembl", "") and "atomic" not in text.replace("no float atomics", "")
     core = open(os.path.join(CSRC, "vmlmf_beam_core.h")).read()
     assert len(re.findall(r"if constexpr \(moves_states<P>::value\)", core)) == 1       # the one hook
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _automaton, _beam, _beamctl, _decode, _history, _score, _truncate, _lib
-_lib.lib()
-def refused(call):
-    try:
-        call()
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e)
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-for kw in (dict(), dict(top_k=3), dict(eos=2, repetition_penalty=1.2), dict(no_repeat_ngram_size=2), dict(banned_sequences=[[1, 2]]),
-           dict(min_p=0.1), dict(typical_p=0.9, eos=3)):
-    refused(lambda: m.generate(tok, 4, **kw))
-for kw in (dict(), dict(eos=3), dict(eos=3, min_length=2, banned_tokens=[5]), dict(no_repeat_ngram_size=2), dict(banned_sequences=[[1, 2]])):
-    refused(lambda: m.beam_search(tok, 4, **kw))
-refused(lambda: m.score(tok))
-A = vmlmf_amd.TokenAutomaton.avoiding(97, [[1, 2], [3]])
-assert A.advance(tok).tolist() == [0, 0] and A.accepts([1, 1, 4])
-for B in (vmlmf_amd.TokenAutomaton.forced(97, [4, 5], 3), vmlmf_amd.TokenAutomaton.one_of(97, [[4], [5, 6]]),
-          vmlmf_amd.TokenAutomaton.template(97, [[1, 2], 3])):
-    assert B.S >= 3
-c = vmlmf_amd.AutomatonControls(2, 97, 'cpu', A, eos=3, banned_tokens=[5], prompt=tok)
-assert c.row_state.tolist() == [0, 0] and c.clone().struct().S == A.S
-b = vmlmf_amd.AutomatonBeamControls(2, 4, 97, 'cpu', A, eos=3, min_length=1)
-assert b.start().tolist() == [0] * 8
-refused(lambda: m.generate(tok, 4, automaton=A, eos=3))
-refused(lambda: m.beam_search(tok, 4, automaton=A, eos=3, min_length=2))
-names = %r + ['libvmlmf_automaton.so']
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_hip.so' in maps
-for name in names:
-    assert name not in maps, name
-others = (_beam, _beamctl, _decode, _history, _score, _truncate)
-assert not _automaton.loaded() and not any(x.loaded() for x in others)
-_automaton.lib()
-maps = open('/proc/self/maps').read()
-for name in names:
-    assert (name in maps) == (name == 'libvmlmf_automaton.so'), name
-assert _automaton.loaded() and not any(x.loaded() for x in others)
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    """Every uncontrolled and previously controlled call up to its refusal of CPU tensors, and building a TokenAutomaton, an
-    AutomatonControls and an AutomatonBeamControls on the CPU, leave the library closed; then its own first call opens it alone."""
-    r = subprocess.run([sys.executable, "-c", WALK % (ROOT, SIDE_FILES)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the C ABI's refusals: all on the host, in front of any launch ----

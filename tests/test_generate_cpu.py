@@ -2,6 +2,7 @@
 (host only: they refuse before anything reaches a device), the workspace size, and the numpy restatement of the sampler's draw that
 the GPU tests hold the kernel to (vmlmf_decode_oracle.gumbel_restated), checked on itself."""
 import ctypes
+import inspect
 import os
 import re
 
@@ -85,3 +86,49 @@ def test_generate_refuses_cpu_tensors():
     from vmlmf_amd import lm_sample
     with pytest.raises(RuntimeError, match="cuda"):
         lm_sample(torch.zeros(2, 32), m.fc.w.detach(), m.fc.b.detach(), 0.0)
+
+
+GENERATE = ["prompt", "steps", "states", "temperature", "seed", "chunk", "layer_path", "top_k", "top_p", "eos", "min_length",
+            "repetition_penalty", "logit_bias", "banned_tokens", "return_lengths", "no_repeat_ngram_size", "banned_sequences",
+            "frequency_penalty", "presence_penalty"]
+BEAM_SEARCH = ["prompt", "steps", "beams", "states", "eos", "length_penalty", "chunk", "min_length", "banned_tokens", "no_repeat_ngram_size",
+               "banned_sequences"]
+
+
+def test_the_decoders_signatures():
+    """Model.generate / Model.beam_search and decoding's functions behind them: the positional parameters are what they have been, in
+    their order; what came later - the truncation samplers, the automaton - is keyword-only and None by default."""
+    from vmlmf_amd import Model, TokenAutomaton, decoding
+    table = [(Model.generate, decoding.generate, GENERATE, "generate", {"no_repeat_ngram_size": 0, "banned_sequences": None,
+                                                                        "frequency_penalty": 0.0, "presence_penalty": 0.0},
+              ["min_p", "typical_p", "epsilon_cutoff", "eta_cutoff", "automaton", "automaton_state"]),
+             (Model.beam_search, decoding.beam_search, BEAM_SEARCH, "beam_search", {"min_length": 0, "banned_tokens": None,
+                                                                                    "no_repeat_ngram_size": 0, "banned_sequences": None},
+              ["automaton", "automaton_state"])]
+    for method, function, positional, name, defaults, keywords in table:
+        for fn, first in ((method, "self"), (function, "model")):
+            params = inspect.signature(fn).parameters
+            assert [n for n, p in params.items() if p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD] == [first] + positional
+            assert list(params) == [first] + positional + keywords                  # ... and nothing of another kind
+            assert {n: params[n].default for n in defaults} == defaults
+            assert all(params[n].kind is inspect.Parameter.KEYWORD_ONLY and params[n].default is None for n in keywords)
+            assert fn.__name__ == name
+        assert "keyword-only" in method.__doc__ and "automaton" in method.__doc__
+    torch.manual_seed(0)
+    m, tok = Model(8, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type="vmlmf"), torch.zeros((3, 2), dtype=torch.int64)
+    a = TokenAutomaton.forced(8, [1])
+    for call in (m.generate, m.beam_search):
+        with pytest.raises(RuntimeError, match="cuda"):                      # accepted as keywords ...
+            call(tok, 4, automaton=a, automaton_state=None)
+        with pytest.raises(RuntimeError, match="cuda"):                      # ... and None is "not given": the call it was
+            call(tok, 4, automaton=None, automaton_state=None)
+        with pytest.raises(TypeError):
+            call(tok, 4, automatons=a)
+    with pytest.raises(RuntimeError, match="cuda"):
+        m.generate(tok, 4, min_p=0.1, typical_p=None, epsilon_cutoff=None, eta_cutoff=None)
+    with pytest.raises(TypeError):
+        m.generate(tok, 4, min_ps=0.1)
+    with pytest.raises(TypeError):
+        m.generate(tok, 4, None, 1.0, None, None, "layers", None, None, None, 0, 1.0, None, None, False, 0, None, 0.0, 0.0, a)   # keyword-only
+    with pytest.raises(TypeError):
+        m.beam_search(tok, 4, 4, None, None, 0.0, None, 0, None, 0, None, a)

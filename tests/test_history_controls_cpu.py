@@ -4,7 +4,6 @@ the table test_side_libraries_cpu.py holds every side library to - the two state
 other; the condition on the reference's sets that the GPU test of the choice relies on; every
 refusal, in Python and at the C ABI; the struct of the binding."""
 import ctypes
-import inspect
 import os
 import re
 import subprocess
@@ -157,15 +156,7 @@ def test_the_room_for_a_choice_and_the_widest_vocabulary():
     assert _history.history_on(presence_penalty=0.1)
 
 
-def test_generates_signature_starts_as_it_did():
-    from vmlmf_amd import Model, decoding
-    old = ["self", "prompt", "steps", "states", "temperature", "seed", "chunk", "layer_path", "top_k", "top_p", "eos", "min_length",
-           "repetition_penalty", "logit_bias", "banned_tokens", "return_lengths"]
-    new = ["no_repeat_ngram_size", "banned_sequences", "frequency_penalty", "presence_penalty"]
-    sig = inspect.signature(Model.generate)
-    assert list(sig.parameters) == old + new
-    assert [sig.parameters[n].default for n in new] == [0, None, 0.0, 0.0]
-    assert list(inspect.signature(decoding.generate).parameters) == ["model"] + old[1:] + new
+def test_history_controls_is_exported_as_a_decode_controls():
     import vmlmf_amd
     assert "HistoryControls" in vmlmf_amd.__all__ and issubclass(vmlmf_amd.HistoryControls, vmlmf_amd.DecodeControls)
 

@@ -1,12 +1,11 @@
 """The truncation samplers of Model.generate (min_p, typical_p, epsilon_cutoff, eta_cutoff; C ABI vmlmf_truncate_choose in
 libvmlmf_truncate.so, include/vmlmf_truncate.h): what can be checked without a GPU - the fp64 statement of the contract
 (truncation_cases.py) on hand-made rows and against filtered_sets, the condition on its sets that the GPU tests
-(test_gpu_truncation.py) rely on, every refusal in Python and at the C ABI, the library's table, its Makefile target and its lazy load."""
+(test_gpu_truncation.py) rely on, every refusal in Python and at the C ABI.  (The library's exports, build rule and lazy load: its row
+of test_side_libraries_cpu.py.)"""
 import ctypes
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ import vmlmf_decode_oracle as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-SIDE_FILES = ["libvmlmf_beam.so", "libvmlmf_decode.so", "libvmlmf_score.so", "libvmlmf_history.so", "libvmlmf_beamctl.so"]
 
 
 # ---- the oracle on hand-made rows ----
@@ -244,66 +242,6 @@ def test_the_entry_point_refuses_on_the_host():
         assert rc == code and words in msg and msg.startswith("vmlmf_truncate_choose: "), (kw, rc, msg)
 
 
-# ---- the library's table ----
-ROW = dict(header="vmlmf_truncate.h", file="libvmlmf_truncate.so", abi_macro="VMLMF_TRUNCATE_ABI_VERSION", obj="vmlmf_truncate.o",
-           functions=["vmlmf_truncate_abi_version", "vmlmf_truncate_choose", "vmlmf_truncate_last_error"],
-           no_fallback="no stock-op fallback for the truncation samplers of Model.generate")
-
-
-def test_every_declared_function_is_exported_and_bound():
-    from vmlmf_amd import _beam, _beamctl, _decode, _history, _lib, _score, _truncate as b
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", ROW["header"])).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(b.SYMBOLS) == ROW["functions"] and all(n.startswith("vmlmf_truncate_") for n in declared)
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    assert all(hasattr(handle, name) for name in ROW["functions"])
-    header = open(os.path.join(ROOT, "include", ROW["header"])).read()
-    in_header = int(re.search(r"#define %s (\d+)" % ROW["abi_macro"], header).group(1))
-    assert b.LIBRARY.abi_symbol == "vmlmf_truncate_abi_version" and b.LIBRARY.error_symbol == "vmlmf_truncate_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_truncate_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == ROW["file"] and b.LIBRARY.no_fallback in ROW["no_fallback"]
-    # its entry points are its own: no other library exports them, and it exports none of theirs
-    for other in (_beam, _beamctl, _decode, _history, _score):
-        assert not set(other.SYMBOLS) & set(b.SYMBOLS)
-        theirs = ctypes.CDLL(other.LIBRARY.path)
-        assert not any(hasattr(theirs, n) for n in b.SYMBOLS) and not any(hasattr(handle, n) for n in other.SYMBOLS)
-    main = ctypes.CDLL(_lib.LIB_PATH)
-    assert not any(hasattr(main, n) for n in b.SYMBOLS) and not any(hasattr(handle, n) for n in ("vmlmf_lm_choose", "vmlmf_abi_version"))
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _truncate as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / ROW["file"]))
-    with pytest.raises(RuntimeError, match=ROW["file"] + " is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match=ROW["no_fallback"]):
-        b.lib()
-    assert not b.loaded()
-
-
-def test_the_makefile_links_the_library_outside_all():
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert r.returncode == 0 and len(links) == 6 and "truncate" not in r.stdout                # `all` is what it was
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "extra"], capture_output=True, text=True, timeout=120)
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert r.returncode == 0 and len(links) == 1 and "-o ../lib/" + ROW["file"] in links[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links[0]) == [ROW["obj"]]                           # from its own object alone
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    deps = re.search(r"^vmlmf_truncate\.o:(.*)$", text, flags=re.M).group(1).split()
-    for h in ("vmlmf_side.h", "vmlmf_refusals.h", "vmlmf_select.h", "vmlmf_controlled.h", "vmlmf_truncate.h", "vmlmf_dropout.h",
-              "../../include/vmlmf_decode.h", "../../include/vmlmf_truncate.h"):
-        assert h in deps, h
-    assert "vmlmf_controlled.h" in re.search(r"^vmlmf_decode\.o:(.*)$", text, flags=re.M).group(1).split()
-    r = subprocess.run(["make", "-n", "-C", CSRC, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and ROW["file"] in r.stdout and ROW["obj"] in r.stdout
-    build = open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    assert '"all", "extra"' in build
-    assert "make -C vmlmf_amd/csrc -j8 all extra" in open(os.path.join(ROOT, "README.md")).read()
-
-
 def test_the_controlled_rows_are_written_once():
     """ControlledScores and the rows' state update live in vmlmf_controlled.h; both libraries include it and neither holds a copy; the
     select over a key view is the new header's, vmlmf_select.h's functions are called, not copied."""
@@ -318,38 +256,3 @@ def test_the_controlled_rows_are_written_once():
         assert not re.search(r"__device__[^;{]*\b%s\s*\(" % fn, dev), fn
     for fn in ("radix_select", "tie_cutoff", "for_quads", "mass_of", "view_select", "view_tie_cut", "sum_pass"):
         assert re.search(r"\b%s\s*\(" % fn, dev), fn
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _beam, _beamctl, _decode, _history, _score, _truncate, _lib
-_lib.lib()
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(16, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-for kw in (dict(min_p=0.1), dict(typical_p=0.9, eos=3), dict(epsilon_cutoff=0.01, eta_cutoff=0.01, top_k=4)):
-    try:
-        m.generate(tok, 4, **kw)
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e)
-t = vmlmf_amd.Truncation(min_p=0.1, typical_p=0.9, epsilon_cutoff=0.01, eta_cutoff=0.01)
-assert t.on and t.struct().min_p > 0
-names = %r + ['libvmlmf_truncate.so']
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_hip.so' in maps
-for name in names:
-    assert name not in maps, name
-assert not any(b.loaded() for b in (_beam, _beamctl, _decode, _history, _score, _truncate))
-_truncate.lib()
-maps = open('/proc/self/maps').read()
-for name in names:
-    assert (name in maps) == (name == 'libvmlmf_truncate.so'), name
-assert _truncate.loaded() and not any(b.loaded() for b in (_beam, _beamctl, _decode, _history, _score))
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    r = subprocess.run([sys.executable, "-c", WALK % (ROOT, SIDE_FILES)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]

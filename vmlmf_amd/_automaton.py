@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in include/vmlmf_automaton.h (libvmlmf_automaton.so, built in-tree by csrc/Makefile's `automaton` target
-beside libvmlmf_hip.so): decoding under a token automaton - automaton= of Model.generate and Model.beam_search.  The library is loaded on
+"""ctypes binding of the C ABI in include/vmlmf_automaton.h (libvmlmf_automaton.so, built in-tree by csrc/Makefile beside
+libvmlmf_hip.so): decoding under a token automaton - automaton= of Model.generate and Model.beam_search.  The library is loaded on
 the first constrained call: every other generate() and beam_search(), and a training process, never open it; building a TokenAutomaton or
 the controls on the CPU does not either.
 
@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _decode, _lib
-from ._beam import check_beams, step_buffers
+from ._beam import check_beams, check_step_controls, step_buffers, step_outputs
 from ._beamctl import pack_words
 from ._decode import DecodeControls
 from ._lib import ptr
@@ -48,7 +48,6 @@ LIBRARY = _lib.Library("libvmlmf_automaton.so", SYMBOLS, "vmlmf_automaton_abi_ve
                        "stock-op fallback for decoding under a token automaton")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
-KEYWORDS = ("automaton", "automaton_state")     # the keyword-only arguments of Model.generate and Model.beam_search
 GENERATE_REFUSAL = ("vmlmf_amd: automaton= together with {what} is out of scope: the constrained choice runs under the stopping and token "
                     "controls (eos, min_length, repetition_penalty, logit_bias, banned_tokens) only")
 BEAM_REFUSAL = ("vmlmf_amd: automaton= together with {what} is out of scope: the constrained beam step runs under eos, min_length and "
@@ -349,6 +348,7 @@ class AutomatonControls(DecodeControls):
 
     STATE = DecodeControls.STATE + ("row_state", "dead")
     LIBRARY, ENTRY, STRUCT = LIBRARY, "vmlmf_automaton_choose", Controls
+    TRUNCATION_REFUSAL = GENERATE_REFUSAL.format(what="min_p / typical_p / epsilon_cutoff / eta_cutoff")
 
     def values(self):
         return dict(super().values(), next=ptr(self.automaton.next), S=self.automaton.S, row_state=ptr(self.row_state), dead=ptr(self.dead))
@@ -360,9 +360,11 @@ class AutomatonBeamControls:
       eos, min_length, banned_tokens   Model.beam_search's, as BeamControls'
     They only close candidates, so scores stay sums of plain log-probabilities.  Owns the `closed` words.  The beams' states are CARRIED,
     not owned: start() gives the first beam_state (B W) int32, every lm_beam_step(..., controls=, beam_state=) returns the survivors' as a
-    fresh buffer behind its seven results."""
+    fresh buffer behind its seven results.  `carried` names it as lm_beam_step's keyword, first_carried() is [start()], select() the
+    step's launch."""
 
     keeps_history = False
+    carried = ("beam_state",)
 
     def __init__(self, B, W, V, device, automaton, state=None, eos=None, min_length=0, banned_tokens=None, _checked=False):
         B, V = int(B), int(V)
@@ -373,14 +375,22 @@ class AutomatonBeamControls:
             raise ValueError(f"vmlmf_amd: eos={self.eos} is among banned_tokens: a finished beam offers eos alone")
         if not _checked:
             automaton.check_reachable(start, closed_tokens(V, None, self.banned), self.eos, self.min_length)
-        self.B, self.W, self.V, self.device = B, W, V, torch.device(device)
-        self.automaton = automaton.to(self.device)
+        self.B, self.W, self.V = B, W, V
+        self.automaton = automaton.to(device)
+        self.device = self.automaton.device             # (with its index: what a launch's tensors are compared with)
         self.closed = pack_words(self.banned, V).to(self.device) if self.banned else None
         self._start = torch.from_numpy(start.astype(np.int32)).to(self.device).repeat_interleave(W, 0).contiguous()
 
     def start(self):
         """beam_state (B W) int32 of a search that starts: every beam of a batch row in the row's start state - a fresh copy."""
         return self._start.clone()
+
+    def first_carried(self):
+        return [self.start()]
+
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, beam_state=None, **others):
+        """lm_beam_step's selection under these controls (automaton_select); of the carried keywords it takes its own."""
+        return automaton_select(scores, bias, cum, finished, length, eos, embed, self, beam_state, buffers)
 
     def clone(self):
         """These controls (they own no state a launch moves: a BeamGraph's warm-up runs on the same object)."""
@@ -393,10 +403,7 @@ def automaton_select(scores, bias, cum, finished, length, eos, embed, controls, 
     B, W = cum.shape
     V = scores.shape[1]
     dev = scores.device
-    if not isinstance(controls, AutomatonBeamControls) or (controls.B, controls.W, controls.V) != (B, W, V) or controls.automaton.device != dev:
-        raise RuntimeError(f"vmlmf_amd.lm_beam_step: controls must be an AutomatonBeamControls for {B} x {W} beams over {V} tokens on {dev}")
-    if (controls.eos >= 0 or controls.min_length > 0) and controls.eos != eos:
-        raise ValueError(f"vmlmf_amd.lm_beam_step: the controls' eos ({controls.eos}) is not the step's ({eos})")
+    check_step_controls(controls, AutomatonBeamControls, B, W, V, dev, eos)
     if beam_state is None:
         beam_state = controls.start()
     if not (isinstance(beam_state, torch.Tensor) and beam_state.device == dev and beam_state.dtype == torch.int32
@@ -405,13 +412,7 @@ def automaton_select(scores, bias, cum, finished, length, eos, embed, controls, 
                            "(AutomatonBeamControls.start())")
     ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
     H = embed.shape[1] if embed is not None else 1
-    parent = torch.empty((B, W), device=dev, dtype=torch.int32)
-    token = torch.empty((B, W), device=dev, dtype=torch.int64)
-    total = torch.empty((B, W), device=dev, dtype=torch.float32)
-    fin = torch.empty((B, W), device=dev, dtype=torch.int32)
-    ln = torch.empty((B, W), device=dev, dtype=torch.int32)
-    src = torch.empty(B * W, device=dev, dtype=torch.int32)
-    xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
+    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
     state_out = torch.empty_like(beam_state)
     table = controls.automaton.table()
     LIBRARY.call(dev, "vmlmf_automaton_beam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),

@@ -119,12 +119,31 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
         raise ValueError(f"vmlmf_amd.lm_beam_step: eos={eos} is not a token of the vocabulary ({V})")
     args = (torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
             length.contiguous(), eos_c, None if embed is None else embed.contiguous())
-    if controls is not None:
-        from . import _automaton, _beamctl
-        if isinstance(controls, _automaton.AutomatonBeamControls):
-            return _automaton.automaton_select(*args, controls, beam_state, buffers)
-        return _beamctl.beamctl_select(*args, controls, hist, hist_len, buffers)
-    return beam_select(*args, buffers)
+    if controls is None:
+        return beam_select(*args, buffers)
+    return controls.select(*args, buffers, hist=hist, hist_len=hist_len, beam_state=beam_state)    # (it takes what it carries)
+
+
+def step_outputs(B, W, H, dev, embed):
+    """The seven results of a beam step, uninitialised: parent, token, total, finished, length (B, W), x_next (B W, H) - None without
+    embed -, src_row (B W)."""
+    parent = torch.empty((B, W), device=dev, dtype=torch.int32)
+    token = torch.empty((B, W), device=dev, dtype=torch.int64)
+    total = torch.empty((B, W), device=dev, dtype=torch.float32)
+    fin = torch.empty((B, W), device=dev, dtype=torch.int32)
+    ln = torch.empty((B, W), device=dev, dtype=torch.int32)
+    src = torch.empty(B * W, device=dev, dtype=torch.int32)
+    xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
+    return parent, token, total, fin, ln, xn, src
+
+
+def check_step_controls(controls, kind, B, W, V, dev, eos):
+    """RuntimeError unless `controls` is a `kind` for B x W beams over V tokens on dev; ValueError if it holds another eos than the step's."""
+    if not isinstance(controls, kind) or (controls.B, controls.W, controls.V) != (B, W, V) or controls.device != dev:
+        a = "an" if kind.__name__[0] in "AEIOU" else "a"
+        raise RuntimeError(f"vmlmf_amd.lm_beam_step: controls must be {a} {kind.__name__} for {B} x {W} beams over {V} tokens on {dev}")
+    if (controls.eos >= 0 or controls.min_length > 0) and controls.eos != eos:
+        raise ValueError(f"vmlmf_amd.lm_beam_step: the controls' eos ({controls.eos}) is not the step's ({eos})")
 
 
 def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
@@ -135,13 +154,7 @@ def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
     dev = scores.device
     ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
     H = embed.shape[1] if embed is not None else 1
-    parent = torch.empty((B, W), device=dev, dtype=torch.int32)
-    token = torch.empty((B, W), device=dev, dtype=torch.int64)
-    total = torch.empty((B, W), device=dev, dtype=torch.float32)
-    fin = torch.empty((B, W), device=dev, dtype=torch.int32)
-    ln = torch.empty((B, W), device=dev, dtype=torch.int32)
-    src = torch.empty(B * W, device=dev, dtype=torch.int32)
-    xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
+    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
     LIBRARY.call(dev, "vmlmf_beam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
                  ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8)
     return parent, token, total, fin, ln, xn, src

@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _decode, _history, _lib
-from ._beam import check_beams, step_buffers
+from ._beam import check_beams, check_step_controls, step_buffers, step_outputs
 from ._lib import ptr
 
 ABI_VERSION = 1
@@ -88,8 +88,10 @@ class BeamControls:
                              full history leaves it as it is and sets the batch row's `overflow`
     Owns the `closed` words, the flat sequence arrays and overflow (B) int32.  The histories are CARRIED, not owned: history() gives the
     first (hist (B W, capacity), hist_len (B W)) - None, None without an n-gram or sequence control -, every lm_beam_step(...,
-    controls=, hist=, hist_len=) returns the survivors' as fresh buffers.  ValueError for whatever check_beam_controls refuses, before
-    any device work; whether W candidates always stay open depends on the steps that follow, which Model.beam_search checks."""
+    controls=, hist=, hist_len=) returns the survivors' as fresh buffers.  `carried` names them as lm_beam_step's keywords - ("hist",
+    "hist_len"), or () where no history is kept -, first_carried() gives those of a search that starts, select() is the step's launches.
+    ValueError for whatever check_beam_controls refuses, before any device work; whether W candidates always stay open depends on the
+    steps that follow, which Model.beam_search checks."""
 
     def __init__(self, B, W, V, device, prompt=None, capacity=None, min_length=0, banned_tokens=None, no_repeat_ngram_size=0,
                  banned_sequences=None, eos=None):
@@ -101,11 +103,12 @@ class BeamControls:
                                        and prompt.shape[1] == B):
             raise ValueError(f"vmlmf_amd: BeamControls takes a (T0, {B}) int64 prompt")
         capacity = _history.check_capacity("BeamControls", capacity, int(prompt.shape[0]) if prompt is not None else 0)
-        self.B, self.W, self.V, self.device, self.capacity = B, W, V, torch.device(device), capacity
+        self.B, self.W, self.V, self.capacity = B, W, V, capacity
         self.keeps_history = self.no_repeat_ngram_size > 0 or bool(self.sequences)
-        dev = self.device
+        self.carried = ("hist", "hist_len") if self.keeps_history else ()
+        self.overflow = torch.zeros(B, dtype=torch.int32, device=torch.device(device))
+        self.device = dev = self.overflow.device        # (with its index: what a launch's tensors are compared with)
         self.closed = pack_words(self.banned, V).to(dev) if self.banned else None
-        self.overflow = torch.zeros(B, dtype=torch.int32, device=dev)
         self.seq_tokens, self.seq_offsets = _history.flat_sequences(self.sequences, dev)
         self._hist0 = None
         if self.keeps_history:
@@ -118,6 +121,14 @@ class BeamControls:
         if self._hist0 is None:
             return None, None
         return self._hist0[0].clone(), self._hist0[1].clone()
+
+    def first_carried(self):
+        """[hist, hist_len] of a search that starts - [] when no history is kept."""
+        return list(self.history()) if self.keeps_history else []
+
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, hist=None, hist_len=None, **others):
+        """lm_beam_step's selection under these controls (beamctl_select); of the carried keywords it takes its own."""
+        return beamctl_select(scores, bias, cum, finished, length, eos, embed, self, hist, hist_len, buffers)
 
     def clone(self):
         """The same controls on a copy of the state (overflow; a BeamGraph's warm-up runs on one)."""
@@ -139,10 +150,7 @@ def beamctl_select(scores, bias, cum, finished, length, eos, embed, controls, hi
     B, W = cum.shape
     V = scores.shape[1]
     dev = scores.device
-    if not isinstance(controls, BeamControls) or (controls.B, controls.W, controls.V) != (B, W, V) or controls.overflow.device != dev:
-        raise RuntimeError(f"vmlmf_amd.lm_beam_step: controls must be a BeamControls for {B} x {W} beams over {V} tokens on {dev}")
-    if (controls.eos >= 0 or controls.min_length > 0) and controls.eos != eos:
-        raise ValueError(f"vmlmf_amd.lm_beam_step: the controls' eos ({controls.eos}) is not the step's ({eos})")
+    check_step_controls(controls, BeamControls, B, W, V, dev, eos)
     cap = controls.capacity
     bans = hist_out = len_out = None
     if controls.keeps_history:
@@ -156,13 +164,7 @@ def beamctl_select(scores, bias, cum, finished, length, eos, embed, controls, hi
         hist = hist_len = None
     ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
     H = embed.shape[1] if embed is not None else 1
-    parent = torch.empty((B, W), device=dev, dtype=torch.int32)
-    token = torch.empty((B, W), device=dev, dtype=torch.int64)
-    total = torch.empty((B, W), device=dev, dtype=torch.float32)
-    fin = torch.empty((B, W), device=dev, dtype=torch.int32)
-    ln = torch.empty((B, W), device=dev, dtype=torch.int32)
-    src = torch.empty(B * W, device=dev, dtype=torch.int32)
-    xn = torch.empty((B * W, H), device=dev, dtype=torch.float32) if embed is not None else None
+    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
     c = Controls(controls.min_length, cap, ptr(controls.closed), ptr(bans), ptr(hist), ptr(hist_len), ptr(hist_out), ptr(len_out),
                  ptr(controls.overflow) if hist is not None else None)
     LIBRARY.call(dev, "vmlmf_beamctl_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),

@@ -127,6 +127,7 @@ class DecodeControls:
 
     STATE = ("seen", "finished", "length")                                  # the buffers a launch moves on: what clone() copies
     LIBRARY, ENTRY, STRUCT = LIBRARY, "vmlmf_decode_choose", Controls       # where decode_choose goes with these controls
+    TRUNCATION_REFUSAL = None       # a subclass whose choice cannot run under a Truncation: lm_sample's ValueError for the two together
 
     def clone(self):
         """The same controls on a copy of ALL the state (a DecodeGraph's warm-up runs on one)."""

@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from . import _decode, _lib
+from . import _decode, _lib, _truncate
 from ._decode import DecodeControls
 from ._lib import ptr
 
@@ -151,6 +151,7 @@ class HistoryControls(DecodeControls):
 
     STATE = DecodeControls.STATE + ("hist", "hist_len", "count", "overflow")
     LIBRARY, ENTRY, STRUCT = LIBRARY, "vmlmf_history_choose", Controls
+    TRUNCATION_REFUSAL = _truncate.HISTORY_REFUSAL
 
     def values(self):
         return dict(super().values(), no_repeat_ngram_size=self.no_repeat_ngram_size, frequency_penalty=self.frequency_penalty,

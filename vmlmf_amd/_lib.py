@@ -176,12 +176,11 @@ class VmlmfError(RuntimeError):
 
 
 def build(force=False, jobs=8):
-    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so, libvmlmf_beam.so, libvmlmf_decode.so,
-    libvmlmf_score.so, libvmlmf_history.so and libvmlmf_beamctl.so (the Makefile's `all`), libvmlmf_truncate.so (its `extra`) and
-    libvmlmf_automaton.so (its `automaton`); hipcc cross-compiles."""
+    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so and the seven side libraries beside it (the Makefile's
+    `all`); hipcc cross-compiles."""
     if force:
         subprocess.run(["make", "-C", CSRC, "clean"], check=True, stdout=subprocess.DEVNULL)
-    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "all", "extra", "automaton"], check=True, stdout=subprocess.DEVNULL)
+    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "all"], check=True, stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -263,7 +262,7 @@ def check(rc):
 
 
 class Library:
-    """A side library beside libvmlmf_hip.so (beam, decode, score, history, beamctl, truncate, automaton: a header, an ABI version and a last-error text of its own), opened
+    """A side library beside libvmlmf_hip.so (the Makefile's SIDE: a header, an ABI version and a last-error text of its own), opened
     and bound on first use - a process that never calls into it never maps it.  `path` may be repointed before the first use."""
 
     def __init__(self, filename, symbols, abi_symbol, abi_version, error_symbol, no_fallback):

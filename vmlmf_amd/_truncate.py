@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vmlmf_truncate.h (libvmlmf_truncate.so, built in-tree by csrc/Makefile's `extra` target beside
+"""ctypes binding of the C ABI in include/vmlmf_truncate.h (libvmlmf_truncate.so, built in-tree by csrc/Makefile beside
 libvmlmf_hip.so): the truncation samplers of the LM decoder - min_p, typical_p, epsilon_cutoff and eta_cutoff of Model.generate.  The
 library is loaded on the first truncated call: every other generate(), and a training process, never open it.
 
@@ -7,7 +7,6 @@ There is no fallback: if the library is missing, or a call fails, this raises.
 from __future__ import annotations
 
 import ctypes
-import functools
 import math
 
 from . import _decode, _lib
@@ -91,39 +90,16 @@ def truncation(min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
     return t if t.on else None
 
 
-KEYWORDS = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
-
-
-def further_keywords(plain, extended, names, name):
-    """`plain` - a method as its signature is pinned - taking `names` as further KEYWORD-ONLY arguments, all None by default: with none
-    of them given the call is `plain` itself; otherwise `extended(*args, **kw)` with those that were.  The result carries plain's
-    docstring and, for inspect.signature, plain's parameters: the further keywords come behind them (tests/test_history_controls_cpu.py
-    and tests/test_beam_controls_cpu.py hold generate's and beam_search's parameter lists to what they were)."""
-    @functools.wraps(plain)
-    def call(*args, **kw):
-        if all(kw.get(k) is None for k in names):
-            return plain(*args, **{k: v for k, v in kw.items() if k not in names})
-        return extended(*args, **kw)
-    call.__name__ = name
-    call.__qualname__ = plain.__qualname__.rsplit(".", 1)[0] + "." + name if "." in plain.__qualname__ else name
-    return call
-
-
-def keywords(plain, truncated, name="generate"):
-    """further_keywords for the four truncation samplers: min_p, typical_p, epsilon_cutoff, eta_cutoff."""
-    return further_keywords(plain, truncated, KEYWORDS, name)
-
-
 def truncate_choose(scores, bias, embed, inv, top_k, top_p, trunc, state, step, controls, tokens, logp, xn, kept):
     """The launch of vmlmf_truncate_choose on checked, contiguous arguments: scores (B, V) without the bias; controls: a DecodeControls
-    or None; outputs (and the controls' state) are written in place."""
+    whose class takes a truncation (TRUNCATION_REFUSAL), or None; outputs (and the controls' state) are written in place."""
     B, V = scores.shape
     dev = scores.device
     c = None
     if controls is not None:
         _decode.check_launch(controls, _decode.DecodeControls, B, V, dev, "lm_sample")
-        if type(controls) is not _decode.DecodeControls:
-            raise ValueError(HISTORY_REFUSAL)
+        if controls.TRUNCATION_REFUSAL is not None:
+            raise ValueError(controls.TRUNCATION_REFUSAL)
         held = controls.struct()
         c = ctypes.byref(held)
     H = embed.shape[1] if embed is not None else 1

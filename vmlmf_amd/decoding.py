@@ -109,10 +109,8 @@ def lm_sample(h, weight, bias, temperature, state=None, step=0, embed=None, form
     truncated = truncation is not None and truncation.on
     if truncated and form not in (None, "gemm"):
         raise ValueError(f"vmlmf_amd.lm_sample: the truncation samplers have no fused-head form (form must be 'gemm' or None, got {form!r})")
-    if truncated and isinstance(controls, HistoryControls):
-        raise ValueError(_truncate.HISTORY_REFUSAL)
-    if truncated and isinstance(controls, AutomatonControls):
-        raise ValueError(_automaton.GENERATE_REFUSAL.format(what="min_p / typical_p / epsilon_cutoff / eta_cutoff"))
+    if truncated and getattr(controls, "TRUNCATION_REFUSAL", None) is not None:      # (a HistoryControls', an AutomatonControls')
+        raise ValueError(controls.TRUNCATION_REFUSAL)
     truncated = truncated and inv > 0.0
     dev = h2.device
     lib = _lib.lib()
@@ -211,7 +209,7 @@ def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None
     parents, toks = [], []
     # what the controls carry from step to step behind cum, finished and length (lm_beam_step takes it by these names)
     names = _beam_extras(controls)
-    extra = _beam_start(controls, hist, hist_len, beam_state)
+    extra = _beam_start(controls, hist=hist, hist_len=hist_len, beam_state=beam_state)
     for _ in range(steps):
         par, tok, cum, finished, length, x, src, *rest = lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w,
                                                                       buffers=buffers, controls=controls, **dict(zip(names, extra)))
@@ -245,17 +243,14 @@ def _join_beams(h, states, cum, finished, length, history):
 
 
 def _beam_extras(controls):                 # the names of what the controls carry behind cum, finished and length (beam_steps' keywords)
-    if isinstance(controls, AutomatonBeamControls):
-        return ("beam_state",)
-    return ("hist", "hist_len") if controls is not None and controls.keeps_history else ()
+    return () if controls is None else controls.carried
 
 
-def _beam_start(controls, hist=None, hist_len=None, beam_state=None):      # those tensors: the given ones, or a search that starts
-    if isinstance(controls, AutomatonBeamControls):
-        return [controls.start() if beam_state is None else beam_state]
-    if controls is not None and controls.keeps_history:
-        return list(controls.history()) if hist is None else [hist, hist_len]
-    return []
+def _beam_start(controls, **given):         # those tensors: the given ones (hist=, hist_len= / beam_state=), or a search that starts
+    names = _beam_extras(controls)
+    if names and given.get(names[0]) is None:
+        return controls.first_carried()
+    return [given[name] for name in names]
 
 
 def _split_beams(carried, controls):        # _join_beams' arguments back; history: [hist, hist_len] / [beam_state] where the controls carry them
@@ -399,13 +394,14 @@ class BeamGraph(_StepGraph):
         fresh = _fresh_beams(B, W, h.device)
         cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), fresh))
         self.buffers = _beam.new_step_buffers(h.device, B, W, model.vocab_size)
-        history = _beam_start(controls, hist, hist_len, beam_state)
+        history = _beam_start(controls, hist=hist, hist_len=hist_len, beam_state=beam_state)
         step = lambda carried, controls=controls: _beamed(model, carried, self.steps, eos, self.buffers, controls)
         self._capture(model, _join_beams(h, states, cum, finished.to(torch.int32), length.to(torch.int32), history), step,
                       None if controls is None else lambda carried: step(carried, controls.clone()))
         self.h, self.states, self.cum, self.finished, self.length, history = _split_beams(self.carried, controls)
-        self.hist, self.hist_len = history if len(history) == 2 else (None, None)
-        self.beam_state = history[0] if len(history) == 1 else None
+        self.hist = self.hist_len = self.beam_state = None
+        for name, t in zip(_beam_extras(controls), history):
+            setattr(self, name, t)
         self.parents, self.tokens = self.outputs
 
 
@@ -458,11 +454,11 @@ def _run(steps, chunk, eager, graph):
     return tuple(torch.cat(o) for o in zip(*outs)), [t.clone() for t in g.carried]
 
 
-def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-              eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
-              no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0, min_p=None, typical_p=None,
-              epsilon_cutoff=None, eta_cutoff=None, automaton=None, automaton_state=None):
-    """Model.generate with every argument (lm.py has the contract)."""
+def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+             eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+             no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0, *, min_p=None, typical_p=None,
+             epsilon_cutoff=None, eta_cutoff=None, automaton=None, automaton_state=None):
+    """Model.generate (lm.py has the contract)."""
     sample_filters(top_k, top_p)
     trunc_args = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
     hist_args = dict(no_repeat_ngram_size=no_repeat_ngram_size, banned_sequences=banned_sequences, frequency_penalty=frequency_penalty,
@@ -517,21 +513,9 @@ def _generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chu
         return tokens, logprobs, lengths, states
 
 
-def _generate_plain(model, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-                    eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
-                    no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
-    """Model.generate (lm.py has the contract).  The truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff - and automaton,
-    automaton_state are further keyword-only arguments (_truncate.further_keywords)."""
-    return _generate(model, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length, repetition_penalty,
-                     logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty)
-
-
-generate = _truncate.further_keywords(_generate_plain, _generate, _truncate.KEYWORDS + _automaton.KEYWORDS, "generate")
-
-
-def _beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
-                 no_repeat_ngram_size=0, banned_sequences=None, automaton=None, automaton_state=None):
-    """Model.beam_search with every argument (lm.py has the contract)."""
+def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                no_repeat_ngram_size=0, banned_sequences=None, *, automaton=None, automaton_state=None):
+    """Model.beam_search (lm.py has the contract)."""
     W = _beam.check_beams(beams, model.vocab_size)
     steps, alpha = int(steps), float(length_penalty)
     if eos is not None and not 0 <= int(eos) < model.vocab_size:
@@ -586,14 +570,3 @@ def _beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pe
             states = _pairs(beam_gather([t for st in states for t in st], rows))
             order = order.to(torch.int32)
         return beam_backtrack(parents, toks, order), cum, length, states
-
-
-def _beam_search_plain(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
-                       no_repeat_ngram_size=0, banned_sequences=None):
-    """Model.beam_search (lm.py has the contract).  automaton and automaton_state are further keyword-only arguments
-    (_truncate.further_keywords)."""
-    return _beam_search(model, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens, no_repeat_ngram_size,
-                        banned_sequences)
-
-
-beam_search = _truncate.further_keywords(_beam_search_plain, _beam_search, _automaton.KEYWORDS, "beam_search")

@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import _automaton, _lib, _truncate
+from . import _lib
 from .functional import vmlmf_sequence
 
 
@@ -347,9 +347,10 @@ class Model(nn.Module):
             st = self._sample_state = dropout_state(dev, seed)
         return st
 
-    def _generate_plain(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
-                        eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
-                        no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0):
+    def generate(self, prompt, steps, states=None, temperature=1.0, seed=None, chunk=None, layer_path="layers", top_k=None, top_p=None,
+                 eos=None, min_length=0, repetition_penalty=1.0, logit_bias=None, banned_tokens=None, return_lengths=False,
+                 no_repeat_ngram_size=0, banned_sequences=None, frequency_penalty=0.0, presence_penalty=0.0, *, min_p=None, typical_p=None,
+                 epsilon_cutoff=None, eta_cutoff=None, automaton=None, automaton_state=None):
         """Continue `prompt` (T0, B) int64 - time-major as lm_test.minibatch - by `steps` tokens per row.  Returns (tokens (steps, B)
         int64, logprobs (steps, B), states); logprobs are the untempered log-softmax of the chosen tokens (what nll_loss charges), states
         have taken in the prompt and every generated token (Model.forward over torch.cat([prompt, tokens]) ends in the same states).
@@ -394,9 +395,7 @@ class Model(nn.Module):
         for a negative n, a negative or non-finite penalty, an empty sequence or one with a token outside the vocabulary, more than
         4096 sequence tokens in all, and - with a ban on - for a vocabulary that might run out of open tokens: V must exceed the tokens
         the other controls close + the prompt's length + steps + the number of sequences + 1.
-        Truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff: four further KEYWORD-ONLY arguments behind the ones above
-        (taken by _truncate.keywords around this function, so inspect.signature lists the parameters up to presence_penalty only) -
-        (all off by default: None, and min_p = 0, typical_p = 1.0, a cutoff of 0; with any of them on the choice
+        Truncation samplers - min_p, typical_p, epsilon_cutoff, eta_cutoff, keyword-only - (all off by default: None, and min_p = 0, typical_p = 1.0, a cutoff of 0; with any of them on the choice
         of every step is ONE launch of a library of its own behind the head's GEMM - vmlmf_truncate_choose,
         include/vmlmf_truncate.h - which runs top_k and top_p too; without them this is the call above, launch for launch, and that
         library is never opened).  They act on the tempered score z = c / tau - c the raw score, or the controlled score when eos,
@@ -410,8 +409,7 @@ class Model(nn.Module):
         unprocessed log-softmax; greedy decoding accepts them and is unchanged.  The choice is exact and repeats bit for bit.
         ValueError, before any device work, for a value outside those ranges and for any of them together with the history controls
         (no_repeat_ngram_size, banned_sequences, frequency_penalty, presence_penalty): that composition is out of scope.
-        Token automaton - automaton, automaton_state: two further KEYWORD-ONLY arguments, taken by the same wrapper (off by default:
-        None; with automaton= the choice of every step is ONE launch of a library of its own behind the head's GEMM -
+        Token automaton - automaton, automaton_state, keyword-only - (off by default: None; with automaton= the choice of every step is ONE launch of a library of its own behind the head's GEMM -
         vmlmf_automaton_choose, include/vmlmf_automaton.h -; without it this is the call above, launch for launch, and that library is
         never opened).  automaton: a vmlmf_amd.TokenAutomaton over the vocabulary - a dense table next (S, V) on the device, next[s][v]
         >= 0: in state s token v is open and leads to that state; forced, one_of, template and avoiding build the usual ones.  Every row
@@ -427,16 +425,11 @@ class Model(nn.Module):
         from . import decoding
         return decoding.generate(self, prompt, steps, states, temperature, seed, chunk, layer_path, top_k, top_p, eos, min_length,
                                  repetition_penalty, logit_bias, banned_tokens, return_lengths, no_repeat_ngram_size, banned_sequences,
-                                 frequency_penalty, presence_penalty)
+                                 frequency_penalty, presence_penalty, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                                 eta_cutoff=eta_cutoff, automaton=automaton, automaton_state=automaton_state)
 
-    def _generate_extended(self, *args, **kw):
-        from . import decoding
-        return decoding.generate(self, *args, **kw)
-
-    generate = _truncate.further_keywords(_generate_plain, _generate_extended, _truncate.KEYWORDS + _automaton.KEYWORDS, "generate")
-
-    def _beam_search_plain(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0,
-                           banned_tokens=None, no_repeat_ngram_size=0, banned_sequences=None):
+    def beam_search(self, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
+                    no_repeat_ngram_size=0, banned_sequences=None, *, automaton=None, automaton_state=None):
         """Continue `prompt` (T0, B) int64 by `steps` tokens along the `beams` (W) most probable hypotheses per row.  Returns (tokens
         (steps, B, W) int64, scores (B, W) fp32, lengths (B, W) int32, states): tokens[:, b, w] is hypothesis w of row b, best first;
         its score is the fp32 sum of the untempered log-softmax (bias included) of its tokens - what nll_loss charges -; states are per
@@ -462,8 +455,7 @@ class Model(nn.Module):
         beam's ban set from its history (vmlmf_history_bans on B W rows); without them the call is launch for launch what it was.
         ValueError for what generate() refuses for the same arguments, for eos among banned_tokens, and for a vocabulary in which a
         beam might run short of candidates: V < closed + T0 + steps + len(banned_sequences) + beams.
-        automaton, automaton_state: two further KEYWORD-ONLY arguments (taken by _truncate.further_keywords around this function, so
-        inspect.signature lists the parameters up to banned_sequences only) - generate()'s of the same names, per HYPOTHESIS: every beam
+        automaton, automaton_state (keyword-only): generate()'s of the same names, per HYPOTHESIS: every beam
         carries a state of the vmlmf_amd.TokenAutomaton, a live beam offers only what its state's table row opens, a survivor's state is
         its parent's moved on by its token (a finished parent's: unchanged).  The selection is then ONE launch of
         vmlmf_automaton_beam_step (include/vmlmf_automaton.h: the same kernel under a third offer policy); the beams' states travel with
@@ -472,16 +464,8 @@ class Model(nn.Module):
         constraint that admits fewer than `beams` sequences leaves the surplus hypotheses at score -inf: they repeat admitted ones,
         continued from the beams that start at -inf.  Without automaton= the call is launch for launch what it was."""
         from . import decoding
-        if min_length == 0 and banned_tokens is None and no_repeat_ngram_size == 0 and banned_sequences is None:
-            return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk)
         return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens,
-                                    no_repeat_ngram_size, banned_sequences)
-
-    def _beam_search_extended(self, *args, **kw):
-        from . import decoding
-        return decoding.beam_search(self, *args, **kw)
-
-    beam_search = _truncate.further_keywords(_beam_search_plain, _beam_search_extended, _automaton.KEYWORDS, "beam_search")
+                                    no_repeat_ngram_size, banned_sequences, automaton=automaton, automaton_state=automaton_state)
 
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
