@@ -90,7 +90,9 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     survivors' (hist, hist_len), fresh buffers - (None, None) when the controls keep no history.
     controls: an AutomatonBeamControls (_automaton.py: a TokenAutomaton, min_length, banned_tokens) - the selection is ONE launch of
     vmlmf_automaton_beam_step (csrc/vmlmf_automaton.hip) on beam_state (B W) int32, the beams' states (default: controls.start()); one
-    more result follows the seven: the survivors' states, a fresh buffer."""
+    more result follows the seven: the survivors' states, a fresh buffer.
+    controls: a GroupBeams (_beamgroup.py: groups, diversity_penalty) - the selection is ONE launch of vmlmf_beamgroup_step
+    (csrc/vmlmf_beamgroup.hip), the same kernel whose merge runs group by group; the seven results, nothing carried."""
     for t, what in ((h, "h"), (weight, "weight"), (cum, "cum")):
         _require(t, what)
     if bias is not None:

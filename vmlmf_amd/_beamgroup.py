@@ -1,0 +1,110 @@
+"""ctypes binding of the C ABI in include/vmlmf_beamgroup.h (libvmlmf_beamgroup.so, built in-tree by csrc/Makefile's `more` beside
+libvmlmf_hip.so): the step of diverse (group) beam search of the LM decoder - Model.group_beam_search.  The library is loaded on the
+first group step: beam_search(), generate(), score() and a training process never open it.
+
+There is no fallback: if the library is missing, or a call fails, this raises.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+from ._beam import check_beams, step_buffers, step_outputs
+from ._lib import ptr
+
+ABI_VERSION = 1
+
+# every symbol include/vmlmf_beamgroup.h declares: (restype, argtypes)
+_vp, _sz, _i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+SYMBOLS = {
+    "vmlmf_beamgroup_abi_version": (_i, []),
+    "vmlmf_beamgroup_last_error": (ctypes.c_char_p, []),
+    "vmlmf_beamgroup_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vmlmf_beamgroup_step": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i,
+                                  ctypes.c_float, _vp]),
+}
+
+LIBRARY = _lib.Library("libvmlmf_beamgroup.so", SYMBOLS, "vmlmf_beamgroup_abi_version", ABI_VERSION, "vmlmf_beamgroup_last_error",
+                       "stock-op fallback for the group beam-search step")
+lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
+
+
+def check_groups(beams, groups, diversity_penalty, V=None):
+    """(W, G, lambda) as the C ABI takes them; ValueError for what check_beams refuses, for groups < 1, for groups that do not divide
+    beams and for a diversity_penalty that is negative or not finite."""
+    W = check_beams(beams, V)
+    G = int(groups)
+    if G < 1:
+        raise ValueError(f"vmlmf_amd: groups must be >= 1, got {groups}")
+    if W % G != 0:
+        raise ValueError(f"vmlmf_amd: groups={G} must divide beams={W}: a group owns beams / groups slots")
+    lam = float(diversity_penalty)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"vmlmf_amd: diversity_penalty must be finite and >= 0, got {diversity_penalty}")
+    return W, G, lam
+
+
+def group_start(B, W, groups, device):
+    """(cum, finished, length), each (B, W), of a group search that starts: the first slot g W / G of every group at score 0, the
+    others at -inf."""
+    W, G, _ = check_groups(W, groups, 0.0)
+    cum = torch.full((B, W), float("-inf"), device=device)
+    cum[:, ::W // G] = 0.0
+    return cum, torch.zeros((B, W), dtype=torch.int32, device=device), torch.zeros((B, W), dtype=torch.int32, device=device)
+
+
+class GroupBeams:
+    """The grouping of one diverse beam search (Vijayakumar et al.) over B batch rows of W beams and a V-token vocabulary on `device`
+    (include/vmlmf_beamgroup.h): `groups` = G divides W, group g owns slots g W / G .. (g + 1) W / G - 1 of a row and keeps the best of
+    its own beams' candidates under total - diversity_penalty n, n the number of survivors the groups before it chose in this step with
+    the same token; the totals stay raw, so `scores` stay sums of plain log-probabilities.  It carries nothing from step to step
+    (`carried` is (), first_carried() is []) and owns no state; select() is the step's ONE launch (vmlmf_beamgroup_step), so
+    lm_beam_step(controls=), decoding.beam_steps and BeamGraph(controls=) take it as they take BeamControls.  start() gives a search's
+    first (cum, finished, length).  ValueError for what check_groups refuses, before any device work."""
+
+    carried = ()
+    keeps_history = False
+    eos, min_length = -1, 0        # (it holds no eos of its own: the step's is used)
+
+    def __init__(self, B, W, V, device, groups=2, diversity_penalty=0.5):
+        self.B, self.V = int(B), int(V)
+        self.W, self.groups, self.diversity_penalty = check_groups(W, groups, diversity_penalty, self.V)
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev                           # (with its index: what a launch's tensors are compared with)
+
+    def first_carried(self):
+        return []
+
+    def start(self):
+        """(cum, finished, length) of a search that starts (group_start)."""
+        return group_start(self.B, self.W, self.groups, self.device)
+
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, **others):
+        """lm_beam_step's selection in groups (group_select); it takes none of the carried keywords."""
+        return group_select(scores, bias, cum, finished, length, eos, embed, self, buffers)
+
+    def clone(self):
+        """These controls (they own no state a launch moves: a BeamGraph's warm-up runs on the same object)."""
+        return self
+
+
+def group_select(scores, bias, cum, finished, length, eos, embed, controls, buffers=None):
+    """The vmlmf_beamgroup_step launch on checked, contiguous arguments (scores (B W, V) without the bias, eos an int, -1: none).
+    lm_beam_step's seven results."""
+    B, W = cum.shape
+    V = scores.shape[1]
+    dev = scores.device
+    if not isinstance(controls, GroupBeams) or (controls.B, controls.W, controls.V) != (B, W, V) or controls.device != dev:
+        raise RuntimeError(f"vmlmf_amd.lm_beam_step: controls must be a GroupBeams for {B} x {W} beams over {V} tokens on {dev}")
+    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
+    H = embed.shape[1] if embed is not None else 1
+    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
+    LIBRARY.call(dev, "vmlmf_beamgroup_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
+                 ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8,
+                 controls.groups, controls.diversity_penalty)
+    return parent, token, total, fin, ln, xn, src

@@ -10,6 +10,14 @@
 //   hist / hist_len / hist_out / hist_len_out / overflow / cap    the histories the last workgroup of a batch row copies
 // (a policy without keeps_history() keeps none), and, where it moves a state of its own on with the survivors,
 //   survivor(slot, parent's row, parent finished, token, has a candidate)    called by the thread that writes the slot's outputs
+// and, where the merge runs in GROUPS (libvmlmf_beamgroup.so, vmlmf_beamgroup.hip: diverse beam search), the members
+//   int groups; float lambda     G divides W; group g owns beams and slots g Wg .. g Wg + Wg - 1 (Wg = W / G) and keeps the first Wg of
+//                                ITS beams' candidates under aug = total - lambda n, n = how many survivors the groups before it chose in
+//                                this step with the candidate's token and a live parent (include/vmlmf_beamgroup.h has the contract)
+// The per-beam half needs no change for it.  Group g penalises at most g Wg <= W - Wg distinct tokens, and a beam holds each token
+// once: among the beam's first W raw candidates at least Wg are unpenalised.  Each of those precedes every candidate of that beam
+// outside its first W - in the raw order, and still after the penalty, because aug <= total (a rounded non-negative product is
+// subtracted).  So a survivor of group g is among the first W raw candidates of one of the group's Wg beams: what the workspace holds.
 // Selection: a workgroup per BEAM, a ticket per batch row.  A survivor of the row is among its own beam's first W candidates, so each
 // workgroup forms those (W rounds of a workgroup-wide argmax over the threads' own best candidates; after a round only the thread
 // that held the winner looks for its next one, strictly after the winner in the order - the winners wait in LDS, a global store per
@@ -69,6 +77,10 @@ template <class P, class = void>
 struct moves_states : std::false_type {};
 template <class P>
 struct moves_states<P, std::void_t<decltype(&P::survivor)>> : std::true_type {};
+template <class P, class = void>
+struct merges_in_groups : std::false_type {};
+template <class P>
+struct merges_in_groups<P, std::void_t<decltype(&P::groups), decltype(&P::lambda)>> : std::true_type {};
 
 typedef unsigned long long u64;
 // A candidate as ONE 64-bit key whose unsigned order is the order of the search: the order-preserving image of the total in the high
@@ -260,10 +272,41 @@ __global__ __launch_bounds__(BS_NT) void beam_step_kernel(BeamStepArgs a, P p) {
   // thread that held a winner is out)
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   u64 mine = tid < W * W ? a.cand[(size_t)b * W * W + tid] : BS_NONE;
-  for (int r = 0; r < W; ++r) {
-    const u64 k = wg_max(S, r, mine);
-    if (tid == 0) S.sel[r] = k;
-    if (mine == k) mine = BS_NONE;
+  if constexpr (merges_in_groups<P>::value) {
+    // G passes, W rounds in all: in pass g the threads of group g's beams (thread tid holds a candidate of beam tid / W) rank their
+    // candidate by aug, everybody else holds BS_NONE; the thread that held a round's winner leaves its RAW key in the slot and the
+    // token it chose (-1: a finished parent's eos, which is no choice) in the totals' room, free since the rounds; behind a barrier
+    // the next group counts its tokens there.  Every thread calls every wg_max.
+    const int Wg = W / p.groups;
+    int* chosen = reinterpret_cast<int*>(S.vals);
+    const int beam = tid < W * W ? tid / W : 0, idx = index_of(mine);
+    const int tok = idx - beam * V;   // (meaningful where mine is a candidate)
+    const bool pdone = mine != BS_NONE && a.eos >= 0 && a.finished[b * W + beam] != 0;
+    for (int g = 0; g < p.groups; ++g) {
+      u64 key = BS_NONE;
+      if (mine != BS_NONE && beam / Wg == g) {
+        int n = 0;
+        for (int i = 0; i < g * Wg; ++i) n += chosen[i] == tok ? 1 : 0;
+        key = pdone || n == 0 ? mine : key_of(__fsub_rn(total_of(mine), __fmul_rn(p.lambda, (float)n)), idx);
+      }
+      for (int r = 0; r < Wg; ++r) {
+        const int slot = g * Wg + r;
+        const u64 k = wg_max(S, slot, key);
+        if (k == BS_NONE) {   // nothing left that can be ordered in this group, and nothing will be
+          if (tid == 0) S.sel[slot] = BS_NONE, chosen[slot] = -1;
+        } else if (key == k) {
+          S.sel[slot] = mine, chosen[slot] = pdone ? -1 : tok;
+          key = BS_NONE;
+        }
+      }
+      __syncthreads();
+    }
+  } else {
+    for (int r = 0; r < W; ++r) {
+      const u64 k = wg_max(S, r, mine);
+      if (tid == 0) S.sel[r] = k;
+      if (mine == k) mine = BS_NONE;
+    }
   }
   __syncthreads();
   if (tid == 0) __hip_atomic_store(a.ticket + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,11 +1,11 @@
-"""Decoding the language model (lm.Model): what stands behind Model.generate and Model.beam_search.  The reference has no decoder;
+"""Decoding the language model (lm.Model): what stands behind Model.generate, Model.beam_search and Model.group_beam_search.  The reference has no decoder;
 lm.py holds its layers, this module everything that continues a prompt with them.
 
   lm_sample, sample_filters                  the head and the choice of the next token in one launch (C ABI: vmlmf_lm_sample ...)
   lm_beam_step, beam_gather, beam_backtrack  the beam step, the state reorder and the read-back (_beam.py, a library of its own)
   decode_steps, beam_steps                   the step loops: a choice, then the layers at T = 1 - no host synchronisation
   DecodeGraph, BeamGraph                     those loops captured into a hipGraph
-  generate, beam_search                      the calls behind Model's methods of the same names, where the contract is written down
+  generate, beam_search, group_beam_search   the calls behind Model's methods of the same names, where the contract is written down
 (scoring.py - Model.score - runs on this module's session too.)
 """
 from __future__ import annotations
@@ -14,10 +14,11 @@ import contextlib
 
 import torch
 
-from . import _automaton, _beam, _beamctl, _decode, _history, _lib, _truncate
+from . import _automaton, _beam, _beamctl, _beamgroup, _decode, _history, _lib, _truncate
 from ._automaton import AutomatonBeamControls, AutomatonControls, TokenAutomaton  # noqa: F401
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._beamctl import BeamControls
+from ._beamgroup import GroupBeams
 from ._decode import DecodeControls
 from ._history import HistoryControls
 from ._lib import ptr
@@ -565,6 +566,45 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
         if alpha > 0.0:
             key = cum / length.to(torch.float32) ** alpha
             order = torch.sort(key, dim=1, descending=True, stable=True).indices
+            cum, length = cum.gather(1, order), length.gather(1, order)
+            rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
+            states = _pairs(beam_gather([t for st in states for t in st], rows))
+            order = order.to(torch.int32)
+        return beam_backtrack(parents, toks, order), cum, length, states
+
+
+def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_penalty=0.5, states=None, eos=None, length_penalty=0.0,
+                      chunk=None):
+    """Model.group_beam_search (lm.py has the contract)."""
+    W, G, lam = _beamgroup.check_groups(beams, groups, diversity_penalty, model.vocab_size)
+    steps, alpha = int(steps), float(length_penalty)
+    if eos is not None and not 0 <= int(eos) < model.vocab_size:
+        raise ValueError(f"vmlmf_amd: Model.group_beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
+    if not alpha >= 0.0:
+        raise ValueError(f"vmlmf_amd: Model.group_beam_search: length_penalty must be >= 0, got {length_penalty}")
+    if steps < 0:
+        raise ValueError(f"vmlmf_amd: Model.group_beam_search: steps must be >= 0, got {steps}")
+    _check_chunk("group_beam_search", chunk, steps)
+    _check_call(model, prompt, "group_beam_search", "group beam-step kernel (vmlmf_beamgroup_step)")
+    B, dev = prompt.shape[1], prompt.device
+    Wg = W // G
+    with _session(model, prompt, states) as (h, states):
+        controls = GroupBeams(B, W, model.vocab_size, dev, G, lam)
+        h = h.repeat_interleave(W, 0)
+        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        cum, finished, length = controls.start()
+        if steps == 0:
+            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
+        (parents, toks), carried = _run(
+            steps, chunk,
+            lambda: _beamed(model, _join_beams(h, states, cum, finished, length, []), steps, eos, None, controls),
+            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls))
+        _, states, cum, finished, length, _ = _split_beams(carried, controls)
+        order = None
+        if alpha > 0.0:      # the stable re-sort within each group: no hypothesis leaves its group
+            key = (cum / length.to(torch.float32) ** alpha).view(B, G, Wg)
+            order = torch.sort(key, dim=2, descending=True, stable=True).indices
+            order = (order + torch.arange(G, device=dev)[None, :, None] * Wg).view(B, W)
             cum, length = cum.gather(1, order), length.gather(1, order)
             rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
             states = _pairs(beam_gather([t for st in states for t in st], rows))

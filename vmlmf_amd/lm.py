@@ -467,6 +467,35 @@ class Model(nn.Module):
         return decoding.beam_search(self, prompt, steps, beams, states, eos, length_penalty, chunk, min_length, banned_tokens,
                                     no_repeat_ngram_size, banned_sequences, automaton=automaton, automaton_state=automaton_state)
 
+    def group_beam_search(self, prompt, steps, beams=4, *, groups=2, diversity_penalty=0.5, states=None, eos=None, length_penalty=0.0,
+                          chunk=None):
+        """Diverse beam search (Vijayakumar et al., "Diverse Beam Search"): beam_search() whose `beams` (W) hypotheses per row are kept
+        in `groups` (G, dividing W) groups of Wg = W / G that never exchange beams, each group steered away from the tokens the groups
+        before it chose in the same step.  Everything behind `beams` is keyword-only.  Returns beam_search()'s (tokens (steps, B, W)
+        int64, scores (B, W) fp32, lengths (B, W) int32, states), group-major: group g owns slots g Wg .. g Wg + Wg - 1, the best
+        hypothesis of each group first; scores are fp32 sums of plain log-probabilities, as beam_search()'s.
+        Start: slot g Wg of every group at score 0, the other slots at -inf, all on the prompt's state.
+        Step: the groups are processed in order g = 0 .. G - 1.  The beams of group g offer what they offer in beam_search() - a live
+        beam w every token v at total = score[w] + log_softmax[v], a finished beam (w, eos) alone at its score so far.  A live beam's
+        candidate is ranked by aug = total - diversity_penalty n, where n counts the survivors that groups 0 .. g - 1 of this row chose
+        in this step with token v and a live parent (a finished beam's padding eos is not a choice and does not count); aug is formed
+        in fp32 as two separately rounded operations (no fused multiply-add; for n = 0 it is the total).  A finished beam's candidate is
+        not penalised.  Larger aug first, equal aug to the lower flat index w V + v (w the beam's index in the whole row); the first
+        Wg candidates go to the group's slots in that order, each at its RAW total.  The penalty steers the step's choice and is never
+        accumulated: this is the paper's objective.  (Hugging Face's num_beam_groups / diversity_penalty adds the penalty into the
+        beam scores it carries; its scores are therefore not sums of log-probabilities, and its later steps differ.)
+        One launch per step behind the head's GEMM (decoding.GroupBeams, vmlmf_beamgroup_step - beam_search()'s kernel whose merge runs
+        group by group; a library of its own, opened by the first call), exact and bit-identical from run to run; the state reorder
+        and the layers are beam_search()'s.  With length_penalty = a > 0 the stable re-sort by score / length ** a happens within each
+        group.  chunk=K captures K steps into a hipGraph (BeamGraph): the eager call's bits.  groups=1 is beam_search() to the bit;
+        diversity_penalty=0 with G > 1 gives G identical groups.
+        ValueError, before any device work, for groups < 1, beams % groups != 0, a diversity_penalty that is negative or not finite,
+        and for what beam_search() refuses of beams, eos, length_penalty, steps and chunk.  There are no token controls and no
+        automaton here."""
+        from . import decoding
+        return decoding.group_beam_search(self, prompt, steps, beams, groups=groups, diversity_penalty=diversity_penalty, states=states,
+                                          eos=eos, length_penalty=length_penalty, chunk=chunk)
+
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
         tokens[:-1] and the targets tokens[1:].  Otherwise tokens and targets are both (T, B) int64, as lm_test.minibatch hands them
