@@ -1,4 +1,4 @@
-"""Decoding the language model (lm.Model): what stands behind Model.generate, Model.beam_search and Model.group_beam_search.  The reference has no decoder;
+"""Decoding the language model (lm.Model): what stands behind Model.generate, Model.beam_search, Model.group_beam_search and Model.contrastive_search.  The reference has no decoder;
 lm.py holds its layers, this module everything that continues a prompt with them.
 
   lm_sample, sample_filters                  the head and the choice of the next token in one launch (C ABI: vmlmf_lm_sample ...)
@@ -6,6 +6,8 @@ lm.py holds its layers, this module everything that continues a prompt with them
   decode_steps, beam_steps                   the step loops: a choice, then the layers at T = 1 - no host synchronisation
   DecodeGraph, BeamGraph                     those loops captured into a hipGraph
   generate, beam_search, group_beam_search   the calls behind Model's methods of the same names, where the contract is written down
+  lm_contrast_step, contrast_steps, ContrastGraph, contrastive_search    contrastive search: the step's one launch (_contrast.py, a
+                                             library of its own), its loop, the loop captured, the call behind Model.contrastive_search
 (scoring.py - Model.score - runs on this module's session too.)
 """
 from __future__ import annotations
@@ -14,11 +16,12 @@ import contextlib
 
 import torch
 
-from . import _automaton, _beam, _beamctl, _beamgroup, _decode, _history, _lib, _truncate
+from . import _automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _truncate
 from ._automaton import AutomatonBeamControls, AutomatonControls, TokenAutomaton  # noqa: F401
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._beamctl import BeamControls
 from ._beamgroup import GroupBeams
+from ._contrast import ContrastControls, lm_contrast_step
 from ._decode import DecodeControls
 from ._history import HistoryControls
 from ._lib import ptr
@@ -610,3 +613,89 @@ def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_pena
             states = _pairs(beam_gather([t for st in states for t in st], rows))
             order = order.to(torch.int32)
         return beam_backtrack(parents, toks, order), cum, length, states
+
+
+# ---- contrastive search ------------------------------------------------------------------------------------------------------------
+def _block_heads(t, k):
+    """Row b k of every block of k rows (the rows of a block are equal): (..., B k, H) -> (..., B, H)."""
+    return t.index_select(t.dim() - 2, torch.arange(0, t.shape[-2], k, device=t.device))
+
+
+def contrast_steps(model, h, states, controls, steps, return_penalties=False):
+    """`steps` steps of contrastive search from the top layer's output h (B, H) and the layers' states on B k rows (row b k + j: the
+    rows of a block equal): per step the head's GEMM and the vmlmf_score_rows launch that names the k candidates (scoring.lm_score,
+    top=k: the project's one selection), the embedding, the layers at T = 1 on the B k candidate rows, ONE vmlmf_contrast_choose launch
+    (lm_contrast_step) and ONE vmlmf_beam_gather launch that makes every state row of a block follow the chosen candidate.  No host
+    synchronisation: capturable (ContrastGraph).  Returns (tokens, logprobs[, penalties] (steps, B), h, states, before): `before` are
+    the states in front of the last step's layers - they have taken in everything but the last token."""
+    from .scoring import lm_score
+    toks, lps, pens = [], [], []
+    before = states
+    for _ in range(steps):
+        _, _, cand_tok, cand_logp = lm_score(h, model.fc.w, model.fc.b, None, controls.k)
+        x = model.embed(cand_tok.reshape(-1))
+        y, after = decode_layers(model, x.unsqueeze(0), states, "layers")
+        tok, lp, chosen, sim, h, src = lm_contrast_step(y[-1], cand_tok, cand_logp, controls)
+        toks.append(tok)
+        lps.append(lp)
+        if return_penalties:
+            pens.append(sim.gather(1, chosen.to(torch.int64)[:, None])[:, 0])
+        before = states
+        states = _pairs(beam_gather([t for st in after for t in st], src))
+    outs = (torch.stack(toks), torch.stack(lps)) + ((torch.stack(pens),) if return_penalties else ())
+    return (*outs, h, states, before)
+
+
+def _contrasted(model, carried, controls, steps, return_penalties):
+    """contrast_steps on a flat list [h, before ..., states ...] -> (outputs, that list after the steps).  `before` stands in front of
+    the states: after one step it IS the incoming states, and a graph's copy-back (_StepGraph._capture) writes its buffers in list
+    order - the states' buffers must still hold the old states when `before` is copied out of them."""
+    n = (len(carried) - 1) // 2
+    *outs, h, states, before = contrast_steps(model, carried[0], _pairs(carried[1 + n:]), controls, steps, return_penalties)
+    return tuple(outs), [h, *(t for st in before for t in st), *(t for st in states for t in st)]
+
+
+class ContrastGraph(_StepGraph):
+    """`steps` steps of Model.contrastive_search (contrast_steps) captured once into a hipGraph - linear, on one stream.  h (B, H) and
+    states (B k rows) are those of contrast_steps; replay() continues from where the previous replay stopped - h and the states live in
+    this object's buffers, the history, its length on the device, finished and length in `controls`, which the captured launches read
+    and write in place (the warm-up runs on a clone) - and returns (tokens, logprobs[, penalties]), each (steps, B).  The ticket and
+    the workspace are the controls' own; the layers read parameter images packed at construction: build a new graph after the
+    parameters change.  The controls' capacity must cover every replay."""
+
+    def __init__(self, model, h, states, steps, controls, return_penalties=False):
+        self.model, self.steps, self.controls = model, int(steps), controls
+        flat = [t for st in states for t in st]
+        step = lambda carried, controls=controls: _contrasted(model, carried, controls, self.steps, return_penalties)
+        self._capture(model, [h, *flat, *flat], step, lambda carried: step(carried, controls.clone()))
+        n = len(flat)
+        self.h, self.before, self.states = self.carried[0], _pairs(self.carried[1:1 + n]), _pairs(self.carried[1 + n:])
+        self.tokens, self.logprobs = self.outputs[:2]
+
+
+def contrastive_search(model, prompt, steps, top_k=4, penalty_alpha=0.6, *, states=None, eos=None, chunk=None, return_penalties=False):
+    """Model.contrastive_search (lm.py has the contract)."""
+    k, alpha = _contrast.check_contrast(top_k, penalty_alpha, model.vocab_size, model.hidden_size)
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError(f"vmlmf_amd: Model.contrastive_search: steps must be >= 0, got {steps}")
+    if eos is not None and not 0 <= int(eos) < model.vocab_size:
+        raise ValueError(f"vmlmf_amd: Model.contrastive_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
+    if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 and prompt.shape[0] < 1:
+        raise ValueError("vmlmf_amd: Model.contrastive_search: the prompt needs T0 >= 1 tokens: the first step compares with the history behind them")
+    _check_chunk("contrastive_search", chunk, steps)
+    _check_call(model, prompt, "contrastive_search", "contrastive-step kernel (vmlmf_contrast_choose)")
+    T0, B = prompt.shape
+    dev = prompt.device
+    with _activations(model, prompt, states) as (hs, states):
+        controls = ContrastControls(B, model.hidden_size, dev, T0 + max(steps, 1), k, alpha, eos, model.vocab_size)
+        controls.append(hs)
+        if steps == 0:
+            empty = torch.empty((0, B), device=dev)
+            return (empty.to(torch.int64), empty, controls.length, *((empty.clone(),) if return_penalties else ()), states)
+        wide = [tuple(t.repeat_interleave(k, t.dim() - 2) for t in st) for st in states]
+        flat = [t for st in wide for t in st]
+        outs, carried = _run(steps, chunk, lambda: _contrasted(model, [hs[-1], *flat, *flat], controls, steps, return_penalties),
+                             lambda: ContrastGraph(model, hs[-1], wide, int(chunk), controls, return_penalties))
+        before = _pairs([_block_heads(t, k) for t in carried[1:1 + len(flat)]])
+        return (outs[0], outs[1], controls.length.clone(), *outs[2:], before)

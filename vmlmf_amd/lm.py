@@ -496,6 +496,39 @@ class Model(nn.Module):
         return decoding.group_beam_search(self, prompt, steps, beams, groups=groups, diversity_penalty=diversity_penalty, states=states,
                                           eos=eos, length_penalty=length_penalty, chunk=chunk)
 
+    def contrastive_search(self, prompt, steps, top_k=4, penalty_alpha=0.6, *, states=None, eos=None, chunk=None, return_penalties=False):
+        """Contrastive search (Su et al., "A Contrastive Framework for Neural Text Generation"; Hugging Face's penalty_alpha / top_k):
+        the deterministic decoder that weighs a candidate's probability against its similarity with what the row has already said, and
+        so does not fall into the repetition loops of greedy and beam decoding.  Continue `prompt` (T0, B) int64, T0 >= 1, by `steps`
+        tokens per row; everything behind penalty_alpha is keyword-only.  Returns (tokens (steps, B) int64, logprobs (steps, B),
+        lengths (B) int32, states) - with return_penalties=True (tokens, logprobs, lengths, penalties (steps, B), states).
+        Per step and row b: (1) the candidates are the k = top_k most probable tokens in the project's one total order (larger score
+        first, equal scores to the lower index; Model.score's selection, vmlmf_score_rows), p_j = exp(logprob_j) under the WHOLE
+        distribution; (2) every candidate is embedded and taken through the layers at T = 1 from the row's states (B k rows), h_j the
+        top layer's output; (3) s_j = the largest cosine of h_j with the row's history - the top layer's outputs behind every prompt
+        token, the last included, and behind every token chosen so far; a zero vector has cosine 0 with everything; (4) j* = argmax_j
+        (1 - penalty_alpha) p_j - penalty_alpha s_j in fp32, equal values to the lower j, a NaN value loses to every number; (5) the
+        token is candidate j*'s, its logprob the plain log-softmax (what score() and generate() report for it), penalties hold s_j*;
+        h_j* goes behind the history and to the next head GEMM, the states follow candidate j*.  Steps (3) to (5) are ONE launch
+        (decoding.lm_contrast_step: vmlmf_contrast_choose, include/vmlmf_contrast.h; a library of its own, opened by the first call)
+        that reads the row's history once; its results are the same bits from run to run.  penalty_alpha = 0 and top_k = 1 are greedy
+        decoding.
+        eos: a row that emits it is finished - it is padded with eos at log-probability 0, its history stops growing; lengths count
+        the tokens up to and including eos (`steps` where none came).  Decoding always runs the full `steps`.
+        states (default: state_init) are taken in front of the prompt; the returned states have taken in the prompt and tokens[:-1] -
+        everything but the last token, so a further call continues from them with tokens[-1:] as its prompt (Model.forward over
+        torch.cat([prompt, tokens[:-1]]) ends in them; with steps = 0 they are the prompt's).  A finished row's states are not
+        meaningful.  chunk=K (steps % K == 0): K steps are captured into a hipGraph (decoding.ContrastGraph) and replayed steps / K
+        times, the history's length living on the device: the eager call's bits.  No random generator is touched; every module's
+        train / eval flag is as the caller left it afterwards.
+        ValueError, before any device work, for top_k outside [1, min(16, V)], a penalty_alpha outside [0, 1] or not finite, a hidden
+        size whose top_k candidates exceed the kernel's LDS budget (top_k * 4 * ceil(H / 4) > 14336), T0 < 1, eos outside [0, V), steps
+        < 0 and a chunk that does not divide steps; RuntimeError for CPU tensors.  There are no token controls, filters or automata
+        here: that composition is out of scope."""
+        from . import decoding
+        return decoding.contrastive_search(self, prompt, steps, top_k, penalty_alpha, states=states, eos=eos, chunk=chunk,
+                                           return_penalties=return_penalties)
+
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
         tokens[:-1] and the targets tokens[1:].  Otherwise tokens and targets are both (T, B) int64, as lm_test.minibatch hands them
