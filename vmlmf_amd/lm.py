@@ -552,3 +552,34 @@ class Model(nn.Module):
         reads a value back from the device, so it does not to look for them (such a target's position gives NaN and -1)."""
         from . import scoring
         return scoring.score(self, tokens, targets, states, lengths, top, chunk_rows)
+
+    def cache_score(self, tokens, targets=None, *, theta=0.3, lam=0.1, window=500, cache=None, states=None, return_parts=False,
+                    chunk_rows=2048):
+        """score() under a continuous cache (Grave, Joulin and Usunier, "Improving Neural Language Models with a Continuous Cache"):
+        the model's distribution mixed with one over the tokens that followed the last `window` positions, each weighted by how
+        close the top layer's output behind it is to the current one - what lowers an LSTM language model's perplexity on a text
+        that repeats its words, without retraining.  tokens / targets are score()'s: targets=None takes (T + 1, B) int64 tokens,
+        time-major, else both are (T, B); everything behind targets is keyword-only.  Returns (logprobs (T, B) fp32, states, cache) -
+        with return_parts=True (logprobs, vocab_logprobs, cache_logprobs, states, cache).
+        Per row a cache holds pairs (k_j, w_j): k_j the top layer's output behind a token, w_j the token that came next.  For a
+        position with output q, target y, vocabulary log-probability lv (score()'s logprobs, unchanged: scoring.lm_score) and the
+        band of the last m = min(window, pairs so far) pairs strictly before it:
+            s_j  = theta * dot(q, k_j)
+            lc   = log(sum_{j: w_j == y} exp(s_j - M)) - log(sum_j exp(s_j - M)),  M = max_j s_j        -inf where no w_j == y
+            logp = logaddexp(log1p(-lam) + lv, log(lam) + lc)
+        m == 0 (an empty cache) and lam == 0 give lv's bits; no match in the band gives log1p(-lam) + lv; a band whose every token
+        is y gives lc == 0.0 exactly.  The position's own pair (q, y) enters the cache after it has been scored.
+        cache (default: an empty NeuralCache(B, H, device, window)) is moved on in place and returned with the states: both feed the
+        next call, which is how a corpus is walked in chunks (lm_test.py's perplexity: 35 positions at a time); the chunking changes
+        the results in rounding only.  A given cache must be one of this B, H and window.
+        The inputs run once through features() in eval mode, without autograd and on kept parameter images; then score()'s head and,
+        for the whole call, ONE launch of a library of its own (scoring.lm_cache_score: vmlmf_ncache_score, include/vmlmf_ncache.h;
+        opened by the first call) behind one copy of the carried keys and the call's outputs into a (B, n + T, H) buffer.  Its
+        results are the same bits from run to run.  Every module's train / eval flag is as the caller left it afterwards; no random
+        generator is touched; no value is read back from the device.
+        ValueError, before any device work, for a window < 1, a theta that is not finite, a lam outside [0, 1), a hidden size above
+        2048, chunk_rows < 1, tokens that are not 2-D int64, targets of another shape or type, fewer than one position and a cache
+        of another B, H or window; RuntimeError for CPU tensors.  A target outside [0, V) is the caller's error, as in score()."""
+        from . import scoring
+        return scoring.cache_score(self, tokens, targets, theta=theta, lam=lam, window=window, cache=cache, states=states,
+                                   return_parts=return_parts, chunk_rows=chunk_rows)

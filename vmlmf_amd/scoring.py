@@ -4,12 +4,16 @@ module says how probable a text is, token by token.
   lm_score    the head's GEMM and ONE launch per chunk of rows (C ABI: vmlmf_score_rows, a library of its own; _score.py): a target
               token's log-probability and rank, and the row's most probable tokens
   score       the call behind Model.score, where the contract is written down
+  lm_cache_score  ONE launch per call (C ABI: vmlmf_ncache_score, a library of its own; _ncache.py): the positions' log-probabilities
+              under the model mixed with a continuous cache of the last `window` outputs and the tokens that followed them
+  cache_score the call behind Model.cache_score, where the contract is written down
 """
 from __future__ import annotations
 
 import torch
 
-from . import _score
+from . import _ncache, _score
+from ._ncache import NeuralCache, lm_cache_score  # noqa: F401 (the package's exports)
 from .functional import _require_hip
 
 
@@ -94,3 +98,37 @@ def score(model, tokens, targets=None, states=None, lengths=None, top=0, chunk_r
     with decoding._activations(model, inputs, states) as (h, states):
         out = lm_score(h, model.fc.w, model.fc.b, y.reshape(-1), k, chunk_rows)
     return (*(t.view(T, B, *t.shape[1:]) for t in out), states)
+
+
+def cache_score(model, tokens, targets=None, *, theta=0.3, lam=0.1, window=500, cache=None, states=None, return_parts=False,
+                chunk_rows=2048):
+    """Model.cache_score (lm.py has the contract)."""
+    from . import decoding
+    H = model.hidden_size
+    window, theta, lam = _ncache.check_ncache(window, theta, lam, H)
+    chunk_rows = _check_chunk_rows(chunk_rows, "Model.cache_score")
+    if not (isinstance(tokens, torch.Tensor) and tokens.dim() == 2 and tokens.dtype == torch.int64):
+        raise ValueError("vmlmf_amd: Model.cache_score takes (T, B) int64 tokens, time-major")
+    if targets is None:
+        if tokens.shape[0] < 2:
+            raise ValueError(f"vmlmf_amd: Model.cache_score without targets takes (T + 1, B) tokens, T >= 1; got {tuple(tokens.shape)}")
+    elif not (isinstance(targets, torch.Tensor) and targets.dtype == torch.int64 and targets.shape == tokens.shape and tokens.shape[0] >= 1):
+        raise ValueError(f"vmlmf_amd: Model.cache_score takes int64 targets of the tokens' shape {tuple(tokens.shape)}, T >= 1")
+    B = tokens.shape[1]
+    if cache is not None:
+        if not isinstance(cache, NeuralCache):
+            raise ValueError(f"vmlmf_amd: Model.cache_score: cache must be a NeuralCache, got {type(cache).__name__}")
+        if (cache.B, cache.H, cache.window) != (B, H, window):
+            raise ValueError(f"vmlmf_amd: Model.cache_score: the cache is one of B={cache.B}, H={cache.H}, window={cache.window}; the call "
+                             f"needs B={B}, H={H}, window={window}")
+    decoding._check_call(model, tokens, "cache_score", "cache-scoring kernel (vmlmf_ncache_score)")
+    if targets is not None:
+        decoding._check_call(model, targets, "cache_score", "cache-scoring kernel (vmlmf_ncache_score)")
+    inputs, y = (tokens[:-1], tokens[1:]) if targets is None else (tokens, targets)
+    T = inputs.shape[0]
+    if cache is None:
+        cache = NeuralCache(B, H, tokens.device, window)
+    with decoding._activations(model, inputs, states) as (h, states):
+        lv = lm_score(h, model.fc.w, model.fc.b, y.reshape(-1), 0, chunk_rows)[0].view(T, B)
+        logp, lc = lm_cache_score(h, y, lv, cache, theta, lam)
+    return (logp, lv, lc, states, cache) if return_parts else (logp, states, cache)
