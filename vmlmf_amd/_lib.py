@@ -177,14 +177,15 @@ class VmlmfError(RuntimeError):
 
 def build(force=False, jobs=8):
     """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so and the seven side libraries beside it (the Makefile's
-    `all`), then libvmlmf_beamgroup.so (its `more`), libvmlmf_contrast.so (its `extra`) and libvmlmf_ncache.so (its `further`); hipcc
-    cross-compiles."""
+    `all`), then libvmlmf_beamgroup.so (its `more`), libvmlmf_contrast.so (its `extra`), libvmlmf_ncache.so (its `further`) and
+    libvmlmf_sbeam.so (its `beyond`); hipcc cross-compiles."""
     if force:
         subprocess.run(["make", "-C", CSRC, "clean"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "all"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "more"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "extra"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "further"], check=True, stdout=subprocess.DEVNULL)
+    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "beyond"], check=True, stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 

@@ -8,6 +8,9 @@ lm.py holds its layers, this module everything that continues a prompt with them
   generate, beam_search, group_beam_search   the calls behind Model's methods of the same names, where the contract is written down
   lm_contrast_step, contrast_steps, ContrastGraph, contrastive_search    contrastive search: the step's one launch (_contrast.py, a
                                              library of its own), its loop, the loop captured, the call behind Model.contrastive_search
+  lm_sbeam_step, sbeam_steps, StochasticBeamGraph, stochastic_beam_search    stochastic beam search - sequences sampled without
+                                             replacement: the step's one launch (_sbeam.py, a library of its own), its loop, the loop
+                                             captured, the call behind Model.stochastic_beam_search
 (scoring.py - Model.score - runs on this module's session too.)
 """
 from __future__ import annotations
@@ -16,7 +19,7 @@ import contextlib
 
 import torch
 
-from . import _automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _truncate
+from . import _automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _sbeam, _truncate
 from ._automaton import AutomatonBeamControls, AutomatonControls, TokenAutomaton  # noqa: F401
 from ._beam import lm_beam_step, beam_gather, beam_backtrack  # noqa: F401
 from ._beamctl import BeamControls
@@ -24,6 +27,7 @@ from ._beamgroup import GroupBeams
 from ._contrast import ContrastControls, lm_contrast_step
 from ._decode import DecodeControls
 from ._history import HistoryControls
+from ._sbeam import StochasticBeams, lm_sbeam_step
 from ._lib import ptr
 from ._truncate import Truncation
 from .functional import PackCache, _require_hip, _workspace, dropout_advance, sample_ticket
@@ -699,3 +703,82 @@ def contrastive_search(model, prompt, steps, top_k=4, penalty_alpha=0.6, *, stat
                              lambda: ContrastGraph(model, hs[-1], wide, int(chunk), controls, return_penalties))
         before = _pairs([_block_heads(t, k) for t in carried[1:1 + len(flat)]])
         return (outs[0], outs[1], controls.length.clone(), *outs[2:], before)
+
+
+# ---- stochastic beam search --------------------------------------------------------------------------------------------------------
+def sbeam_steps(model, h, states, cum, finished, length, perturbed, draw, steps, eos, state, buffers=None):
+    """`steps` steps of stochastic beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE
+    selection launch (lm_sbeam_step: totals, Gumbel noise, the top-down perturbed values, the W survivors of each batch row in order,
+    their next input rows), ONE launch that makes the 2 L state tensors follow their hypotheses (beam_gather), then the layers at
+    T = 1 on the B W rows.  state: the {seed, offset} snapshot every step draws from; the steps differ by `draw`, which the launch
+    counts on the device.  No host synchronisation: capturable (StochasticBeamGraph).  Returns (parents, tokens (steps, B, W), h,
+    states, cum, finished, length, perturbed, draw)."""
+    parents, toks = [], []
+    for _ in range(steps):
+        par, tok, cum, finished, length, x, src, perturbed, draw = lm_sbeam_step(h, model.fc.w, model.fc.b, cum, finished, length, perturbed,
+                                                                                 draw, state, eos, model.embed.w, buffers)
+        parents.append(par)
+        toks.append(tok)
+        flat = beam_gather([t for st in states for t in st], src)
+        states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
+        y, states = decode_layers(model, x.unsqueeze(0), states, "layers")
+        h = y[-1]
+    return (torch.stack(parents), torch.stack(toks), h, states, cum, finished, length, perturbed, draw)
+
+
+def _sbeamed(model, carried, steps, eos, state, buffers=None):
+    """sbeam_steps on a flat list [h, states ..., cum, finished, length, perturbed, draw] -> (outputs, that list after the steps)."""
+    h, *flat, cum, finished, length, perturbed, draw = carried
+    par, tok, h, states, *rest = sbeam_steps(model, h, _pairs(flat), cum, finished, length, perturbed, draw, steps, eos, state, buffers)
+    return (par, tok), [h, *(t for st in states for t in st), *rest]
+
+
+class StochasticBeamGraph(_StepGraph):
+    """`steps` steps of Model.stochastic_beam_search (sbeam_steps: per step the head's GEMM, the vmlmf_sbeam_step launch, the
+    vmlmf_beam_gather launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are
+    the beams' (row b W + w); cum / finished / length / perturbed / draw default to a search that starts (StochasticBeams.start()).
+    state: a {seed, offset} snapshot (dropout_advance()); the graph draws from its own copy, `self.state` - copy another snapshot into
+    it for another sample.  replay() continues from where the previous replay stopped - h, states, cum, finished, length, perturbed
+    and draw live in this object's buffers, so the noise of a replay is that of the eager steps at the same count - and returns
+    (parents, tokens), both (steps, B, W), for beam_backtrack.  The ticket words and the workspace are this graph's own; the layers
+    read parameter images packed at construction: build a new graph after the parameters change."""
+
+    def __init__(self, model, h, states, steps, beams, state, eos=None, cum=None, finished=None, length=None, perturbed=None, draw=None):
+        self.model, self.steps, self.eos = model, int(steps), eos
+        W = _sbeam.check_sbeam(beams, model.vocab_size)
+        self.beams = StochasticBeams(h.shape[0] // W, W, model.vocab_size, h.device)
+        given = (cum, finished, length, perturbed, draw)
+        cum, finished, length, perturbed, draw = (new if t is None else t for t, new in zip(given, self.beams.start()))
+        self.state = state.detach().clone()
+        self.buffers = self.beams.buffers()
+        step = lambda carried: _sbeamed(model, carried, self.steps, eos, self.state, self.buffers)
+        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32), perturbed, draw],
+                      step)
+        self.h, *flat, self.cum, self.finished, self.length, self.perturbed, self.draw = self.carried
+        self.states, (self.parents, self.tokens) = _pairs(flat), self.outputs
+
+
+def stochastic_beam_search(model, prompt, steps, beams=4, *, seed=None, states=None, eos=None, chunk=None):
+    """Model.stochastic_beam_search (lm.py has the contract)."""
+    W = _sbeam.check_sbeam(beams, model.vocab_size)
+    steps = int(steps)
+    if eos is not None and not 0 <= int(eos) < model.vocab_size:
+        raise ValueError(f"vmlmf_amd: Model.stochastic_beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
+    if steps < 0:
+        raise ValueError(f"vmlmf_amd: Model.stochastic_beam_search: steps must be >= 0, got {steps}")
+    _check_chunk("stochastic_beam_search", chunk, steps)
+    _check_call(model, prompt, "stochastic_beam_search", "stochastic beam-step kernel (vmlmf_sbeam_step)")
+    B, dev = prompt.shape[1], prompt.device
+    snap = dropout_advance(model.sampler_state(seed))      # once per call: the steps differ by `draw`, on the device
+    with _session(model, prompt, states) as (h, states):
+        h = h.repeat_interleave(W, 0)
+        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        cum, finished, length, perturbed, draw = StochasticBeams(B, W, model.vocab_size, dev).start()
+        if steps == 0:
+            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, perturbed, length, states
+        start = [h, *(t for st in states for t in st), cum, finished, length, perturbed, draw]
+        (parents, toks), carried = _run(
+            steps, chunk, lambda: _sbeamed(model, start, steps, eos, snap),
+            lambda: StochasticBeamGraph(model, h, states, int(chunk), W, snap, eos, cum, finished, length, perturbed, draw))
+        _, *flat, cum, finished, length, perturbed, draw = carried
+        return beam_backtrack(parents, toks), cum, perturbed, length, _pairs(flat)

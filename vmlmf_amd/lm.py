@@ -529,6 +529,41 @@ class Model(nn.Module):
         return decoding.contrastive_search(self, prompt, steps, top_k, penalty_alpha, states=states, eos=eos, chunk=chunk,
                                            return_penalties=return_penalties)
 
+    def stochastic_beam_search(self, prompt, steps, beams=4, *, seed=None, states=None, eos=None, chunk=None):
+        """Stochastic beam search (Kool, van Hoof and Welling, "Stochastic Beams and Where to Find Them", ICML 2019): `beams` (W)
+        DIFFERENT continuations of each row of `prompt` (T0, B) int64, drawn as an exact sample without replacement from the model's
+        distribution over sequences of `steps` tokens - what repeating generate() cannot give (it repeats itself) and beam_search()
+        is not (it is no sample).  Everything behind `beams` is keyword-only.  Returns (tokens (steps, B, W) int64, scores (B, W)
+        fp32, perturbed (B, W) fp32, lengths (B, W) int32, states), the hypotheses of a row in order of `perturbed`, largest first:
+        scores are fp32 sums of plain log-probabilities, as beam_search()'s; the first k hypotheses of a row are a sample without
+        replacement of size k, in the order of the draw; with beams = k + 1 the last `perturbed` is the threshold kappa of the paper's
+        estimators (a hypothesis s of the first k has inclusion probability q = 1 - exp(-exp(score_s - kappa))).
+        Start: beam 0 of every row at score 0 and perturbed value 0, the other beams at -inf, all on the prompt's state.
+        Step (one launch behind the head's GEMM: decoding.lm_sbeam_step, vmlmf_sbeam_step; include/vmlmf_sbeam.h has the contract; a
+        library of its own, opened by the first call).  A live beam w of row b with score cum and perturbed value T offers every
+        token v at phi = cum + log_softmax[v] - beam_search()'s fp32 total, to the bit - perturbed to gt = phi + Gumbel noise, the
+        sampler's counter-based noise (Philox4x32-10 under a snapshot of sampler_state()) at position draw B W + b W + w, draw the
+        number of steps taken, counted on the device.  With Z = max_v gt the candidate's perturbed value is G = T where gt == Z and
+        otherwise G = T - max(u, 0) - log1p(exp(-|u|)), u = T - gt + log1p(-exp(gt - Z)): the noise drawn top-down, so the largest
+        child inherits its parent's value and no child exceeds it.  A finished beam offers (w, eos) alone at its score and value.
+        The W candidates of a row with the largest G survive, equal G to the lower flat index w V + v, in that order; the state
+        reorder and the layers are beam_search()'s.  With beams = 1 the tokens are generate(temperature=1.0)'s for the same seed
+        wherever fp32 rounding does not decide (the noise is the same; generate adds it to the raw score, this to the
+        log-probability).
+        seed follows generate(): it re-seeds sampler_state(), which is snapshotted and advanced ONCE per call - the same seed gives
+        the same sample, the next call a fresh one.  chunk=K (steps % K == 0) captures K steps into a hipGraph
+        (decoding.StochasticBeamGraph) and replays it steps / K times; the snapshot is the call's and the step count lives on the
+        device, so it gives the eager call's bits (unlike generate(chunk=K), which snapshots per replay).  The results are the same
+        bits from run to run.  eos: a hypothesis that emits it is finished - padded with eos, its score and perturbed value frozen;
+        lengths count the tokens up to and including eos.  Decoding always runs the full `steps`.  states (default: state_init) are
+        taken in front of the prompt; the returned states are the hypotheses', rows b W + w.  Every module's train / eval flag is as
+        the caller left it afterwards.
+        ValueError, before any device work, for beams outside [1, min(32, V)], eos outside [0, V), steps < 0 and a chunk that does
+        not divide steps; RuntimeError for CPU tensors.  There is no temperature, no token control and no automaton here: that
+        composition is out of scope."""
+        from . import decoding
+        return decoding.stochastic_beam_search(self, prompt, steps, beams, seed=seed, states=states, eos=eos, chunk=chunk)
+
     def score(self, tokens, targets=None, states=None, lengths=None, top=0, chunk_rows=2048):
         """How probable a given text is, token by token.  targets=None: `tokens` is (T + 1, B) int64, time-major; the inputs are
         tokens[:-1] and the targets tokens[1:].  Otherwise tokens and targets are both (T, B) int64, as lm_test.minibatch hands them
