@@ -1,6 +1,6 @@
 /* C ABI of libvmlmf_contrast.so: the step of CONTRASTIVE SEARCH of the LM decoder (Model.contrastive_search, vmlmf_amd/lm.py; Su et
  * al., "A Contrastive Framework for Neural Text Generation") for the AMD Instinct MI355X (gfx950).  A library of its own, loaded on the
- * first contrastive call only; built by the Makefile's `extra` target, outside `all` and `more`.
+ * first contrastive call only; one of the Makefile's SIDE.
  *
  * Conventions are vmlmf_beamgroup.h's: every pointer is a device pointer, every launch goes to `stream` (a hipStream_t passed as
  * void*), nothing synchronises.  Return value: 0 = ok, <0 = VMLMF_E_*, >0 = hipError_t; the text of the last failure of THIS library

@@ -1,7 +1,7 @@
 /* C ABI of libvmlmf_ncache.so: scoring a text under the language model mixed with a CONTINUOUS CACHE (Model.cache_score,
  * vmlmf_amd/lm.py; Grave, Joulin and Usunier, "Improving Neural Language Models with a Continuous Cache", ICLR 2017) for the AMD
- * Instinct MI355X (gfx950).  A library of its own, loaded on the first cache-scoring call only; built by the Makefile's `further`
- * target, outside `all`, `more` and `extra`.
+ * Instinct MI355X (gfx950).  A library of its own, loaded on the first cache-scoring call only; one of the Makefile's
+ * SIDE.
  *
  * Conventions are vmlmf_contrast.h's: every pointer is a device pointer, every launch goes to `stream` (a hipStream_t passed as
  * void*), nothing synchronises.  Return value: 0 = ok, <0 = VMLMF_E_*, >0 = hipError_t; the text of the last failure of THIS library

@@ -1,6 +1,6 @@
 /* C ABI of libvmlmf_sbeam.so: the step of STOCHASTIC beam search of the LM decoder (Model.stochastic_beam_search, vmlmf_amd/lm.py) for
  * the AMD Instinct MI355X (gfx950).  A library of its own beside libvmlmf_beam.so (include/vmlmf_beam.h), loaded on the first
- * stochastic-beam call only; built by the Makefile's `beyond` target, outside `all`, `more`, `extra` and `further`.
+ * stochastic-beam call only; one of the Makefile's SIDE.
  *
  * Conventions are vmlmf_hip.h's: every pointer is a device pointer, every launch goes to `stream` (a hipStream_t passed as void*),
  * nothing synchronises.  Return value: 0 = ok, <0 = VMLMF_E_*, >0 = hipError_t; the text of the last failure of THIS library is

@@ -1,13 +1,11 @@
 """Model.contrastive_search and libvmlmf_contrast.so without a GPU: the kernel-level cases of contrast_cases.py are all clear in the
 fp64 reference and have the properties their names promise; the refusals, from Python and from the C entry points; the workspace;
-header, SYMBOLS, exports and ABI number; the Makefile's `extra` target beside an unchanged `all` and `more`; lazy loading; the
-signature."""
+what the package exports; the signature.  Header, SYMBOLS, exports, ABI number, Makefile and lazy loading:
+test_side_libraries_cpu.py's table."""
 import ctypes
 import inspect
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,9 +14,6 @@ import torch
 import contrast_cases as CC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_contrast_abi_version", "vmlmf_contrast_append", "vmlmf_contrast_choose", "vmlmf_contrast_last_error",
-             "vmlmf_contrast_workspace_bytes"]
 
 
 # ---- the cases and the reference ----
@@ -170,125 +165,16 @@ def test_workspace_bytes():
         assert int(re.search(r"#define VMLMF_CONTRAST_%s (\d+)" % name, text).group(1)) == value
 
 
-# ---- header, SYMBOLS, exports, ABI ----
-def test_every_declared_function_is_exported_and_bound():
+# ---- what the package exports ----
+def test_the_package_exports_the_contrast_controls():
     import vmlmf_amd
     from vmlmf_amd import _contrast as b
     from vmlmf_amd import decoding
-    text = open(os.path.join(ROOT, "include", "vmlmf_contrast.h")).read()
-    in_header = int(re.search(r"#define VMLMF_CONTRAST_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", code))) == sorted(b.SYMBOLS) == FUNCTIONS
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    for name in FUNCTIONS:
-        assert hasattr(handle, name), f"missing export {name}"
-    from vmlmf_amd import _automaton, _beam, _beamctl, _beamgroup, _decode, _history, _lib, _score, _truncate
-    for other in (_automaton, _beam, _beamctl, _beamgroup, _decode, _history, _lib, _score, _truncate):
-        assert not set(other.SYMBOLS) & set(b.SYMBOLS)
-        for name in other.SYMBOLS:                                                    # none of the other libraries' entry points
-            assert not hasattr(handle, name), name
-    assert b.LIBRARY.abi_symbol == "vmlmf_contrast_abi_version" and b.LIBRARY.error_symbol == "vmlmf_contrast_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_contrast_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == "libvmlmf_contrast.so"
-    assert "stock-op fallback for the contrastive-search step" in b.LIBRARY.no_fallback
     for name in ("ContrastControls", "ContrastGraph", "lm_contrast_step"):
         assert name in vmlmf_amd.__all__ and getattr(vmlmf_amd, name) is getattr(decoding, name)
     assert vmlmf_amd.ContrastControls is b.ContrastControls and vmlmf_amd.lm_contrast_step is b.lm_contrast_step
     assert issubclass(vmlmf_amd.ContrastGraph, decoding._StepGraph)
     assert callable(decoding.contrastive_search) and callable(vmlmf_amd.Model.contrastive_search)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _contrast as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / "libvmlmf_contrast.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_contrast.so is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for the contrastive-search step"):
-        b.lib()
-    assert not b.loaded()
-
-
-# ---- the Makefile ----
-def test_the_makefile_builds_it_by_a_third_target():
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert len(links) == 8 and "contrast" not in r.stdout                     # `all` is what it was: the main library and seven beside it
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SIDE := beam decode score history beamctl truncate automaton$", text, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\) \$\(SIDE_OUT\)$", text, flags=re.M)
-    assert re.search(r"^MORE := beamgroup$", text, flags=re.M)
-    assert re.search(r"^EXTRA := contrast$", text, flags=re.M) and re.search(r"^extra: \$\(EXTRA_OUT\)$", text, flags=re.M)
-    assert re.search(r"^\.PHONY:.*\bmore\b", text, flags=re.M) and re.search(r"^\.PHONY:.*\bextra\b", text, flags=re.M)
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "more"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "contrast" not in r.stdout
-    assert len([ln for ln in r.stdout.splitlines() if " -shared " in ln]) == 1  # `more` too
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "extra"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert len(links) == 1 and "-o ../lib/libvmlmf_contrast.so" in links[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links[0]) == ["vmlmf_contrast.o"]   # linked from its own object alone
-    compiles = [ln for ln in r.stdout.splitlines() if " -c " in ln]
-    assert len(compiles) == 1 and "vmlmf_contrast.hip" in compiles[0] and "--offload-arch=gfx950" in compiles[0]
-    side = [ln for ln in subprocess.run(["make", "-n", "-B", "-C", CSRC, "../lib/libvmlmf_beam.so"], capture_output=True,
-                                        text=True, timeout=120).stdout.splitlines() if " -c " in ln or " -shared " in ln]
-    strip = lambda ln: ln.replace("contrast", "beam")
-    assert [strip(ln) for ln in compiles + links] == side                     # the side libraries' rule and flags
-    deps = re.search(r"^vmlmf_contrast\.o:(.*)$", text, flags=re.M).group(1).split()
-    source = open(os.path.join(CSRC, "vmlmf_contrast.hip")).read()
-    for h in re.findall(r'#include "([^"]+)"', source):                         # rebuilt when a header it includes moves
-        assert h in deps, h
-    assert "vmlmf_side.h" in deps and "../../include/vmlmf_contrast.h" in deps
-    r = subprocess.run(["make", "-n", "-C", CSRC, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "../lib/libvmlmf_contrast.so" in r.stdout and "vmlmf_contrast.o" in r.stdout
-    assert "../lib/libvmlmf_beamgroup.so" in r.stdout and "../lib/libvmlmf_beam.so" in r.stdout
-    # build() makes `all`, `more` behind it and `extra` behind that
-    lib_py = open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    a = lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "all"]')
-    m = lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "more"]')
-    assert a < m < lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "extra"]')
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert re.search(r"for side in \([^)]*_contrast\)", entry)                   # ... and checks its exports like the others'
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _contrast, _lib
-_lib.lib()
-def refused(call):
-    try:
-        call()
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e), e
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-for call in (lambda: m.generate(tok, 4), lambda: m.beam_search(tok, 4), lambda: m.score(tok), lambda: m.group_beam_search(tok, 4),
-             lambda: m.contrastive_search(tok, 4), lambda: m.contrastive_search(tok, 4, 8, 0.3, eos=3, chunk=2, return_penalties=True),
-             lambda: m.contrastive_search(tok, 0), lambda: m.contrastive_search(tok, 4, top_k=1, penalty_alpha=0.0, states=None),
-             lambda: vmlmf_amd.lm_contrast_step(torch.zeros(8, 8), torch.zeros((2, 4), dtype=torch.int64), torch.zeros(2, 4),
-                                                vmlmf_amd.ContrastControls(2, 8, 'cpu', 6)),
-             lambda: vmlmf_amd.ContrastControls(2, 8, 'cpu', 6).append(torch.zeros(3, 2, 8))):
-    refused(call)
-c = vmlmf_amd.ContrastControls(2, 8, 'cpu', 12, top_k=4, penalty_alpha=0.6, eos=3, V=97)
-assert c.clone().hist.shape == (2, 12, 8) and c.hist_len.tolist() == [0, 0]
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_hip.so' in maps and 'libvmlmf_contrast.so' not in maps and not _contrast.loaded()
-_contrast.lib()
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_contrast.so' in maps and _contrast.loaded()
-mapped = sorted(set(ln.rsplit('/', 1)[-1] for ln in maps.splitlines() if 'libvmlmf_' in ln))
-assert mapped == ['libvmlmf_contrast.so', 'libvmlmf_hip.so'], mapped
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    r = subprocess.run([sys.executable, "-c", WALK % ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the signature ----

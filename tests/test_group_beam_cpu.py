@@ -1,24 +1,16 @@
 """Model.group_beam_search and libvmlmf_beamgroup.so without a GPU: the kernel-level cases of group_beam_cases.py are all clear in the
 fp64 reference and the penalty decides where the groups share their inputs; the refusals, from Python and from the C entry point; the
-workspace; header, SYMBOLS, exports and ABI number; the Makefile's `more` target beside an unchanged `all`; lazy loading; the
-signature."""
+workspace; what the package exports; the signature.  Header, SYMBOLS, exports, ABI number, Makefile and lazy loading:
+test_side_libraries_cpu.py's table."""
 import ctypes
 import inspect
 import math
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import group_beam_cases as GC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_beamgroup_abi_version", "vmlmf_beamgroup_last_error", "vmlmf_beamgroup_step", "vmlmf_beamgroup_workspace_bytes"]
 
 
 # ---- the cases ----
@@ -155,105 +147,13 @@ def test_workspace_bytes():
         assert ws(*shape) == _beam.lib().vmlmf_beam_workspace_bytes(*shape)
 
 
-# ---- header, SYMBOLS, exports, ABI ----
-def test_every_declared_function_is_exported_and_bound():
+# ---- what the package exports ----
+def test_the_package_exports_the_group_beams():
     import vmlmf_amd
     from vmlmf_amd import _beamgroup as b
     from vmlmf_amd import decoding
-    text = open(os.path.join(ROOT, "include", "vmlmf_beamgroup.h")).read()
-    in_header = int(re.search(r"#define VMLMF_BEAMGROUP_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", code))) == sorted(b.SYMBOLS) == FUNCTIONS
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    for name in FUNCTIONS:
-        assert hasattr(handle, name), f"missing export {name}"
-    for other in ("vmlmf_beam_step", "vmlmf_beam_gather", "vmlmf_beamctl_step", "vmlmf_abi_version"):
-        assert not hasattr(handle, other), other
-    assert b.LIBRARY.abi_symbol == "vmlmf_beamgroup_abi_version" and b.LIBRARY.error_symbol == "vmlmf_beamgroup_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_beamgroup_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == "libvmlmf_beamgroup.so"
-    assert "stock-op fallback for the group beam-search step" in b.LIBRARY.no_fallback
     assert "GroupBeams" in vmlmf_amd.__all__ and vmlmf_amd.GroupBeams is decoding.GroupBeams is b.GroupBeams
     assert callable(decoding.group_beam_search) and callable(vmlmf_amd.Model.group_beam_search)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _beamgroup as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / "libvmlmf_beamgroup.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_beamgroup.so is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for the group beam-search step"):
-        b.lib()
-    assert not b.loaded()
-
-
-# ---- the Makefile ----
-def test_the_makefile_builds_it_by_a_target_of_its_own():
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert len(links) == 8 and "beamgroup" not in r.stdout                    # `all` is what it was: the main library and seven beside it
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SIDE := beam decode score history beamctl truncate automaton$", text, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\) \$\(SIDE_OUT\)$", text, flags=re.M)
-    assert re.search(r"^MORE := beamgroup$", text, flags=re.M) and re.search(r"^\.PHONY:.*\bmore\b", text, flags=re.M)
-    r = subprocess.run(["make", "-n", "-B", "-C", CSRC, "more"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0
-    links = [ln for ln in r.stdout.splitlines() if " -shared " in ln]
-    assert len(links) == 1 and "-o ../lib/libvmlmf_beamgroup.so" in links[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links[0]) == ["vmlmf_beamgroup.o"]  # linked from its own object alone
-    compiles = [ln for ln in r.stdout.splitlines() if " -c " in ln]
-    assert len(compiles) == 1 and "vmlmf_beamgroup.hip" in compiles[0] and "--offload-arch=gfx950" in compiles[0]
-    side = [ln for ln in subprocess.run(["make", "-n", "-B", "-C", CSRC, "../lib/libvmlmf_beam.so"], capture_output=True,
-                                        text=True, timeout=120).stdout.splitlines() if " -c " in ln or " -shared " in ln]
-    strip = lambda ln: ln.replace("beamgroup", "beam")
-    assert [strip(ln) for ln in compiles + links] == side                     # the side libraries' rule and flags
-    deps = re.search(r"^vmlmf_beamgroup\.o:(.*)$", text, flags=re.M).group(1).split()
-    for h in ("vmlmf_side.h", "vmlmf_beam_core.h", "../../include/vmlmf_beam.h", "../../include/vmlmf_beamgroup.h"):
-        assert h in deps, h
-    r = subprocess.run(["make", "-n", "-C", CSRC, "clean"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "../lib/libvmlmf_beamgroup.so" in r.stdout and "vmlmf_beamgroup.o" in r.stdout
-    # build() makes `all` as before and `more` after it
-    lib_py = open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    a = lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "all"]')
-    assert lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "more"]') > a
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _beamgroup, _lib
-_lib.lib()
-def refused(call):
-    try:
-        call()
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e)
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-for call in (lambda: m.generate(tok, 4), lambda: m.generate(tok, 4, eos=2, repetition_penalty=1.2), lambda: m.beam_search(tok, 4),
-             lambda: m.beam_search(tok, 4, eos=3, min_length=2), lambda: m.score(tok), lambda: m.group_beam_search(tok, 4),
-             lambda: m.group_beam_search(tok, 4, beams=6, groups=3, diversity_penalty=1.0, eos=3, length_penalty=1.0)):
-    refused(call)
-c = vmlmf_amd.GroupBeams(2, 4, 97, 'cpu', groups=2, diversity_penalty=0.5)
-assert c.start()[0].shape == (2, 4)
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_hip.so' in maps and 'libvmlmf_beamgroup.so' not in maps and not _beamgroup.loaded()
-_beamgroup.lib()
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_beamgroup.so' in maps and _beamgroup.loaded()
-mapped = sorted(set(ln.rsplit('/', 1)[-1] for ln in maps.splitlines() if 'libvmlmf_' in ln))
-assert mapped == ['libvmlmf_beamgroup.so', 'libvmlmf_hip.so'], mapped
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    r = subprocess.run([sys.executable, "-c", WALK % ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the signature ----

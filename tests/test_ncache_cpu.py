@@ -1,13 +1,11 @@
 """Model.cache_score and libvmlmf_ncache.so without a GPU: the fp64 reference of ncache_cases.py against the brute-force definition
 and on its special cases; the cases of the GPU tests; NeuralCache's bookkeeping; the refusals, from Python and from the C entry point;
-the workspace; header, SYMBOLS, exports and ABI number; the Makefile's `further` target beside an unchanged `all`, `more` and `extra`;
-lazy loading; the signatures."""
+the workspace; what the package exports; the signatures.  Header, SYMBOLS, exports, ABI number, Makefile and lazy loading:
+test_side_libraries_cpu.py's table."""
 import ctypes
 import inspect
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,8 +14,6 @@ import torch
 import ncache_cases as NC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_ncache_abi_version", "vmlmf_ncache_last_error", "vmlmf_ncache_score", "vmlmf_ncache_workspace_bytes"]
 
 
 # ---- the reference ----
@@ -222,126 +218,15 @@ def test_workspace_bytes():
         assert int(re.search(r"#define VMLMF_NCACHE_%s (\d+)" % name, text).group(1)) == value
 
 
-# ---- header, SYMBOLS, exports, ABI ----
-def test_every_declared_function_is_exported_and_bound():
+# ---- what the package exports ----
+def test_the_package_exports_the_neural_cache():
     import vmlmf_amd
     from vmlmf_amd import _ncache as b
     from vmlmf_amd import scoring
-    text = open(os.path.join(ROOT, "include", "vmlmf_ncache.h")).read()
-    in_header = int(re.search(r"#define VMLMF_NCACHE_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", code))) == sorted(b.SYMBOLS) == FUNCTIONS
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    for name in FUNCTIONS:
-        assert hasattr(handle, name), f"missing export {name}"
-    from vmlmf_amd import _automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _score, _truncate
-    for other in (_automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _score, _truncate):
-        assert not set(other.SYMBOLS) & set(b.SYMBOLS)
-        for name in other.SYMBOLS:                                                    # none of the other libraries' entry points
-            assert not hasattr(handle, name), name
-        theirs = ctypes.CDLL(other.LIB_PATH if other is _lib else other.LIBRARY.path)
-        for name in FUNCTIONS:                                                        # ... and none of these in theirs
-            assert not hasattr(theirs, name), (other.__name__, name)
-    assert b.LIBRARY.abi_symbol == "vmlmf_ncache_abi_version" and b.LIBRARY.error_symbol == "vmlmf_ncache_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_ncache_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == "libvmlmf_ncache.so"
-    assert "stock-op fallback for the continuous-cache scoring" in b.LIBRARY.no_fallback
     assert vmlmf_amd.__all__[-2:] == ["NeuralCache", "lm_cache_score"]
     assert vmlmf_amd.NeuralCache is scoring.NeuralCache is b.NeuralCache
     assert vmlmf_amd.lm_cache_score is scoring.lm_cache_score is b.lm_cache_score
     assert callable(scoring.cache_score) and callable(vmlmf_amd.Model.cache_score)
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _ncache as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / "libvmlmf_ncache.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_ncache.so is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for the continuous-cache scoring"):
-        b.lib()
-    assert not b.loaded()
-
-
-# ---- the Makefile ----
-def _make(*args):
-    r = subprocess.run(["make", "-n", *args, "-C", CSRC], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    return r.stdout
-
-
-def test_the_makefile_builds_it_by_a_fourth_target():
-    links = lambda out: [ln for ln in out.splitlines() if " -shared " in ln]
-    out = _make("-B", "all")
-    assert len(links(out)) == 8 and "ncache" not in out                        # `all` is what it was: the main library and seven beside it
-    for target in ("more", "extra"):
-        out = _make("-B", target)
-        assert len(links(out)) == 1 and "ncache" not in out
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SIDE := beam decode score history beamctl truncate automaton$", text, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\) \$\(SIDE_OUT\)$", text, flags=re.M)
-    assert re.search(r"^MORE := beamgroup$", text, flags=re.M) and re.search(r"^EXTRA := contrast$", text, flags=re.M)
-    assert re.search(r"^FURTHER := ncache$", text, flags=re.M) and re.search(r"^further: \$\(FURTHER_OUT\)$", text, flags=re.M)
-    assert re.search(r"^\.PHONY:.*\bfurther\b", text, flags=re.M)
-    out = _make("-B", "further")
-    assert len(links(out)) == 1 and "-o ../lib/libvmlmf_ncache.so" in links(out)[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links(out)[0]) == ["vmlmf_ncache.o"]   # linked from its own object alone
-    compiles = [ln for ln in out.splitlines() if " -c " in ln]
-    assert len(compiles) == 1 and "vmlmf_ncache.hip" in compiles[0] and "--offload-arch=gfx950" in compiles[0]
-    side = [ln for ln in _make("-B", "../lib/libvmlmf_beam.so").splitlines() if " -c " in ln or " -shared " in ln]
-    assert [ln.replace("ncache", "beam") for ln in compiles + links(out)] == side   # the side libraries' rule and flags
-    deps = re.search(r"^vmlmf_ncache\.o:(.*)$", text, flags=re.M).group(1).split()
-    source = open(os.path.join(CSRC, "vmlmf_ncache.hip")).read()
-    included = re.findall(r'#include "([^"]+)"', source)
-    assert included and all(h in deps for h in included), (included, deps)       # rebuilt when a header it includes moves
-    assert "vmlmf_side.h" in deps and "../../include/vmlmf_ncache.h" in deps
-    out = _make("clean")
-    for name in ("../lib/libvmlmf_ncache.so", "vmlmf_ncache.o", "../lib/libvmlmf_contrast.so", "../lib/libvmlmf_beamgroup.so",
-                 "../lib/libvmlmf_beam.so"):
-        assert name in out, name
-    # build() makes `all`, `more`, `extra` and `further`, in this order, and checks the new binding's exports
-    lib_py = open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    at = [lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "%s"]' % t) for t in ("all", "more", "extra", "further")]
-    assert at == sorted(at)
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert re.search(r"_ncache\.lib\(\)\.vmlmf_ncache_abi_version\(\) == _ncache\.ABI_VERSION", entry)
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _ncache, _lib
-_lib.lib()
-def refused(call):
-    try:
-        call()
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e) or 'HIP device' in str(e), e
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-c = vmlmf_amd.NeuralCache(2, 8, 'cpu', 12)
-for call in (lambda: m.generate(tok, 4), lambda: m.beam_search(tok, 4), lambda: m.score(tok), lambda: m.contrastive_search(tok, 4),
-             lambda: m.cache_score(tok), lambda: m.cache_score(tok, tok, theta=1.0, lam=0.5, window=12, cache=c, return_parts=True),
-             lambda: vmlmf_amd.lm_cache_score(torch.zeros(3, 2, 8), tok, torch.zeros(3, 2), c)):
-    refused(call)
-c.update(torch.zeros(3, 2, 8), tok)
-assert c.n == 3 and c.clone().keys.shape == (2, 3, 8)
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_hip.so' in maps and 'libvmlmf_ncache.so' not in maps and not _ncache.loaded()
-_ncache.lib()
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_ncache.so' in maps and _ncache.loaded()
-mapped = sorted(set(ln.rsplit('/', 1)[-1] for ln in maps.splitlines() if 'libvmlmf_' in ln))
-assert mapped == ['libvmlmf_hip.so', 'libvmlmf_ncache.so'], mapped
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    r = subprocess.run([sys.executable, "-c", WALK % ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the signatures ----

@@ -1,14 +1,12 @@
 """Model.stochastic_beam_search and libvmlmf_sbeam.so without a GPU: the kernel-level cases of sbeam_cases.py are all clear in the fp64
 reference, the reference's own properties (the largest child inherits its parent's value, no child exceeds it, the first tokens are a
-sample without replacement); the refusals, from Python and from the C entry point; the workspace; header, SYMBOLS, exports and ABI
-number; the Makefile's `beyond` target beside an unchanged `all`, `more`, `extra` and `further`; lazy loading; the signatures."""
+sample without replacement); the refusals, from Python and from the C entry point; the workspace; what the package exports; the
+signatures.  Header, SYMBOLS, exports, ABI number, Makefile and lazy loading: test_side_libraries_cpu.py's table."""
 import ctypes
 import inspect
 import math
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,7 +17,6 @@ from vmlmf_amd import _sbeam            # (the binding under test: without it no
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vmlmf_amd", "csrc")
-FUNCTIONS = ["vmlmf_sbeam_abi_version", "vmlmf_sbeam_last_error", "vmlmf_sbeam_step", "vmlmf_sbeam_workspace_bytes"]
 
 
 # ---- the cases and the reference ----
@@ -196,31 +193,11 @@ def test_workspace_bytes():
         assert ws(*shape) * 8 == _beam.lib().vmlmf_beam_workspace_bytes(*shape) * 12 and ws(*shape) % 4 == 0
 
 
-# ---- header, SYMBOLS, exports, ABI ----
-def test_every_declared_function_is_exported_and_bound():
+# ---- what the package exports ----
+def test_the_package_exports_the_stochastic_beams():
     import vmlmf_amd
     from vmlmf_amd import _sbeam as b
     from vmlmf_amd import decoding
-    text = open(os.path.join(ROOT, "include", "vmlmf_sbeam.h")).read()
-    in_header = int(re.search(r"#define VMLMF_SBEAM_ABI_VERSION (\d+)", text).group(1))
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert sorted(set(re.findall(r"\b(vmlmf_[a-z0-9_]+)\s*\(", code))) == sorted(b.SYMBOLS) == FUNCTIONS
-    assert os.path.exists(b.LIBRARY.path), "run __graft_entry__.build() first"
-    handle = ctypes.CDLL(b.LIBRARY.path)
-    for name in FUNCTIONS:
-        assert hasattr(handle, name), f"missing export {name}"
-    from vmlmf_amd import _automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _ncache, _score, _truncate
-    for other in (_automaton, _beam, _beamctl, _beamgroup, _contrast, _decode, _history, _lib, _ncache, _score, _truncate):
-        assert not set(other.SYMBOLS) & set(b.SYMBOLS)
-        for name in other.SYMBOLS:                                                    # none of the other libraries' entry points
-            assert not hasattr(handle, name), name
-        theirs = ctypes.CDLL(other.LIB_PATH if other is _lib else other.LIBRARY.path)
-        for name in FUNCTIONS:                                                        # ... and none of these in theirs
-            assert not hasattr(theirs, name), (other.__name__, name)
-    assert b.LIBRARY.abi_symbol == "vmlmf_sbeam_abi_version" and b.LIBRARY.error_symbol == "vmlmf_sbeam_last_error"
-    assert in_header == b.ABI_VERSION == b.LIBRARY.abi_version == b.lib().vmlmf_sbeam_abi_version() == 1
-    assert os.path.basename(b.LIBRARY.path) == "libvmlmf_sbeam.so"
-    assert b.LIBRARY.no_fallback == "stock-op fallback for the stochastic beam-search step"
     names = ["StochasticBeams", "StochasticBeamGraph", "lm_sbeam_step"]
     at = vmlmf_amd.__all__.index("NeuralCache")
     assert vmlmf_amd.__all__[at - 3:at] == names and vmlmf_amd.__all__[-2:] == ["NeuralCache", "lm_cache_score"]
@@ -244,103 +221,6 @@ def test_the_kernel_takes_the_selection_and_the_noise_from_the_shared_headers():
     assert "BeamScratch" in text and "struct BeamScratch" not in text
     assert len(re.findall(r"__global__", text)) == 1 and "asm" not in text.replace("no inline assembly", "") and "atomicAdd" not in text
     assert "VMLMF_SIDE_LIBRARY(vmlmf_sbeam, VMLMF_SBEAM_ABI_VERSION)" in text
-
-
-def test_a_missing_library_is_a_clear_error(monkeypatch, tmp_path):
-    from vmlmf_amd import _sbeam as b
-    monkeypatch.setattr(b.LIBRARY, "_handle", None)
-    monkeypatch.setattr(b.LIBRARY, "path", str(tmp_path / "libvmlmf_sbeam.so"))
-    with pytest.raises(RuntimeError, match="libvmlmf_sbeam.so is missing: build it"):
-        b.lib()
-    with pytest.raises(RuntimeError, match="no stock-op fallback for the stochastic beam-search step"):
-        b.lib()
-    assert not b.loaded()
-
-
-# ---- the Makefile ----
-def _make(*args):
-    r = subprocess.run(["make", "-n", *args, "-C", CSRC], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    return r.stdout
-
-
-def test_the_makefile_builds_it_by_a_fifth_target():
-    links = lambda out: [ln for ln in out.splitlines() if " -shared " in ln]
-    out = _make("-B", "all")
-    assert len(links(out)) == 8 and "sbeam" not in out                         # `all` is what it was: the main library and seven beside it
-    for target in ("more", "extra", "further"):
-        out = _make("-B", target)
-        assert len(links(out)) == 1 and "sbeam" not in out
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SIDE := beam decode score history beamctl truncate automaton$", text, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\) \$\(SIDE_OUT\)$", text, flags=re.M)
-    assert re.search(r"^MORE := beamgroup$", text, flags=re.M) and re.search(r"^EXTRA := contrast$", text, flags=re.M)
-    assert re.search(r"^FURTHER := ncache$", text, flags=re.M)
-    assert re.search(r"^BEYOND := sbeam$", text, flags=re.M) and re.search(r"^beyond: \$\(BEYOND_OUT\)$", text, flags=re.M)
-    assert re.search(r"^\.PHONY:.*\bbeyond\b", text, flags=re.M)
-    out = _make("-B", "beyond")
-    assert len(links(out)) == 1 and "-o ../lib/libvmlmf_sbeam.so" in links(out)[0]
-    assert re.findall(r"\bvmlmf_\w+\.o\b", links(out)[0]) == ["vmlmf_sbeam.o"]    # linked from its own object alone
-    compiles = [ln for ln in out.splitlines() if " -c " in ln]
-    assert len(compiles) == 1 and "vmlmf_sbeam.hip" in compiles[0] and "--offload-arch=gfx950" in compiles[0]
-    side = [ln for ln in _make("-B", "../lib/libvmlmf_beam.so").splitlines() if " -c " in ln or " -shared " in ln]
-    assert [ln.replace("sbeam", "beam") for ln in compiles + links(out)] == side    # the side libraries' rule and flags
-    deps = re.search(r"^vmlmf_sbeam\.o:(.*)$", text, flags=re.M).group(1).split()
-    source = open(os.path.join(CSRC, "vmlmf_sbeam.hip")).read()
-    included = re.findall(r'#include "([^"]+)"', source)
-    assert included and all(h in deps for h in included), (included, deps)       # rebuilt when a header it includes moves
-    for h in ("vmlmf_side.h", "vmlmf_beam_core.h", "vmlmf_select.h", "vmlmf_dropout.h", "../../include/vmlmf_beam.h",
-              "../../include/vmlmf_sbeam.h"):                                    # ... or one that those include
-        assert h in deps, h
-    out = _make("clean")
-    for name in ("../lib/libvmlmf_sbeam.so", "vmlmf_sbeam.o", "../lib/libvmlmf_ncache.so", "../lib/libvmlmf_contrast.so",
-                 "../lib/libvmlmf_beamgroup.so", "../lib/libvmlmf_beam.so"):
-        assert name in out, name
-    # build() makes `all`, `more`, `extra`, `further` and `beyond`, in this order, and checks the new binding's exports
-    lib_py = open(os.path.join(ROOT, "vmlmf_amd", "_lib.py")).read()
-    at = [lib_py.index('["make", "-C", CSRC, f"-j{jobs}", "%s"]' % t) for t in ("all", "more", "extra", "further", "beyond")]
-    assert at == sorted(at)
-    entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
-    assert re.search(r"_sbeam\.lib\(\)\.vmlmf_sbeam_abi_version\(\) == _sbeam\.ABI_VERSION", entry)
-    assert re.search(r"^make -C vmlmf_amd/csrc -j8 .*\bbeyond\b", open(os.path.join(ROOT, "README.md")).read(), flags=re.M)
-
-
-# ---- lazy loading ----
-WALK = """
-import sys; sys.path.insert(0, %r)
-import torch, vmlmf_amd
-from vmlmf_amd import _sbeam, _lib
-_lib.lib()
-def refused(call):
-    try:
-        call()
-        raise SystemExit('no refusal')
-    except RuntimeError as e:
-        assert 'cuda' in str(e) or 'HIP device' in str(e), e
-tok = torch.zeros((3, 2), dtype=torch.int64)
-m = vmlmf_amd.Model(97, 8, 1, 0.0, 0.1, w_rank=4, u_ranks=[4], lstm_type='vmlmf')
-c = vmlmf_amd.NeuralCache(2, 8, 'cpu', 12)
-for call in (lambda: m.generate(tok, 4), lambda: m.generate(tok, 4, seed=3, top_k=5), lambda: m.beam_search(tok, 4),
-             lambda: m.beam_search(tok, 4, eos=3, min_length=2), lambda: m.group_beam_search(tok, 4), lambda: m.score(tok),
-             lambda: m.contrastive_search(tok, 4), lambda: m.cache_score(tok), lambda: m.cache_score(tok, tok, cache=c, window=12),
-             lambda: m.stochastic_beam_search(tok, 4), lambda: m.stochastic_beam_search(tok, 4, 6, seed=5, eos=3, chunk=2)):
-    refused(call)
-s = vmlmf_amd.StochasticBeams(2, 4, 97, 'cpu')
-assert s.start()[3].shape == (2, 4) and s.start()[4].shape == (2,)
-maps = open('/proc/self/maps').read()
-mapped = sorted(set(ln.rsplit('/', 1)[-1] for ln in maps.splitlines() if 'libvmlmf_' in ln))
-assert mapped == ['libvmlmf_hip.so'] and not _sbeam.loaded(), mapped
-_sbeam.lib()
-maps = open('/proc/self/maps').read()
-assert 'libvmlmf_sbeam.so' in maps and _sbeam.loaded()
-mapped = sorted(set(ln.rsplit('/', 1)[-1] for ln in maps.splitlines() if 'libvmlmf_' in ln))
-assert mapped == ['libvmlmf_hip.so', 'libvmlmf_sbeam.so'], mapped
-"""
-
-
-def test_the_library_is_loaded_by_its_own_first_call_only():
-    r = subprocess.run([sys.executable, "-c", WALK % ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
 
 
 # ---- the signatures ----

@@ -44,8 +44,7 @@ SYMBOLS = {
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_automaton.so", SYMBOLS, "vmlmf_automaton_abi_version", ABI_VERSION, "vmlmf_automaton_last_error",
-                       "stock-op fallback for decoding under a token automaton")
+LIBRARY = _lib.Library("automaton", SYMBOLS, ABI_VERSION, "stock-op fallback for decoding under a token automaton")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 GENERATE_REFUSAL = ("vmlmf_amd: automaton= together with {what} is out of scope: the constrained choice runs under the stopping and token "

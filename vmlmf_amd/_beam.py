@@ -27,8 +27,7 @@ SYMBOLS = {
     "vmlmf_beam_backtrack": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_beam.so", SYMBOLS, "vmlmf_beam_abi_version", ABI_VERSION, "vmlmf_beam_last_error",
-                       "stock-op fallback for the beam-search step")
+LIBRARY = _lib.Library("beam", SYMBOLS, ABI_VERSION, "stock-op fallback for the beam-search step")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 
@@ -93,6 +92,18 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     more result follows the seven: the survivors' states, a fresh buffer.
     controls: a GroupBeams (_beamgroup.py: groups, diversity_penalty) - the selection is ONE launch of vmlmf_beamgroup_step
     (csrc/vmlmf_beamgroup.hip), the same kernel whose merge runs group by group; the seven results, nothing carried."""
+    h2, w, *rest = check_step("lm_beam_step", h, weight, bias, cum, finished, length, eos, embed)
+    args = (torch.mm(h2, w.t()), *rest)
+    if controls is None:
+        return beam_select(*args, buffers)
+    return controls.select(*args, buffers, hist=hist, hist_len=hist_len, beam_state=beam_state)    # (it takes what it carries)
+
+
+def check_step(caller, h, weight, bias, cum, finished, length, eos, embed):
+    """What a beam step (`caller`: lm_beam_step, lm_sbeam_step - named in the messages) asks of its arguments: fp32 h, weight, cum and -
+    where given - bias and embed on a HIP device, cum (B, W) with W beams the C ABI takes, h (B W, H) against weight (V, H), bias (V)
+    and embed (V, H), finished (bool or int32) and length (int32) like cum, eos None or a token.  Returns (h (B W, H), weight, bias,
+    cum, finished as int32, length, eos as an int - -1: none -, embed), the tensors contiguous."""
     for t, what in ((h, "h"), (weight, "weight"), (cum, "cum")):
         _require(t, what)
     if bias is not None:
@@ -100,7 +111,7 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     if embed is not None:
         _require(embed, "embedding table")
     if cum.dim() != 2:
-        raise RuntimeError(f"vmlmf_amd.lm_beam_step: cum must be (B, W), got {tuple(cum.shape)}")
+        raise RuntimeError(f"vmlmf_amd.{caller}: cum must be (B, W), got {tuple(cum.shape)}")
     B, W = cum.shape
     h2 = h.reshape(-1, h.shape[-1]).contiguous()
     H = h2.shape[1]
@@ -108,22 +119,19 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     V = w.shape[0]
     check_beams(W, V)
     if h2.shape[0] != B * W or w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
-        raise RuntimeError(f"vmlmf_amd.lm_beam_step: h {tuple(h.shape)} must be (B W, H) for cum {tuple(cum.shape)}, weight "
+        raise RuntimeError(f"vmlmf_amd.{caller}: h {tuple(h.shape)} must be (B W, H) for cum {tuple(cum.shape)}, weight "
                            f"{tuple(weight.shape)} (V, H), bias / embed (V) / (V, H)")
     if tuple(finished.shape) != (B, W) or tuple(length.shape) != (B, W):
-        raise RuntimeError("vmlmf_amd.lm_beam_step: finished and length must be (B, W) like cum")
+        raise RuntimeError(f"vmlmf_amd.{caller}: finished and length must be (B, W) like cum")
     _require(length, "length", torch.int32)
     if finished.dtype == torch.bool:
         finished = finished.to(torch.int32)
     _require(finished, "finished", torch.int32)
     eos_c = -1 if eos is None else int(eos)
     if eos is not None and not 0 <= eos_c < V:
-        raise ValueError(f"vmlmf_amd.lm_beam_step: eos={eos} is not a token of the vocabulary ({V})")
-    args = (torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
-            length.contiguous(), eos_c, None if embed is None else embed.contiguous())
-    if controls is None:
-        return beam_select(*args, buffers)
-    return controls.select(*args, buffers, hist=hist, hist_len=hist_len, beam_state=beam_state)    # (it takes what it carries)
+        raise ValueError(f"vmlmf_amd.{caller}: eos={eos} is not a token of the vocabulary ({V})")
+    return (h2, w, None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(), length.contiguous(), eos_c,
+            None if embed is None else embed.contiguous())
 
 
 def step_outputs(B, W, H, dev, embed):

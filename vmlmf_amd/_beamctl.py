@@ -36,8 +36,7 @@ SYMBOLS = {
                                 _vp, _vp, _vp, _sz, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_beamctl.so", SYMBOLS, "vmlmf_beamctl_abi_version", ABI_VERSION, "vmlmf_beamctl_last_error",
-                       "stock-op fallback for the controlled beam-search step")
+LIBRARY = _lib.Library("beamctl", SYMBOLS, ABI_VERSION, "stock-op fallback for the controlled beam-search step")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

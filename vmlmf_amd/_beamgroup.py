@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vmlmf_beamgroup.h (libvmlmf_beamgroup.so, built in-tree by csrc/Makefile's `more` beside
+"""ctypes binding of the C ABI in include/vmlmf_beamgroup.h (libvmlmf_beamgroup.so, built in-tree by csrc/Makefile beside
 libvmlmf_hip.so): the step of diverse (group) beam search of the LM decoder - Model.group_beam_search.  The library is loaded on the
 first group step: beam_search(), generate(), score() and a training process never open it.
 
@@ -27,8 +27,7 @@ SYMBOLS = {
                                   ctypes.c_float, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_beamgroup.so", SYMBOLS, "vmlmf_beamgroup_abi_version", ABI_VERSION, "vmlmf_beamgroup_last_error",
-                       "stock-op fallback for the group beam-search step")
+LIBRARY = _lib.Library("beamgroup", SYMBOLS, ABI_VERSION, "stock-op fallback for the group beam-search step")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

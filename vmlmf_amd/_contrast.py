@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vmlmf_contrast.h (libvmlmf_contrast.so, built in-tree by csrc/Makefile's `extra` beside
+"""ctypes binding of the C ABI in include/vmlmf_contrast.h (libvmlmf_contrast.so, built in-tree by csrc/Makefile beside
 libvmlmf_hip.so): the step of contrastive search of the LM decoder - Model.contrastive_search.  The library is loaded on the first
 launch: generate(), beam_search(), group_beam_search(), score() and a training process never open it, nor does building the controls.
 
@@ -30,8 +30,7 @@ SYMBOLS = {
                                    _vp, _sz, _i, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_contrast.so", SYMBOLS, "vmlmf_contrast_abi_version", ABI_VERSION, "vmlmf_contrast_last_error",
-                       "stock-op fallback for the contrastive-search step")
+LIBRARY = _lib.Library("contrast", SYMBOLS, ABI_VERSION, "stock-op fallback for the contrastive-search step")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

@@ -31,8 +31,7 @@ SYMBOLS = {
     "vmlmf_decode_choose": (_i, [_i, _i, _i, _vp, _vp, _vp, _f, _i, _f, _vp, _i, ctypes.POINTER(Controls), _vp, _vp, _vp, _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_decode.so", SYMBOLS, "vmlmf_decode_abi_version", ABI_VERSION, "vmlmf_decode_last_error",
-                       "stock-op fallback for the controlled choice of Model.generate")
+LIBRARY = _lib.Library("decode", SYMBOLS, ABI_VERSION, "stock-op fallback for the controlled choice of Model.generate")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

@@ -39,8 +39,7 @@ SYMBOLS = {
     "vmlmf_history_bans": (_i, [_i, _i, ctypes.POINTER(Controls), _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_history.so", SYMBOLS, "vmlmf_history_abi_version", ABI_VERSION, "vmlmf_history_last_error",
-                       "stock-op fallback for the history controls of Model.generate")
+LIBRARY = _lib.Library("history", SYMBOLS, ABI_VERSION, "stock-op fallback for the history controls of Model.generate")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

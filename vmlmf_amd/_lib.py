@@ -176,16 +176,11 @@ class VmlmfError(RuntimeError):
 
 
 def build(force=False, jobs=8):
-    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so and the seven side libraries beside it (the Makefile's
-    `all`), then libvmlmf_beamgroup.so (its `more`), libvmlmf_contrast.so (its `extra`), libvmlmf_ncache.so (its `further`) and
-    libvmlmf_sbeam.so (its `beyond`); hipcc cross-compiles."""
+    """Compile every HIP source for gfx950 into vmlmf_amd/lib/libvmlmf_hip.so and the side libraries of SIDE beside it (the Makefile's
+    `all`); hipcc cross-compiles."""
     if force:
         subprocess.run(["make", "-C", CSRC, "clean"], check=True, stdout=subprocess.DEVNULL)
     subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "all"], check=True, stdout=subprocess.DEVNULL)
-    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "more"], check=True, stdout=subprocess.DEVNULL)
-    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "extra"], check=True, stdout=subprocess.DEVNULL)
-    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "further"], check=True, stdout=subprocess.DEVNULL)
-    subprocess.run(["make", "-C", CSRC, f"-j{jobs}", "beyond"], check=True, stdout=subprocess.DEVNULL)
     return LIB_PATH
 
 
@@ -266,14 +261,19 @@ def check(rc):
         raise VmlmfError(rc, lib().vmlmf_last_error().decode())
 
 
-class Library:
-    """A side library beside libvmlmf_hip.so (the Makefile's SIDE: a header, an ABI version and a last-error text of its own), opened
-    and bound on first use - a process that never calls into it never maps it.  `path` may be repointed before the first use."""
+# the decoder's side libraries, in the order of the Makefile's SIDE: libvmlmf_<name>.so, include/vmlmf_<name>.h, vmlmf_amd/_<name>.py
+SIDE = ("beam", "decode", "score", "history", "beamctl", "truncate", "automaton", "beamgroup", "contrast", "ncache", "sbeam")
 
-    def __init__(self, filename, symbols, abi_symbol, abi_version, error_symbol, no_fallback):
-        self.path = os.path.join(os.path.dirname(LIB_PATH), filename)
-        self.symbols, self.abi_symbol, self.abi_version = symbols, abi_symbol, abi_version
-        self.error_symbol, self.no_fallback = error_symbol, no_fallback
+
+class Library:
+    """The side library `name` of SIDE beside libvmlmf_hip.so - libvmlmf_<name>.so, with a header, an ABI version
+    (vmlmf_<name>_abi_version) and a last-error text (vmlmf_<name>_last_error) of its own -, opened and bound on first use: a process
+    that never calls into it never maps it.  `path` may be repointed before the first use."""
+
+    def __init__(self, name, symbols, abi_version, no_fallback):
+        self.path = os.path.join(os.path.dirname(LIB_PATH), f"libvmlmf_{name}.so")
+        self.symbols, self.abi_version, self.no_fallback = symbols, abi_version, no_fallback
+        self.abi_symbol, self.error_symbol = f"vmlmf_{name}_abi_version", f"vmlmf_{name}_last_error"
         self._handle = None
 
     def handle(self):

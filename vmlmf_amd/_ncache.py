@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vmlmf_ncache.h (libvmlmf_ncache.so, built in-tree by csrc/Makefile's `further` beside
+"""ctypes binding of the C ABI in include/vmlmf_ncache.h (libvmlmf_ncache.so, built in-tree by csrc/Makefile beside
 libvmlmf_hip.so): scoring a text under the language model mixed with a continuous cache - Model.cache_score.  The library is loaded
 on the first launch: generate(), beam_search(), score(), contrastive_search() and a training process never open it, nor does building
 a NeuralCache.
@@ -29,8 +29,7 @@ SYMBOLS = {
     "vmlmf_ncache_score": (_i, [_i, _i, _i, _i, _i, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_ncache.so", SYMBOLS, "vmlmf_ncache_abi_version", ABI_VERSION, "vmlmf_ncache_last_error",
-                       "stock-op fallback for the continuous-cache scoring")
+LIBRARY = _lib.Library("ncache", SYMBOLS, ABI_VERSION, "stock-op fallback for the continuous-cache scoring")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/vmlmf_sbeam.h (libvmlmf_sbeam.so, built in-tree by csrc/Makefile's `beyond` beside
+"""ctypes binding of the C ABI in include/vmlmf_sbeam.h (libvmlmf_sbeam.so, built in-tree by csrc/Makefile beside
 libvmlmf_hip.so): the step of stochastic beam search of the LM decoder - Model.stochastic_beam_search.  The library is loaded on the
 first stochastic step: generate(), beam_search(), score(), contrastive_search(), cache_score() and a training process never open it.
 
@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._beam import _require, check_beams, step_outputs
+from ._beam import _require, check_beams, check_step, step_outputs
 from ._lib import ptr
 
 ABI_VERSION = 1
@@ -26,8 +26,7 @@ SYMBOLS = {
                               _vp, _vp, _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_sbeam.so", SYMBOLS, "vmlmf_sbeam_abi_version", ABI_VERSION, "vmlmf_sbeam_last_error",
-                       "stock-op fallback for the stochastic beam-search step")
+LIBRARY = _lib.Library("sbeam", SYMBOLS, ABI_VERSION, "stock-op fallback for the stochastic beam-search step")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 
@@ -82,38 +81,16 @@ def lm_sbeam_step(h, weight, bias, cum, finished, length, perturbed, draw, state
     Returns lm_beam_step's seven results (parent, token, total, finished, length, x_next, src_row) and behind them the survivors'
     perturbed (B, W) and draw + 1 (B), fresh buffers.  buffers: (ticket, workspace) of a StochasticBeams.buffers() - default: a pair
     kept per (device, stream, B, W, V)."""
-    for t, what in ((h, "h"), (weight, "weight"), (cum, "cum"), (perturbed, "perturbed")):
-        _require(t, what)
-    if bias is not None:
-        _require(bias, "bias")
-    if embed is not None:
-        _require(embed, "embedding table")
-    if cum.dim() != 2:
-        raise RuntimeError(f"vmlmf_amd.lm_sbeam_step: cum must be (B, W), got {tuple(cum.shape)}")
+    h2, w, bias, cum, finished, length, eos_c, embed = check_step("lm_sbeam_step", h, weight, bias, cum, finished, length, eos, embed)
     B, W = cum.shape
-    h2 = h.reshape(-1, h.shape[-1]).contiguous()
-    H = h2.shape[1]
-    w = weight.contiguous()
-    V = w.shape[0]
-    check_sbeam(W, V)
-    if h2.shape[0] != B * W or w.shape[1] != H or (bias is not None and bias.numel() != V) or (embed is not None and tuple(embed.shape) != (V, H)):
-        raise RuntimeError(f"vmlmf_amd.lm_sbeam_step: h {tuple(h.shape)} must be (B W, H) for cum {tuple(cum.shape)}, weight "
-                           f"{tuple(weight.shape)} (V, H), bias / embed (V) / (V, H)")
-    if tuple(finished.shape) != (B, W) or tuple(length.shape) != (B, W) or tuple(perturbed.shape) != (B, W) or tuple(draw.shape) != (B,):
+    _require(perturbed, "perturbed")
+    if tuple(perturbed.shape) != (B, W) or tuple(draw.shape) != (B,):
         raise RuntimeError("vmlmf_amd.lm_sbeam_step: finished, length and perturbed must be (B, W) like cum, draw (B)")
-    _require(length, "length", torch.int32)
     _require(draw, "draw", torch.int32)
-    if finished.dtype == torch.bool:
-        finished = finished.to(torch.int32)
-    _require(finished, "finished", torch.int32)
     if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and state.numel() == 2):
         raise RuntimeError("vmlmf_amd.lm_sbeam_step: state must be a {seed, offset} snapshot: two int64 on the device")
-    eos_c = -1 if eos is None else int(eos)
-    if eos is not None and not 0 <= eos_c < V:
-        raise ValueError(f"vmlmf_amd.lm_sbeam_step: eos={eos} is not a token of the vocabulary ({V})")
-    return sbeam_select(torch.mm(h2, w.t()), None if bias is None else bias.contiguous(), cum.contiguous(), finished.contiguous(),
-                        length.contiguous(), perturbed.contiguous(), draw.contiguous(), state.contiguous(), eos_c,
-                        None if embed is None else embed.contiguous(), buffers)
+    return sbeam_select(torch.mm(h2, w.t()), bias, cum, finished, length, perturbed.contiguous(), draw.contiguous(), state.contiguous(),
+                        eos_c, embed, buffers)
 
 
 _BUFFERS = {}

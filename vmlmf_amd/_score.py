@@ -22,8 +22,7 @@ SYMBOLS = {
     "vmlmf_score_rows": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_score.so", SYMBOLS, "vmlmf_score_abi_version", ABI_VERSION, "vmlmf_score_last_error",
-                       "stock-op fallback for Model.score")
+LIBRARY = _lib.Library("score", SYMBOLS, ABI_VERSION, "stock-op fallback for Model.score")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 

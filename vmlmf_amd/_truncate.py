@@ -29,8 +29,7 @@ SYMBOLS = {
                                    ctypes.POINTER(_decode.Controls), _vp, _vp, _vp, _vp, _vp]),
 }
 
-LIBRARY = _lib.Library("libvmlmf_truncate.so", SYMBOLS, "vmlmf_truncate_abi_version", ABI_VERSION, "vmlmf_truncate_last_error",
-                       "stock-op fallback for the truncation samplers of Model.generate")
+LIBRARY = _lib.Library("truncate", SYMBOLS, ABI_VERSION, "stock-op fallback for the truncation samplers of Model.generate")
 lib, loaded, check = LIBRARY.handle, LIBRARY.loaded, LIBRARY.check
 
 HISTORY_REFUSAL = ("vmlmf_amd: min_p / typical_p / epsilon_cutoff / eta_cutoff together with the history controls (no_repeat_ngram_size, "

@@ -428,6 +428,42 @@ def _check_chunk(method, chunk, steps):
         raise ValueError(f"vmlmf_amd: Model.{method}: chunk={chunk} must divide steps={steps}")
 
 
+def _check_search(method, V, **given):
+    """ValueError for what a search call cannot take of eos= (None or one of the V tokens), length_penalty= (>= 0) and steps= (an int
+    >= 0), looked at in the order given."""
+    for name, value in given.items():
+        if name == "eos" and value is not None and not 0 <= int(value) < V:
+            raise ValueError(f"vmlmf_amd: Model.{method}: eos={value} is not a token of the vocabulary ({V})")
+        if name == "length_penalty" and not float(value) >= 0.0:
+            raise ValueError(f"vmlmf_amd: Model.{method}: length_penalty must be >= 0, got {value}")
+        if name == "steps" and value < 0:
+            raise ValueError(f"vmlmf_amd: Model.{method}: steps must be >= 0, got {value}")
+
+
+def _widen(states, W):
+    """The layers' states with every batch row W times over (row b W + w)."""
+    return [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+
+
+def _ranked(parents, toks, cum, length, states, alpha, groups=1):
+    """The end of a beam search: (hypotheses (steps, B, W) behind the last step's slots, cum, length, states), for alpha > 0 re-sorted
+    (stable) by cum / length ** alpha within each of the `groups` groups of a row - no hypothesis leaves its group."""
+    B, W = cum.shape
+    order = None
+    if alpha > 0.0:
+        key = cum / length.to(torch.float32) ** alpha
+        if groups == 1:
+            order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        else:
+            order = torch.sort(key.view(B, groups, W // groups), dim=2, descending=True, stable=True).indices
+            order = (order + torch.arange(groups, device=cum.device)[None, :, None] * (W // groups)).view(B, W)
+        cum, length = cum.gather(1, order), length.gather(1, order)
+        rows = (torch.arange(B, device=cum.device)[:, None] * W + order).reshape(-1).to(torch.int32)
+        states = _pairs(beam_gather([t for st in states for t in st], rows))
+        order = order.to(torch.int32)
+    return beam_backtrack(parents, toks, order), cum, length, states
+
+
 @contextlib.contextmanager
 def _activations(model, tokens, states):
     """`with _activations(model, tokens, states) as (h, states):` the model in eval mode, without autograd and on kept parameter images
@@ -526,12 +562,7 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
     """Model.beam_search (lm.py has the contract)."""
     W = _beam.check_beams(beams, model.vocab_size)
     steps, alpha = int(steps), float(length_penalty)
-    if eos is not None and not 0 <= int(eos) < model.vocab_size:
-        raise ValueError(f"vmlmf_amd: Model.beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
-    if not alpha >= 0.0:
-        raise ValueError(f"vmlmf_amd: Model.beam_search: length_penalty must be >= 0, got {length_penalty}")
-    if steps < 0:
-        raise ValueError(f"vmlmf_amd: Model.beam_search: steps must be >= 0, got {steps}")
+    _check_search("beam_search", model.vocab_size, eos=eos, length_penalty=length_penalty, steps=steps)
     ctl_args = dict(eos=eos, min_length=min_length, banned_tokens=banned_tokens, no_repeat_ngram_size=no_repeat_ngram_size,
                     banned_sequences=banned_sequences)
     controlled = _beamctl.controls_on(min_length, banned_tokens, no_repeat_ngram_size, banned_sequences)
@@ -558,8 +589,7 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
             controls = AutomatonBeamControls(B, W, model.vocab_size, dev, automaton, automaton_state, eos=eos, min_length=min_length,
                                              banned_tokens=banned_tokens, _checked=True)
         history = _beam_start(controls)
-        h = h.repeat_interleave(W, 0)
-        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        h, states = h.repeat_interleave(W, 0), _widen(states, W)
         cum, finished, length = _fresh_beams(B, W, dev)
         if steps == 0:
             return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
@@ -569,15 +599,7 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
             lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls,
                               **dict(zip(_beam_extras(controls), history))))
         _, states, cum, finished, length, _ = _split_beams(carried, controls)
-        order = None
-        if alpha > 0.0:
-            key = cum / length.to(torch.float32) ** alpha
-            order = torch.sort(key, dim=1, descending=True, stable=True).indices
-            cum, length = cum.gather(1, order), length.gather(1, order)
-            rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
-            states = _pairs(beam_gather([t for st in states for t in st], rows))
-            order = order.to(torch.int32)
-        return beam_backtrack(parents, toks, order), cum, length, states
+        return _ranked(parents, toks, cum, length, states, alpha)
 
 
 def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_penalty=0.5, states=None, eos=None, length_penalty=0.0,
@@ -585,20 +607,13 @@ def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_pena
     """Model.group_beam_search (lm.py has the contract)."""
     W, G, lam = _beamgroup.check_groups(beams, groups, diversity_penalty, model.vocab_size)
     steps, alpha = int(steps), float(length_penalty)
-    if eos is not None and not 0 <= int(eos) < model.vocab_size:
-        raise ValueError(f"vmlmf_amd: Model.group_beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
-    if not alpha >= 0.0:
-        raise ValueError(f"vmlmf_amd: Model.group_beam_search: length_penalty must be >= 0, got {length_penalty}")
-    if steps < 0:
-        raise ValueError(f"vmlmf_amd: Model.group_beam_search: steps must be >= 0, got {steps}")
+    _check_search("group_beam_search", model.vocab_size, eos=eos, length_penalty=length_penalty, steps=steps)
     _check_chunk("group_beam_search", chunk, steps)
     _check_call(model, prompt, "group_beam_search", "group beam-step kernel (vmlmf_beamgroup_step)")
     B, dev = prompt.shape[1], prompt.device
-    Wg = W // G
     with _session(model, prompt, states) as (h, states):
         controls = GroupBeams(B, W, model.vocab_size, dev, G, lam)
-        h = h.repeat_interleave(W, 0)
-        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        h, states = h.repeat_interleave(W, 0), _widen(states, W)
         cum, finished, length = controls.start()
         if steps == 0:
             return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
@@ -607,16 +622,7 @@ def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_pena
             lambda: _beamed(model, _join_beams(h, states, cum, finished, length, []), steps, eos, None, controls),
             lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls))
         _, states, cum, finished, length, _ = _split_beams(carried, controls)
-        order = None
-        if alpha > 0.0:      # the stable re-sort within each group: no hypothesis leaves its group
-            key = (cum / length.to(torch.float32) ** alpha).view(B, G, Wg)
-            order = torch.sort(key, dim=2, descending=True, stable=True).indices
-            order = (order + torch.arange(G, device=dev)[None, :, None] * Wg).view(B, W)
-            cum, length = cum.gather(1, order), length.gather(1, order)
-            rows = (torch.arange(B, device=dev)[:, None] * W + order).reshape(-1).to(torch.int32)
-            states = _pairs(beam_gather([t for st in states for t in st], rows))
-            order = order.to(torch.int32)
-        return beam_backtrack(parents, toks, order), cum, length, states
+        return _ranked(parents, toks, cum, length, states, alpha, G)
 
 
 # ---- contrastive search ------------------------------------------------------------------------------------------------------------
@@ -681,10 +687,7 @@ def contrastive_search(model, prompt, steps, top_k=4, penalty_alpha=0.6, *, stat
     """Model.contrastive_search (lm.py has the contract)."""
     k, alpha = _contrast.check_contrast(top_k, penalty_alpha, model.vocab_size, model.hidden_size)
     steps = int(steps)
-    if steps < 0:
-        raise ValueError(f"vmlmf_amd: Model.contrastive_search: steps must be >= 0, got {steps}")
-    if eos is not None and not 0 <= int(eos) < model.vocab_size:
-        raise ValueError(f"vmlmf_amd: Model.contrastive_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
+    _check_search("contrastive_search", model.vocab_size, steps=steps, eos=eos)
     if isinstance(prompt, torch.Tensor) and prompt.dim() == 2 and prompt.shape[0] < 1:
         raise ValueError("vmlmf_amd: Model.contrastive_search: the prompt needs T0 >= 1 tokens: the first step compares with the history behind them")
     _check_chunk("contrastive_search", chunk, steps)
@@ -697,7 +700,7 @@ def contrastive_search(model, prompt, steps, top_k=4, penalty_alpha=0.6, *, stat
         if steps == 0:
             empty = torch.empty((0, B), device=dev)
             return (empty.to(torch.int64), empty, controls.length, *((empty.clone(),) if return_penalties else ()), states)
-        wide = [tuple(t.repeat_interleave(k, t.dim() - 2) for t in st) for st in states]
+        wide = _widen(states, k)
         flat = [t for st in wide for t in st]
         outs, carried = _run(steps, chunk, lambda: _contrasted(model, [hs[-1], *flat, *flat], controls, steps, return_penalties),
                              lambda: ContrastGraph(model, hs[-1], wide, int(chunk), controls, return_penalties))
@@ -762,17 +765,13 @@ def stochastic_beam_search(model, prompt, steps, beams=4, *, seed=None, states=N
     """Model.stochastic_beam_search (lm.py has the contract)."""
     W = _sbeam.check_sbeam(beams, model.vocab_size)
     steps = int(steps)
-    if eos is not None and not 0 <= int(eos) < model.vocab_size:
-        raise ValueError(f"vmlmf_amd: Model.stochastic_beam_search: eos={eos} is not a token of the vocabulary ({model.vocab_size})")
-    if steps < 0:
-        raise ValueError(f"vmlmf_amd: Model.stochastic_beam_search: steps must be >= 0, got {steps}")
+    _check_search("stochastic_beam_search", model.vocab_size, eos=eos, steps=steps)
     _check_chunk("stochastic_beam_search", chunk, steps)
     _check_call(model, prompt, "stochastic_beam_search", "stochastic beam-step kernel (vmlmf_sbeam_step)")
     B, dev = prompt.shape[1], prompt.device
     snap = dropout_advance(model.sampler_state(seed))      # once per call: the steps differ by `draw`, on the device
     with _session(model, prompt, states) as (h, states):
-        h = h.repeat_interleave(W, 0)
-        states = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in st) for st in states]
+        h, states = h.repeat_interleave(W, 0), _widen(states, W)
         cum, finished, length, perturbed, draw = StochasticBeams(B, W, model.vocab_size, dev).start()
         if steps == 0:
             return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, perturbed, length, states
