@@ -51,6 +51,51 @@ def test_the_model_level_cases_are_mostly_clear_and_finish_some_beams(kind, B, W
                 assert (hyps[hit[0]:, b, w] == MODEL_EOS).all()
 
 
+# ---- the protocol of a beam policy ----
+def test_the_four_policies_share_one_protocol():
+    """BeamControls, AutomatonBeamControls, GroupBeams and StochasticBeams are BeamPolicy objects: a search that starts has beam 0 of a
+    row at 0 and the others at -inf (a group search: the first slot of every group), and a keyword a policy does not carry is refused."""
+    import math
+    from vmlmf_amd import AutomatonBeamControls, BeamControls, GroupBeams, StochasticBeams, TokenAutomaton, _beam, decoding, lm_beam_step
+    B, W, V, inf = 2, 4, 97, math.inf
+    prompt = torch.zeros((3, B), dtype=torch.int64)
+    plain = _beam.BeamPolicy(B, W, V, "cpu")
+    policies = [BeamControls(B, W, V, "cpu"), BeamControls(B, W, V, "cpu", prompt=prompt, no_repeat_ngram_size=2),
+                AutomatonBeamControls(B, W, V, "cpu", TokenAutomaton.avoiding(V, [[1, 2]])), GroupBeams(B, W, V, "cpu", groups=2),
+                StochasticBeams(B, W, V, "cpu")]
+    zeros = torch.zeros((B, W), dtype=torch.int32)
+    for p in [plain] + policies:
+        assert isinstance(p, _beam.BeamPolicy) and (p.B, p.W, p.V, p.device) == (B, W, V, torch.device("cpu"))
+        cum, fin, ln = p.first_beams()
+        grouped = isinstance(p, GroupBeams)
+        assert cum.dtype == torch.float32 and cum.tolist() == [[0.0, -inf, 0.0 if grouped else -inf, -inf]] * B, type(p).__name__
+        assert fin.dtype == ln.dtype == torch.int32 and torch.equal(fin, zeros) and torch.equal(ln, zeros)
+        assert fin.data_ptr() != ln.data_ptr()
+        assert len(p.first_carried()) == len(p.carried) and p.keeps_history == (p.carried == ("hist", "hist_len"))
+    assert [p.carried for p in [plain] + policies] == [(), (), ("hist", "hist_len"), ("beam_state",), (), ("perturbed", "draw")]
+    assert policies[3].clone() is policies[3] and policies[1].clone() is not policies[1] and plain.first_carried() == []
+    assert all(torch.equal(x, y) for x, y in zip(policies[3].first_beams(), policies[3].start()))
+    # a keyword the controls do not carry: a TypeError that names it, before anything else is looked at
+    x = torch.zeros(B * W, dtype=torch.int32)
+    step = (torch.zeros(B * W, 8), torch.zeros(V, 8), None, *plain.first_beams(), None)
+    for controls, kw in ((policies[3], dict(hist=x)), (policies[3], dict(beam_state=x)), (None, dict(hist=x)), (policies[2], dict(hist_len=x)),
+                         (policies[0], dict(hist=x)), (policies[4], dict(beam_state=x)), (policies[1], dict(perturbed=x))):
+        with pytest.raises(TypeError, match=next(iter(kw))):
+            lm_beam_step(*step, controls=controls, **kw)
+        with pytest.raises(TypeError, match=next(iter(kw))):
+            decoding.beam_steps(None, None, [], *plain.first_beams(), 1, None, controls=controls, **kw)
+        with pytest.raises(TypeError, match=next(iter(kw))):
+            decoding._beam_start(controls, **kw)
+    with pytest.raises(RuntimeError, match="HIP device"):                  # (a carried keyword passes on to the step's own checks)
+        lm_beam_step(*step, controls=policies[2], beam_state=x)
+    assert decoding._beam_start(None) == [] and decoding._beam_start(policies[3]) == []
+    hist, hist_len = decoding._beam_start(policies[1])
+    assert hist.shape == (B * W, policies[1].capacity) and hist_len.tolist() == [3] * (B * W)
+    assert decoding._beam_start(policies[1], hist=hist, hist_len=hist_len)[0] is hist
+    pert, draw = decoding._beam_start(policies[4], draw=x[:B])
+    assert draw.data_ptr() == x.data_ptr() and pert.tolist() == [[0.0, -inf, -inf, -inf]] * B      # each default on its own
+
+
 # ---- host-side checks ----
 def test_beam_search_refuses_bad_beam_counts_before_anything_else():
     from vmlmf_amd import Model

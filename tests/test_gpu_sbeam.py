@@ -238,7 +238,7 @@ def _walk(m, prompt, W, steps, eos, seed):
     """The search step by step - Model.stochastic_beam_search's own prologue, its loop one step at a time: per step (parent, token,
     cum, finished, length, perturbed) on the CPU."""
     from vmlmf_amd import StochasticBeams, dropout_advance
-    from vmlmf_amd.decoding import _KeptImages, sbeam_steps
+    from vmlmf_amd.decoding import _KeptImages, beam_steps
     B = prompt.shape[1]
     m.eval()
     hist = []
@@ -248,9 +248,11 @@ def _walk(m, prompt, W, steps, eos, seed):
         h, st = m.features(prompt, m.state_init(B))
         h = h[-1].repeat_interleave(W, 0)
         st = [tuple(t.repeat_interleave(W, t.dim() - 2) for t in s) for s in st]
-        cum, fin, ln, pert, draw = StochasticBeams(B, W, 97, _dev()).start()
+        beams = StochasticBeams(B, W, 97, _dev())
+        beams.state = snap
+        cum, fin, ln, pert, draw = beams.start()
         for j in range(steps):
-            par, tok, h, st, cum, fin, ln, pert, draw = sbeam_steps(m, h, st, cum, fin, ln, pert, draw, 1, eos, snap)
+            par, tok, h, st, cum, fin, ln, pert, draw = beam_steps(m, h, st, cum, fin, ln, 1, eos, controls=beams, perturbed=pert, draw=draw)
             assert draw.tolist() == [j + 1] * B
             hist.append(tuple(t.cpu() for t in (par[0], tok[0], cum, fin, ln, pert)))
     return hist
@@ -383,3 +385,43 @@ def test_one_beam_is_generate_where_the_choice_is_clear():
         agreed += 1
     print("seeds at which every choice is clear:", agreed, "of 6")
     assert agreed >= 2
+
+
+# ---- 3. one loop, one graph: the launches a search makes ----
+def test_the_search_runs_through_the_one_beam_loop_and_graph(monkeypatch):
+    """An eager stochastic_beam_search is beam_steps under a StochasticBeams - per step vmlmf_sbeam_step, then vmlmf_beam_gather, one
+    vmlmf_beam_backtrack at the end, never the plain step -, its graph a BeamGraph whose workspace vmlmf_sbeam_workspace_bytes sizes
+    (12 bytes a candidate: the plain step's 8 are refused), and two replays of 2 captured steps are the eager call's 4, bit for bit.
+    group_beam_search makes its launches in the same order."""
+    from lm_util import beam_model
+    from vmlmf_amd import BeamGraph, StochasticBeamGraph, _lib, _sbeam, beam_backtrack, dropout_advance
+    from vmlmf_amd.decoding import _KeptImages, _widen
+    B, W, V, steps, eos = 2, 3, 97, 4, 3
+    m = beam_model("plain").to(DEV)
+    prompt = _prompt(B, seed=13)
+    calls, sized = [], []
+    call, workspace_bytes = _lib.Library.call, _lib.Library.workspace_bytes
+    monkeypatch.setattr(_lib.Library, "call", lambda self, dev, name, *args: (calls.append(name), call(self, dev, name, *args))[1])
+    monkeypatch.setattr(_lib.Library, "workspace_bytes",
+                        lambda self, *shape: (sized.append(f"vmlmf_{self.name}_workspace_bytes"), workspace_bytes(self, *shape))[1])
+    tokens, scores, perturbed, lengths, _ = m.stochastic_beam_search(prompt, steps, beams=W, seed=5, eos=eos)
+    assert calls == ["vmlmf_sbeam_step", "vmlmf_beam_gather"] * steps + ["vmlmf_beam_backtrack"]
+    assert "vmlmf_beam_step" not in calls and set(sized) <= {"vmlmf_sbeam_workspace_bytes"}      # (the stream's pair: sbeam's own)
+    del calls[:], sized[:]
+    m.group_beam_search(prompt, steps, beams=W, groups=W, eos=eos)
+    assert calls == ["vmlmf_beamgroup_step", "vmlmf_beam_gather"] * steps + ["vmlmf_beam_backtrack"]
+    del calls[:], sized[:]
+    m.eval()
+    with torch.no_grad(), _KeptImages(m):
+        h, st = m.features(prompt, m.state_init(B))
+        graph = StochasticBeamGraph(m, h[-1].repeat_interleave(W, 0), _widen(st, W), 2, W, dropout_advance(m.sampler_state(5)), eos)
+    assert isinstance(graph, BeamGraph) and graph.controls is graph.beams and graph.beams.state is graph.state
+    assert set(sized) == {"vmlmf_sbeam_workspace_bytes"}                                         # not vmlmf_beam_workspace_bytes
+    assert calls.count("vmlmf_sbeam_step") == 2 * 2 and "vmlmf_beam_step" not in calls           # the warm-up and the capture
+    need = _sbeam.lib().vmlmf_sbeam_workspace_bytes(B, W, V)
+    assert need == B * W * W * 12 and graph.buffers[1].numel() * 8 >= need and graph.buffers[0].numel() == B
+    replays = [graph.replay() for _ in range(2)]
+    parents, toks = (torch.cat(o) for o in zip(*replays))
+    assert torch.equal(beam_backtrack(parents, toks), tokens) and torch.equal(graph.cum, scores) and torch.equal(graph.perturbed, perturbed)
+    assert torch.equal(graph.length, lengths) and graph.draw.tolist() == [steps] * B
+    assert int(graph.buffers[0].abs().sum()) == 0

@@ -205,8 +205,26 @@ def test_the_package_exports_the_stochastic_beams():
         assert getattr(vmlmf_amd, name) is getattr(decoding, name)
     assert vmlmf_amd.StochasticBeams is b.StochasticBeams and vmlmf_amd.lm_sbeam_step is b.lm_sbeam_step
     assert issubclass(decoding.StochasticBeamGraph, decoding._StepGraph)
-    assert callable(decoding.sbeam_steps) and callable(decoding.stochastic_beam_search) and callable(vmlmf_amd.Model.stochastic_beam_search)
+    assert callable(decoding.stochastic_beam_search) and callable(vmlmf_amd.Model.stochastic_beam_search)
     assert callable(b.check_sbeam) and b.check_sbeam(4, 97) == 4
+
+
+def test_stochastic_beams_are_a_policy_of_the_one_beam_loop():
+    """No second loop, graph or buffer cache: StochasticBeams goes through beam_steps / BeamGraph as the other policies do."""
+    from vmlmf_amd import StochasticBeams, _beam, _sbeam as b, decoding
+    assert issubclass(decoding.StochasticBeamGraph, decoding.BeamGraph) and issubclass(StochasticBeams, _beam.BeamPolicy)
+    assert StochasticBeams.carried == ("perturbed", "draw")
+    s = StochasticBeams(2, 4, 97, "cpu")
+    first, start = s.first_carried(), s.start()
+    assert len(first) == 2 and len(start) == 5 and all(torch.equal(x, y) and x.dtype == y.dtype for x, y in zip(first, start[3:]))
+    assert all(torch.equal(x, y) and x.dtype == y.dtype for x, y in zip(s.first_beams(), start[:3]))
+    assert not hasattr(decoding, "sbeam_steps") and not hasattr(decoding, "_sbeamed") and not hasattr(b, "_BUFFERS")
+    assert s.state is None
+    was = b.loaded()
+    cum, fin, ln, pert, draw = start
+    with pytest.raises(RuntimeError, match="state"):          # refused before any library is opened
+        s.select(torch.zeros(8, 97), None, cum, fin, ln, -1, None, perturbed=pert, draw=draw)
+    assert b.loaded() == was
 
 
 def test_the_kernel_takes_the_selection_and_the_noise_from_the_shared_headers():
@@ -241,7 +259,10 @@ def test_the_signatures():
     assert list(inspect.signature(_sbeam.check_sbeam).parameters) == ["beams", "V"]
     assert list(inspect.signature(StochasticBeams.__init__).parameters) == ["self", "B", "W", "V", "device"]
     assert list(inspect.signature(StochasticBeamGraph.__init__).parameters)[:7] == ["self", "model", "h", "states", "steps", "beams", "state"]
-    assert list(inspect.signature(decoding.sbeam_steps).parameters)[:4] == ["model", "h", "states", "cum"]
+    assert list(inspect.signature(StochasticBeamGraph.__init__).parameters) == [
+        "self", "model", "h", "states", "steps", "beams", "state", "eos", "cum", "finished", "length", "perturbed", "draw"]
+    assert list(inspect.signature(StochasticBeams.select).parameters) == [
+        "self", "scores", "bias", "cum", "finished", "length", "eos", "embed", "buffers", "perturbed", "draw"]
     doc = Model.stochastic_beam_search.__doc__
     for word in ("without replacement", "perturbed", "no temperature", "chunk=K", "Kool"):
         assert word in doc, word

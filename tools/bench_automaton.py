@@ -146,7 +146,7 @@ def main():
             emit(rec)
             rec = {"kind": "step", "form": "beam_search", "B": B, "W": W}
             for name, controls in (("plain", None), ("automaton", ca)):
-                g = BeamGraph(m, h, st, K, W, eos, cum, zero, zero, controls=controls, beam_state=state if controls is not None else None)
+                g = BeamGraph(m, h, st, K, W, eos, cum, zero, zero, controls=controls, **({} if controls is None else {"beam_state": state}))
                 ms, spread = wall_ms(g.replay, a.reps)
                 rec[f"{name}_step_ms"], rec[f"{name}_step_spread"] = round(ms / K, 5), round(spread, 3)
                 del g

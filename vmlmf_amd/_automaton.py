@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _decode, _lib
-from ._beam import check_beams, check_step_controls, step_buffers, step_outputs
+from ._beam import BeamPolicy, check_step_controls, launch_step
 from ._beamctl import pack_words
 from ._decode import DecodeControls
 from ._lib import ptr
@@ -353,7 +353,7 @@ class AutomatonControls(DecodeControls):
         return dict(super().values(), next=ptr(self.automaton.next), S=self.automaton.S, row_state=ptr(self.row_state), dead=ptr(self.dead))
 
 
-class AutomatonBeamControls:
+class AutomatonBeamControls(BeamPolicy):
     """The controls of one beam search over B batch rows of W beams under a TokenAutomaton on `device` (include/vmlmf_automaton.h):
       automaton, state   as AutomatonControls': (B) int32 start states of the batch rows (None: automaton.start)
       eos, min_length, banned_tokens   Model.beam_search's, as BeamControls'
@@ -362,21 +362,18 @@ class AutomatonBeamControls:
     fresh buffer behind its seven results.  `carried` names it as lm_beam_step's keyword, first_carried() is [start()], select() the
     step's launch."""
 
-    keeps_history = False
     carried = ("beam_state",)
 
     def __init__(self, B, W, V, device, automaton, state=None, eos=None, min_length=0, banned_tokens=None, _checked=False):
-        B, V = int(B), int(V)
-        W = check_beams(W, V)
+        super().__init__(B, W, V, device)
+        B, W, V = self.B, self.W, self.V
         start = check_automaton(automaton, V, B, state)
         self.eos, self.min_length, _, self.banned = _decode.check_controls(V, eos=eos, min_length=min_length, banned_tokens=banned_tokens)
         if self.eos >= 0 and self.eos in self.banned:
             raise ValueError(f"vmlmf_amd: eos={self.eos} is among banned_tokens: a finished beam offers eos alone")
         if not _checked:
             automaton.check_reachable(start, closed_tokens(V, None, self.banned), self.eos, self.min_length)
-        self.B, self.W, self.V = B, W, V
-        self.automaton = automaton.to(device)
-        self.device = self.automaton.device             # (with its index: what a launch's tensors are compared with)
+        self.automaton = automaton.to(self.device)
         self.closed = pack_words(self.banned, V).to(self.device) if self.banned else None
         self._start = torch.from_numpy(start.astype(np.int32)).to(self.device).repeat_interleave(W, 0).contiguous()
 
@@ -387,13 +384,9 @@ class AutomatonBeamControls:
     def first_carried(self):
         return [self.start()]
 
-    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, beam_state=None, **others):
-        """lm_beam_step's selection under these controls (automaton_select); of the carried keywords it takes its own."""
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, beam_state=None):
+        """lm_beam_step's selection under these controls (automaton_select)."""
         return automaton_select(scores, bias, cum, finished, length, eos, embed, self, beam_state, buffers)
-
-    def clone(self):
-        """These controls (they own no state a launch moves: a BeamGraph's warm-up runs on the same object)."""
-        return self
 
 
 def automaton_select(scores, bias, cum, finished, length, eos, embed, controls, beam_state=None, buffers=None):
@@ -409,12 +402,8 @@ def automaton_select(scores, bias, cum, finished, length, eos, embed, controls, 
             and tuple(beam_state.shape) == (B * W,) and beam_state.is_contiguous()):
         raise RuntimeError(f"vmlmf_amd.lm_beam_step: beam_state must be a contiguous int32 ({B * W},) tensor on {dev} "
                            "(AutomatonBeamControls.start())")
-    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
-    H = embed.shape[1] if embed is not None else 1
-    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
     state_out = torch.empty_like(beam_state)
     table = controls.automaton.table()
-    LIBRARY.call(dev, "vmlmf_automaton_beam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                 controls.min_length, ptr(controls.closed), ctypes.byref(table), ptr(beam_state), ptr(state_out), ptr(parent), ptr(token),
-                 ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8)
-    return parent, token, total, fin, ln, xn, src, state_out
+    outs = launch_step(LIBRARY, "vmlmf_automaton_beam_step", scores, bias, cum, finished, length, eos, embed, buffers,
+                       before=(controls.min_length, ptr(controls.closed), ctypes.byref(table), ptr(beam_state), ptr(state_out)))
+    return (*outs, state_out)

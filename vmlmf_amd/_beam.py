@@ -52,27 +52,75 @@ def _require(t, what, dtype=torch.float32):
 _BUFFERS = {}
 
 
-def step_buffers(dev, B, W, V):
-    """(ticket (B) int32 - zero, and left zero by every launch -, workspace) of vmlmf_beam_step, kept per (device, stream): launches
-    that share them must be ordered on one stream.  Not to be called inside a stream capture (BeamGraph brings its own)."""
-    nbytes = lib().vmlmf_beam_workspace_bytes(B, W, V)
-    key = (dev.index, _lib.raw_stream(dev).value)
+def step_buffers(dev, B, W, V, library=None):
+    """(ticket (B) int32 - zero, and left zero by every launch -, workspace) of a beam step at this shape, kept per (library, device,
+    stream): launches that share them must be ordered on one stream.  library: the side library whose vmlmf_<name>_workspace_bytes sizes
+    the workspace (default: this one; the controlled, automaton and group steps need what vmlmf_beam_step needs) - a pair is never
+    shared between two libraries.  Not to be called inside a stream capture (BeamGraph brings its own)."""
+    key = (library or LIBRARY, dev.index, _lib.raw_stream(dev).value, B, W, V)
     got = _BUFFERS.get(key)
-    if got is None or got[0].numel() < B or got[1].numel() * 8 < nbytes:
-        if got is not None:
-            B, nbytes = max(B, got[0].numel()), max(nbytes, got[1].numel() * 8)
-        got = _BUFFERS[key] = (torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64))
+    if got is None:
+        got = _BUFFERS[key] = new_step_buffers(dev, B, W, V, library)
     return got
 
 
-def new_step_buffers(dev, B, W, V):
-    """A ticket and a workspace of one's own (a captured graph's: its launches must not meet another stream's on one ticket)."""
-    nbytes = lib().vmlmf_beam_workspace_bytes(B, W, V)
+def new_step_buffers(dev, B, W, V, library=None):
+    """A ticket and a workspace of one's own (a captured graph's: its launches must not meet another stream's on one ticket), sized
+    as step_buffers' by `library`."""
+    nbytes = (library or LIBRARY).workspace_bytes(B, W, V)
     return torch.zeros(B, device=dev, dtype=torch.int32), torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
 
 
-def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None, controls=None, hist=None, hist_len=None,
-                 beam_state=None):
+class BeamPolicy:
+    """What lm_beam_step, decoding.beam_steps and BeamGraph ask of a `controls` object - a beam step that differs from the plain one
+    over B batch rows of W beams and a V-token vocabulary on `device` -, with the defaults of a policy that carries nothing:
+      carried            the names of the tensors it hands on from step to step behind cum, finished and length (lm_beam_step's keywords)
+      first_carried()    those tensors for a search that starts
+      first_beams()      (cum, finished, length), each (B, W), of a search that starts: beam 0 of a row at score 0, the others at -inf
+      select(scores, bias, cum, finished, length, eos, embed, buffers, **carried)    the step's launch on checked arguments: the seven
+                         results of lm_beam_step, the survivors' carried tensors behind them (each policy's own; None is the plain step)
+      clone()            what a graph's warm-up runs on: a copy of whatever state a launch moves (default: none, the object itself)
+      new_buffers()      a (ticket, workspace) pair of its own for a captured graph, of the size ITS step needs
+      keeps_history, eos, min_length    what check_step_controls reads (it holds no eos of its own: the step's is used)
+    ValueError for what check_beams refuses, before any device work."""
+
+    carried = ()
+    keeps_history = False
+    eos, min_length = -1, 0
+
+    def __init__(self, B, W, V, device):
+        self.B, self.V = int(B), int(V)
+        self.W = check_beams(W, self.V)
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev                           # (with its index: what a launch's tensors are compared with)
+
+    def first_carried(self):
+        return []
+
+    def first_beams(self):
+        cum = torch.full((self.B, self.W), float("-inf"), device=self.device)
+        cum[:, 0] = 0.0
+        return cum, torch.zeros_like(cum, dtype=torch.int32), torch.zeros_like(cum, dtype=torch.int32)
+
+    def new_buffers(self):
+        return new_step_buffers(self.device, self.B, self.W, self.V)
+
+    def clone(self):
+        return self
+
+
+def check_carried(controls, given):
+    """TypeError for a keyword among `given` - carried tensors by name - that the controls (None: the plain step) do not carry."""
+    names = () if controls is None else controls.carried
+    for name in given:
+        if name not in names:
+            who = "the plain beam step" if controls is None else f"this {type(controls).__name__}"
+            raise TypeError(f"vmlmf_amd: {name}= is not carried by {who} (it carries {', '.join(names) or 'nothing'})")
+
+
+def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffers=None, controls=None, **carried):
     """One step of beam search over B batch rows of W beams (cum is (B, W)): the head's GEMM over the beams' top-layer outputs h (B W, H)
     - row b W + w is beam w of batch row b -, then ONE launch (vmlmf_beam_step, csrc/vmlmf_beam.hip) that forms every candidate's total
     cum[b, w] + log_softmax(h fc.w^T + bias)[v] in fp32, keeps the W best of each batch row under the total order (larger total first,
@@ -82,21 +130,27 @@ def lm_beam_step(h, weight, bias, cum, finished, length, eos, embed=None, buffer
     Returns (parent (B, W) int32, token (B, W) int64, total (B, W) fp32, finished (B, W) int32, length (B, W) int32,
     x_next (B W, H) = embed[token] or None without embed, src_row (B W) int32 = b W + parent: the state row a survivor continues).
     buffers: (ticket, workspace) of new_step_buffers() - default: the current stream's.
-    controls: a BeamControls (_beamctl.py: min_length, banned_tokens, no_repeat_ngram_size, banned_sequences) - the selection is then
+    controls: a BeamPolicy - the selection is then its select(), which takes the tensors it carries (controls.carried) as keywords
+    **carried and returns the survivors' behind the seven results; a keyword it does not carry is a TypeError.
+    A BeamControls (_beamctl.py: min_length, banned_tokens, no_repeat_ngram_size, banned_sequences) - the selection is
     ONE launch of vmlmf_beamctl_step (csrc/vmlmf_beamctl.hip, a library of its own) in which a live beam withholds what the controls
     close, behind ONE vmlmf_history_bans launch on the beams' histories hist (B W, capacity) / hist_len (B W) when an n-gram or a
     sequence control is on; the totals of what is offered are the plain step's to the bit.  Two more results follow the seven: the
     survivors' (hist, hist_len), fresh buffers - (None, None) when the controls keep no history.
-    controls: an AutomatonBeamControls (_automaton.py: a TokenAutomaton, min_length, banned_tokens) - the selection is ONE launch of
+    An AutomatonBeamControls (_automaton.py: a TokenAutomaton, min_length, banned_tokens) - the selection is ONE launch of
     vmlmf_automaton_beam_step (csrc/vmlmf_automaton.hip) on beam_state (B W) int32, the beams' states (default: controls.start()); one
     more result follows the seven: the survivors' states, a fresh buffer.
-    controls: a GroupBeams (_beamgroup.py: groups, diversity_penalty) - the selection is ONE launch of vmlmf_beamgroup_step
-    (csrc/vmlmf_beamgroup.hip), the same kernel whose merge runs group by group; the seven results, nothing carried."""
+    A GroupBeams (_beamgroup.py: groups, diversity_penalty) - the selection is ONE launch of vmlmf_beamgroup_step
+    (csrc/vmlmf_beamgroup.hip), the same kernel whose merge runs group by group; the seven results, nothing carried.
+    A StochasticBeams (_sbeam.py) whose `state` is set - the selection is lm_sbeam_step's ONE launch of vmlmf_sbeam_step on perturbed
+    (B, W) and draw (B); the survivors' perturbed and draw + 1 follow the seven."""
+    if carried:
+        check_carried(controls, carried)
     h2, w, *rest = check_step("lm_beam_step", h, weight, bias, cum, finished, length, eos, embed)
     args = (torch.mm(h2, w.t()), *rest)
     if controls is None:
         return beam_select(*args, buffers)
-    return controls.select(*args, buffers, hist=hist, hist_len=hist_len, beam_state=beam_state)    # (it takes what it carries)
+    return controls.select(*args, buffers, **carried)
 
 
 def check_step(caller, h, weight, bias, cum, finished, length, eos, embed):
@@ -156,18 +210,26 @@ def check_step_controls(controls, kind, B, W, V, dev, eos):
         raise ValueError(f"vmlmf_amd.lm_beam_step: the controls' eos ({controls.eos}) is not the step's ({eos})")
 
 
-def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
-    """The vmlmf_beam_step launch on checked, contiguous arguments: scores (B W, V) without the bias, eos an int (-1: none).
-    lm_beam_step's results."""
+def launch_step(library, entry, scores, bias, cum, finished, length, eos, embed, buffers, before=(), behind=(), sized_by=None):
+    """ONE launch of a beam step - `entry` of `library` - on checked, contiguous arguments (scores (B W, V) without the bias, eos an
+    int, -1: none): the 21 arguments every step's entry point shares, in ABI order - B, W, H, V, the five inputs, eos, embed, the seven
+    outputs, ticket, workspace, workspace_bytes -, the entry point's own `before` the outputs or `behind` workspace_bytes.  buffers:
+    (ticket, workspace), default: the current stream's of the library `sized_by` (step_buffers).  Returns step_outputs' seven."""
     B, W = cum.shape
     V = scores.shape[1]
     dev = scores.device
-    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
+    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V, sized_by)
     H = embed.shape[1] if embed is not None else 1
-    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
-    LIBRARY.call(dev, "vmlmf_beam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                 ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8)
-    return parent, token, total, fin, ln, xn, src
+    outs = step_outputs(B, W, H, dev, embed)
+    library.call(dev, entry, B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed), *before,
+                 *map(ptr, outs), ptr(ticket), ptr(ws), ws.numel() * 8, *behind)
+    return outs
+
+
+def beam_select(scores, bias, cum, finished, length, eos, embed, buffers=None):
+    """The vmlmf_beam_step launch on checked, contiguous arguments: scores (B W, V) without the bias, eos an int (-1: none).
+    lm_beam_step's results."""
+    return launch_step(LIBRARY, "vmlmf_beam_step", scores, bias, cum, finished, length, eos, embed, buffers)
 
 
 def beam_gather(tensors, src_row):

@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _decode, _history, _lib
-from ._beam import check_beams, check_step_controls, step_buffers, step_outputs
+from ._beam import BeamPolicy, check_step_controls, launch_step
 from ._lib import ptr
 
 ABI_VERSION = 1
@@ -74,7 +74,7 @@ def pack_words(tokens, V):
     return torch.tensor([w - (1 << 32) if w >= (1 << 31) else w for w in words], dtype=torch.int32)
 
 
-class BeamControls:
+class BeamControls(BeamPolicy):
     """The controls of one beam search over B batch rows of W beams and a V-token vocabulary on `device` (include/vmlmf_beamctl.h).
     They only close candidates - a candidate is offered or it is not -, so `scores` stay sums of plain log-probabilities:
       eos                    the token that finishes a beam (the search's own eos, needed by min_length)
@@ -94,19 +94,18 @@ class BeamControls:
 
     def __init__(self, B, W, V, device, prompt=None, capacity=None, min_length=0, banned_tokens=None, no_repeat_ngram_size=0,
                  banned_sequences=None, eos=None):
-        B, V = int(B), int(V)
-        W = check_beams(W, V)
+        super().__init__(B, W, V, device)
+        B, W, V, dev = self.B, self.W, self.V, self.device
         self.eos, self.min_length, self.banned, self.no_repeat_ngram_size, self.sequences = check_beam_controls(
             V, W, eos, min_length, banned_tokens, no_repeat_ngram_size, banned_sequences)
         if prompt is not None and not (isinstance(prompt, torch.Tensor) and prompt.dtype == torch.int64 and prompt.dim() == 2
                                        and prompt.shape[1] == B):
             raise ValueError(f"vmlmf_amd: BeamControls takes a (T0, {B}) int64 prompt")
         capacity = _history.check_capacity("BeamControls", capacity, int(prompt.shape[0]) if prompt is not None else 0)
-        self.B, self.W, self.V, self.capacity = B, W, V, capacity
+        self.capacity = capacity
         self.keeps_history = self.no_repeat_ngram_size > 0 or bool(self.sequences)
         self.carried = ("hist", "hist_len") if self.keeps_history else ()
-        self.overflow = torch.zeros(B, dtype=torch.int32, device=torch.device(device))
-        self.device = dev = self.overflow.device        # (with its index: what a launch's tensors are compared with)
+        self.overflow = torch.zeros(B, dtype=torch.int32, device=dev)
         self.closed = pack_words(self.banned, V).to(dev) if self.banned else None
         self.seq_tokens, self.seq_offsets = _history.flat_sequences(self.sequences, dev)
         self._hist0 = None
@@ -125,8 +124,8 @@ class BeamControls:
         """[hist, hist_len] of a search that starts - [] when no history is kept."""
         return list(self.history()) if self.keeps_history else []
 
-    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, hist=None, hist_len=None, **others):
-        """lm_beam_step's selection under these controls (beamctl_select); of the carried keywords it takes its own."""
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, hist=None, hist_len=None):
+        """lm_beam_step's selection under these controls (beamctl_select)."""
         return beamctl_select(scores, bias, cum, finished, length, eos, embed, self, hist, hist_len, buffers)
 
     def clone(self):
@@ -161,12 +160,7 @@ def beamctl_select(scores, bias, cum, finished, length, eos, embed, controls, hi
         hist_out, len_out = torch.empty_like(hist), torch.empty_like(hist_len)
     else:
         hist = hist_len = None
-    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
-    H = embed.shape[1] if embed is not None else 1
-    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
     c = Controls(controls.min_length, cap, ptr(controls.closed), ptr(bans), ptr(hist), ptr(hist_len), ptr(hist_out), ptr(len_out),
                  ptr(controls.overflow) if hist is not None else None)
-    LIBRARY.call(dev, "vmlmf_beamctl_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                 ctypes.byref(c), ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws),
-                 ws.numel() * 8)
-    return parent, token, total, fin, ln, xn, src, hist_out, len_out
+    outs = launch_step(LIBRARY, "vmlmf_beamctl_step", scores, bias, cum, finished, length, eos, embed, buffers, before=(ctypes.byref(c),))
+    return (*outs, hist_out, len_out)

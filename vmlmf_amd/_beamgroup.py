@@ -12,8 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._beam import check_beams, step_buffers, step_outputs
-from ._lib import ptr
+from ._beam import BeamPolicy, check_beams, check_step_controls, launch_step
 
 ABI_VERSION = 1
 
@@ -55,7 +54,7 @@ def group_start(B, W, groups, device):
     return cum, torch.zeros((B, W), dtype=torch.int32, device=device), torch.zeros((B, W), dtype=torch.int32, device=device)
 
 
-class GroupBeams:
+class GroupBeams(BeamPolicy):
     """The grouping of one diverse beam search (Vijayakumar et al.) over B batch rows of W beams and a V-token vocabulary on `device`
     (include/vmlmf_beamgroup.h): `groups` = G divides W, group g owns slots g W / G .. (g + 1) W / G - 1 of a row and keeps the best of
     its own beams' candidates under total - diversity_penalty n, n the number of survivors the groups before it chose in this step with
@@ -64,46 +63,24 @@ class GroupBeams:
     lm_beam_step(controls=), decoding.beam_steps and BeamGraph(controls=) take it as they take BeamControls.  start() gives a search's
     first (cum, finished, length).  ValueError for what check_groups refuses, before any device work."""
 
-    carried = ()
-    keeps_history = False
-    eos, min_length = -1, 0        # (it holds no eos of its own: the step's is used)
-
     def __init__(self, B, W, V, device, groups=2, diversity_penalty=0.5):
-        self.B, self.V = int(B), int(V)
-        self.W, self.groups, self.diversity_penalty = check_groups(W, groups, diversity_penalty, self.V)
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev                           # (with its index: what a launch's tensors are compared with)
-
-    def first_carried(self):
-        return []
+        super().__init__(B, W, V, device)
+        _, self.groups, self.diversity_penalty = check_groups(self.W, groups, diversity_penalty, self.V)
 
     def start(self):
         """(cum, finished, length) of a search that starts (group_start)."""
         return group_start(self.B, self.W, self.groups, self.device)
 
-    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, **others):
-        """lm_beam_step's selection in groups (group_select); it takes none of the carried keywords."""
-        return group_select(scores, bias, cum, finished, length, eos, embed, self, buffers)
+    first_beams = start
 
-    def clone(self):
-        """These controls (they own no state a launch moves: a BeamGraph's warm-up runs on the same object)."""
-        return self
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None):
+        """lm_beam_step's selection in groups (group_select)."""
+        return group_select(scores, bias, cum, finished, length, eos, embed, self, buffers)
 
 
 def group_select(scores, bias, cum, finished, length, eos, embed, controls, buffers=None):
     """The vmlmf_beamgroup_step launch on checked, contiguous arguments (scores (B W, V) without the bias, eos an int, -1: none).
     lm_beam_step's seven results."""
-    B, W = cum.shape
-    V = scores.shape[1]
-    dev = scores.device
-    if not isinstance(controls, GroupBeams) or (controls.B, controls.W, controls.V) != (B, W, V) or controls.device != dev:
-        raise RuntimeError(f"vmlmf_amd.lm_beam_step: controls must be a GroupBeams for {B} x {W} beams over {V} tokens on {dev}")
-    ticket, ws = buffers if buffers is not None else step_buffers(dev, B, W, V)
-    H = embed.shape[1] if embed is not None else 1
-    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
-    LIBRARY.call(dev, "vmlmf_beamgroup_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                 ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8,
-                 controls.groups, controls.diversity_penalty)
-    return parent, token, total, fin, ln, xn, src
+    check_step_controls(controls, GroupBeams, *cum.shape, scores.shape[1], scores.device, eos)
+    return launch_step(LIBRARY, "vmlmf_beamgroup_step", scores, bias, cum, finished, length, eos, embed, buffers,
+                       behind=(controls.groups, controls.diversity_penalty))

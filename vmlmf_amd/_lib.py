@@ -272,7 +272,7 @@ class Library:
 
     def __init__(self, name, symbols, abi_version, no_fallback):
         self.path = os.path.join(os.path.dirname(LIB_PATH), f"libvmlmf_{name}.so")
-        self.symbols, self.abi_version, self.no_fallback = symbols, abi_version, no_fallback
+        self.name, self.symbols, self.abi_version, self.no_fallback = name, symbols, abi_version, no_fallback
         self.abi_symbol, self.error_symbol = f"vmlmf_{name}_abi_version", f"vmlmf_{name}_last_error"
         self._handle = None
 
@@ -289,6 +289,10 @@ class Library:
     def check(self, rc):
         if rc != 0:
             raise VmlmfError(rc, getattr(self.handle(), self.error_symbol)().decode())
+
+    def workspace_bytes(self, *shape):
+        """vmlmf_<name>_workspace_bytes(*shape): what a launch of this library's step needs at that shape (0: a shape it refuses)."""
+        return getattr(self.handle(), f"vmlmf_{self.name}_workspace_bytes")(*shape)
 
     def call(self, dev, name, *args):
         """One launch: `dev` made current, the entry point `name` called with torch's current stream on `dev` as its last argument,

@@ -11,7 +11,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._beam import _require, check_beams, check_step, step_outputs
+from ._beam import BeamPolicy, _require, check_beams, check_step, check_step_controls, launch_step, new_step_buffers
 from ._lib import ptr
 
 ABI_VERSION = 1
@@ -35,39 +35,65 @@ def check_sbeam(beams, V=None):
     return check_beams(beams, V)
 
 
-class StochasticBeams:
-    """What one stochastic beam search (Kool, van Hoof and Welling) over B batch rows of W beams and a V-token vocabulary on `device`
-    owns: its ticket words and workspace (created on the first launch, so a CPU object costs nothing and opens no library).  start()
-    gives a search's first (cum, finished, length, perturbed, draw): beam 0 of a row at total 0 and perturbed value 0, the others at
-    -inf, no step drawn.  ValueError for what check_sbeam refuses, before any device work."""
+class StochasticBeams(BeamPolicy):
+    """Stochastic beam search (Kool, van Hoof and Welling) over B batch rows of W beams and a V-token vocabulary on `device` as a beam
+    policy: lm_beam_step(controls=), decoding.beam_steps and BeamGraph(controls=) take it as they take BeamControls.  It carries the
+    beams' perturbed values and the steps drawn so far (`carried` is ("perturbed", "draw")); select() is the step's ONE launch
+    (vmlmf_sbeam_step) on `state`, the {seed, offset} snapshot every step draws from - None until whoever builds the object for a
+    search sets it.  start() gives a search's first (cum, finished, length, perturbed, draw): beam 0 of a row at total 0 and perturbed
+    value 0, the others at -inf, no step drawn.  It owns a ticket and a workspace (buffers(): created on the first call, so a CPU
+    object costs nothing and opens no library).  ValueError for what check_sbeam refuses, before any device work."""
+
+    carried = ("perturbed", "draw")
 
     def __init__(self, B, W, V, device):
-        self.B, self.V = int(B), int(V)
-        self.W = check_sbeam(W, self.V)
+        super().__init__(B, W, V, device)
         if self.B < 1:
             raise ValueError(f"vmlmf_amd: StochasticBeams needs B >= 1 batch rows, got {B}")
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
+        self.state = None
         self._buffers = None
 
     def start(self):
         """(cum, finished, length, perturbed, draw) of a search that starts."""
-        B, W, dev = self.B, self.W, self.device
-        cum = torch.full((B, W), float("-inf"), device=dev)
-        cum[:, 0] = 0.0
-        zeros = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
-        return cum, zeros(B, W), zeros(B, W), cum.clone(), zeros(B)
+        return (*self.first_beams(), *self.first_carried())
+
+    def first_carried(self):
+        """[perturbed, draw] of a search that starts: start()'s last two."""
+        return [self.first_beams()[0], torch.zeros(self.B, dtype=torch.int32, device=self.device)]
+
+    def new_buffers(self):
+        """A (ticket, workspace) pair sized by vmlmf_sbeam_workspace_bytes: half as much again as the plain step's."""
+        return new_step_buffers(self.device, self.B, self.W, self.V, LIBRARY)
 
     def buffers(self):
         """(ticket (B) int32 - zero, and left zero by every launch -, workspace): this object's own, so its launches never meet
         another search's on one ticket.  Not to be created inside a stream capture (a graph's warm-up creates them)."""
         if self._buffers is None:
-            nbytes = lib().vmlmf_sbeam_workspace_bytes(self.B, self.W, self.V)
-            self._buffers = (torch.zeros(self.B, device=self.device, dtype=torch.int32),
-                             torch.empty((nbytes + 7) // 8, device=self.device, dtype=torch.int64))
+            self._buffers = self.new_buffers()
         return self._buffers
+
+    def select(self, scores, bias, cum, finished, length, eos, embed, buffers=None, perturbed=None, draw=None):
+        """lm_beam_step's selection by perturbed values (sbeam_select on `state`): the seven results, the survivors' perturbed, draw + 1.
+        RuntimeError while `state` is None."""
+        if self.state is None:
+            raise RuntimeError("vmlmf_amd: this StochasticBeams has no `state` yet: set the {seed, offset} snapshot (dropout_advance()) "
+                               "its steps draw from")
+        if buffers is not None:         # (a pair of new_buffers() is sized for B, W, V; the stream's default is sized for the step's own)
+            check_step_controls(self, StochasticBeams, *cum.shape, scores.shape[1], scores.device, eos)
+        _check_noise("lm_beam_step", cum, perturbed, draw, self.state)
+        return sbeam_select(scores, bias, cum, finished, length, perturbed.contiguous(), draw.contiguous(), self.state.contiguous(), eos,
+                            embed, buffers)
+
+
+def _check_noise(caller, cum, perturbed, draw, state):
+    """RuntimeError unless perturbed is (B, W) fp32 like cum, draw (B) int32 and state two int64, all on a HIP device."""
+    B, W = cum.shape
+    _require(perturbed, "perturbed")
+    if tuple(perturbed.shape) != (B, W) or tuple(draw.shape) != (B,):
+        raise RuntimeError(f"vmlmf_amd.{caller}: finished, length and perturbed must be (B, W) like cum, draw (B)")
+    _require(draw, "draw", torch.int32)
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and state.numel() == 2):
+        raise RuntimeError(f"vmlmf_amd.{caller}: state must be a {{seed, offset}} snapshot: two int64 on the device")
 
 
 def lm_sbeam_step(h, weight, bias, cum, finished, length, perturbed, draw, state, eos, embed=None, buffers=None):
@@ -79,39 +105,18 @@ def lm_sbeam_step(h, weight, bias, cum, finished, length, perturbed, draw, state
     perturbed (B, W) fp32: the beams' perturbed values; draw (B) int32: the steps taken so far; state: a {seed, offset} snapshot of
     dropout_advance() - two int64 on the device; finished, length, eos, embed: lm_beam_step's.
     Returns lm_beam_step's seven results (parent, token, total, finished, length, x_next, src_row) and behind them the survivors'
-    perturbed (B, W) and draw + 1 (B), fresh buffers.  buffers: (ticket, workspace) of a StochasticBeams.buffers() - default: a pair
-    kept per (device, stream, B, W, V)."""
+    perturbed (B, W) and draw + 1 (B), fresh buffers.  buffers: (ticket, workspace) of a StochasticBeams.buffers() - default: the
+    current stream's (step_buffers, sized by this library)."""
     h2, w, bias, cum, finished, length, eos_c, embed = check_step("lm_sbeam_step", h, weight, bias, cum, finished, length, eos, embed)
-    B, W = cum.shape
-    _require(perturbed, "perturbed")
-    if tuple(perturbed.shape) != (B, W) or tuple(draw.shape) != (B,):
-        raise RuntimeError("vmlmf_amd.lm_sbeam_step: finished, length and perturbed must be (B, W) like cum, draw (B)")
-    _require(draw, "draw", torch.int32)
-    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and state.numel() == 2):
-        raise RuntimeError("vmlmf_amd.lm_sbeam_step: state must be a {seed, offset} snapshot: two int64 on the device")
+    _check_noise("lm_sbeam_step", cum, perturbed, draw, state)
     return sbeam_select(torch.mm(h2, w.t()), bias, cum, finished, length, perturbed.contiguous(), draw.contiguous(), state.contiguous(),
                         eos_c, embed, buffers)
-
-
-_BUFFERS = {}
 
 
 def sbeam_select(scores, bias, cum, finished, length, perturbed, draw, state, eos, embed, buffers=None):
     """The vmlmf_sbeam_step launch on checked, contiguous arguments: scores (B W, V) without the bias, eos an int (-1: none).
     lm_sbeam_step's results."""
-    B, W = cum.shape
-    V = scores.shape[1]
-    dev = scores.device
-    if buffers is None:
-        key = (dev.index, _lib.raw_stream(dev).value, B, W, V)
-        if key not in _BUFFERS:
-            _BUFFERS[key] = StochasticBeams(B, W, V, dev).buffers()
-        buffers = _BUFFERS[key]
-    ticket, ws = buffers
-    H = embed.shape[1] if embed is not None else 1
-    parent, token, total, fin, ln, xn, src = step_outputs(B, W, H, dev, embed)
-    pert, drawn = torch.empty_like(total), torch.empty_like(draw)
-    LIBRARY.call(dev, "vmlmf_sbeam_step", B, W, H, V, ptr(scores), ptr(bias), ptr(cum), ptr(finished), ptr(length), eos, ptr(embed),
-                 ptr(parent), ptr(token), ptr(total), ptr(fin), ptr(ln), ptr(xn), ptr(src), ptr(ticket), ptr(ws), ws.numel() * 8,
-                 ptr(perturbed), ptr(pert), ptr(draw), ptr(drawn), ptr(state))
-    return parent, token, total, fin, ln, xn, src, pert, drawn
+    pert, drawn = torch.empty_like(perturbed), torch.empty_like(draw)
+    outs = launch_step(LIBRARY, "vmlmf_sbeam_step", scores, bias, cum, finished, length, eos, embed, buffers, sized_by=LIBRARY,
+                       behind=(ptr(perturbed), ptr(pert), ptr(draw), ptr(drawn), ptr(state)))
+    return (*outs, pert, drawn)

@@ -5,12 +5,15 @@ lm.py holds its layers, this module everything that continues a prompt with them
   lm_beam_step, beam_gather, beam_backtrack  the beam step, the state reorder and the read-back (_beam.py, a library of its own)
   decode_steps, beam_steps                   the step loops: a choice, then the layers at T = 1 - no host synchronisation
   DecodeGraph, BeamGraph                     those loops captured into a hipGraph
+  (a beam step that differs from the plain one is a _beam.BeamPolicy - BeamControls, AutomatonBeamControls, GroupBeams,
+   StochasticBeams -: beam_steps and BeamGraph are written once, against that protocol)
   generate, beam_search, group_beam_search   the calls behind Model's methods of the same names, where the contract is written down
   lm_contrast_step, contrast_steps, ContrastGraph, contrastive_search    contrastive search: the step's one launch (_contrast.py, a
                                              library of its own), its loop, the loop captured, the call behind Model.contrastive_search
-  lm_sbeam_step, sbeam_steps, StochasticBeamGraph, stochastic_beam_search    stochastic beam search - sequences sampled without
-                                             replacement: the step's one launch (_sbeam.py, a library of its own), its loop, the loop
-                                             captured, the call behind Model.stochastic_beam_search
+  lm_sbeam_step, StochasticBeams, StochasticBeamGraph, stochastic_beam_search    stochastic beam search - sequences sampled without
+                                             replacement: the step's one launch (_sbeam.py, a library of its own), the policy that
+                                             puts it into beam_steps, a BeamGraph under that policy, the call behind
+                                             Model.stochastic_beam_search
 (scoring.py - Model.score - runs on this module's session too.)
 """
 from __future__ import annotations
@@ -204,20 +207,21 @@ def decode_steps(model, h, states, steps, temperature, snap, layer_path, top_k=N
     return torch.stack(toks), torch.stack(lps), h, states
 
 
-def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None, controls=None, hist=None, hist_len=None, beam_state=None):
+def beam_steps(model, h, states, cum, finished, length, steps, eos, buffers=None, controls=None, **carried):
     """`steps` steps of beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE selection launch
     (lm_beam_step: totals, the W survivors of each batch row in order, their next input rows), ONE launch that makes the
     2 L state tensors follow their hypotheses (beam_gather), then the layers at T = 1 on the B W rows.  No host
     synchronisation: capturable (BeamGraph).  Returns (parents, tokens (steps, B, W), h, states, cum, finished, length).
-    controls: a BeamControls - the selection is then the controlled launch (vmlmf_beamctl_step) and, where the controls keep a history,
-    the vmlmf_history_bans launch in front of it on hist / hist_len, the beams' histories (default: controls.history(), a search that
-    starts); the survivors' (hist, hist_len) then follow the seven results.  An AutomatonBeamControls: the selection is
-    vmlmf_automaton_beam_step on beam_state (B W) int32, the beams' states (default: controls.start()); the survivors' states follow the
-    seven results."""
+    controls: a BeamPolicy - the selection is its select(), and the tensors it carries from step to step (controls.carried) are taken as
+    keywords **carried (default: controls.first_carried(), a search that starts; TypeError for a keyword it does not carry) and follow
+    the seven results as they stand after the steps.  A BeamControls: the controlled launch (vmlmf_beamctl_step) and, where the controls
+    keep a history, the vmlmf_history_bans launch in front of it on hist / hist_len, the beams' histories.  An AutomatonBeamControls:
+    vmlmf_automaton_beam_step on beam_state (B W) int32, the beams' states.  A GroupBeams: vmlmf_beamgroup_step, nothing carried.  A
+    StochasticBeams: vmlmf_sbeam_step on perturbed (B, W) and draw (B), drawing from controls.state."""
     parents, toks = [], []
     # what the controls carry from step to step behind cum, finished and length (lm_beam_step takes it by these names)
     names = _beam_extras(controls)
-    extra = _beam_start(controls, hist=hist, hist_len=hist_len, beam_state=beam_state)
+    extra = _beam_start(controls, **carried)
     for _ in range(steps):
         par, tok, cum, finished, length, x, src, *rest = lm_beam_step(h, model.fc.w, model.fc.b, cum, finished, length, eos, model.embed.w,
                                                                       buffers=buffers, controls=controls, **dict(zip(names, extra)))
@@ -254,11 +258,12 @@ def _beam_extras(controls):                 # the names of what the controls car
     return () if controls is None else controls.carried
 
 
-def _beam_start(controls, **given):         # those tensors: the given ones (hist=, hist_len= / beam_state=), or a search that starts
-    names = _beam_extras(controls)
-    if names and given.get(names[0]) is None:
-        return controls.first_carried()
-    return [given[name] for name in names]
+def _beam_start(controls, **carried):       # those tensors: the given ones (hist=, hist_len= / beam_state= ...), or a search that starts
+    _beam.check_carried(controls, carried)
+    given = [carried.get(name) for name in _beam_extras(controls)]
+    if any(t is None for t in given):
+        given = [first if t is None else t for t, first in zip(given, controls.first_carried())]
+    return given
 
 
 def _split_beams(carried, controls):        # _join_beams' arguments back; history: [hist, hist_len] / [beam_state] where the controls carry them
@@ -273,13 +278,6 @@ def _beamed(model, carried, steps, eos, buffers=None, controls=None):
     par, tok, h, states, cum, finished, length, *history = beam_steps(model, h, states, cum, finished, length, steps, eos, buffers, controls,
                                                                       **dict(zip(_beam_extras(controls), history)))
     return (par, tok), _join_beams(h, states, cum, finished, length, history)
-
-
-def _fresh_beams(B, W, dev):
-    """(cum, finished, length), each (B, W), of a search that starts: beam 0 of a row at score 0, the others at -inf."""
-    cum = torch.full((B, W), float("-inf"), device=dev)
-    cum[:, 0] = 0.0
-    return cum, torch.zeros((B, W), dtype=torch.int32, device=dev), torch.zeros((B, W), dtype=torch.int32, device=dev)
 
 
 # ---- the step loops as captured graphs ---------------------------------------------------------------------------------------------
@@ -384,33 +382,47 @@ class DecodeGraph(_StepGraph):
 class BeamGraph(_StepGraph):
     """`steps` steps of Model.beam_search (beam_steps: per step the head's GEMM, the vmlmf_beam_step launch, the vmlmf_beam_gather
     launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are the beams' (row
-    b W + w) of `beams` = W beams per batch row; cum / finished / length (B, W) default to a fresh search (beam 0 at 0, the others at -inf).  replay() continues from where
-    the previous replay stopped - h, states, cum, finished and length live in this object's buffers - and returns (parents, tokens),
-    both (steps, B, W), for beam_backtrack.  The ticket words and the workspace of the selection are this graph's own, so
-    graphs may be replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after
-    the parameters change.
-    controls: a BeamControls (min_length, token, n-gram and sequence bans).  Where they keep a history, hist / hist_len (default:
-    controls.history()) are carried with cum, finished and length - in this object's buffers, so a replay continues the hypotheses of
-    the last one; the captured launches set the controls' own `overflow` (the warm-up runs on a clone).  An AutomatonBeamControls:
-    beam_state (default: controls.start()) is carried in the same way - a replay continues the states of the last one."""
+    b W + w) of `beams` = W beams per batch row; cum / finished / length (B, W) default to a fresh search (beam 0 at 0, the others at
+    -inf; the controls' first_beams()).  replay() continues from where the previous replay stopped - h, states, cum, finished and length
+    live in this object's buffers - and returns (parents, tokens), both (steps, B, W), for beam_backtrack.  The ticket words and the
+    workspace of the selection are this graph's own (`buffers`: the controls' new_buffers(), sized for THEIR step), so graphs may be
+    replayed on whatever streams; the layers read parameter images packed at construction: build a new BeamGraph after the parameters
+    change.
+    controls: a BeamPolicy.  What it carries (controls.carried, given as keywords **carried - default: controls.first_carried(), a
+    search that starts) is carried with cum, finished and length - in this object's buffers, one attribute per name, so a replay
+    continues the hypotheses of the last one; the warm-up runs on controls.clone().  A BeamControls that keeps a history: hist /
+    hist_len; the captured launches set the controls' own `overflow`.  An AutomatonBeamControls: beam_state.  A StochasticBeams:
+    perturbed and draw (StochasticBeamGraph)."""
 
-    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None, controls=None, hist=None,
-                 hist_len=None, beam_state=None):
+    def __init__(self, model, h, states, steps, beams, eos=None, cum=None, finished=None, length=None, controls=None, **carried):
         self.model, self.steps, self.eos, self.controls = model, int(steps), eos, controls
         W = _beam.check_beams(beams, model.vocab_size)
-        B = h.shape[0] // W
-        fresh = _fresh_beams(B, W, h.device)
-        cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), fresh))
-        self.buffers = _beam.new_step_buffers(h.device, B, W, model.vocab_size)
-        history = _beam_start(controls, hist=hist, hist_len=hist_len, beam_state=beam_state)
+        policy = controls if controls is not None else _beam.BeamPolicy(h.shape[0] // W, W, model.vocab_size, h.device)
+        cum, finished, length = (new if t is None else t for t, new in zip((cum, finished, length), policy.first_beams()))
+        self.buffers = policy.new_buffers()
+        history = _beam_start(controls, **carried)
         step = lambda carried, controls=controls: _beamed(model, carried, self.steps, eos, self.buffers, controls)
         self._capture(model, _join_beams(h, states, cum, finished.to(torch.int32), length.to(torch.int32), history), step,
                       None if controls is None else lambda carried: step(carried, controls.clone()))
         self.h, self.states, self.cum, self.finished, self.length, history = _split_beams(self.carried, controls)
-        self.hist = self.hist_len = self.beam_state = None
         for name, t in zip(_beam_extras(controls), history):
             setattr(self, name, t)
         self.parents, self.tokens = self.outputs
+
+
+class StochasticBeamGraph(BeamGraph):
+    """`steps` steps of Model.stochastic_beam_search captured once into a hipGraph: a BeamGraph under a StochasticBeams (`beams`) of its
+    own - per step the head's GEMM, the vmlmf_sbeam_step launch, the vmlmf_beam_gather launch and the layers at T = 1.  cum / finished /
+    length / perturbed / draw default to a search that starts (StochasticBeams.start()).  state: a {seed, offset} snapshot
+    (dropout_advance()); the graph draws from its own copy, `self.state` - copy another snapshot into it for another sample.  replay()
+    continues from where the previous replay stopped - perturbed and draw live in this object's buffers with BeamGraph's, so the noise of
+    a replay is that of the eager steps at the same count."""
+
+    def __init__(self, model, h, states, steps, beams, state, eos=None, cum=None, finished=None, length=None, perturbed=None, draw=None):
+        W = _sbeam.check_sbeam(beams, model.vocab_size)
+        self.beams = StochasticBeams(h.shape[0] // W, W, model.vocab_size, h.device)
+        self.beams.state = self.state = state.detach().clone()
+        super().__init__(model, h, states, steps, W, eos, cum, finished, length, self.beams, perturbed=perturbed, draw=draw)
 
 
 # ---- one call: the checks, the prompt, the steps -----------------------------------------------------------------------------------
@@ -450,7 +462,7 @@ def _ranked(parents, toks, cum, length, states, alpha, groups=1):
     (stable) by cum / length ** alpha within each of the `groups` groups of a row - no hypothesis leaves its group."""
     B, W = cum.shape
     order = None
-    if alpha > 0.0:
+    if alpha > 0.0 and len(parents):                # (no step: the start values as they are)
         key = cum / length.to(torch.float32) ** alpha
         if groups == 1:
             order = torch.sort(key, dim=1, descending=True, stable=True).indices
@@ -557,6 +569,27 @@ def generate(model, prompt, steps, states=None, temperature=1.0, seed=None, chun
         return tokens, logprobs, lengths, states
 
 
+def _search(model, prompt, states, steps, chunk, W, eos, controls):
+    """What beam_search, group_beam_search and stochastic_beam_search share behind their checks: the session on the prompt, h and the
+    states W times over, the start of a search (the controls' first_beams() and first_carried(); controls None: the plain step), the
+    steps - eager, or chunk=K: a BeamGraph of K steps replayed - and the carried list taken apart.  Returns ((parents, tokens), each
+    (steps, B, W), states, cum, finished, length, [what the controls carry]); steps == 0: the start values."""
+    B, dev = prompt.shape[1], prompt.device
+    policy = controls if controls is not None else _beam.BeamPolicy(B, W, model.vocab_size, dev)
+    with _session(model, prompt, states) as (h, states):
+        h, states = h.repeat_interleave(W, 0), _widen(states, W)
+        (cum, finished, length), history = policy.first_beams(), policy.first_carried()
+        if steps == 0:
+            none = torch.empty((0, B, W), dtype=torch.int32, device=dev)
+            return (none, none.to(torch.int64)), states, cum, finished, length, history
+        outs, carried = _run(
+            steps, chunk,
+            lambda: _beamed(model, _join_beams(h, states, cum, finished, length, history), steps, eos, None, controls),
+            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls,
+                              **dict(zip(policy.carried, history))))
+        return (outs, *_split_beams(carried, controls)[1:])
+
+
 def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_penalty=0.0, chunk=None, min_length=0, banned_tokens=None,
                 no_repeat_ngram_size=0, banned_sequences=None, *, automaton=None, automaton_state=None):
     """Model.beam_search (lm.py has the contract)."""
@@ -582,24 +615,13 @@ def beam_search(model, prompt, steps, beams=4, states=None, eos=None, length_pen
     _check_chunk("beam_search", chunk, steps)
     _check_call(model, prompt, "beam_search", "beam-step kernel (vmlmf_beam_step)")
     B, dev = prompt.shape[1], prompt.device
-    with _session(model, prompt, states) as (h, states):
-        # capacity: the prompt and every step - the history never overflows
-        controls = BeamControls(B, W, model.vocab_size, dev, prompt=prompt, capacity=max(T0 + steps, 1), **ctl_args) if controlled else None
-        if automaton is not None:
-            controls = AutomatonBeamControls(B, W, model.vocab_size, dev, automaton, automaton_state, eos=eos, min_length=min_length,
-                                             banned_tokens=banned_tokens, _checked=True)
-        history = _beam_start(controls)
-        h, states = h.repeat_interleave(W, 0), _widen(states, W)
-        cum, finished, length = _fresh_beams(B, W, dev)
-        if steps == 0:
-            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
-        (parents, toks), carried = _run(
-            steps, chunk,
-            lambda: _beamed(model, _join_beams(h, states, cum, finished, length, history), steps, eos, None, controls),
-            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls,
-                              **dict(zip(_beam_extras(controls), history))))
-        _, states, cum, finished, length, _ = _split_beams(carried, controls)
-        return _ranked(parents, toks, cum, length, states, alpha)
+    # capacity: the prompt and every step - the history never overflows
+    controls = BeamControls(B, W, model.vocab_size, dev, prompt=prompt, capacity=max(T0 + steps, 1), **ctl_args) if controlled else None
+    if automaton is not None:
+        controls = AutomatonBeamControls(B, W, model.vocab_size, dev, automaton, automaton_state, eos=eos, min_length=min_length,
+                                         banned_tokens=banned_tokens, _checked=True)
+    (parents, toks), states, cum, _, length, _ = _search(model, prompt, states, steps, chunk, W, eos, controls)
+    return _ranked(parents, toks, cum, length, states, alpha)
 
 
 def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_penalty=0.5, states=None, eos=None, length_penalty=0.0,
@@ -610,19 +632,9 @@ def group_beam_search(model, prompt, steps, beams=4, *, groups=2, diversity_pena
     _check_search("group_beam_search", model.vocab_size, eos=eos, length_penalty=length_penalty, steps=steps)
     _check_chunk("group_beam_search", chunk, steps)
     _check_call(model, prompt, "group_beam_search", "group beam-step kernel (vmlmf_beamgroup_step)")
-    B, dev = prompt.shape[1], prompt.device
-    with _session(model, prompt, states) as (h, states):
-        controls = GroupBeams(B, W, model.vocab_size, dev, G, lam)
-        h, states = h.repeat_interleave(W, 0), _widen(states, W)
-        cum, finished, length = controls.start()
-        if steps == 0:
-            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, length, states
-        (parents, toks), carried = _run(
-            steps, chunk,
-            lambda: _beamed(model, _join_beams(h, states, cum, finished, length, []), steps, eos, None, controls),
-            lambda: BeamGraph(model, h, states, int(chunk), W, eos, cum, finished, length, controls))
-        _, states, cum, finished, length, _ = _split_beams(carried, controls)
-        return _ranked(parents, toks, cum, length, states, alpha, G)
+    controls = GroupBeams(prompt.shape[1], W, model.vocab_size, prompt.device, G, lam)
+    (parents, toks), states, cum, _, length, _ = _search(model, prompt, states, steps, chunk, W, eos, controls)
+    return _ranked(parents, toks, cum, length, states, alpha, G)
 
 
 # ---- contrastive search ------------------------------------------------------------------------------------------------------------
@@ -709,58 +721,6 @@ def contrastive_search(model, prompt, steps, top_k=4, penalty_alpha=0.6, *, stat
 
 
 # ---- stochastic beam search --------------------------------------------------------------------------------------------------------
-def sbeam_steps(model, h, states, cum, finished, length, perturbed, draw, steps, eos, state, buffers=None):
-    """`steps` steps of stochastic beam search from the beams' top-layer outputs h (B W, H): per step the head's GEMM and ONE
-    selection launch (lm_sbeam_step: totals, Gumbel noise, the top-down perturbed values, the W survivors of each batch row in order,
-    their next input rows), ONE launch that makes the 2 L state tensors follow their hypotheses (beam_gather), then the layers at
-    T = 1 on the B W rows.  state: the {seed, offset} snapshot every step draws from; the steps differ by `draw`, which the launch
-    counts on the device.  No host synchronisation: capturable (StochasticBeamGraph).  Returns (parents, tokens (steps, B, W), h,
-    states, cum, finished, length, perturbed, draw)."""
-    parents, toks = [], []
-    for _ in range(steps):
-        par, tok, cum, finished, length, x, src, perturbed, draw = lm_sbeam_step(h, model.fc.w, model.fc.b, cum, finished, length, perturbed,
-                                                                                 draw, state, eos, model.embed.w, buffers)
-        parents.append(par)
-        toks.append(tok)
-        flat = beam_gather([t for st in states for t in st], src)
-        states = [(flat[2 * i], flat[2 * i + 1]) for i in range(len(states))]
-        y, states = decode_layers(model, x.unsqueeze(0), states, "layers")
-        h = y[-1]
-    return (torch.stack(parents), torch.stack(toks), h, states, cum, finished, length, perturbed, draw)
-
-
-def _sbeamed(model, carried, steps, eos, state, buffers=None):
-    """sbeam_steps on a flat list [h, states ..., cum, finished, length, perturbed, draw] -> (outputs, that list after the steps)."""
-    h, *flat, cum, finished, length, perturbed, draw = carried
-    par, tok, h, states, *rest = sbeam_steps(model, h, _pairs(flat), cum, finished, length, perturbed, draw, steps, eos, state, buffers)
-    return (par, tok), [h, *(t for st in states for t in st), *rest]
-
-
-class StochasticBeamGraph(_StepGraph):
-    """`steps` steps of Model.stochastic_beam_search (sbeam_steps: per step the head's GEMM, the vmlmf_sbeam_step launch, the
-    vmlmf_beam_gather launch and the layers at T = 1) captured once into a hipGraph - linear, on one stream.  h (B W, H) and states are
-    the beams' (row b W + w); cum / finished / length / perturbed / draw default to a search that starts (StochasticBeams.start()).
-    state: a {seed, offset} snapshot (dropout_advance()); the graph draws from its own copy, `self.state` - copy another snapshot into
-    it for another sample.  replay() continues from where the previous replay stopped - h, states, cum, finished, length, perturbed
-    and draw live in this object's buffers, so the noise of a replay is that of the eager steps at the same count - and returns
-    (parents, tokens), both (steps, B, W), for beam_backtrack.  The ticket words and the workspace are this graph's own; the layers
-    read parameter images packed at construction: build a new graph after the parameters change."""
-
-    def __init__(self, model, h, states, steps, beams, state, eos=None, cum=None, finished=None, length=None, perturbed=None, draw=None):
-        self.model, self.steps, self.eos = model, int(steps), eos
-        W = _sbeam.check_sbeam(beams, model.vocab_size)
-        self.beams = StochasticBeams(h.shape[0] // W, W, model.vocab_size, h.device)
-        given = (cum, finished, length, perturbed, draw)
-        cum, finished, length, perturbed, draw = (new if t is None else t for t, new in zip(given, self.beams.start()))
-        self.state = state.detach().clone()
-        self.buffers = self.beams.buffers()
-        step = lambda carried: _sbeamed(model, carried, self.steps, eos, self.state, self.buffers)
-        self._capture(model, [h, *(t for st in states for t in st), cum, finished.to(torch.int32), length.to(torch.int32), perturbed, draw],
-                      step)
-        self.h, *flat, self.cum, self.finished, self.length, self.perturbed, self.draw = self.carried
-        self.states, (self.parents, self.tokens) = _pairs(flat), self.outputs
-
-
 def stochastic_beam_search(model, prompt, steps, beams=4, *, seed=None, states=None, eos=None, chunk=None):
     """Model.stochastic_beam_search (lm.py has the contract)."""
     W = _sbeam.check_sbeam(beams, model.vocab_size)
@@ -768,16 +728,7 @@ def stochastic_beam_search(model, prompt, steps, beams=4, *, seed=None, states=N
     _check_search("stochastic_beam_search", model.vocab_size, eos=eos, steps=steps)
     _check_chunk("stochastic_beam_search", chunk, steps)
     _check_call(model, prompt, "stochastic_beam_search", "stochastic beam-step kernel (vmlmf_sbeam_step)")
-    B, dev = prompt.shape[1], prompt.device
-    snap = dropout_advance(model.sampler_state(seed))      # once per call: the steps differ by `draw`, on the device
-    with _session(model, prompt, states) as (h, states):
-        h, states = h.repeat_interleave(W, 0), _widen(states, W)
-        cum, finished, length, perturbed, draw = StochasticBeams(B, W, model.vocab_size, dev).start()
-        if steps == 0:
-            return torch.empty((0, B, W), dtype=torch.int64, device=dev), cum, perturbed, length, states
-        start = [h, *(t for st in states for t in st), cum, finished, length, perturbed, draw]
-        (parents, toks), carried = _run(
-            steps, chunk, lambda: _sbeamed(model, start, steps, eos, snap),
-            lambda: StochasticBeamGraph(model, h, states, int(chunk), W, snap, eos, cum, finished, length, perturbed, draw))
-        _, *flat, cum, finished, length, perturbed, draw = carried
-        return beam_backtrack(parents, toks), cum, perturbed, length, _pairs(flat)
+    controls = StochasticBeams(prompt.shape[1], W, model.vocab_size, prompt.device)
+    controls.state = dropout_advance(model.sampler_state(seed))      # once per call: the steps differ by `draw`, on the device
+    (parents, toks), states, cum, _, length, (perturbed, _) = _search(model, prompt, states, steps, chunk, W, eos, controls)
+    return beam_backtrack(parents, toks), cum, perturbed, length, states

@@ -552,7 +552,7 @@ class Model(nn.Module):
         log-probability).
         seed follows generate(): it re-seeds sampler_state(), which is snapshotted and advanced ONCE per call - the same seed gives
         the same sample, the next call a fresh one.  chunk=K (steps % K == 0) captures K steps into a hipGraph
-        (decoding.StochasticBeamGraph) and replays it steps / K times; the snapshot is the call's and the step count lives on the
+        (decoding.BeamGraph under a StochasticBeams) and replays it steps / K times; the snapshot is the call's and the step count lives on the
         device, so it gives the eager call's bits (unlike generate(chunk=K), which snapshots per replay).  The results are the same
         bits from run to run.  eos: a hypothesis that emits it is finished - padded with eos, its score and perturbed value frozen;
         lengths count the tokens up to and including eos.  Decoding always runs the full `steps`.  states (default: state_init) are
