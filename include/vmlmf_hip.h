@@ -375,6 +375,38 @@ int vmlmf_nll_forward_grad(int R, int V, float *scores, const float *bias, const
                            float *rowloss, float *dbias, float *scratch, void *stream);
 
 /*
+ * Knowledge distillation at the LM head: the loss above plus tau^2 KL(P || Q) against a teacher's distribution P, loss and the
+ * scores' gradient in the same ONE pass, in place.  (Added under ABI 13 without a bump: two new entry points and one new struct,
+ * nothing that exists changes its signature, layout or meaning, so a caller built against 13 keeps working; a caller that needs
+ * them finds out through the missing symbol.)  With z = scores + bias, tau = temperature, Q = softmax(z / tau), per row r:
+ *   hard_r = logsumexp(z_r) - z_r[y_r]                  soft_r = tau^2 sum_v P_r[v] (log P_r[v] - log Q_r[v])
+ *   loss   = scale * sum_r ((1 - alpha) hard_r + alpha soft_r)
+ *   dz_r   = scale * ((1 - alpha) (softmax(z_r) - onehot(y_r)) + alpha tau (Q_r - P_r))        written over scores
+ * The teacher is a constant and comes in exactly one of two forms (VMLMF_E_BADARG otherwise):
+ *   teacher (R,V) fp32, finite, its own bias included: P_r = softmax(teacher_r / tau);
+ *   top_tokens (R,top) int64, distinct within a row and in [0, V), with top_scores (R,top) fp32, finite, 1 <= top <= 32 (scores or
+ *   log-probabilities: a per-row constant changes nothing): P_r = softmax(top_scores_r / tau) on those tokens, zero elsewhere.
+ *   Distinctness and range are the caller's responsibility and are not looked for; a token outside [0, V) touches no memory.
+ * alpha in [0, 1], temperature finite and > 0.  Everything is formed around the row maxima of z and of the teacher.
+ * loss (3): total, hard, soft - hard and soft each scaled by `scale`, total = (1 - alpha) hard + alpha soft; a target outside
+ * [0, V) makes hard and total NaN at every alpha.  rowloss (2,R): hard_r | soft_r.  bias, dbias (the column sums of the returned
+ * gradient) may be NULL.  scratch: vmlmf_distill_scratch_floats(R, V) floats.  Limits, alignment and determinism are
+ * vmlmf_nll_forward_grad's: scores, bias, teacher and scratch 16-byte aligned, V % 4 == 0, V <= 12288 (VMLMF_E_UNSUPPORTED
+ * otherwise), fixed summation orders, no atomics.  Two launches, no allocation, no synchronisation: capturable.
+ */
+typedef struct vmlmf_distill {
+  float alpha;
+  float temperature;
+  const float *teacher;       /* (R,V), or NULL for the top-k form */
+  const int64_t *top_tokens;  /* (R,top), or NULL for the dense form */
+  const float *top_scores;    /* (R,top), or NULL for the dense form */
+  int32_t top;                /* 1 .. 32; 0 for the dense form */
+} vmlmf_distill;
+size_t vmlmf_distill_scratch_floats(int R, int V);
+int vmlmf_distill_forward_grad(int R, int V, float *scores, const float *bias, const int64_t *y, float scale,
+                               const vmlmf_distill *kd, float *loss, float *rowloss, float *dbias, float *scratch, void *stream);
+
+/*
  * Gradient of the embedding table (Embed, V/src/models/vmlmf_lm.py:46-48: x = w[tokens]; autograd's backward scatter-adds the
  * R = T*B rows of dy (R,H) into a zero (V,H) matrix).  dweight[v] = sum of dy[p] over the positions p with tokens[p] == v, in
  * ascending position order (deterministic, no float atomics); rows no token selects are written as zeros: the call fills all of

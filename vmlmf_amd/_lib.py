@@ -64,6 +64,12 @@ class Dropout(ctypes.Structure):
     _fields_ = [("p", ctypes.c_float), ("site", ctypes.c_int32), ("state", ctypes.c_void_p), ("y_dropped", ctypes.c_void_p)]
 
 
+class Distill(ctypes.Structure):
+    """vmlmf_distill: the soft-target term of vmlmf_distill_forward_grad; exactly one teacher form is set."""
+    _fields_ = [("alpha", ctypes.c_float), ("temperature", ctypes.c_float), ("teacher", ctypes.c_void_p), ("top_tokens", ctypes.c_void_p),
+                ("top_scores", ctypes.c_void_p), ("top", ctypes.c_int32)]
+
+
 class Extra(ctypes.Structure):
     _fields_ = [("packed", ctypes.c_void_p), ("head", ctypes.POINTER(Head)), ("ce", ctypes.POINTER(Ce)), ("drop", ctypes.POINTER(Dropout))]
 
@@ -128,6 +134,8 @@ SYMBOLS = {
     "vmlmf_nll_backward": (_i, [_i, _i, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "vmlmf_nll_grad_scratch_floats": (_sz, [_i, _i]),
     "vmlmf_nll_forward_grad": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "vmlmf_distill_scratch_floats": (_sz, [_i, _i]),
+    "vmlmf_distill_forward_grad": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.POINTER(Distill), _vp, _vp, _vp, _vp, _vp]),
     "vmlmf_embed_backward_scratch_bytes": (_sz, [_i, _i]),
     "vmlmf_embed_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vmlmf_dropout_fused": (_i, [ctypes.POINTER(Desc)]),

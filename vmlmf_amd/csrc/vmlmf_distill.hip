@@ -1,0 +1,296 @@
+// Knowledge distillation at the LM head (Hinton, Vinyals, Dean: "Distilling the Knowledge in a Neural Network"): the hard loss of
+// vmlmf_nll.hip's training form and tau^2 KL(P || Q) against a teacher's distribution P, loss AND gradient in ONE pass over the
+// student's (R, V) score matrix, in place.  Per row r, z = scores + bias, Q = softmax(z / tau):
+//   hard = logsumexp(z) - z[y]                                soft = tau^2 sum_v P[v] (log P[v] - log Q[v])
+//   dz   = scale ((1 - alpha)(softmax(z) - onehot(y)) + alpha tau (Q - P))
+// P comes from a teacher SOURCE (a template parameter of the one kernel body): a dense (R, V) score matrix, P = softmax(t / tau),
+// or the row's k <= 32 top tokens and their scores, P = softmax over those k and zero elsewhere.  Everything is formed around the
+// row maxima m_z and m_t: with x = z - m_z, u = t - m_t and the four sums
+//   s1 = sum exp(x)    sq = sum exp(x / tau)    st = sum exp(u / tau)    d = sum exp(u / tau) (u - x)
+// hard = log s1 - x[y] and soft = tau^2 (d / (tau st) - log st + log sq); at tau == 1 (a uniform branch) sq is s1 and the row's
+// second exponential is skipped.  The shape is nll_grad_kernel's: a 256-thread workgroup walks rows w, w + NWG, ..., a row lives
+// in its registers as twelve float4 slots - first x, then the numerators exp(x) and exp(x / tau) side by side, so every
+// exponential is taken once -, every load unconditional, the gradient written back in place, the column sums of the workgroup's
+// rows kept for the bias gradient.  Two block reductions per row (the two maxima; the four sums), no atomics, fixed summation
+// orders: the same bits from run to run.
+// The teacher's row lies in one V-wide row of LDS, each lane reading and writing its own slots only:
+//   dense:  the teacher's scores, loaded through registers; the sum pass replaces them by the numerators exp(u / tau)
+//   top-k:  zeros but at the row's k columns, where lanes j < k scatter exp(u_j / tau) behind the maxima and clear it behind the
+//           write pass (a barrier each) - a column's owner reads P like a dense operand and the k entries need no search
+// so the write pass is the same for both.  The bias is read again with every row (V floats that stay in the cache): student
+// numerators (2 x 48) + column sums (48) already are 144 VGPRs, and the LDS row is taken.
+// Register, LDS and occupancy numbers: docs/design/lm_distill.md.
+#include <hip/hip_runtime.h>
+
+#include "vmlmf_launch.h"
+
+namespace {
+
+constexpr int DQ = 12;   // float4 per thread: rows up to 256 * 12 * 4 = 12288 wide, nll_grad_kernel's limit
+
+// workgroup-wide reduction of N values per thread (256 threads) in ONE exchange, results broadcast; `red` has 4 * N floats
+template <int N, bool MAX>
+__device__ __forceinline__ void block_reduce(float (&v)[N], float* red) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v[n] = MAX ? fmaxf(v[n], __shfl_xor(v[n], o, 64)) : v[n] + __shfl_xor(v[n], o, 64);
+  }
+  __syncthreads();   // red may still be read from the previous reduction
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) red[4 * n + (threadIdx.x >> 6)] = v[n];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const float* r = red + 4 * n;
+    v[n] = MAX ? fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3])) : (r[0] + r[1]) + (r[2] + r[3]);
+  }
+}
+
+__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
+// A row as a buffer: one descriptor per row in scalar registers, a lane's slot at the 32-bit byte offset 16 (tid + 256 i).  The
+// hardware's range check takes the place of index clamps and of 64-bit addresses per slot (48 VGPRs of loop invariants with plain
+// pointers): a load past the row's `bytes` returns zeros, a store there is dropped (the stores are predicated all the same).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_buffer(const float* row, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 load4(__amdgpu_buffer_rsrc_t r, int off) {
+  const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
+  return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
+}
+__device__ __forceinline__ void store4(__amdgpu_buffer_rsrc_t r, int off, const float4& v) {
+  const u32x4 w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(w, r, off, 0, 0);
+}
+// A lane's index behind a compiler barrier: what a phase of the row loop derives from it (slot offsets, column numbers) is formed
+// in that phase again, not carried through the loop as a dozen and more invariant registers per use.
+__device__ __forceinline__ int fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ float pick(const float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
+
+// ---- the teacher sources -------------------------------------------------------------------------------------------------------
+// What differs between them in the body: how the teacher's row gets into LDS (`aux`), its maximum (a per-thread partial, folded
+// into the reduction of the student's maximum), and who forms the sums st and d.
+struct DenseTeacher {   // (R, V) scores
+  static constexpr bool DENSE = true;
+  const float* teacher;
+};
+struct TopTeacher {     // (R, k) tokens and scores
+  static constexpr bool DENSE = false;
+  const long long* tokens;
+  const float* scores;
+  int k;
+};
+
+template <class SRC>
+__global__ __launch_bounds__(256, 2) void distill_grad_kernel(int R, int V, float scale, float alpha, float tau, float* __restrict__ scores,
+                                                              const float* __restrict__ bias, const long long* __restrict__ y, SRC src,
+                                                              float* __restrict__ rowloss, float* __restrict__ dbpart) {
+  __shared__ float4 aux[256 * DQ];   // the teacher's row - dense: its scores; top-k: its numerators at the k columns, zero elsewhere
+  __shared__ float red[16];
+  const int tid = threadIdx.x, nq = V >> 2;
+  const float it = 1.f / tau;
+  const bool unit = tau == 1.f;      // Q is the hard softmax: one exponential per score
+  const float c1 = scale * (1.f - alpha), c2 = scale * alpha * tau;
+  const __amdgpu_buffer_rsrc_t bias_row = row_buffer(bias, bias != nullptr ? 4 * V : 0);   // no bias: no records, zeros
+  float4 cs[DQ];
+#pragma unroll
+  for (int i = 0; i < DQ; ++i) {
+    aux[tid + 256 * i] = f4(0.f);
+    cs[i] = f4(0.f);
+  }
+  __syncthreads();
+  for (int row = blockIdx.x; row < R; row += gridDim.x) {
+    const __amdgpu_buffer_rsrc_t z = row_buffer(scores + (size_t)row * V, 4 * V);
+    float4 v[DQ];
+    float mx[2] = {-INFINITY, -INFINITY};   // of the student's row, of the teacher's
+    long long tok = -1;                     // top-k: lane j < k holds the row's j-th token and score
+    float tsc = -INFINITY;
+    {
+      const int tl = fresh(tid);
+#pragma unroll
+      for (int i = 0; i < DQ; ++i) v[i] = load4(z, 16 * (tl + 256 * i));   // every load unconditional
+      if constexpr (SRC::DENSE) {           // the teacher's row through registers into LDS, a lane's slots its own: no barrier
+        const __amdgpu_buffer_rsrc_t trow = row_buffer(src.teacher + (size_t)row * V, 4 * V);
+        float4 u[DQ];
+#pragma unroll
+        for (int i = 0; i < DQ; ++i) u[i] = load4(trow, 16 * (tl + 256 * i));
+#pragma unroll
+        for (int i = 0; i < DQ; ++i) {
+          const int q = tl + 256 * i;
+          if (q < nq) mx[1] = fmaxf(mx[1], fmaxf(fmaxf(u[i].x, u[i].y), fmaxf(u[i].z, u[i].w)));
+          aux[q] = u[i];
+        }
+      } else {
+        const int j = tid < src.k ? tid : 0;
+        const long long a = src.tokens[(size_t)row * src.k + j];
+        const float s = src.scores[(size_t)row * src.k + j];
+        if (tid < src.k) tok = a, tsc = s;
+        mx[1] = tsc;
+      }
+#pragma unroll
+      for (int i = 0; i < DQ; ++i) {        // the bias: the same V floats for every row, from the cache
+        const int q = tl + 256 * i;
+        const float4 b = load4(bias_row, 16 * q);
+        v[i].x += b.x, v[i].y += b.y, v[i].z += b.z, v[i].w += b.w;
+        if (q >= nq) v[i] = f4(-INFINITY);
+        mx[0] = fmaxf(mx[0], fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+      }
+    }
+    block_reduce<2, true>(mx, red);
+    const float mz = mx[0], mt = mx[1];
+    float sm[4] = {0.f, 0.f, 0.f, 0.f};   // s1, sq, st, d
+    if constexpr (!SRC::DENSE) {          // lane j: its numerator into the LDS row; st and the teacher's half of d
+      if (tid < src.k) {
+        const float u = tsc - mt, et = __expf(u * it);
+        sm[2] = et, sm[3] = et * u;
+        if (tok >= 0 && tok < V) reinterpret_cast<float*>(aux)[tok] = et;
+      }
+      __syncthreads();
+    }
+    const long long t = y[row];
+    const bool inr = t >= 0 && t < V;
+    const int tc = inr ? (int)t : -1;     // the target's column: float4 (tc >> 2) is slot (tc >> 10) of lane (tc >> 2) & 255
+    const bool own = inr && ((tc >> 2) & 255) == tid;
+    float xt = 0.f;                       // x of the target, held by the thread that owns the target's column
+    float4 w[DQ];                         // Q's numerators exp(x / tau); v becomes the hard softmax's, exp(x)
+    {
+      const int ts = fresh(tid);
+#pragma unroll
+      for (int i = 0; i < DQ; ++i) {
+        const int q = ts + 256 * i;
+        v[i].x -= mz, v[i].y -= mz, v[i].z -= mz, v[i].w -= mz;   // x; -inf in the padding
+        if (own && (tc >> 10) == i) xt = pick(v[i], tc & 3);
+        if (q < nq) {                     // (the padding: 0 * (inf - inf))
+          const float4 a = aux[q];
+          if constexpr (SRC::DENSE) {     // the teacher's numerators take its scores' place in LDS
+            const float4 u = make_float4(a.x - mt, a.y - mt, a.z - mt, a.w - mt);
+            const float4 e = make_float4(__expf(u.x * it), __expf(u.y * it), __expf(u.z * it), __expf(u.w * it));
+            sm[2] += (e.x + e.y) + (e.z + e.w);
+            sm[3] += (e.x * (u.x - v[i].x) + e.y * (u.y - v[i].y)) + (e.z * (u.z - v[i].z) + e.w * (u.w - v[i].w));
+            aux[q] = e;
+          } else {                        // zero but at the teacher's columns: the student's half of d
+            sm[3] -= (a.x * v[i].x + a.y * v[i].y) + (a.z * v[i].z + a.w * v[i].w);
+          }
+        }
+        if (!unit) {
+          w[i] = make_float4(__expf(v[i].x * it), __expf(v[i].y * it), __expf(v[i].z * it), __expf(v[i].w * it));
+          sm[1] += (w[i].x + w[i].y) + (w[i].z + w[i].w);
+        }
+        v[i] = make_float4(__expf(v[i].x), __expf(v[i].y), __expf(v[i].z), __expf(v[i].w));
+        sm[0] += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+      }
+    }
+    block_reduce<4, false>(sm, red);
+    const float s1 = sm[0], sq = unit ? sm[0] : sm[1], st = sm[2], d = sm[3];
+    const float k1 = unit ? (c1 + c2) / s1 : c1 / s1, k2 = unit ? 0.f : c2 / sq, kt = c2 / st;
+    {                                     // the gradient: the student's two shares minus the teacher's and the target's
+      const int tw = fresh(tid);
+#pragma unroll
+      for (int i = 0; i < DQ; ++i) {
+        const int q = tw + 256 * i, dc = tc - 4 * q;   // dc: the target's column within this float4, if it is in 0 .. 3
+        if (q < nq) {
+          const float4 p = aux[q];        // the teacher's numerators
+          if (unit) w[i] = f4(0.f);
+          float4 o;
+          o.x = v[i].x * k1 + w[i].x * k2 - (p.x * kt + (dc == 0 ? c1 : 0.f));
+          o.y = v[i].y * k1 + w[i].y * k2 - (p.y * kt + (dc == 1 ? c1 : 0.f));
+          o.z = v[i].z * k1 + w[i].z * k2 - (p.z * kt + (dc == 2 ? c1 : 0.f));
+          o.w = v[i].w * k1 + w[i].w * k2 - (p.w * kt + (dc == 3 ? c1 : 0.f));
+          store4(z, 16 * q, o);
+          cs[i].x += o.x, cs[i].y += o.y, cs[i].z += o.z, cs[i].w += o.w;
+        }
+      }
+    }
+    if (own) rowloss[row] = __logf(s1) - xt;   // lse - z_t
+    if (tid == 0) {
+      if (!inr) rowloss[row] = NAN;       // a target outside [0, V): NaN loss, as in nll_grad_kernel
+      rowloss[(size_t)R + row] = tau * tau * (d * it / st - __logf(st) + __logf(sq));
+    }
+    if constexpr (!SRC::DENSE) {          // the LDS row back to zeros, behind the last read of it
+      __syncthreads();
+      if (tid < src.k && tok >= 0 && tok < V) reinterpret_cast<float*>(aux)[tok] = 0.f;
+    }
+  }
+  const __amdgpu_buffer_rsrc_t part = row_buffer(dbpart + (size_t)blockIdx.x * V, 4 * V);
+#pragma unroll
+  for (int i = 0; i < DQ; ++i) {
+    if (tid + 256 * i < nq) store4(part, 16 * (tid + 256 * i), cs[i]);
+  }
+}
+
+// dbias[v] = sum over the workgroups' column partials, in nll_finish_kernel's order (a workgroup takes 32 columns, its eight
+// 32-lane groups an eighth of the partial rows each, the eight sums meet in LDS in group order); block 0 finishes the losses:
+// loss = {total, hard, soft}, hard and soft scaled by `scale`, total = (1 - alpha) hard + alpha soft.
+__global__ __launch_bounds__(256) void distill_finish_kernel(int R, int V, int nwg, float scale, float alpha,
+                                                             const float* __restrict__ rowloss, const float* __restrict__ dbpart,
+                                                             float* __restrict__ dbias, float* __restrict__ loss) {
+  __shared__ float red[8];
+  __shared__ float col[8][32];
+  const int li = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + li, cc = c < V ? c : V - 1;
+  if (dbias != nullptr) {
+    const int per = (nwg + 7) / 8;
+    const int w0 = grp * per < nwg ? grp * per : nwg, w1 = w0 + per < nwg ? w0 + per : nwg;
+    float a[4] = {0.f, 0.f, 0.f, 0.f};
+    int w = w0;
+    for (; w + 7 < w1; w += 8) {
+      float t[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) t[i] = dbpart[(size_t)(w + i) * V + cc];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[i & 3] += t[i];
+    }
+    for (; w < w1; ++w) a[0] += dbpart[(size_t)w * V + cc];
+    col[grp][li] = (a[0] + a[1]) + (a[2] + a[3]);
+    __syncthreads();
+    if (grp == 0 && c < V) {
+      float total = col[0][li];
+#pragma unroll
+      for (int q = 1; q < 8; ++q) total += col[q][li];
+      dbias[c] = total;
+    }
+  }
+  if (blockIdx.x == 0) {
+    float part[2] = {0.f, 0.f};
+    for (int r = threadIdx.x; r < R; r += 256) part[0] += rowloss[r], part[1] += rowloss[(size_t)R + r];
+    block_reduce<2, false>(part, red);
+    if (threadIdx.x == 0) {
+      const float hard = scale * part[0], soft = scale * part[1];
+      loss[0] = (1.f - alpha) * hard + alpha * soft, loss[1] = hard, loss[2] = soft;
+    }
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+// workgroups of distill_grad_kernel (two per CU, as nll_grad_kernel's); the column partials need NWG x V floats of scratch
+int distill_workgroups(int R) { return R < 512 ? R : 512; }
+
+// VMLMF_E_UNSUPPORTED (-3) when the in-register form does not cover the row width or an operand's alignment
+int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
+                            const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
+                            float* rowloss, float* dbias, float* scratch, hipStream_t s) {
+  if (V % 4 != 0 || V > 256 * DQ * 4 || !aligned16(scores) || !aligned16(bias) || !aligned16(teacher) || !aligned16(scratch)) return -3;
+  const int nwg = distill_workgroups(R);
+  if (teacher != nullptr) {
+    const DenseTeacher src = {teacher};
+    hipLaunchKernelGGL(distill_grad_kernel<DenseTeacher>, dim3(nwg), dim3(256), 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss,
+                       scratch);
+  } else {
+    const TopTeacher src = {top_tokens, top_scores, top};
+    hipLaunchKernelGGL(distill_grad_kernel<TopTeacher>, dim3(nwg), dim3(256), 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss,
+                       scratch);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(distill_finish_kernel, dim3((V + 31) / 32), dim3(256), 0, s, R, V, nwg, scale, alpha, rowloss, scratch, dbias, loss);
+  return (int)hipGetLastError();
+}

@@ -277,6 +277,12 @@ hipError_t launch_nll_bwd(int R, int V, const float* scores, const long long* y,
 int nll_grad_workgroups(int R);
 int launch_nll_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float* loss,
                         float* rowloss, float* dbias, float* scratch, hipStream_t s);
+// the same pass with a soft-target term against a teacher's distribution (vmlmf_distill.hip): exactly one of `teacher` (R, V) and
+// (top_tokens, top_scores) (R, top) is given; loss (3): total, hard, soft; rowloss (2, R): hard | soft
+int distill_workgroups(int R);
+int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
+                            const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
+                            float* rowloss, float* dbias, float* scratch, hipStream_t s);
 // embedding-table gradient (vmlmf_embed.hip)
 size_t embed_bwd_scratch_bytes(int R, int V);
 int launch_transpose(int rows, int cols, const float* src, float* dst, hipStream_t s);   // dst (cols x rows) = src^T

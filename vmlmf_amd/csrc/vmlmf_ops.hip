@@ -69,6 +69,25 @@ int vmlmf_nll_forward_grad(int R, int V, float* scores, const float* bias, const
   return hip_tail(rc);
 }
 
+size_t vmlmf_distill_scratch_floats(int R, int V) { return (size_t)distill_workgroups(R < 1 ? 1 : R) * (size_t)(V < 1 ? 1 : V); }
+
+int vmlmf_distill_forward_grad(int R, int V, float* scores, const float* bias, const int64_t* y, float scale, const vmlmf_distill* kd,
+                               float* loss, float* rowloss, float* dbias, float* scratch, void* stream) {
+  if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "distill: R and V must be >= 1");
+  if (!scores || !y || !kd || !loss || !rowloss || !scratch) return fail(VMLMF_E_BADARG, "distill: null pointer");
+  if (!(kd->alpha >= 0.f && kd->alpha <= 1.f)) return fail(VMLMF_E_BADARG, "distill: alpha must lie in [0, 1]");
+  if (!(kd->temperature > 0.f) || !(kd->temperature < INFINITY)) return fail(VMLMF_E_BADARG, "distill: the temperature must be finite and positive");
+  const bool dense = kd->teacher != nullptr, topk = kd->top_tokens != nullptr || kd->top_scores != nullptr || kd->top != 0;
+  if (dense == topk) return fail(VMLMF_E_BADARG, "distill: exactly one teacher form - teacher (R, V), or top_tokens and top_scores (R, top)");
+  if (topk && (!kd->top_tokens || !kd->top_scores)) return fail(VMLMF_E_BADARG, "distill: the top-k form takes top_tokens and top_scores");
+  if (topk && (kd->top < 1 || kd->top > 32)) return fail(VMLMF_E_BADARG, "distill: top must lie in [1, 32]");
+  const int rc = launch_distill_fwd_grad(R, V, scores, bias, (const long long*)y, scale, kd->alpha, kd->temperature, kd->teacher,
+                                         (const long long*)kd->top_tokens, kd->top_scores, kd->top, loss, rowloss, dbias, scratch,
+                                         (hipStream_t)stream);
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "distill_forward_grad: rows must be 16-byte aligned, a multiple of four and at most 12288 wide");
+  return hip_tail(rc);
+}
+
 size_t vmlmf_embed_backward_scratch_bytes(int R, int V) { return embed_bwd_scratch_bytes(R < 1 ? 1 : R, V < 1 ? 1 : V); }
 
 int vmlmf_embed_backward(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, void* scratch,

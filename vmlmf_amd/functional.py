@@ -1025,46 +1025,61 @@ def _run_form(form, *args):
         return fn(*args)
 
 
+def _head_loss_forward(ctx, h, w, b, y, stats_floats, launch):
+    """The forward of the LM head's training losses, written once: the projection in its tuned form, then `launch(lib, R, V, scores,
+    bias, yrow, scale, stats, dbias, stream)` - the one thing the losses differ in - takes the loss into `stats`
+    (stats_floats(R) floats) and overwrites the scores with their own gradient, which is what is saved for _head_loss_backward."""
+    _require_hip(h, "h")
+    _require_hip(w, "fc.w")
+    H = h.shape[-1]
+    h2 = h.reshape(-1, H).contiguous()
+    w = w.contiguous()
+    R, V = h2.shape[0], w.shape[0]
+    forms = head_forms(R, H, V, h.device)
+    scores = _run_form(forms["fwd"], h2, w)                       # (R, V), no bias
+    yrow = y.reshape(-1).contiguous()
+    scale = float(y.size(1)) / float(R)
+    stats = torch.empty(stats_floats(R), device=h.device, dtype=torch.float32)
+    dbias = torch.empty(V, device=h.device, dtype=torch.float32) if b is not None else None
+    lib = _lib.lib()
+    with _lib.on_device(h.device):
+        launch(lib, R, V, scores, None if b is None else b.contiguous(), yrow, scale, stats, dbias, _lib.raw_stream(h.device))
+    ctx.save_for_backward(h2, w, scores, *([dbias] if dbias is not None else []))
+    ctx.hshape, ctx.forms, ctx.has_b = h.shape, forms, b is not None
+    return stats
+
+
+def _head_loss_backward(ctx, dloss):
+    """(dh, dw, db) of the LM head's training losses: the two GEMMs read the scores' gradient where the forward left it."""
+    h2, w, dz = ctx.saved_tensors[:3]
+    dbias = ctx.saved_tensors[3] if ctx.has_b else None
+    scaled = not _is_unit(dloss)
+    dh = _run_form(ctx.forms["dh"], dz, w) if ctx.needs_input_grad[0] else None
+    dw = _run_form(ctx.forms["dw"], dz, h2) if ctx.needs_input_grad[1] else None
+    db = dbias if (ctx.has_b and ctx.needs_input_grad[2]) else None
+    if scaled:                                   # d(loss) is not the package's constant one: the stored gradient is for 1
+        dh = None if dh is None else dh.mul_(dloss)
+        dw = None if dw is None else dw.mul_(dloss)
+        db = None if db is None else db * dloss
+    return (None if dh is None else dh.view(ctx.hshape)), dw, db
+
+
+def _nll_launch(lib, R, V, scores, bias, yrow, scale, stats, dbias, stream):
+    scratch = _workspace(scores.device, 4 * lib.vmlmf_nll_grad_scratch_floats(R, V))
+    _lib.check(lib.vmlmf_nll_forward_grad(R, V, _ptr(scores), _ptr(bias), _ptr(yrow), scale, stats.data_ptr(), stats.data_ptr() + 4,
+                                          _ptr(dbias), scratch.data_ptr(), stream))
+
+
 class LmHeadLossFn(torch.autograd.Function):
     """loss = nll_loss(Linear(h), y) (vmlmf_lm.py:355-358 + lm_test.py:140-153) for training; see the block comment above."""
 
     @staticmethod
     def forward(ctx, h, w, b, y):
-        _require_hip(h, "h")
-        _require_hip(w, "fc.w")
-        H = h.shape[-1]
-        h2 = h.reshape(-1, H).contiguous()
-        w = w.contiguous()
-        R, V = h2.shape[0], w.shape[0]
-        forms = head_forms(R, H, V, h.device)
-        scores = _run_form(forms["fwd"], h2, w)                       # (R, V), no bias
-        yrow = y.reshape(-1).contiguous()
-        scale = float(y.size(1)) / float(R)
-        stats = torch.empty(1 + R, device=h.device, dtype=torch.float32)          # loss | rowloss
-        dbias = torch.empty(V, device=h.device, dtype=torch.float32) if b is not None else None
-        lib = _lib.lib()
-        scratch = _workspace(h.device, 4 * lib.vmlmf_nll_grad_scratch_floats(R, V))
-        with _lib.on_device(h.device):
-            _lib.check(lib.vmlmf_nll_forward_grad(R, V, _ptr(scores), _ptr(None if b is None else b.contiguous()), _ptr(yrow), scale,
-                                                  stats.data_ptr(), stats.data_ptr() + 4, _ptr(dbias), scratch.data_ptr(),
-                                                  _lib.raw_stream(h.device)))
-        ctx.save_for_backward(h2, w, scores, *([dbias] if dbias is not None else []))
-        ctx.hshape, ctx.forms, ctx.has_b = h.shape, forms, b is not None
-        return stats[0]
+        return _head_loss_forward(ctx, h, w, b, y, lambda R: 1 + R, _nll_launch)[0]          # loss | rowloss
 
     @staticmethod
     def backward(ctx, dloss):
-        h2, w, dz = ctx.saved_tensors[:3]
-        dbias = ctx.saved_tensors[3] if ctx.has_b else None
-        scaled = not _is_unit(dloss)
-        dh = _run_form(ctx.forms["dh"], dz, w) if ctx.needs_input_grad[0] else None
-        dw = _run_form(ctx.forms["dw"], dz, h2) if ctx.needs_input_grad[1] else None
-        db = dbias if (ctx.has_b and ctx.needs_input_grad[2]) else None
-        if scaled:                                   # d(loss) is not the package's constant one: the stored gradient is for 1
-            dh = None if dh is None else dh.mul_(dloss)
-            dw = None if dw is None else dw.mul_(dloss)
-            db = None if db is None else db * dloss
-        return (None if dh is None else dh.view(ctx.hshape)), dw, db, None
+        return (*_head_loss_backward(ctx, dloss), None)
 
 
 def lm_head_loss(h, weight, bias, y):
@@ -1076,6 +1091,124 @@ def lm_head_loss(h, weight, bias, y):
     if h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288:
         return LmHeadLossFn.apply(h, weight, bias, y)
     return nll_loss(torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t()), y)
+
+
+# ---- knowledge distillation at the LM head (C ABI vmlmf_distill_forward_grad; csrc/vmlmf_distill.hip; docs/design/lm_distill.md) ----
+# loss = scale sum_r ((1 - alpha) hard_r + alpha soft_r) against a teacher's distribution P: hard_r is lm_head_loss's row term,
+# soft_r = tau^2 KL(P_r || softmax(z_r / tau)) (Hinton, Vinyals, Dean).  The same three GEMMs as lm_head_loss; between them ONE
+# pass over the scores takes both losses and leaves the gradient of their mix in place.
+DISTILL_MAX_TOP = 32
+
+
+def check_distill(alpha, temperature, top=0):
+    """ValueError for an alpha outside [0, 1], a temperature that is not finite and positive, a top outside [0, 32]."""
+    import math
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"vmlmf_amd: distillation's alpha must lie in [0, 1], got {alpha!r}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"vmlmf_amd: distillation's temperature must be finite and positive, got {temperature!r}")
+    if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= DISTILL_MAX_TOP:
+        raise ValueError(f"vmlmf_amd: distillation's top must lie in [0, {DISTILL_MAX_TOP}], got {top!r}")
+
+
+def distill_teacher(teacher, R, V, dtype=torch.float32):
+    """A teacher in one of its two forms, checked against the student's R rows of V scores of type `dtype` and flattened to rows:
+    (scores (R, V), None, None) for a (T, B, V) or (R, V) tensor; (None, top_tokens (R, k) int64, top_scores (R, k)) for a pair of
+    (T, B, k) or (R, k) tensors, 1 <= k <= min(32, V).  ValueError for another shape or type; no value is looked at."""
+    if isinstance(teacher, torch.Tensor):
+        if teacher.dtype != dtype or teacher.dim() not in (2, 3) or teacher.shape[-1] != V or teacher.numel() != R * V:
+            raise ValueError(f"vmlmf_amd: a dense teacher is (T, B, V) or (R, V) {dtype} scores for {R} rows of {V}, "
+                             f"got {tuple(teacher.shape)} {teacher.dtype}")
+        return teacher.reshape(R, V), None, None
+    if not (isinstance(teacher, (tuple, list)) and len(teacher) == 2 and all(isinstance(t, torch.Tensor) for t in teacher)):
+        raise ValueError("vmlmf_amd: a teacher is a score tensor or a pair (top_tokens, top_scores)")
+    tok, sc = teacher
+    k = tok.shape[-1] if tok.dim() in (2, 3) else 0
+    if (tok.dtype != torch.int64 or sc.dtype != dtype or tok.shape != sc.shape or not 1 <= k <= min(DISTILL_MAX_TOP, V)
+            or tok.numel() != R * k):
+        raise ValueError(f"vmlmf_amd: a top-k teacher is top_tokens int64 and top_scores {dtype}, both (T, B, k) or (R, k) with "
+                         f"1 <= k <= {min(DISTILL_MAX_TOP, V)} for {R} rows, got {tuple(tok.shape)} {tok.dtype} and {tuple(sc.shape)} {sc.dtype}")
+    return None, tok.reshape(R, k), sc.reshape(R, k)
+
+
+def distill_loss_stock(scores, y, teacher, alpha, temperature):
+    """The distillation loss in stock ops under autograd - the path of CPU tensors, of widths and types the kernel does not
+    cover, and the baseline tools/bench_distill.py measures the kernel against.  scores (R, V) with the bias in them, y (T, B),
+    teacher as distill_teacher() takes it.  Returns (loss, hard, soft), hard and soft scaled as nll_loss scales."""
+    R, V = scores.shape
+    dense, tok, tsc = distill_teacher(teacher, R, V, scores.dtype)
+    scale, tau = float(y.size(1)) / float(R), float(temperature)
+    hard = torch.nn.functional.cross_entropy(scores, y.reshape(-1), reduction="sum") * scale
+    logq = torch.log_softmax(scores / tau, dim=1)
+    if dense is not None:
+        logp = torch.log_softmax(dense.detach() / tau, dim=1)
+    else:
+        logp, logq = torch.log_softmax(tsc.detach() / tau, dim=1), logq.gather(1, tok)
+    soft = torch.nn.functional.kl_div(logq, logp, reduction="sum", log_target=True) * (tau * tau * scale)
+    return (1.0 - alpha) * hard + alpha * soft, hard, soft
+
+
+class LmHeadDistillFn(torch.autograd.Function):
+    """(loss, hard, soft) of lm_head_distill_loss; the forward product, the tuned forms and the backward are lm_head_loss's, the
+    loss launch is vmlmf_distill_forward_grad.  hard and soft are reported, not differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, y, dense, tok, tsc, alpha, tau):
+        kd = _lib.Distill(alpha=alpha, temperature=tau, teacher=None if dense is None else dense.data_ptr(),
+                          top_tokens=None if tok is None else tok.data_ptr(), top_scores=None if tsc is None else tsc.data_ptr(),
+                          top=0 if tok is None else tok.shape[1])
+
+        def launch(lib, R, V, scores, bias, yrow, scale, stats, dbias, stream):
+            scratch = _workspace(scores.device, 4 * lib.vmlmf_distill_scratch_floats(R, V))
+            _lib.check(lib.vmlmf_distill_forward_grad(R, V, _ptr(scores), _ptr(bias), _ptr(yrow), scale, ctypes.byref(kd), stats.data_ptr(),
+                                                      stats.data_ptr() + 12, _ptr(dbias), scratch.data_ptr(), stream))
+
+        stats = _head_loss_forward(ctx, h, w, b, y, lambda R: 3 + 2 * R, launch)             # total, hard, soft | rowloss (2, R)
+        hard, soft = stats[1], stats[2]
+        ctx.mark_non_differentiable(hard, soft)
+        return stats[0], hard, soft
+
+    @staticmethod
+    def backward(ctx, dloss, dhard, dsoft):
+        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None)
+
+
+def lm_head_distill_loss(h, weight, bias, y, teacher, *, alpha=0.5, temperature=2.0, return_parts=False):
+    """lm_head_loss with a soft-target term (knowledge distillation): h (T, B, H), weight (V, H), bias (V) or None, y (T, B) int64.
+    With z = Linear(h), tau = temperature, Q = softmax(z / tau) and the teacher's distribution P, per row
+        hard = logsumexp(z) - z[y]        soft = tau^2 KL(P || Q)        loss = scale sum ((1 - alpha) hard + alpha soft)
+    scaled as nll_loss scales (scale = B / (T B)).  teacher: (T, B, V) or (R, V) fp32 scores, the teacher's bias in them -
+    P = softmax(teacher / tau) -, or a pair (top_tokens (T, B, k) int64, top_scores (T, B, k) fp32), 1 <= k <= 32, as
+    Model.score(top=k) returns them - P = softmax(top_scores / tau) on those tokens and zero elsewhere (scores or log-probabilities:
+    a constant per row changes nothing).  The teacher is a constant: no gradient flows into it.  Returns the scalar loss; with
+    return_parts=True (loss, hard, soft), the parts detached and scaled like the loss.
+    On a HIP device one pass over the scores takes both terms and leaves the gradient of the mix in place for the two backward
+    GEMMs (vmlmf_distill_forward_grad); alpha == 0 IS lm_head_loss, launch for launch, and does not read the teacher (soft is then
+    reported as zero).  CPU tensors, other types and widths the kernel does not cover (not a multiple of four, beyond 12288) take
+    distill_loss_stock under autograd.  ValueError, before any device work, for alpha outside [0, 1], a temperature that is not
+    finite and positive and teacher tensors of the wrong shape or type.  That the top tokens of a row are distinct and in [0, V) is
+    the caller's responsibility: the call never reads a value back from the device, so it does not look."""
+    check_distill(alpha, temperature)
+    V = weight.shape[0]
+    R = h.numel() // h.shape[-1]
+    dense, tok, tsc = distill_teacher(teacher, R, V, h.dtype)
+    alpha, tau = float(alpha), float(temperature)
+    fused = h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288
+    if fused and alpha == 0.0:
+        loss = LmHeadLossFn.apply(h, weight, bias, y)
+        return (loss, loss.detach(), torch.zeros_like(loss)) if return_parts else loss
+    if fused:
+        given = [t.detach().contiguous() for t in (dense, tok, tsc) if t is not None]
+        if any(t.device != h.device for t in given):
+            raise ValueError(f"vmlmf_amd: the teacher's tensors must be on the student's device {h.device}")
+        dense, tok, tsc = (given[0], None, None) if dense is not None else (None, given[0], given[1])
+        loss, hard, soft = LmHeadDistillFn.apply(h, weight, bias, y, dense, tok, tsc, alpha, tau)
+    else:
+        h2 = h.reshape(-1, h.shape[-1])
+        scores = torch.mm(h2, weight.t()) if bias is None else torch.addmm(bias, h2, weight.t())
+        loss, hard, soft = distill_loss_stock(scores, y, teacher, alpha, tau)
+        hard, soft = hard.detach(), soft.detach()
+    return (loss, hard, soft) if return_parts else loss
 
 
 class EmbedFn(torch.autograd.Function):

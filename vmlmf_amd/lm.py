@@ -290,6 +290,58 @@ class Model(nn.Module):
         h, states = self.features(x, states)
         return lm_head_loss(h, self.fc.w, self.fc.b, y), states
 
+    def distill_loss(self, x, y, states, teacher, *, alpha=0.5, temperature=2.0, teacher_states=None, top=0, return_parts=False):
+        """loss() with a soft-target term: this model, the student, is trained against a teacher's output distribution as well as
+        against the corpus (knowledge distillation; Hinton, Vinyals, Dean) - how a low-rank Model gets close to its dense or
+        wide-rank parent.  loss = scale sum_r ((1 - alpha) hard_r + alpha tau^2 KL(P_r || softmax(z_r / tau))), tau = temperature,
+        hard_r what loss() charges, scaled as loss() scales (functional.lm_head_distill_loss: on a HIP device both terms and the
+        gradient of their mix come from one pass over the scores, which are never handed out).  The student's features, dropout
+        included, run as in loss().  The teacher is a constant; alpha == 0 is loss() and leaves a teacher tensor unread.
+        teacher is
+          - a (T, B, V) or (T B, V) fp32 score tensor, or a pair (top_tokens (T, B, k) int64, top_scores (T, B, k) fp32) as
+            score(top=k) returns them (k <= 32; P is then softmax(top_scores / tau) on those tokens, zero elsewhere) - an offline
+            teacher: returns (loss, states);
+          - a module with forward(x, states) -> (scores, states) - any Model, nn.LSTM layers included: it runs on x in eval mode
+            without autograd, every module's train / eval flag restored whatever is raised, from teacher_states (default:
+            teacher.state_init(B)): returns (loss, states, teacher_states), the latter to hand back in with the next minibatch.
+            top=k > 0 reduces the teacher to its k best tokens per position - on a HIP device through its own
+            score(x, y, states=teacher_states, top=k), so no (T B, V) teacher matrix exists beyond score()'s chunk; on the CPU by
+            torch.topk of its scores.
+        return_parts=True: loss is the triple (loss, hard, soft), the parts detached.
+        ValueError, before any device work, for alpha outside [0, 1], a temperature that is not finite and positive, top outside
+        [0, 32] or given with a teacher that is not a module, and teacher tensors of the wrong shape or type.  That a row's top
+        tokens are distinct and inside the vocabulary is the caller's responsibility: no value is read back from the device."""
+        from .functional import check_distill, lm_head_distill_loss
+        check_distill(alpha, temperature, top)
+        module = isinstance(teacher, nn.Module)
+        if top and not module:
+            raise ValueError("vmlmf_amd: top reduces a teacher module; a teacher given as tensors is taken as it is")
+        if module:
+            if teacher_states is None:
+                teacher_states = teacher.state_init(x.size(1))
+            if top and x.is_cuda and hasattr(teacher, "score"):
+                _, _, tokens, logprobs, teacher_states = teacher.score(x, y, states=teacher_states, top=top)
+                teacher = (tokens, logprobs)
+            else:
+                flags = [(m, m.training) for m in teacher.modules()]
+                try:
+                    teacher.eval()
+                    with torch.no_grad():
+                        scores, teacher_states = teacher(x, teacher_states)
+                finally:
+                    for m, was in flags:
+                        m.training = was
+                teacher = scores
+                if top:
+                    values, tokens = scores.topk(top, dim=-1)
+                    teacher = (tokens.reshape(*x.shape, top), values.reshape(*x.shape, top))
+        else:
+            from .functional import distill_teacher
+            distill_teacher(teacher, x.numel(), self.vocab_size, self.fc.w.dtype)
+        h, states = self.features(x, states)
+        loss = lm_head_distill_loss(h, self.fc.w, self.fc.b, y, teacher, alpha=alpha, temperature=temperature, return_parts=return_parts)
+        return (loss, states, teacher_states) if module else (loss, states)
+
     def features(self, x, states):
         """Everything of forward() in front of the vocabulary projection (vmlmf_lm.py:434-439): (T, B, H) activations, states.
         Training with p > 0 on a HIP device: the three dropouts run without mask tensors (functional.dropout_*: Philox factors
