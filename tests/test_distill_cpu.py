@@ -213,13 +213,14 @@ def test_model_distill_loss_with_a_teacher_model_on_the_cpu():
 
 @pytest.mark.skipif(not os.path.exists(OBJDUMP), reason="llvm-objdump of the ROCm toolchain not present")
 def test_the_distillation_kernels_use_no_scratch_and_keep_two_workgroups_per_cu():
-    """distill_grad_kernel claims __launch_bounds__(256, 2): its VGPRs + AGPRs must stay within 256, and nothing of a row may spill."""
+    """distill_grad_kernel claims __launch_bounds__(256, 2): its VGPRs + AGPRs must stay within 256, and nothing of a row may spill;
+    the same for the finish it shares with the NLL head, with one row-loss vector and with two."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_budget
-    ks = {d: k for d, k in kernel_budget.kernels(_lib.LIB_PATH).items() if "distill_" in d}
+    ks = {d: k for d, k in kernel_budget.kernels(_lib.LIB_PATH).items() if "distill_" in d or "head_loss_" in d}
     grad = [d for d in ks if "distill_grad_kernel<" in d]
     assert len(grad) == 2 and any("DenseTeacher" in d for d in grad) and any("TopTeacher" in d for d in grad), sorted(ks)
-    assert any("distill_finish_kernel" in d for d in ks) and len(ks) == 3, sorted(ks)
+    assert all(any(f"head_loss_finish_kernel<{parts}>" in d for d in ks) for parts in (1, 2)) and len(ks) == 4, sorted(ks)
     for d, k in ks.items():
         assert k.get("scratch_insts", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, (d, k)
         assert k.get("vgpr_count", 0) + k.get("agpr_count", 0) <= 256, (d, k)

@@ -129,6 +129,80 @@ def test_alpha_zero_is_the_nll_head_and_a_target_outside_the_vocabulary_is_nan()
             assert np.isnan(rowloss[0, 7].item()) and torch.isfinite(dz).all()
 
 
+def call_nll(R, V, scale, z, bias, y, alloc=None):
+    """One vmlmf_nll_forward_grad on copies of the numpy operands; returns (loss (1), rowloss (R), dz (R, V), dbias (V) or None)."""
+    if alloc is None:
+        def alloc(shape, dtype, init, name):
+            t = torch.empty(shape, dtype=dtype, device=DEV)
+            return t if init is None else t.copy_(torch.as_tensor(init).reshape(t.shape))
+    lib = _lib.lib()
+    zt = alloc((R, V), torch.float32, z, "scores")
+    bt = None if bias is None else alloc((V,), torch.float32, bias, "bias")
+    yt = alloc((R,), torch.int64, y, "y")
+    loss = alloc((1,), torch.float32, None, "loss")
+    rowloss = alloc((R,), torch.float32, None, "rowloss")
+    db = None if bias is None else alloc((V,), torch.float32, None, "dbias")
+    scratch = alloc((int(lib.vmlmf_nll_grad_scratch_floats(R, V)),), torch.float32, None, "scratch")
+    _lib.check(lib.vmlmf_nll_forward_grad(R, V, zt.data_ptr(), _lib.ptr(bt), yt.data_ptr(), ctypes.c_float(scale), loss.data_ptr(),
+                                          rowloss.data_ptr(), _lib.ptr(db), scratch.data_ptr(),
+                                          _lib.raw_stream(torch.device(DEV, torch.cuda.current_device()))))
+    torch.cuda.synchronize()
+    return loss, rowloss, zt, db
+
+
+# one row, every lane but two padding; a partly filled last slot; all twelve slots full; one workgroup walks two rows (its column
+# sums carry over); every workgroup walks two or three rows and the finish groups 512 partial rows
+NLL_SHAPES = [(1, 8, 1), (3, 1028, 1), (4, 12288, 2), (513, 64, 3), (1030, 64, 2)]
+
+
+@pytest.mark.parametrize("R,V,B", NLL_SHAPES)
+def test_nll_forward_grad_against_the_fp64_oracle_at_alpha_zero(R, V, B):
+    """vmlmf_nll_forward_grad: the loss, its rows, the in-place gradient and dbias against the oracle's hard part, score amplitude
+    2 and 30, with and without bias."""
+    scale = B / R
+    for amp in (2.0, 30.0):
+        z, bias, y, _, _ = D.scores_case(R, V, amp, 200 + R + V, 0)
+        for use_bias in (True, False):
+            want = D.oracle(z.astype(np.float64) + (bias if use_bias else 0.0), y, scale, 0.0, 1.0, teacher=z)
+            loss, rowloss, dz, db = call_nll(R, V, scale, z, bias if use_bias else None, y)
+            what = f"amp {amp} bias {use_bias}"
+            assert np.isfinite(loss.item()) and abs(loss.item() - want["hard"]) <= D.LOSS_REL * abs(want["hard"]), (what, loss.item(), want["hard"])
+            rl = rowloss.cpu().numpy().astype(np.float64)
+            assert np.abs(rl - want["row_hard"]).max() <= D.LOSS_REL * np.abs(want["row_hard"]).max(), what
+            assert_grad(dz.cpu().numpy(), want["dz"], what + ": dz")
+            if use_bias:
+                assert_grad(db.cpu().numpy(), want["db"], what + ": dbias")
+
+
+@pytest.mark.parametrize("bad", [-1, 64], ids=["minus_one", "V"])
+def test_nll_forward_grad_with_a_target_outside_the_vocabulary_is_nan_with_a_finite_gradient(bad):
+    R, V, B = 513, 64, 3
+    z, bias, y, _, _ = D.scores_case(R, V, 2.0, 22, 0)
+    y[7] = bad
+    loss, rowloss, dz, db = call_nll(R, V, B / R, z, bias, y)
+    assert np.isnan(loss.item()) and np.isnan(rowloss[7].item())
+    assert torch.isfinite(rowloss[:7]).all() and torch.isfinite(rowloss[8:]).all()
+    assert torch.isfinite(dz).all() and torch.isfinite(db).all()
+
+
+def test_nll_forward_grad_on_poisoned_exactly_sized_buffers_between_guard_bands():
+    """loss is 1 float and rowloss R floats; the same bits whatever the scratch and the outputs held before, twice in a row as well."""
+    R, V, B = 513, 64, 3
+    z, bias, y, _, _ = D.scores_case(R, V, 2.0, 34, 0)
+    runs = []
+    for fill in FILLS + (FILLS[0],):
+        arena = Arena(DEV, fill)
+        out = call_nll(R, V, B / R, z, bias, y, alloc=lambda shape, dtype, init, name: arena.buf(shape, dtype, init=init, name=name))
+        assert out[0].numel() == 1 and out[1].numel() == R
+        arena.check_guards()
+        for name, t in zip(("loss", "rowloss", "scores", "dbias"), out):
+            assert_written(arena, name, t)
+        runs.append([t.clone() for t in out])
+    for other in runs[1:]:
+        for name, a, c in zip(("loss", "rowloss", "scores", "dbias"), runs[0], other):
+            assert_same_bits(name, a, c, "between fills / runs")
+
+
 @pytest.mark.parametrize("k", [0, 8], ids=["dense", "top8"])
 @pytest.mark.parametrize("R,V,B", [(3, 1028, 1), (513, 64, 3)])
 def test_poisoned_exactly_sized_buffers_between_guard_bands(R, V, B, k):

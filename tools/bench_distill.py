@@ -1,5 +1,5 @@
 """What the distillation loss costs at the LM head (functional.lm_head_distill_loss: vmlmf_distill_forward_grad, two launches,
-csrc/vmlmf_distill.hip), at the PTB width V 10 000: R = 1120 rows (35 x 32, the LM step at 32 rows) and R = 8960 (35 x 256,
+csrc/vmlmf_head_loss.hip), at the PTB width V 10 000: R = 1120 rows (35 x 32, the LM step at 32 rows) and R = 8960 (35 x 256,
 BASELINE configs[4] on one GPU).
   fused_dense_us / fused_top8_us   the launch pair on a fixed (R, V) score matrix with a bias, alpha 0.5, tau 2: the teacher as an
                                    (R, V) score matrix, or as 8 tokens and scores per row

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/vmlmf_contrast.h"
+#include "vmlmf_rowops.h"
 #include "vmlmf_side.h"
 
 namespace {
@@ -31,11 +32,6 @@ constexpr int cs_unroll() { return VW == 4 ? 4 : 8; }
 using vmlmf_side::fail;
 
 // ---- the normalisation rule, written once: every lane of ONE full wave calls it and gets 1 / |x| (0: x stays or becomes zero) ----
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float unit_scale(const float* __restrict__ x, int H, int lane) {
   float s = 0.f;
   for (int e0 = lane; e0 < H; e0 += 4 * 64) {   // four loads in flight; the order of the sum is the plain loop's

@@ -5,16 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include "vmlmf_launch.h"
+#include "vmlmf_rowops.h"
 
 namespace {
 
 constexpr int HEAD_CMAX = 32;   // classes held in registers by the weight-gradient blocks
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // grid B, block 256: wave w owns classes w, w+4, ... (<= 8 of them, accumulated together so that every load
 // of the feature loop is independent of the others); lanes stride the H features.

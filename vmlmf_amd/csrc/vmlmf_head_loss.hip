@@ -1,77 +1,108 @@
-// Knowledge distillation at the LM head (Hinton, Vinyals, Dean: "Distilling the Knowledge in a Neural Network"): the hard loss of
-// vmlmf_nll.hip's training form and tau^2 KL(P || Q) against a teacher's distribution P, loss AND gradient in ONE pass over the
-// student's (R, V) score matrix, in place.  Per row r, z = scores + bias, Q = softmax(z / tau):
+// The LM head's losses in their training form: loss AND the gradient of the (R, V) score matrix in ONE pass over it, in place - the
+// softmax negative log-likelihood of vmlmf_nll.hip (vmlmf_nll_forward_grad, ABI 9) and knowledge distillation (Hinton, Vinyals, Dean:
+// "Distilling the Knowledge in a Neural Network"; vmlmf_distill_forward_grad), which adds tau^2 KL(P || Q) against a teacher's
+// distribution P.  Per row r, z = scores + bias, Q = softmax(z / tau):
 //   hard = logsumexp(z) - z[y]                                soft = tau^2 sum_v P[v] (log P[v] - log Q[v])
 //   dz   = scale ((1 - alpha)(softmax(z) - onehot(y)) + alpha tau (Q - P))
-// P comes from a teacher SOURCE (a template parameter of the one kernel body): a dense (R, V) score matrix, P = softmax(t / tau),
-// or the row's k <= 32 top tokens and their scores, P = softmax over those k and zero elsewhere.  Everything is formed around the
-// row maxima m_z and m_t: with x = z - m_z, u = t - m_t and the four sums
+// The LM head's backward needs dz and the bias gradient (its column sums); the two-kernel form of vmlmf_nll.hip reads the scores twice,
+// writes a second 358 MB matrix and leaves the column sums to a third pass.  Here a 256-thread workgroup walks rows w, w + NWG, ...:
+// a row (plus the bias, which the GEMM in front then need not add) lives in its registers as twelve float4 slots between max, sum and
+// target pick, every load unconditional, is written back IN PLACE as its own gradient (for d(loss) = 1; the caller scales
+// otherwise), and every thread keeps the column sums of the columns it owns over all its rows for the bias gradient.  One read + one
+// write of the matrix; NWG x V column partials (fixed-order sum in head_loss_finish_kernel).  No atomics, fixed summation orders: the
+// same bits from run to run.  Two bodies of that one walk, one finish and one launch tail:
+//   nll_grad_kernel           the NLL alone: plain pointers, the bias held in registers (a teacher-less source of the body below was
+//                             measured at 1.3 x its time: docs/design/head_loss_optim_lm.md)
+//   distill_grad_kernel<SRC>  with a teacher SOURCE: DenseTeacher, an (R, V) score matrix, P = softmax(t / tau), or TopTeacher, the
+//                             row's k <= 32 top tokens and their scores, P = softmax over those k and zero elsewhere
+// With a teacher everything is formed around the row maxima m_z and m_t: with x = z - m_z, u = t - m_t and the four sums
 //   s1 = sum exp(x)    sq = sum exp(x / tau)    st = sum exp(u / tau)    d = sum exp(u / tau) (u - x)
 // hard = log s1 - x[y] and soft = tau^2 (d / (tau st) - log st + log sq); at tau == 1 (a uniform branch) sq is s1 and the row's
-// second exponential is skipped.  The shape is nll_grad_kernel's: a 256-thread workgroup walks rows w, w + NWG, ..., a row lives
-// in its registers as twelve float4 slots - first x, then the numerators exp(x) and exp(x / tau) side by side, so every
-// exponential is taken once -, every load unconditional, the gradient written back in place, the column sums of the workgroup's
-// rows kept for the bias gradient.  Two block reductions per row (the two maxima; the four sums), no atomics, fixed summation
-// orders: the same bits from run to run.
-// The teacher's row lies in one V-wide row of LDS, each lane reading and writing its own slots only:
+// second exponential is skipped.  The slots hold first x, then the numerators exp(x) and exp(x / tau) side by side, so every
+// exponential is taken once; two block reductions per row (the two maxima; the four sums).  The teacher's row lies in one V-wide
+// row of LDS, each lane reading and writing its own slots only:
 //   dense:  the teacher's scores, loaded through registers; the sum pass replaces them by the numerators exp(u / tau)
 //   top-k:  zeros but at the row's k columns, where lanes j < k scatter exp(u_j / tau) behind the maxima and clear it behind the
 //           write pass (a barrier each) - a column's owner reads P like a dense operand and the k entries need no search
-// so the write pass is the same for both.  The bias is read again with every row (V floats that stay in the cache): student
-// numerators (2 x 48) + column sums (48) already are 144 VGPRs, and the LDS row is taken.
+// so the write pass is the same for both.  There the bias is read again with every row (V floats that stay in the cache): student
+// numerators (2 x 48) + column sums (48) already are 144 VGPRs, and the LDS row is taken; rows are buffers (vmlmf_rowops.h).
 // Register, LDS and occupancy numbers: docs/design/lm_distill.md.
 #include <hip/hip_runtime.h>
 
 #include "vmlmf_launch.h"
+#include "vmlmf_rowops.h"
 
 namespace {
 
-constexpr int DQ = 12;   // float4 per thread: rows up to 256 * 12 * 4 = 12288 wide, nll_grad_kernel's limit
+constexpr int DQ = 12;   // float4 per thread: rows up to 256 * 12 * 4 = 12288 wide
 
-// workgroup-wide reduction of N values per thread (256 threads) in ONE exchange, results broadcast; `red` has 4 * N floats
-template <int N, bool MAX>
-__device__ __forceinline__ void block_reduce(float (&v)[N], float* red) {
+// ---- the NLL alone ---------------------------------------------------------------------------------------------------------------
+constexpr int NLL_GQ = DQ;   // (192 VGPRs of row + bias + column sums)
+__global__ __launch_bounds__(256, 2) void nll_grad_kernel(int R, int V, float scale, float* __restrict__ scores,
+                                                          const float* __restrict__ bias, const long long* __restrict__ y,
+                                                          float* __restrict__ rowloss, float* __restrict__ dbpart) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, nq = V >> 2;
+  float4 bv[NLL_GQ], cs[NLL_GQ];
 #pragma unroll
-  for (int n = 0; n < N; ++n) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[n] = MAX ? fmaxf(v[n], __shfl_xor(v[n], o, 64)) : v[n] + __shfl_xor(v[n], o, 64);
+  for (int i = 0; i < NLL_GQ; ++i) {
+    const int q = tid + 256 * i;
+    const float4 t = bias != nullptr ? reinterpret_cast<const float4*>(bias)[q < nq ? q : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bv[i] = q < nq ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+    cs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  __syncthreads();   // red may still be read from the previous reduction
-  if ((threadIdx.x & 63) == 0) {
+  for (int row = blockIdx.x; row < R; row += gridDim.x) {
+    float* z = scores + (size_t)row * V;
+    float4 v[NLL_GQ];
 #pragma unroll
-    for (int n = 0; n < N; ++n) red[4 * n + (threadIdx.x >> 6)] = v[n];
-  }
-  __syncthreads();
+    for (int i = 0; i < NLL_GQ; ++i) {   // clamped index: every load unconditional
+      const int q = tid + 256 * i;
+      v[i] = reinterpret_cast<const float4*>(z)[q < nq ? q : 0];
+    }
+    float m = -INFINITY;
 #pragma unroll
-  for (int n = 0; n < N; ++n) {
-    const float* r = red + 4 * n;
-    v[n] = MAX ? fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3])) : (r[0] + r[1]) + (r[2] + r[3]);
+    for (int i = 0; i < NLL_GQ; ++i) {
+      const int q = tid + 256 * i;
+      v[i].x += bv[i].x, v[i].y += bv[i].y, v[i].z += bv[i].z, v[i].w += bv[i].w;
+      if (q >= nq) v[i] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      m = fmaxf(m, fmaxf(fmaxf(v[i].x, v[i].y), fmaxf(v[i].z, v[i].w)));
+    }
+    m = block_reduce<true>(m, red);
+    const long long t = y[row];
+    const bool inr = t >= 0 && t < V;
+    const int tc = inr ? (int)t : -1;
+    float s = 0.f, ztm = 0.f;   // ztm: (target's score - m), held by the thread that owns the target's column
+#pragma unroll
+    for (int i = 0; i < NLL_GQ; ++i) {   // keep the exponentials: they are the softmax numerators
+      const int q = tid + 256 * i;
+      if ((tc >> 2) == q) ztm = ((tc & 3) == 0 ? v[i].x : (tc & 3) == 1 ? v[i].y : (tc & 3) == 2 ? v[i].z : v[i].w) - m;
+      v[i].x = __expf(v[i].x - m), v[i].y = __expf(v[i].y - m), v[i].z = __expf(v[i].z - m), v[i].w = __expf(v[i].w - m);
+      s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+    s = block_reduce<false>(s, red);
+    const float inv = scale / s;
+#pragma unroll
+    for (int i = 0; i < NLL_GQ; ++i) {
+      const int q = tid + 256 * i;
+      if (q < nq) {
+        if ((tc >> 2) == q) rowloss[row] = __logf(s) - ztm;   // lse - z_t
+        float4 o;
+        o.x = v[i].x * inv - (4 * q + 0 == tc ? scale : 0.f);
+        o.y = v[i].y * inv - (4 * q + 1 == tc ? scale : 0.f);
+        o.z = v[i].z * inv - (4 * q + 2 == tc ? scale : 0.f);
+        o.w = v[i].w * inv - (4 * q + 3 == tc ? scale : 0.f);
+        reinterpret_cast<float4*>(z)[q] = o;
+        cs[i].x += o.x, cs[i].y += o.y, cs[i].z += o.z, cs[i].w += o.w;
+      }
+    }
+    if (!inr && tid == 0) rowloss[row] = NAN;   // a target outside [0, V): NaN loss (the reference's indexing raises)
+  }
+#pragma unroll
+  for (int i = 0; i < NLL_GQ; ++i) {
+    const int q = tid + 256 * i;
+    if (q < nq) reinterpret_cast<float4*>(dbpart + (size_t)blockIdx.x * V)[q] = cs[i];
   }
 }
-
-__device__ __forceinline__ float4 f4(float a) { return make_float4(a, a, a, a); }
-// A row as a buffer: one descriptor per row in scalar registers, a lane's slot at the 32-bit byte offset 16 (tid + 256 i).  The
-// hardware's range check takes the place of index clamps and of 64-bit addresses per slot (48 VGPRs of loop invariants with plain
-// pointers): a load past the row's `bytes` returns zeros, a store there is dropped (the stores are predicated all the same).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_buffer(const float* row, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 load4(__amdgpu_buffer_rsrc_t r, int off) {
-  const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-  return make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
-}
-__device__ __forceinline__ void store4(__amdgpu_buffer_rsrc_t r, int off, const float4& v) {
-  const u32x4 w = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-  __builtin_amdgcn_raw_buffer_store_b128(w, r, off, 0, 0);
-}
-// A lane's index behind a compiler barrier: what a phase of the row loop derives from it (slot offsets, column numbers) is formed
-// in that phase again, not carried through the loop as a dozen and more invariant registers per use.
-__device__ __forceinline__ int fresh(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-__device__ __forceinline__ float pick(const float4& v, int c) { return c == 0 ? v.x : c == 1 ? v.y : c == 2 ? v.z : v.w; }
 
 // ---- the teacher sources -------------------------------------------------------------------------------------------------------
 // What differs between them in the body: how the teacher's row gets into LDS (`aux`), its maximum (a per-thread partial, folded
@@ -224,13 +255,16 @@ __global__ __launch_bounds__(256, 2) void distill_grad_kernel(int R, int V, floa
   }
 }
 
-// dbias[v] = sum over the workgroups' column partials, in nll_finish_kernel's order (a workgroup takes 32 columns, its eight
-// 32-lane groups an eighth of the partial rows each, the eight sums meet in LDS in group order); block 0 finishes the losses:
-// loss = {total, hard, soft}, hard and soft scaled by `scale`, total = (1 - alpha) hard + alpha soft.
-__global__ __launch_bounds__(256) void distill_finish_kernel(int R, int V, int nwg, float scale, float alpha,
-                                                             const float* __restrict__ rowloss, const float* __restrict__ dbpart,
-                                                             float* __restrict__ dbias, float* __restrict__ loss) {
-  __shared__ float red[8];
+// dbias[v] = sum over the workgroups' column partials (fixed order); block 0 also finishes the losses.  A workgroup takes 32
+// columns, its eight 32-lane groups an eighth of the partial rows each (eight loads in flight), the eight sums meet in LDS in
+// group order.  (One thread per column walking all 512 partial rows was a chain of 64 round trips on 40 workgroups: 34 us.)
+// PARTS = 1: rowloss (R), loss = scale * sum.  PARTS = 2: rowloss (2, R) hard | soft, loss = {total, hard, soft}, hard and soft
+// scaled by `scale`, total = (1 - alpha) hard + alpha soft.
+template <int PARTS>
+__global__ __launch_bounds__(256) void head_loss_finish_kernel(int R, int V, int nwg, float scale, float alpha,
+                                                               const float* __restrict__ rowloss, const float* __restrict__ dbpart,
+                                                               float* __restrict__ dbias, float* __restrict__ loss) {
+  __shared__ float red[4 * PARTS];
   __shared__ float col[8][32];
   const int li = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + li, cc = c < V ? c : V - 1;
@@ -257,40 +291,65 @@ __global__ __launch_bounds__(256) void distill_finish_kernel(int R, int V, int n
     }
   }
   if (blockIdx.x == 0) {
-    float part[2] = {0.f, 0.f};
-    for (int r = threadIdx.x; r < R; r += 256) part[0] += rowloss[r], part[1] += rowloss[(size_t)R + r];
-    block_reduce<2, false>(part, red);
+    float part[PARTS];
+#pragma unroll
+    for (int p = 0; p < PARTS; ++p) part[p] = 0.f;
+    for (int r = threadIdx.x; r < R; r += 256) {
+#pragma unroll
+      for (int p = 0; p < PARTS; ++p) part[p] += rowloss[(size_t)p * R + r];
+    }
+    block_reduce<PARTS, false>(part, red);
     if (threadIdx.x == 0) {
-      const float hard = scale * part[0], soft = scale * part[1];
-      loss[0] = (1.f - alpha) * hard + alpha * soft, loss[1] = hard, loss[2] = soft;
+      if constexpr (PARTS == 1) {
+        *loss = scale * part[0];
+      } else {
+        const float hard = scale * part[0], soft = scale * part[1];
+        loss[0] = (1.f - alpha) * hard + alpha * soft, loss[1] = hard, loss[2] = soft;
+      }
     }
   }
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
-
-// workgroups of distill_grad_kernel (two per CU, as nll_grad_kernel's); the column partials need NWG x V floats of scratch
-int distill_workgroups(int R) { return R < 512 ? R : 512; }
-
-// VMLMF_E_UNSUPPORTED (-3) when the in-register form does not cover the row width or an operand's alignment
-int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
-                            const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
-                            float* rowloss, float* dbias, float* scratch, hipStream_t s) {
+// A pass and the finish; `kd`: with a teacher - dense where `teacher` is given, else the top-k form.  -3 (VMLMF_E_UNSUPPORTED at
+// the C ABI) when the in-register form does not cover the row width or an operand's alignment.  The scratch pointer's alignment is
+// part of the check for every source: the column partials are stored sixteen bytes at a time (before the sources shared this tail,
+// vmlmf_nll_forward_grad made that store on a misaligned scratch).
+int launch_head_loss(bool kd, int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
+                     const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss, float* rowloss,
+                     float* dbias, float* scratch, hipStream_t s) {
   if (V % 4 != 0 || V > 256 * DQ * 4 || !aligned16(scores) || !aligned16(bias) || !aligned16(teacher) || !aligned16(scratch)) return -3;
-  const int nwg = distill_workgroups(R);
-  if (teacher != nullptr) {
+  const int nwg = head_loss_workgroups(R);
+  const dim3 grid(nwg), block(256);
+  if (!kd) {
+    hipLaunchKernelGGL(nll_grad_kernel, grid, block, 0, s, R, V, scale, scores, bias, y, rowloss, scratch);
+  } else if (teacher != nullptr) {
     const DenseTeacher src = {teacher};
-    hipLaunchKernelGGL(distill_grad_kernel<DenseTeacher>, dim3(nwg), dim3(256), 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss,
-                       scratch);
+    hipLaunchKernelGGL(distill_grad_kernel<DenseTeacher>, grid, block, 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss, scratch);
   } else {
     const TopTeacher src = {top_tokens, top_scores, top};
-    hipLaunchKernelGGL(distill_grad_kernel<TopTeacher>, dim3(nwg), dim3(256), 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss,
-                       scratch);
+    hipLaunchKernelGGL(distill_grad_kernel<TopTeacher>, grid, block, 0, s, R, V, scale, alpha, tau, scores, bias, y, src, rowloss, scratch);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(distill_finish_kernel, dim3((V + 31) / 32), dim3(256), 0, s, R, V, nwg, scale, alpha, rowloss, scratch, dbias, loss);
+  const auto finish = kd ? head_loss_finish_kernel<2> : head_loss_finish_kernel<1>;
+  hipLaunchKernelGGL(finish, dim3((V + 31) / 32), block, 0, s, R, V, nwg, scale, alpha, rowloss, scratch, dbias, loss);
   return (int)hipGetLastError();
+}
+
+}  // namespace
+
+// workgroups of nll_grad_kernel and distill_grad_kernel (two per CU: 192 + VGPRs each); the column partials need NWG x V floats of scratch
+int head_loss_workgroups(int R) { return R < 512 ? R : 512; }
+
+int launch_nll_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float* loss, float* rowloss,
+                        float* dbias, float* scratch, hipStream_t s) {
+  return launch_head_loss(false, R, V, scores, bias, y, scale, 0.f, 1.f, nullptr, nullptr, nullptr, 0, loss, rowloss, dbias, scratch, s);
+}
+
+int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
+                            const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
+                            float* rowloss, float* dbias, float* scratch, hipStream_t s) {
+  return launch_head_loss(true, R, V, scores, bias, y, scale, alpha, tau, teacher, top_tokens, top_scores, top, loss, rowloss, dbias, scratch, s);
 }

@@ -273,13 +273,14 @@ hipError_t launch_nll_fwd(int R, int V, const float* scores, const long long* y,
 hipError_t launch_nll_bwd(int R, int V, const float* scores, const long long* y, float scale, const float* lse,
                           const float* dloss, float* dscores, hipStream_t s);
 
-// training form of the loss: loss, the scores' gradient (in place, for d(loss) = 1) and the bias gradient in one pass
-int nll_grad_workgroups(int R);
+// training form of the loss (vmlmf_head_loss.hip): loss, the scores' gradient (in place, for d(loss) = 1) and the bias gradient in
+// one pass; scratch: head_loss_workgroups(R) x V floats.  Both launches return -3 (VMLMF_E_UNSUPPORTED at the C ABI) unless V is a
+// multiple of four, at most 12288, and scores, bias, teacher and scratch are 16-byte aligned.
+int head_loss_workgroups(int R);
 int launch_nll_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float* loss,
                         float* rowloss, float* dbias, float* scratch, hipStream_t s);
-// the same pass with a soft-target term against a teacher's distribution (vmlmf_distill.hip): exactly one of `teacher` (R, V) and
-// (top_tokens, top_scores) (R, top) is given; loss (3): total, hard, soft; rowloss (2, R): hard | soft
-int distill_workgroups(int R);
+// the same pass with a soft-target term against a teacher's distribution: exactly one of `teacher` (R, V) and (top_tokens,
+// top_scores) (R, top) is given; loss (3): total, hard, soft; rowloss (2, R): hard | soft
 int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
                             const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
                             float* rowloss, float* dbias, float* scratch, hipStream_t s);

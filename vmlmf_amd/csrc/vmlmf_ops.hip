@@ -58,18 +58,23 @@ int vmlmf_nll_backward(int R, int V, const float* scores, const int64_t* y, floa
   return hip_tail((int)launch_nll_bwd(R, V, scores, (const long long*)y, scale, lse, dloss, dscores, (hipStream_t)stream));
 }
 
-size_t vmlmf_nll_grad_scratch_floats(int R, int V) { return (size_t)nll_grad_workgroups(R < 1 ? 1 : R) * (size_t)(V < 1 ? 1 : V); }
+// the training forms of the head's losses (vmlmf_head_loss.hip): one scratch size, one refusal
+static size_t head_loss_scratch_floats(int R, int V) { return (size_t)head_loss_workgroups(R < 1 ? 1 : R) * (size_t)(V < 1 ? 1 : V); }
+static int head_loss_tail(int rc) {
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "head loss: rows must be 16-byte aligned, a multiple of four and at most 12288 wide");
+  return hip_tail(rc);
+}
+
+size_t vmlmf_nll_grad_scratch_floats(int R, int V) { return head_loss_scratch_floats(R, V); }
 
 int vmlmf_nll_forward_grad(int R, int V, float* scores, const float* bias, const int64_t* y, float scale, float* loss,
                            float* rowloss, float* dbias, float* scratch, void* stream) {
   if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "nll: R and V must be >= 1");
   if (!scores || !y || !loss || !rowloss || !scratch) return fail(VMLMF_E_BADARG, "nll: null pointer");
-  const int rc = launch_nll_fwd_grad(R, V, scores, bias, (const long long*)y, scale, loss, rowloss, dbias, scratch, (hipStream_t)stream);
-  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "nll_forward_grad: rows must be 16-byte aligned, a multiple of four and at most 12288 wide");
-  return hip_tail(rc);
+  return head_loss_tail(launch_nll_fwd_grad(R, V, scores, bias, (const long long*)y, scale, loss, rowloss, dbias, scratch, (hipStream_t)stream));
 }
 
-size_t vmlmf_distill_scratch_floats(int R, int V) { return (size_t)distill_workgroups(R < 1 ? 1 : R) * (size_t)(V < 1 ? 1 : V); }
+size_t vmlmf_distill_scratch_floats(int R, int V) { return head_loss_scratch_floats(R, V); }
 
 int vmlmf_distill_forward_grad(int R, int V, float* scores, const float* bias, const int64_t* y, float scale, const vmlmf_distill* kd,
                                float* loss, float* rowloss, float* dbias, float* scratch, void* stream) {
@@ -81,11 +86,9 @@ int vmlmf_distill_forward_grad(int R, int V, float* scores, const float* bias, c
   if (dense == topk) return fail(VMLMF_E_BADARG, "distill: exactly one teacher form - teacher (R, V), or top_tokens and top_scores (R, top)");
   if (topk && (!kd->top_tokens || !kd->top_scores)) return fail(VMLMF_E_BADARG, "distill: the top-k form takes top_tokens and top_scores");
   if (topk && (kd->top < 1 || kd->top > 32)) return fail(VMLMF_E_BADARG, "distill: top must lie in [1, 32]");
-  const int rc = launch_distill_fwd_grad(R, V, scores, bias, (const long long*)y, scale, kd->alpha, kd->temperature, kd->teacher,
-                                         (const long long*)kd->top_tokens, kd->top_scores, kd->top, loss, rowloss, dbias, scratch,
-                                         (hipStream_t)stream);
-  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "distill_forward_grad: rows must be 16-byte aligned, a multiple of four and at most 12288 wide");
-  return hip_tail(rc);
+  return head_loss_tail(launch_distill_fwd_grad(R, V, scores, bias, (const long long*)y, scale, kd->alpha, kd->temperature, kd->teacher,
+                                                (const long long*)kd->top_tokens, kd->top_scores, kd->top, loss, rowloss, dbias, scratch,
+                                                (hipStream_t)stream));
 }
 
 size_t vmlmf_embed_backward_scratch_bytes(int R, int V) { return embed_bwd_scratch_bytes(R < 1 ? 1 : R, V < 1 ? 1 : V); }
