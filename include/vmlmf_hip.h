@@ -407,6 +407,39 @@ int vmlmf_distill_forward_grad(int R, int V, float *scores, const float *bias, c
                                const vmlmf_distill *kd, float *loss, float *rowloss, float *dbias, float *scratch, void *stream);
 
 /*
+ * The general training objective at the LM head: a padding mask, label smoothing, z-loss and token-level unlikelihood (Welleck et
+ * al., "Neural Text Generation with Unlikelihood Training"), loss and the scores' gradient in the same ONE pass, in place.  (Added
+ * under ABI 13 without a bump, as distillation was: two new entry points and one new struct, nothing that exists changes.)  With
+ * z = scores + bias, p = softmax(z_r), lse_r = logsumexp(z_r), eps = label_smoothing, zeta = z_loss, alpha = unlikelihood and
+ * m_r = 0 where y[r] == -1 (the mask), 1 elsewhere, per row r:
+ *   nll_r = lse_r - z_r[y_r]                       sm_r = lse_r - mean_v z_r[v]
+ *   zl_r  = lse_r^2                                ul_r = sum over c in C_r of -log(max(1 - p_c, 1e-5))
+ *   loss  = scale * sum_r m_r ((1 - eps) nll_r + eps sm_r + zeta zl_r + alpha ul_r)
+ *   dz_r[v] = scale m_r (p_v - (1 - eps)[v == y_r] - eps / V + 2 zeta lse_r p_v + alpha (w_v - p_v S_r))     written over scores
+ *             w_v = p_v / (1 - p_v) if v in C_r and 1 - p_v > 1e-5, else 0;  S_r = sum_v w_v
+ * C_r is the SET of the row's negatives (R,k) int64, 0 <= k <= 256: entries outside [0, V) are padding, duplicates count once, an
+ * entry equal to y_r is ignored.  negatives is not read when unlikelihood == 0.  scale_dev (may be NULL): one device float
+ * multiplied into scale (a token count formed on the device).  A masked row adds nothing and its gradient row is written as
+ * zeros; any other target outside [0, V) makes nll and total NaN with a finite gradient.  label_smoothing in [0, 1), z_loss and
+ * unlikelihood finite and >= 0, unlikelihood > 0 needs negatives and k >= 1 (VMLMF_E_BADARG otherwise).
+ * loss (5): total, nll, smooth, z, unlikelihood - the parts each scaled by scale and NOT by eps, zeta, alpha.  rowloss (4,R):
+ * nll_r | sm_r | zl_r | ul_r, zeros in masked rows.  bias, dbias may be NULL.  scratch: vmlmf_objective_scratch_floats(R, V)
+ * floats.  Limits, alignment, determinism and error codes are vmlmf_distill_forward_grad's.  Two launches, no allocation, no
+ * synchronisation: capturable.
+ */
+typedef struct vmlmf_objective {
+  float label_smoothing;
+  float z_loss;
+  float unlikelihood;
+  const int64_t *negatives;   /* (R,k), or NULL */
+  int32_t k;                  /* 0 .. 256 */
+  const float *scale_dev;     /* one device float, or NULL */
+} vmlmf_objective;
+size_t vmlmf_objective_scratch_floats(int R, int V);
+int vmlmf_objective_forward_grad(int R, int V, float *scores, const float *bias, const int64_t *y, float scale,
+                                 const vmlmf_objective *obj, float *loss, float *rowloss, float *dbias, float *scratch, void *stream);
+
+/*
  * Gradient of the embedding table (Embed, V/src/models/vmlmf_lm.py:46-48: x = w[tokens]; autograd's backward scatter-adds the
  * R = T*B rows of dy (R,H) into a zero (V,H) matrix).  dweight[v] = sum of dy[p] over the positions p with tokens[p] == v, in
  * ascending position order (deterministic, no float atomics); rows no token selects are written as zeros: the call fills all of

@@ -70,6 +70,12 @@ class Distill(ctypes.Structure):
                 ("top_scores", ctypes.c_void_p), ("top", ctypes.c_int32)]
 
 
+class Objective(ctypes.Structure):
+    """vmlmf_objective: label smoothing, z-loss and unlikelihood of vmlmf_objective_forward_grad; negatives (R, k) int64 or NULL."""
+    _fields_ = [("label_smoothing", ctypes.c_float), ("z_loss", ctypes.c_float), ("unlikelihood", ctypes.c_float),
+                ("negatives", ctypes.c_void_p), ("k", ctypes.c_int32), ("scale_dev", ctypes.c_void_p)]
+
+
 class Extra(ctypes.Structure):
     _fields_ = [("packed", ctypes.c_void_p), ("head", ctypes.POINTER(Head)), ("ce", ctypes.POINTER(Ce)), ("drop", ctypes.POINTER(Dropout))]
 
@@ -136,6 +142,8 @@ SYMBOLS = {
     "vmlmf_nll_forward_grad": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
     "vmlmf_distill_scratch_floats": (_sz, [_i, _i]),
     "vmlmf_distill_forward_grad": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.POINTER(Distill), _vp, _vp, _vp, _vp, _vp]),
+    "vmlmf_objective_scratch_floats": (_sz, [_i, _i]),
+    "vmlmf_objective_forward_grad": (_i, [_i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.POINTER(Objective), _vp, _vp, _vp, _vp, _vp]),
     "vmlmf_embed_backward_scratch_bytes": (_sz, [_i, _i]),
     "vmlmf_embed_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vmlmf_dropout_fused": (_i, [ctypes.POINTER(Desc)]),

@@ -284,6 +284,17 @@ int launch_nll_fwd_grad(int R, int V, float* scores, const float* bias, const lo
 int launch_distill_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, float alpha, float tau,
                             const float* teacher, const long long* top_tokens, const float* top_scores, int top, float* loss,
                             float* rowloss, float* dbias, float* scratch, hipStream_t s);
+// the same pass for the general training objective (docs/design/lm_objective.md): a padding mask (y == -1), label smoothing,
+// z-loss and token-level unlikelihood against the row's negative set (negatives (R, k) or NULL, entries outside [0, V) padding);
+// scale_dev (or NULL): one device float multiplied into scale; loss (5): total, nll, smooth, z, unlikelihood; rowloss (4, R)
+struct ObjectiveArgs {
+  float eps, zeta, alpha;
+  const long long* negatives;
+  int k;
+  const float* scale_dev;
+};
+int launch_objective_fwd_grad(int R, int V, float* scores, const float* bias, const long long* y, float scale, const ObjectiveArgs& o,
+                              float* loss, float* rowloss, float* dbias, float* scratch, hipStream_t s);
 // embedding-table gradient (vmlmf_embed.hip)
 size_t embed_bwd_scratch_bytes(int R, int V);
 int launch_transpose(int rows, int cols, const float* src, float* dst, hipStream_t s);   // dst (cols x rows) = src^T

@@ -91,6 +91,21 @@ int vmlmf_distill_forward_grad(int R, int V, float* scores, const float* bias, c
                                                 (hipStream_t)stream));
 }
 
+size_t vmlmf_objective_scratch_floats(int R, int V) { return head_loss_scratch_floats(R, V); }
+
+int vmlmf_objective_forward_grad(int R, int V, float* scores, const float* bias, const int64_t* y, float scale, const vmlmf_objective* obj,
+                                 float* loss, float* rowloss, float* dbias, float* scratch, void* stream) {
+  if (R < 1 || V < 1) return fail(VMLMF_E_BADARG, "objective: R and V must be >= 1");
+  if (!scores || !y || !obj || !loss || !rowloss || !scratch) return fail(VMLMF_E_BADARG, "objective: null pointer");
+  if (!(obj->label_smoothing >= 0.f && obj->label_smoothing < 1.f)) return fail(VMLMF_E_BADARG, "objective: label_smoothing must lie in [0, 1)");
+  if (!(obj->z_loss >= 0.f) || !(obj->z_loss < INFINITY)) return fail(VMLMF_E_BADARG, "objective: z_loss must be finite and >= 0");
+  if (!(obj->unlikelihood >= 0.f) || !(obj->unlikelihood < INFINITY)) return fail(VMLMF_E_BADARG, "objective: unlikelihood must be finite and >= 0");
+  if (obj->k < 0 || obj->k > 256) return fail(VMLMF_E_BADARG, "objective: k must lie in [0, 256]");
+  if (obj->unlikelihood > 0.f && (!obj->negatives || obj->k < 1)) return fail(VMLMF_E_BADARG, "objective: unlikelihood > 0 takes negatives (R, k), k >= 1");
+  const ObjectiveArgs o = {obj->label_smoothing, obj->z_loss, obj->unlikelihood, (const long long*)obj->negatives, obj->k, obj->scale_dev};
+  return head_loss_tail(launch_objective_fwd_grad(R, V, scores, bias, (const long long*)y, scale, o, loss, rowloss, dbias, scratch, (hipStream_t)stream));
+}
+
 size_t vmlmf_embed_backward_scratch_bytes(int R, int V) { return embed_bwd_scratch_bytes(R < 1 ? 1 : R, V < 1 ? 1 : V); }
 
 int vmlmf_embed_backward(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, void* scratch,

@@ -1211,6 +1211,181 @@ def lm_head_distill_loss(h, weight, bias, y, teacher, *, alpha=0.5, temperature=
     return (loss, hard, soft) if return_parts else loss
 
 
+# ---- the general training objective at the LM head (C ABI vmlmf_objective_forward_grad; docs/design/lm_objective.md) ----
+# A padding mask, label smoothing (eps), z-loss (zeta) and token-level unlikelihood (alpha; Welleck et al., "Neural Text Generation
+# with Unlikelihood Training") as terms of lm_head_loss's one pass.  With p = softmax(z_r), lse_r = logsumexp(z_r), per row
+#   nll = lse - z[y]    sm = lse - mean z    zl = lse^2    ul = sum over the row's negative set of -log(max(1 - p_c, 1e-5))
+#   loss = scale sum over the unmasked rows of ((1 - eps) nll + eps sm + zeta zl + alpha ul)
+OBJECTIVE_MAX_K = 256
+UNLIKELIHOOD_FLOOR = 1e-5
+
+
+def check_objective(label_smoothing, z_loss, unlikelihood, normalize):
+    """ValueError for a label_smoothing outside [0, 1), a negative or non-finite z_loss or unlikelihood, a normalize that is
+    neither "rows" nor "tokens"."""
+    import math
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+    if not (number(label_smoothing) and 0.0 <= label_smoothing < 1.0):
+        raise ValueError(f"vmlmf_amd: label_smoothing must lie in [0, 1), got {label_smoothing!r}")
+    if not (number(z_loss) and z_loss >= 0.0):
+        raise ValueError(f"vmlmf_amd: z_loss must be finite and >= 0, got {z_loss!r}")
+    if not (number(unlikelihood) and unlikelihood >= 0.0):
+        raise ValueError(f"vmlmf_amd: unlikelihood must be finite and >= 0, got {unlikelihood!r}")
+    if normalize not in ("rows", "tokens"):
+        raise ValueError(f"vmlmf_amd: normalize is \"rows\" or \"tokens\", got {normalize!r}")
+
+
+def check_lengths(lengths, B, who):
+    """The contract Model.score and Model.loss share for lengths: None or an integer tensor of shape (B,)."""
+    if lengths is not None and not (isinstance(lengths, torch.Tensor) and tuple(lengths.shape) == (B,) and not lengths.is_floating_point()
+                                    and not lengths.is_complex() and lengths.dtype != torch.bool):
+        raise ValueError(f"vmlmf_amd: {who}: lengths must be an integer tensor of shape ({B},), one per row")
+
+
+def objective_negatives(negatives, R):
+    """The rows' negative candidates flattened to (R, K): a (T, B, K) or (R, K) int64 tensor, 1 <= K <= 256.  ValueError for
+    another type or shape; no value is looked at (entries outside [0, V) are padding)."""
+    if not (isinstance(negatives, torch.Tensor) and negatives.dtype == torch.int64 and negatives.dim() in (2, 3)
+            and 1 <= negatives.shape[-1] <= OBJECTIVE_MAX_K and negatives.numel() == R * negatives.shape[-1]):
+        got = (tuple(negatives.shape), negatives.dtype) if isinstance(negatives, torch.Tensor) else type(negatives).__name__
+        raise ValueError(f"vmlmf_amd: negatives are a (T, B, K) or (R, K) int64 tensor with 1 <= K <= {OBJECTIVE_MAX_K} for {R} rows, got {got}")
+    return negatives.reshape(R, negatives.shape[-1])
+
+
+def context_negatives(x):
+    """The token-level unlikelihood candidates of the paper within a minibatch: for input tokens x (T, B) int64, a (T, B, T) int64
+    tensor whose row (t, b) holds x[0 .. t, b] - every input token of the row up to and including position t - and -1 (padding)
+    behind them.  The loss takes them as a set and drops the position's own target.  Stock ops on x's device, no read-back."""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.int64):
+        raise ValueError("vmlmf_amd: context_negatives takes (T, B) int64 tokens")
+    T = x.shape[0]
+    steps = torch.arange(T, device=x.device)
+    return x.t().unsqueeze(0).expand(T, -1, -1).masked_fill(steps[None, None, :] > steps[:, None, None], -1)
+
+
+def _mask_targets(y, lengths):
+    """y (T, B) with -1 at the positions t >= lengths[b], as Model.score masks them."""
+    if lengths is None:
+        return y
+    return y.masked_fill(torch.arange(y.shape[0], device=y.device)[:, None] >= lengths.to(y.device)[None, :], -1)
+
+
+def _valid_count(lengths, T, dtype):
+    """max(number of positions t < lengths[b], 1) as a device scalar of `dtype`."""
+    return lengths.clamp(0, T).sum().clamp(min=1).to(dtype)
+
+
+def objective_loss_stock(scores, y, *, lengths=None, label_smoothing=0.0, z_loss=0.0, unlikelihood=0.0, negatives=None, normalize="rows"):
+    """The general objective in stock ops under autograd - the path of CPU tensors, of widths and types the kernel does not cover,
+    and the baseline tools/bench_objective.py measures the kernel against.  scores (R, V) with the bias in them, y (T, B) int64 (-1:
+    masked), the keywords as lm_head_objective_loss takes them.  Returns (loss, nll, smooth, z, unlikelihood), the parts scaled like
+    the loss and not by their weights; smooth and unlikelihood are zero where their weight is."""
+    R, V = scores.shape
+    T, B = y.shape
+    eps, zeta, alpha = float(label_smoothing), float(z_loss), float(unlikelihood)
+    yrow = _mask_targets(y, lengths).reshape(-1)
+    live = yrow != -1
+    scale = float(B) / float(R)
+    if normalize == "tokens" and lengths is not None:
+        scale = float(B) / _valid_count(lengths.to(scores.device), T, scores.dtype)
+    inr = (yrow >= 0) & (yrow < V)
+    lse = torch.logsumexp(scores, dim=1)
+    zt = scores.gather(1, yrow.clamp(0, V - 1)[:, None])[:, 0]
+    nll = lse - torch.where(inr | ~live, zt, torch.full_like(zt, float("nan")))   # a target outside [0, V) that is not the mask
+    zero = torch.zeros_like(lse)
+    smooth = lse - scores.mean(dim=1) if eps > 0 else zero
+    zl = lse * lse
+    ul = zero
+    if alpha > 0:
+        if negatives is None:
+            raise ValueError("vmlmf_amd: unlikelihood > 0 takes negatives (Model.loss builds context_negatives(x) by default)")
+        neg = objective_negatives(negatives, R).to(scores.device)
+        member = torch.zeros(R, V + 1, dtype=torch.bool, device=scores.device)
+        member.scatter_(1, torch.where((neg >= 0) & (neg < V), neg, torch.full_like(neg, V)), True)       # a set: duplicates once
+        member = member[:, :V] & ~(torch.arange(V, device=scores.device)[None, :] == yrow[:, None])       # ... without the target
+        p = torch.softmax(scores, dim=1)
+        ul = -(torch.log(torch.clamp(1.0 - p, min=UNLIKELIHOOD_FLOOR)) * member).sum(dim=1)
+
+    def total(rows):
+        return scale * torch.where(live, rows, zero).sum()
+    parts = [total(nll), total(smooth), total(zl), total(ul)]
+    loss = (1.0 - eps) * parts[0] + eps * parts[1] + zeta * parts[2] + alpha * parts[3]
+    return (loss, *parts)
+
+
+class LmHeadObjectiveFn(torch.autograd.Function):
+    """(loss, nll, smooth, z, unlikelihood) of lm_head_objective_loss; the forward product, the tuned forms and the backward are
+    lm_head_loss's, the loss launch is vmlmf_objective_forward_grad.  The parts are reported, not differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, y, negatives, scale_dev, eps, zeta, alpha):
+        obj = _lib.Objective(label_smoothing=eps, z_loss=zeta, unlikelihood=alpha, negatives=None if negatives is None else negatives.data_ptr(),
+                             k=0 if negatives is None else negatives.shape[1], scale_dev=None if scale_dev is None else scale_dev.data_ptr())
+
+        def launch(lib, R, V, scores, bias, yrow, scale, stats, dbias, stream):
+            scratch = _workspace(scores.device, 4 * lib.vmlmf_objective_scratch_floats(R, V))
+            _lib.check(lib.vmlmf_objective_forward_grad(R, V, _ptr(scores), _ptr(bias), _ptr(yrow), scale, ctypes.byref(obj), stats.data_ptr(),
+                                                        stats.data_ptr() + 20, _ptr(dbias), scratch.data_ptr(), stream))
+
+        stats = _head_loss_forward(ctx, h, w, b, y, lambda R: 5 + 4 * R, launch)             # total and four parts | rowloss (4, R)
+        parts = tuple(stats[i] for i in range(1, 5))
+        ctx.mark_non_differentiable(*parts)
+        return (stats[0], *parts)
+
+    @staticmethod
+    def backward(ctx, dloss, *dparts):
+        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None)
+
+
+def lm_head_objective_loss(h, weight, bias, y, *, lengths=None, label_smoothing=0.0, z_loss=0.0, unlikelihood=0.0, negatives=None,
+                           normalize="rows", return_parts=False):
+    """lm_head_loss with a padding mask, label smoothing, z-loss and token-level unlikelihood: h (T, B, H), weight (V, H), bias (V)
+    or None, y (T, B) int64.  With z = Linear(h), p = softmax(z), eps = label_smoothing, zeta = z_loss, alpha = unlikelihood, per row
+        nll = lse - z[y]    sm = lse - mean z    zl = lse^2    ul = sum over c in C of -log(max(1 - p_c, 1e-5))
+        loss = scale sum over the unmasked rows of ((1 - eps) nll + eps sm + zeta zl + alpha ul)
+    lengths (B) integers: position (t, b) counts iff t < lengths[b] (its target is set to -1, the mask: the row adds nothing and
+    its gradient is zero); any other target outside [0, V) makes the loss NaN.  normalize "rows": scale = B / (T B), lm_head_loss's;
+    "tokens": scale = B / max(number of valid positions, 1), formed on the device from lengths ("tokens" without lengths is "rows").
+    negatives (T, B, K) or (T B, K) int64, 1 <= K <= 256: the row's candidate SET C - entries outside [0, V) are padding,
+    duplicates count once, the row's own target is ignored; required when unlikelihood > 0, not read when it is 0.
+    Returns the scalar loss; with return_parts=True (loss, nll, smooth, z, unlikelihood), the parts detached, scaled like the loss
+    and not multiplied by their weights (smooth and unlikelihood are reported as zero where their weight is zero).
+    On a HIP device (fp32, V a multiple of four, at most 12288) one pass over the scores takes all terms and leaves the gradient in
+    place for the two backward GEMMs (vmlmf_objective_forward_grad); with everything off and no parts asked for the call IS
+    lm_head_loss, launch for launch.  CPU tensors, other types and widths take objective_loss_stock under autograd.  ValueError,
+    before any device work, for arguments out of range, lengths that are not (B) integers and negatives of the wrong type or shape.
+    The call never reads a value back from the device."""
+    check_objective(label_smoothing, z_loss, unlikelihood, normalize)
+    if not (isinstance(y, torch.Tensor) and y.dim() == 2):
+        raise ValueError("vmlmf_amd: lm_head_objective_loss takes targets y of shape (T, B)")
+    check_lengths(lengths, y.shape[1], "lm_head_objective_loss")
+    eps, zeta, alpha = float(label_smoothing), float(z_loss), float(unlikelihood)
+    V, R = weight.shape[0], h.numel() // h.shape[-1]
+    if alpha > 0 and negatives is None:
+        raise ValueError("vmlmf_amd: unlikelihood > 0 takes negatives (Model.loss builds context_negatives(x) by default)")
+    neg = objective_negatives(negatives, R) if alpha > 0 else None
+    fused = h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288
+    if lengths is None and eps == 0.0 and zeta == 0.0 and alpha == 0.0 and not return_parts:
+        return lm_head_loss(h, weight, bias, y)
+    if fused:
+        if neg is not None and neg.device != h.device:
+            raise ValueError(f"vmlmf_amd: negatives must be on the scores' device {h.device}")
+        scale_dev = None
+        if normalize == "tokens" and lengths is not None:
+            scale_dev = float(R) / _valid_count(lengths.to(h.device), y.shape[0], torch.float32)
+        out = LmHeadObjectiveFn.apply(h, weight, bias, _mask_targets(y, lengths), None if neg is None else neg.contiguous(), scale_dev,
+                                      eps, zeta, alpha)
+    else:
+        h2 = h.reshape(-1, h.shape[-1])
+        scores = torch.mm(h2, weight.t()) if bias is None else torch.addmm(bias, h2, weight.t())
+        out = objective_loss_stock(scores, y, lengths=lengths, label_smoothing=eps, z_loss=zeta, unlikelihood=alpha, negatives=neg,
+                                   normalize=normalize)
+        out = (out[0], *(t.detach() for t in out[1:]))
+    return out if return_parts else out[0]
+
+
 class EmbedFn(torch.autograd.Function):
     """x = w[tokens] (Embed, vmlmf_lm.py:46-48) whose backward is the package's deterministic scatter-add (vmlmf_embed_backward:
     every row of the table's gradient summed in position order, no float atomics, the zero fill in the same pass)."""

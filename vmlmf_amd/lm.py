@@ -282,13 +282,43 @@ class Model(nn.Module):
         scores = self.fc(x)
         return scores, states
 
-    def loss(self, x, y, states):
+    def loss(self, x, y, states, *, lengths=None, label_smoothing=0.0, z_loss=0.0, unlikelihood=0.0, negatives=None, normalize="rows",
+             return_parts=False):
         """nll_loss(self(x, states)[0], y) of the training loop (lm_test.py:200-202) without ever handing out the scores: the
         projection's output is overwritten by its own gradient inside the loss (functional.lm_head_loss), which is what the two
-        backward GEMMs read.  Returns (loss, states); same values as the two-call form."""
+        backward GEMMs read.  Returns (loss, states); same values as the two-call form.  With every keyword at its default this is
+        that call and nothing else.  The keywords add a trainer's other loss arguments as terms of the same pass
+        (functional.lm_head_objective_loss; docs/design/lm_objective.md) - with z_r the scores of row r = t B + b, p = softmax(z_r):
+            row_r = (1 - eps)(lse_r - z_r[y_r]) + eps (lse_r - mean z_r) + zeta lse_r^2 + alpha sum_{c in C_r} -log(max(1 - p_c, 1e-5))
+            loss  = scale * sum over the valid rows of row_r
+        lengths (B) integers, Model.score's contract: position (t, b) is valid iff t < lengths[b]; another row adds nothing and has
+          no gradient.  Any other target outside [0, V) still makes the loss NaN.
+        label_smoothing = eps in [0, 1) and z_loss = zeta >= 0: F.cross_entropy's smoothing and the squared log-partition penalty.
+        unlikelihood = alpha >= 0: token-level unlikelihood training (Welleck et al.) against the candidate SET C_r of `negatives`
+          (T, B, K) or (T B, K) int64, 1 <= K <= 256 - entries outside [0, V) (use -1) are padding, duplicates count once, the row's
+          own target is ignored.  negatives=None: the paper's candidates, the input tokens x[0 .. t, b] of the minibatch
+          (context_negatives(x)); given with alpha == 0 they are not read.
+        normalize "rows": scale = B / (T B) as above, a mask only removes terms; "tokens": scale = B / max(valid positions, 1),
+          formed on the device ("tokens" without lengths is "rows").
+        return_parts=True: loss is (loss, nll, smooth, z, unlikelihood), the parts detached, scaled like the loss and not by their
+          weights - nll is what perplexity is computed from whatever regulariser is on.
+        ValueError, before any device work, for eps outside [0, 1), a negative or non-finite zeta or alpha, another normalize,
+        lengths that are not (B) integers, and negatives of the wrong type, shape or K.  No value is read back from the device."""
         from .functional import lm_head_loss
+        if (lengths is None and negatives is None and not return_parts and normalize == "rows"
+                and label_smoothing == 0.0 and z_loss == 0.0 and unlikelihood == 0.0
+                and not any(isinstance(v, bool) for v in (label_smoothing, z_loss, unlikelihood))):
+            h, states = self.features(x, states)
+            return lm_head_loss(h, self.fc.w, self.fc.b, y), states
+        from .functional import check_lengths, check_objective, context_negatives, lm_head_objective_loss, objective_negatives
+        check_objective(label_smoothing, z_loss, unlikelihood, normalize)
+        check_lengths(lengths, x.size(1), "Model.loss")
+        if unlikelihood > 0:
+            negatives = objective_negatives(context_negatives(x) if negatives is None else negatives, x.numel())
         h, states = self.features(x, states)
-        return lm_head_loss(h, self.fc.w, self.fc.b, y), states
+        loss = lm_head_objective_loss(h, self.fc.w, self.fc.b, y, lengths=lengths, label_smoothing=label_smoothing, z_loss=z_loss,
+                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts)
+        return loss, states
 
     def distill_loss(self, x, y, states, teacher, *, alpha=0.5, temperature=2.0, teacher_states=None, top=0, return_parts=False):
         """loss() with a soft-target term: this model, the student, is trained against a teacher's output distribution as well as

@@ -14,7 +14,7 @@ import torch
 
 from . import _ncache, _score
 from ._ncache import NeuralCache, lm_cache_score  # noqa: F401 (the package's exports)
-from .functional import _require_hip
+from .functional import _require_hip, check_lengths
 
 
 def _check_chunk_rows(chunk_rows, who):
@@ -85,9 +85,7 @@ def score(model, tokens, targets=None, states=None, lengths=None, top=0, chunk_r
     elif not (isinstance(targets, torch.Tensor) and targets.dtype == torch.int64 and targets.shape == tokens.shape and tokens.shape[0] >= 1):
         raise ValueError(f"vmlmf_amd: Model.score takes int64 targets of the tokens' shape {tuple(tokens.shape)}, T >= 1")
     B = tokens.shape[1]
-    if lengths is not None and not (isinstance(lengths, torch.Tensor) and tuple(lengths.shape) == (B,) and not lengths.is_floating_point()
-                                    and not lengths.is_complex() and lengths.dtype != torch.bool):
-        raise ValueError(f"vmlmf_amd: Model.score: lengths must be an integer tensor of shape ({B},), one per row")
+    check_lengths(lengths, B, "Model.score")
     decoding._check_call(model, tokens, "score", "scoring kernel (vmlmf_score_rows)")
     if targets is not None:
         decoding._check_call(model, targets, "score", "scoring kernel (vmlmf_score_rows)")
