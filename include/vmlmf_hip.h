@@ -586,6 +586,22 @@ int vmlmf_adam_step_guarded(const vmlmf_tensor_list *tensors, float *exp_avg, fl
 #define VMLMF_ADAM_LAST 2
 int vmlmf_adam_step_ex(const vmlmf_tensor_list *tensors, float *exp_avg, float *exp_avg_sq, float *steps, float lr,
                        float beta1, float beta2, float eps, float weight_decay, void *guard, int flags, void *stream);
+/* Dynamic evaluation (Krause, Kahembwe, Murray, Renals 2018; docs/design/lm_dyneval.md): test-time adaptation of a language model.
+ * (ABI 13 still: new symbols only.)  `ms`, `theta0` and `rms` are flat device buffers, entry i owns [state_offset[i],
+ * state_offset[i] + numel[i]) as with Adam's moments; the offsets need not be multiples of four.  step_index is not read.
+ *   vmlmf_dyneval_accumulate  ms[state_offset[i] + j] += grad[i][j]^2, one launch: the statistics pass behind a training
+ *                             minibatch's backward.  The caller forms r = sqrt(ms / N) and m, the mean over the tensors of each
+ *                             tensor's mean of r.
+ *   vmlmf_dyneval_step        c = 1 if max_norm <= 0, else min(1, max_norm / (|g|_2 + 1e-6)) over every listed gradient
+ *                             (vmlmf_sgd_clip_step's coefficient);  ld_j = min(decay * rms_j * inv_mean_rms, 1);
+ *                             param_j <- param_j + ld_j (theta0_j - param_j) - lr * c * grad_j / (rms_j + eps).
+ *                             The gradients are only read, clipped or not.  `norm` (device scalar) receives |g|_2; a norm that is
+ *                             not finite skips the step: parameters keep their bits and `norm` says so.  inv_mean_rms = 1 / m.
+ *                             `scratch`: VMLMF_MAX_TENSORS * 64 floats.  Three launches, no host read: capturable.
+ * VMLMF_E_BADARG for a null pointer, a count outside 1 .. VMLMF_MAX_TENSORS, a negative numel or state_offset. */
+int vmlmf_dyneval_accumulate(const vmlmf_tensor_list *tensors, float *ms, void *stream);
+int vmlmf_dyneval_step(const vmlmf_tensor_list *tensors, const float *theta0, const float *rms, float lr, float decay,
+                       float inv_mean_rms, float eps, float max_norm, float *norm, float *scratch, void *stream);
 
 /*
  * Data-parallel gradient exchange (no reference line: the reference has no distributed

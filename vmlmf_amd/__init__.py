@@ -12,9 +12,10 @@ from .functional import (vmlmf_sequence, vmlmf_stack, head_linear, cross_entropy
 from .decoding import DecodeGraph, BeamGraph, DecodeControls, HistoryControls, BeamControls, Truncation, TokenAutomaton, AutomatonControls, AutomatonBeamControls, GroupBeams, ContrastControls, ContrastGraph, lm_contrast_step, StochasticBeams, StochasticBeamGraph, lm_sbeam_step, lm_sample, lm_beam_step, beam_gather, beam_backtrack
 from .scoring import lm_score, NeuralCache, lm_cache_score
 from . import optim
+from .dyneval import DynamicEval, dyneval_step, dyneval_accumulate, dyneval_step_stock, dyneval_accumulate_stock
 from .graphed import GraphedTrainStep
 
-__all__ = ["GraphedTrainStep", "vmlmf_stack", "optim", "head_linear", "cross_entropy", "CrossEntropyLoss", "MyVMLMFCell", "MyVMLMFCellg2", "MyVMLMFgCellg2", "MyLSTMCell", "MyLSTM", "Net", "MyVMLSTM", "MyVMLSTMGroup",
+__all__ = ["GraphedTrainStep", "vmlmf_stack", "optim", "DynamicEval", "dyneval_step", "dyneval_accumulate", "dyneval_step_stock", "dyneval_accumulate_stock", "head_linear", "cross_entropy", "CrossEntropyLoss", "MyVMLMFCell", "MyVMLMFCellg2", "MyVMLMFgCellg2", "MyLSTMCell", "MyLSTM", "Net", "MyVMLSTM", "MyVMLSTMGroup",
            "Embed", "Linear", "LSTM", "Model", "DecodeGraph", "BeamGraph", "lm_beam_step", "beam_gather", "beam_backtrack", "nll_loss", "linear_nll", "lm_head_loss", "lm_head_distill_loss", "lm_head_objective_loss", "context_negatives", "embedding", "unit_gradient", "vmlmf_sequence", "dropout", "dropout_state", "dropout_advance", "lm_sample",
            "embedding_dropout", "DecodeControls", "HistoryControls", "BeamControls", "lm_score", "Truncation", "TokenAutomaton", "AutomatonControls",
            "AutomatonBeamControls", "GroupBeams", "ContrastControls", "ContrastGraph", "lm_contrast_step", "StochasticBeams", "StochasticBeamGraph",

@@ -167,6 +167,9 @@ SYMBOLS = {
     "vmlmf_adam_step_ex": (_i, [ctypes.POINTER(TensorList), _vp, _vp, _vp, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_sgd_clip_step": (_i, [ctypes.POINTER(TensorList), ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
+    "vmlmf_dyneval_accumulate": (_i, [ctypes.POINTER(TensorList), _vp, _vp]),
+    "vmlmf_dyneval_step": (_i, [ctypes.POINTER(TensorList), _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                ctypes.c_float, _vp, _vp, _vp]),
     "vmlmf_comm_unique_id": (_i, [_vp]),
     "vmlmf_comm_init": (_i, [ctypes.POINTER(_vp), _i, _i, _vp]),
     "vmlmf_comm_count": (_i, [_vp, ctypes.POINTER(_i)]),

@@ -286,6 +286,80 @@ __global__ __launch_bounds__(256) void sgd_clip_kernel(TensorList t, const float
   }
 }
 
+// ---- dynamic evaluation (Krause et al. 2018; docs/design/lm_dyneval.md): the statistics pass and the update step ----
+// ms[off + j] += g[j]^2 over every tensor of the list: the RMS statistics, collected once per trained model.
+__global__ __launch_bounds__(256) void dyneval_accumulate_kernel(TensorList t, float* __restrict__ ms) {
+  const int ti = blockIdx.y;
+  const long long n = t.n[ti];
+  const float* __restrict__ g = t.g[ti];
+  float* __restrict__ m = ms + t.off[ti];
+  long long done = 0;
+  if (((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m)) & 15) == 0) {
+    const long long n4 = n >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(m);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+      const float4 gv = g4[i];
+      float4 mv = m4[i];
+      mv.x = fmaf(gv.x, gv.x, mv.x), mv.y = fmaf(gv.y, gv.y, mv.y), mv.z = fmaf(gv.z, gv.z, mv.z), mv.w = fmaf(gv.w, gv.w, mv.w);
+      m4[i] = mv;
+    }
+    done = n4 << 2;
+  }
+  for (long long i = done + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    m[i] = fmaf(g[i], g[i], m[i]);
+}
+
+// One element of the update, the operation order the rounding bound of docs/design/lm_dyneval.md counts:
+//   ld = min(dm r, 1)   theta + ld (theta0 - theta) - s (g / (r + eps))       dm = decay / m, s = lr c (both once per thread)
+__device__ __forceinline__ float dyneval_element(float p, float p0, float r, float g, float dm, float s, float eps) {
+  const float ld = fminf(dm * r, 1.f);
+  return (p + ld * (p0 - p)) - s * (g / (r + eps));
+}
+
+// theta <- theta + ld (theta0 - theta) - lr c g / (r + eps), every tensor of the list in one launch; theta0 and r are flat buffers
+// addressed through the state offsets (which need not keep a tensor's 16-byte alignment: a tensor whose four streams are not all
+// aligned takes the scalar loop).  The gradients are only read - the clip coefficient goes into the step, not into them.
+__global__ __launch_bounds__(256) void dyneval_kernel(TensorList t, const float* __restrict__ theta0, const float* __restrict__ rms,
+                                                      const float* __restrict__ norm, float lr, float decay, float inv_mean_rms,
+                                                      float eps, float max_norm) {
+  // a non-finite norm: the step is skipped, `norm` tells the caller (sgd_clip_kernel's guard)
+  if (!isfinite(norm[0])) return;
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    coef = max_norm / (norm[0] + 1e-6f);
+    coef = coef < 1.f ? coef : 1.f;
+  }
+  const float s = lr * coef, dm = decay * inv_mean_rms;
+  const int ti = blockIdx.y;
+  const long long n = t.n[ti];
+  float* __restrict__ p = t.p[ti];
+  const float* __restrict__ g = t.g[ti];
+  const float* __restrict__ p0 = theta0 + t.off[ti];
+  const float* __restrict__ r = rms + t.off[ti];
+  long long done = 0;
+  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(p0) |
+        reinterpret_cast<uintptr_t>(r)) & 15) == 0) {
+    const long long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const float4* q4 = reinterpret_cast<const float4*>(p0);
+    const float4* r4 = reinterpret_cast<const float4*>(r);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+      const float4 gv = g4[i], qv = q4[i], rv = r4[i];
+      float4 pv = p4[i];
+      pv.x = dyneval_element(pv.x, qv.x, rv.x, gv.x, dm, s, eps);
+      pv.y = dyneval_element(pv.y, qv.y, rv.y, gv.y, dm, s, eps);
+      pv.z = dyneval_element(pv.z, qv.z, rv.z, gv.z, dm, s, eps);
+      pv.w = dyneval_element(pv.w, qv.w, rv.w, gv.w, dm, s, eps);
+      p4[i] = pv;
+    }
+    done = n4 << 2;
+  }
+  for (long long i = done + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    p[i] = dyneval_element(p[i], p0[i], r[i], g[i], dm, s, eps);
+}
+
 int fill(const vmlmf_tensor_list* in, TensorList* t, long long* maxn) {
   if (in == nullptr || in->count < 1 || in->count > VMLMF_MAX_TENSORS) return VMLMF_E_BADARG;
   *maxn = 0;
@@ -367,6 +441,37 @@ int vmlmf_sgd_clip_step(const vmlmf_tensor_list* tensors, float lr, float max_no
   hipLaunchKernelGGL(sqsum_kernel, dim3(nb, tensors->count), dim3(maxn >= (1LL << 20) ? 1024 : 256), 0, s, t, scratch);
   hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(nb * tensors->count), norm);
   hipLaunchKernelGGL(sgd_clip_kernel, dim3(blocks_for(maxn), tensors->count), dim3(256), 0, s, t, norm, lr, max_norm);
+  return (int)hipGetLastError();
+}
+
+int vmlmf_dyneval_accumulate(const vmlmf_tensor_list* tensors, float* ms, void* stream) {
+  TensorList t;
+  long long maxn = 0;
+  const int rc = fill(tensors, &t, &maxn);
+  if (rc != 0) return rc;
+  if (ms == nullptr) return VMLMF_E_BADARG;
+  for (int i = 0; i < tensors->count; ++i)
+    if (t.off[i] < 0) return VMLMF_E_BADARG;
+  hipLaunchKernelGGL(dyneval_accumulate_kernel, dim3(blocks_for(maxn), tensors->count), dim3(256), 0, (hipStream_t)stream, t, ms);
+  return (int)hipGetLastError();
+}
+
+int vmlmf_dyneval_step(const vmlmf_tensor_list* tensors, const float* theta0, const float* rms, float lr, float decay,
+                       float inv_mean_rms, float eps, float max_norm, float* norm, float* scratch, void* stream) {
+  TensorList t;
+  long long maxn = 0;
+  const int rc = fill(tensors, &t, &maxn);
+  if (rc != 0) return rc;
+  if (theta0 == nullptr || rms == nullptr || norm == nullptr || scratch == nullptr) return VMLMF_E_BADARG;
+  for (int i = 0; i < tensors->count; ++i)
+    if (t.off[i] < 0) return VMLMF_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned nb = blocks_for(maxn);
+  if (nb > 64) nb = 64;   // scratch holds VMLMF_MAX_TENSORS * 64 partial sums
+  hipLaunchKernelGGL(sqsum_kernel, dim3(nb, tensors->count), dim3(maxn >= (1LL << 20) ? 1024 : 256), 0, s, t, scratch);
+  hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(nb * tensors->count), norm);
+  hipLaunchKernelGGL(dyneval_kernel, dim3(blocks_for(maxn), tensors->count), dim3(256), 0, s, t, theta0, rms, norm, lr, decay,
+                     inv_mean_rms, eps, max_norm);
   return (int)hipGetLastError();
 }
 

@@ -1074,23 +1074,35 @@ class LmHeadLossFn(torch.autograd.Function):
     """loss = nll_loss(Linear(h), y) (vmlmf_lm.py:355-358 + lm_test.py:140-153) for training; see the block comment above."""
 
     @staticmethod
-    def forward(ctx, h, w, b, y):
-        return _head_loss_forward(ctx, h, w, b, y, lambda R: 1 + R, _nll_launch)[0]          # loss | rowloss
+    def forward(ctx, h, w, b, y, rows=False):
+        stats = _head_loss_forward(ctx, h, w, b, y, lambda R: 1 + R, _nll_launch)            # loss | rowloss
+        if not rows:
+            return stats[0]
+        rowloss = stats[1:]
+        ctx.mark_non_differentiable(rowloss)
+        return stats[0], rowloss
 
     @staticmethod
-    def backward(ctx, dloss):
-        return (*_head_loss_backward(ctx, dloss), None)
+    def backward(ctx, dloss, *_):
+        return (*_head_loss_backward(ctx, dloss), None, None)
 
 
-def lm_head_loss(h, weight, bias, y):
+def lm_head_loss(h, weight, bias, y, return_rows=False):
     """Training form of nll_loss(Linear(h), y): h (T, B, H), weight (V, H), bias (V), y (T, B) int64 -> scalar loss whose
     backward reads the scores' gradient where the forward left it.  Call loss.backward(vmlmf_amd.unit_gradient(device)) to spare
     the three scalings a foreign d(loss) tensor costs.  Vocabulary widths the in-register loss does not cover (not a multiple
-    of four, beyond 12288) and CPU tensors take projection + nll_loss."""
+    of four, beyond 12288) and CPU tensors take projection + nll_loss.
+    return_rows=True: (loss, rows) - rows (T B) fp32 is what each position is charged, logsumexp(z_r) - z_r[y_r], unscaled and not
+    differentiable: the row output the loss launch writes anyway (the stock path forms it in stock ops)."""
     V = weight.shape[0]
     if h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288:
-        return LmHeadLossFn.apply(h, weight, bias, y)
-    return nll_loss(torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t()), y)
+        return LmHeadLossFn.apply(h, weight, bias, y, True) if return_rows else LmHeadLossFn.apply(h, weight, bias, y)
+    scores = torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t())
+    if not return_rows:
+        return nll_loss(scores, y)
+    with torch.no_grad():
+        rows = scores.logsumexp(1) - scores.gather(1, y.reshape(-1, 1)).squeeze(1)
+    return nll_loss(scores, y), rows
 
 
 # ---- knowledge distillation at the LM head (C ABI vmlmf_distill_forward_grad; csrc/vmlmf_distill.hip; docs/design/lm_distill.md) ----
