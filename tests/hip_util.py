@@ -1,10 +1,16 @@
 """Helpers for the GPU parity tests: run the HIP path through the package's public entry point
 (vmlmf_amd.vmlmf_sequence -> ctypes -> C ABI) on oracle-style parameter dicts."""
+import os
+import sys
+
 import numpy as np
 import torch
 
 import vmlmf_oracle as O
 from vmlmf_amd import vmlmf_sequence
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import slice_rule  # noqa: E402
 
 ORDER = {
     O.V1: ["dia_x", "dia_h", "u_x", "v_x", "b_x", "b_h", "u_h", "v_h"],
@@ -107,7 +113,28 @@ def assert_grad(a, b, what, rel=GREL):
     assert err <= rel * scale + 1e-6, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
 
 
-def compare_all(got, ref, tag, skip=()):
+# the same rule slice by slice (tools/slice_rule.py, shared with tools/fuzz_parity.py; docs/design/slice_tolerances.md)
+TINY = slice_rule.TINY      # a slice whose reference stays below this is skipped: flush-to-zero of denormal products is no error
+slice_report, slice_cuts = slice_rule.slice_report, slice_rule.slice_cuts
+
+
+def assert_grad_slices(a, b, what, slices, rel=GREL):
+    """The gradient rule slice by slice: for every slice s of every cut in slices, max|a_s - b_s| <= rel * max|b_s|, with no absolute
+    floor.  A cut is an int or a tuple of ints - the axes to cut along - or a list of (label, index) blocks.  Slices whose reference lies
+    below TINY are skipped; their number is returned."""
+    return slice_rule.assert_grad_slices(a, b, what, slices, rel)
+
+
+def compare_slices(got, ref, tag, slices, rel=GREL):
+    """assert_grad_slices on every gradient of a layer's or a stack's result that got holds, by the cuts of slice_cuts.  slices: the
+    layout, a dict of variant, H (a list for a stack whose layers differ), g and time_major.  Returns {"skipped": slices below TINY,
+    "worst": (quantity and slice, share of the slice tolerance)}."""
+    return slice_rule.compare_slices(got, ref, tag, slices, rel)
+
+
+def compare_all(got, ref, tag, skip=(), slices=None):
+    """slices=None: the whole-tensor rules alone.  slices=dict(variant=, H=, g=, time_major=): additionally every gradient slice by slice
+    (compare_slices), whose report is returned."""
     problems = []
     for k in ("y", "hT", "cT"):
         if k in ref and k not in skip:
@@ -127,4 +154,10 @@ def compare_all(got, ref, tag, skip=()):
                 assert_grad(got["G"][k], ref["G"][k], f"{tag}.G.{k}")
             except AssertionError as e:
                 problems.append(str(e))
+    if slices is not None:
+        try:
+            report = compare_slices(got, ref, tag, slices)
+        except AssertionError as e:
+            problems.append(str(e))
     assert not problems, "\n".join(problems)
+    return report if slices is not None else None

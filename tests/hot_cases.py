@@ -101,7 +101,8 @@ def run_stack_literal(variant, Ps, x, h0, c0, dy, dhT, dcT, time_major=False, dt
             loss = loss + (hT * torch.tensor(dhT[l], dtype=dtype)).sum()
         if dcT is not None:
             loss = loss + (cT * torch.tensor(dcT[l], dtype=dtype)).sum()
-    loss = loss + (cur * torch.tensor(dy, dtype=dtype)).sum()
+    if dy is not None:
+        loss = loss + (cur * torch.tensor(dy, dtype=dtype)).sum()
     loss.backward()
     out = {"y": cur.detach().numpy(), "hT": [h.detach().numpy() for h in hs], "cT": [c.detach().numpy() for c in cs],
            "dx": xt.grad.numpy(), "G": [{k: Pt[l][k].grad.numpy() for k in ORDER[variant]} for l in range(L)]}

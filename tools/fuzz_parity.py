@@ -20,6 +20,7 @@ import numpy as np
 import torch
 import vmlmf_oracle as O
 from hip_util import run_hip, run_literal, compare_all, ORDER, ranks_of, assert_out, assert_grad
+from slice_rule import assert_grad_slices, compare_slices, slice_cuts
 from vmlmf_amd import functional as F
 
 import fuzz_draw as D
@@ -87,6 +88,16 @@ def draw_wide():
                     seed=int(rng.integers(0, 2**31)), scale=scale)
 
 
+def layout(c):
+    """seq, rb, wide: every gradient also slice by slice (tools/slice_rule.py::compare_slices; docs/design/slice_tolerances.md), which is what
+    checks the draws without dy - one in five - whose dx decays over the steps.  Not in the hot regime: with saturated gates a whole gate
+    block of a gradient can be rounding residue (sigmoid' = 0 in fp32), and the fp32 literal oracle itself then misses the slice rule - on 7
+    of the 40 draws of `40 21 seq hot` - so those draws keep the whole-tensor rule their redraw criterion is derived for."""
+    if HOT or MODE not in ("seq", "rb", "wide"):
+        return None
+    return dict(variant=c["v"], H=c["H"], g=2 if c["v"] in (O.V2, O.V4, O.V6) else 1, time_major=c["tm"])
+
+
 def run(c, vals=None):
     if vals is not None:              # hot: the values came with the draw (fuzz_draw.draw_hot)
         got = run_hip(c["v"], *vals, time_major=c["tm"])
@@ -110,6 +121,8 @@ def run(c, vals=None):
     got = run_hip(c["v"], P, x, h0, c0, dy, dhT, dcT, time_major=c["tm"])
     ref = run_literal(c["v"], P, x, h0, c0, dy, dhT, dcT, time_major=c["tm"])
     compare_all(got, ref, "fuzz")
+    if layout(c) is not None:         # what compare_all(..., slices=layout) adds, here straight from tools/slice_rule.py
+        compare_slices(got, ref, "fuzz", layout(c))
 
 
 class NotCovered(Exception):
@@ -168,12 +181,20 @@ def run_stack(c, vals=None):
     for l in range(L):
         assert_out(hTs[l].detach().cpu().numpy(), hr[l].detach().numpy(), f"stack.hT[{l}]")
     assert_grad(xt.grad.cpu().numpy(), xr.grad.numpy(), "stack.dx")
+    if vals is None:                  # slice by slice as well (not the hot draws: layout())
+        assert_grad_slices(xt.grad.cpu().numpy(), xr.grad.numpy(), "stack.dx", [0, 1])          # per time step and per row
     if st is not None:
         assert_grad(h0.grad.cpu().numpy(), h0r.grad.numpy(), "stack.dh0")
         assert_grad(c0.grad.cpu().numpy(), c0r.grad.numpy(), "stack.dc0")
+        if vals is None:
+            assert_grad_slices(h0.grad.cpu().numpy(), h0r.grad.numpy(), "stack.dh0", [(0, 1)])     # (L, B, H): per layer and row
+            assert_grad_slices(c0.grad.cpu().numpy(), c0r.grad.numpy(), "stack.dc0", [(0, 1)])
     for l in range(L):
         for k, p in zip(names, params[l]):
             assert_grad(p.grad.cpu().numpy(), Pt[l][k].grad.numpy(), f"stack.G[{l}].{k}")
+            cuts = None if vals is not None else slice_cuts(k, tuple(p.shape), v, Hs[l], g, c["tm"])
+            if cuts is not None:
+                assert_grad_slices(p.grad.cpu().numpy(), Pt[l][k].grad.numpy(), f"stack.G[{l}].{k}", cuts)
 
 
 ok = refused = failed = uncovered = redrawn = 0
