@@ -426,7 +426,7 @@ def test_a_failed_step_is_skipped_for_every_tensor_list_and_parameter_group():
         net, x, t = _har_net()
         _clear_status()
         extra = [torch.nn.Parameter(torch.randn(7, device="cuda")) for _ in range(60)]
-        other = [torch.nn.Parameter(torch.randn(40000 if big else 33, device="cuda"))]     # (> 32768 elements: the two-launch form)
+        other = [torch.nn.Parameter(torch.randn(2 ** 20 + 13 if big else 33, device="cuda"))]     # (> 2^20 elements: the two-launch form)
         opt = vmlmf_amd.optim.Adam([{"params": list(net.parameters()) + extra}, {"params": other, "lr": 0.02}], lr=0.01)
 
         def step():

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(256) void adam_gate_kernel(TensorList t, int count,
       for (int j = 0; j < 16; ++j) {
         const int tj = t0 + j < count ? t0 + j : t0;
         const long long n = t.n[tj];
-        v[j] = reinterpret_cast<const unsigned*>(t.g[tj])[i < n ? i : 0];     // clamped: a repeated element changes nothing
+        // clamped: a repeated element changes nothing.  An empty tensor has no element 0 to repeat: its pointer is not read
+        v[j] = n > 0 ? reinterpret_cast<const unsigned*>(t.g[tj])[i < n ? i : 0] : 0u;
       }
 #pragma unroll
       for (int j = 0; j < 16; ++j) bad |= ((v[j] & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;   // exponent all ones: Inf or NaN
