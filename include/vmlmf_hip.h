@@ -602,6 +602,42 @@ int vmlmf_adam_step_ex(const vmlmf_tensor_list *tensors, float *exp_avg, float *
 int vmlmf_dyneval_accumulate(const vmlmf_tensor_list *tensors, float *ms, void *stream);
 int vmlmf_dyneval_step(const vmlmf_tensor_list *tensors, const float *theta0, const float *rms, float lr, float decay,
                        float inv_mean_rms, float eps, float max_norm, float *norm, float *scratch, void *stream);
+/* NT-ASGD (Merity, Keskar, Socher 2018; docs/design/lm_asgd.md): the LM loop's clip + SGD with L2 weight decay and, once it is
+ * switched on, the running average of the iterates - torch.optim.ASGD with lambd = 0 behind clip_grad_norm_.  (ABI 13 still: a new
+ * symbol only.)  For the applied step k (1-based; counted on the device) and t0 the step count at which averaging was switched on:
+ *   c   = 1 if max_norm <= 0, else min(1, max_norm / (|g|_2 + 1e-6)) over every listed gradient (vmlmf_sgd_clip_step's coefficient)
+ *   g'  = c g                        stored into the gradient only when c < 1
+ *   p'  = p - lr (g' + weight_decay p)
+ *   n   = k - 1 - t0
+ *   ax' = ax (neither read nor written) while averaging is off;  p' (the same bits) when n <= 1;  ax + (p' - ax) (1 / n) when n >= 2
+ * `ax` is a flat device buffer, entry i owns [state_offset[i], state_offset[i] + numel[i]) as with Adam's moments; the offsets need
+ * not be multiples of four.  step_index is not read.  `state`: VMLMF_ASGD_WORDS int32 device words the caller keeps between steps:
+ *   [VMLMF_ASGD_STEP]  applied steps k (a fresh optimizer: 0); advanced by the call, never by a skipped one
+ *   [VMLMF_ASGD_T0]    t0; VMLMF_ASGD_T0_OFF (-1, any negative value) = averaging off.  The caller switches averaging on by copying
+ *                      word STEP into it (a device-to-device copy will do: a captured step goes on working across it)
+ *   [VMLMF_ASGD_COEF]  c of the last applied call (the bits of a float)
+ *   [VMLMF_ASGD_MU]    1 / n of the last applied call, 1 where n <= 1 or averaging was off (the bits of a float)
+ *   [VMLMF_ASGD_GO]    1 when the last call applied its step, 0 when it skipped it
+ *   [VMLMF_ASGD_MODE]  what the last applied call did with ax: VMLMF_ASGD_MODE_OFF / _COPY / _AVERAGE
+ *   the other words are reserved (zero)
+ * `norm` (device scalar) receives |g|_2 with vmlmf_sgd_clip_step's bits.  A norm that is not finite skips the step: parameters,
+ * gradients, ax and the step word keep their bits, word GO is 0 and `norm` says so.  With weight_decay == 0 and averaging off the
+ * parameters, gradients and norm have the bits vmlmf_sgd_clip_step leaves.  `scratch`: VMLMF_MAX_TENSORS * 64 floats.  Three
+ * launches on `stream` (sum of squares; one workgroup that finishes the norm and forms the step's scalars; the update), no host
+ * read: capturable.  VMLMF_E_BADARG for a null pointer, a count outside 1 .. VMLMF_MAX_TENSORS, a negative numel or state_offset. */
+#define VMLMF_ASGD_WORDS 8
+#define VMLMF_ASGD_STEP 0
+#define VMLMF_ASGD_T0 1
+#define VMLMF_ASGD_COEF 2
+#define VMLMF_ASGD_MU 3
+#define VMLMF_ASGD_GO 4
+#define VMLMF_ASGD_MODE 5
+#define VMLMF_ASGD_T0_OFF (-1)
+#define VMLMF_ASGD_MODE_OFF 0
+#define VMLMF_ASGD_MODE_COPY 1
+#define VMLMF_ASGD_MODE_AVERAGE 2
+int vmlmf_asgd_step(const vmlmf_tensor_list *tensors, float *ax, int32_t *state, float lr, float weight_decay,
+                    float max_norm, float *norm, float *scratch, void *stream);
 
 /*
  * Data-parallel gradient exchange (no reference line: the reference has no distributed

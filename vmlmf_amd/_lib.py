@@ -21,6 +21,8 @@ V1_CELL, V2_GROUP_CELL, V3_LM, V4_LM_GROUP, V5_LMF_CELL, V6_GROUP_NOVM = 1, 2, 3
 ABI_VERSION = 13
 GUARD_WORDS, GUARD_GO, GUARD_SKIPPED = 72, 64, 66
 ADAM_FIRST, ADAM_LAST = 1, 2
+ASGD_WORDS, ASGD_STEP, ASGD_T0, ASGD_COEF, ASGD_MU, ASGD_GO, ASGD_MODE = 8, 0, 1, 2, 3, 4, 5    # vmlmf_asgd_step's state block
+ASGD_T0_OFF, ASGD_MODE_OFF, ASGD_MODE_COPY, ASGD_MODE_AVERAGE = -1, 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 E_BADARG, E_SHAPE, E_UNSUPPORTED, E_WORKSPACE, E_COMM, E_PROTOCOL = -1, -2, -3, -4, -5, -6
@@ -170,6 +172,7 @@ SYMBOLS = {
     "vmlmf_dyneval_accumulate": (_i, [ctypes.POINTER(TensorList), _vp, _vp]),
     "vmlmf_dyneval_step": (_i, [ctypes.POINTER(TensorList), _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_float, _vp, _vp, _vp]),
+    "vmlmf_asgd_step": (_i, [ctypes.POINTER(TensorList), _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
     "vmlmf_comm_unique_id": (_i, [_vp]),
     "vmlmf_comm_init": (_i, [ctypes.POINTER(_vp), _i, _i, _vp]),
     "vmlmf_comm_count": (_i, [_vp, ctypes.POINTER(_i)]),

@@ -234,7 +234,9 @@ __global__ __launch_bounds__(1024) void sqsum_kernel(TensorList t, float* __rest
   if (threadIdx.x == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
-__global__ __launch_bounds__(256) void norm_kernel(const float* __restrict__ partial, int count, float* __restrict__ norm) {
+// the partials summed by one workgroup of 256 threads in a fixed order (thread 0 holds the sum): the one reduction behind every
+// norm of this file, so that they all have the same bits
+__device__ __forceinline__ float sum_partials(const float* __restrict__ partial, int count) {
   __shared__ float red[256];
   float s = 0.f;
   for (int i = threadIdx.x; i < count; i += 256) s += partial[i];
@@ -244,7 +246,12 @@ __global__ __launch_bounds__(256) void norm_kernel(const float* __restrict__ par
     if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
     __syncthreads();
   }
-  if (threadIdx.x == 0) norm[0] = sqrtf(red[0]);
+  return red[0];
+}
+
+__global__ __launch_bounds__(256) void norm_kernel(const float* __restrict__ partial, int count, float* __restrict__ norm) {
+  const float s = sum_partials(partial, count);
+  if (threadIdx.x == 0) norm[0] = sqrtf(s);
 }
 
 // clip_grad_norm_ semantics: clip_coef = max_norm / (norm + 1e-6), clamped to 1; the gradients are scaled in
@@ -361,6 +368,112 @@ __global__ __launch_bounds__(256) void dyneval_kernel(TensorList t, const float*
     p[i] = dyneval_element(p[i], p0[i], r[i], g[i], dm, s, eps);
 }
 
+// ---- NT-ASGD (Merity, Keskar, Socher 2018; docs/design/lm_asgd.md): clip, L2 decay, SGD and the running average in one step ----
+// The finishing launch of the norm: sum_partials in norm_kernel's order (the norm has vmlmf_sgd_clip_step's bits), and - once, for
+// every workgroup of the update launch to read - the verdict, the step count, the clip coefficient and the average's weight.  The
+// step word is advanced HERE: the update launch only reads the block.
+__global__ __launch_bounds__(256) void asgd_finish_kernel(const float* __restrict__ partial, int count, float* __restrict__ norm,
+                                                          int* __restrict__ state, float max_norm) {
+  const float s = sum_partials(partial, count);
+  if (threadIdx.x != 0) return;
+  const float nrm = sqrtf(s);
+  norm[0] = nrm;
+  // a non-finite norm: the step is skipped (sgd_clip_kernel's guard) - no word but GO changes, so the next good step lands on the
+  // n it would have had
+  if (!isfinite(nrm)) {
+    state[VMLMF_ASGD_GO] = 0;
+    return;
+  }
+  float coef = 1.f;
+  if (max_norm > 0.f) {
+    coef = max_norm / (nrm + 1e-6f);
+    coef = coef < 1.f ? coef : 1.f;
+  }
+  const int k = state[VMLMF_ASGD_STEP] + 1, t0 = state[VMLMF_ASGD_T0];
+  // torch.optim.ASGD's mu = 1 / max(1, step - t0) as the previous step left it: n = k - 1 - t0; n <= 1 copies
+  int mode = VMLMF_ASGD_MODE_OFF;
+  float mu = 1.f;
+  if (t0 >= 0) {
+    const int n = k - 1 - t0;
+    mode = n <= 1 ? VMLMF_ASGD_MODE_COPY : VMLMF_ASGD_MODE_AVERAGE;
+    if (n >= 2) mu = 1.f / (float)n;
+  }
+  state[VMLMF_ASGD_STEP] = k;
+  state[VMLMF_ASGD_COEF] = __float_as_int(coef);
+  state[VMLMF_ASGD_MU] = __float_as_int(mu);
+  state[VMLMF_ASGD_MODE] = mode;
+  state[VMLMF_ASGD_GO] = 1;
+}
+
+// One element, the operation order the rounding bound of docs/design/lm_asgd.md counts.  gc = g c is formed by the caller (it is
+// what goes back into the gradient).  weight_decay == 0: fma(0, p, gc) is gc, and the parameter takes sgd_clip_kernel's p - lr gc.
+__device__ __forceinline__ float asgd_param(float p, float gc, float lr, float wd) {
+  const float u = fmaf(wd, p, gc);
+  return p - lr * u;
+}
+__device__ __forceinline__ float asgd_average(float a, float p, float mu) { return a + (p - a) * mu; }
+
+// One tensor of the update under a mode known at compile time: the averaging-off loop is sgd_clip_kernel's loop with the decay FMA in
+// it, and ax appears in a loop only where it is used.  16-byte accesses where the streams the mode touches allow them, the scalar
+// loop otherwise and for the n % 4 tail.  (Three bodies inlined into ONE kernel, chosen by a branch that is uniform over the launch.)
+template <int MODE>
+__device__ __forceinline__ void asgd_tensor(float* __restrict__ p, float* __restrict__ g, float* __restrict__ ax, long long n,
+                                            float coef, float mu, float lr, float wd) {
+  const bool keep_g = coef == 1.f;
+  uintptr_t streams = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g);
+  if (MODE != VMLMF_ASGD_MODE_OFF) streams |= reinterpret_cast<uintptr_t>(ax);
+  long long done = 0;
+  if ((streams & 15) == 0) {
+    const long long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* a4 = reinterpret_cast<float4*>(ax);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+      float4 gv = g4[i], pv = p4[i], av = pv;
+      if (MODE == VMLMF_ASGD_MODE_AVERAGE) av = a4[i];
+      gv.x *= coef, gv.y *= coef, gv.z *= coef, gv.w *= coef;
+      if (!keep_g) g4[i] = gv;
+      pv.x = asgd_param(pv.x, gv.x, lr, wd), pv.y = asgd_param(pv.y, gv.y, lr, wd);
+      pv.z = asgd_param(pv.z, gv.z, lr, wd), pv.w = asgd_param(pv.w, gv.w, lr, wd);
+      p4[i] = pv;
+      if (MODE == VMLMF_ASGD_MODE_AVERAGE) {
+        av.x = asgd_average(av.x, pv.x, mu), av.y = asgd_average(av.y, pv.y, mu);
+        av.z = asgd_average(av.z, pv.z, mu), av.w = asgd_average(av.w, pv.w, mu);
+      } else {
+        av = pv;
+      }
+      if (MODE != VMLMF_ASGD_MODE_OFF) a4[i] = av;
+    }
+    done = n4 << 2;
+  }
+  for (long long i = done + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float gi = g[i] * coef;
+    if (!keep_g) g[i] = gi;
+    const float pi = asgd_param(p[i], gi, lr, wd);
+    p[i] = pi;
+    if (MODE == VMLMF_ASGD_MODE_COPY) ax[i] = pi;
+    if (MODE == VMLMF_ASGD_MODE_AVERAGE) ax[i] = asgd_average(ax[i], pi, mu);
+  }
+}
+
+// g <- c g (stored only when c < 1), p <- p - lr (g + wd p), ax <- p | ax + (p - ax) mu, every tensor of the list in one launch.
+// ax is a flat buffer addressed through the state offsets; while averaging is off it is neither loaded nor stored, and its alignment
+// does not count.  The mode is one word of the state block: the branch on it is uniform over the whole launch.
+__global__ __launch_bounds__(256) void asgd_kernel(TensorList t, float* __restrict__ axf, const int* __restrict__ state, float lr,
+                                                   float wd) {
+  if (state[VMLMF_ASGD_GO] == 0) return;
+  const float coef = __int_as_float(state[VMLMF_ASGD_COEF]), mu = __int_as_float(state[VMLMF_ASGD_MU]);
+  const int mode = state[VMLMF_ASGD_MODE];
+  const int ti = blockIdx.y;
+  const long long n = t.n[ti];
+  float* p = t.p[ti];
+  float* g = const_cast<float*>(t.g[ti]);
+  float* ax = axf + t.off[ti];
+  if (mode == VMLMF_ASGD_MODE_OFF) asgd_tensor<VMLMF_ASGD_MODE_OFF>(p, g, ax, n, coef, mu, lr, wd);
+  else if (mode == VMLMF_ASGD_MODE_COPY) asgd_tensor<VMLMF_ASGD_MODE_COPY>(p, g, ax, n, coef, mu, lr, wd);
+  else asgd_tensor<VMLMF_ASGD_MODE_AVERAGE>(p, g, ax, n, coef, mu, lr, wd);
+}
+
 int fill(const vmlmf_tensor_list* in, TensorList* t, long long* maxn) {
   if (in == nullptr || in->count < 1 || in->count > VMLMF_MAX_TENSORS) return VMLMF_E_BADARG;
   *maxn = 0;
@@ -473,6 +586,24 @@ int vmlmf_dyneval_step(const vmlmf_tensor_list* tensors, const float* theta0, co
   hipLaunchKernelGGL(norm_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(nb * tensors->count), norm);
   hipLaunchKernelGGL(dyneval_kernel, dim3(blocks_for(maxn), tensors->count), dim3(256), 0, s, t, theta0, rms, norm, lr, decay,
                      inv_mean_rms, eps, max_norm);
+  return (int)hipGetLastError();
+}
+
+int vmlmf_asgd_step(const vmlmf_tensor_list* tensors, float* ax, int32_t* state, float lr, float weight_decay, float max_norm,
+                    float* norm, float* scratch, void* stream) {
+  TensorList t;
+  long long maxn = 0;
+  const int rc = fill(tensors, &t, &maxn);
+  if (rc != 0) return rc;
+  if (ax == nullptr || state == nullptr || norm == nullptr || scratch == nullptr) return VMLMF_E_BADARG;
+  for (int i = 0; i < tensors->count; ++i)
+    if (t.off[i] < 0) return VMLMF_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned nb = blocks_for(maxn);
+  if (nb > 64) nb = 64;   // scratch holds VMLMF_MAX_TENSORS * 64 partial sums
+  hipLaunchKernelGGL(sqsum_kernel, dim3(nb, tensors->count), dim3(maxn >= (1LL << 20) ? 1024 : 256), 0, s, t, scratch);
+  hipLaunchKernelGGL(asgd_finish_kernel, dim3(1), dim3(256), 0, s, scratch, (int)(nb * tensors->count), norm, (int*)state, max_norm);
+  hipLaunchKernelGGL(asgd_kernel, dim3(blocks_for(maxn), tensors->count), dim3(256), 0, s, t, ax, (const int*)state, lr, weight_decay);
   return (int)hipGetLastError();
 }
 

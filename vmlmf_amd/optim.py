@@ -2,6 +2,9 @@
 
   Adam            drop-in for torch.optim.Adam(model.parameters(), lr=...)      V/src/train_test/train.py:47,65
   clip_sgd_step   clip_grad_norm_(params, max_norm) + `param -= lr * param.grad` V/src/train_test/lm_test.py:203-209
+  ASGD            NT-ASGD for the language model: clip_sgd_step with L2 weight decay and, once switched on, the average of the
+                  iterates (clip_grad_norm_ + torch.optim.ASGD(lambd=0)); asgd_step / asgd_step_stock underneath, the latter the
+                  one form here that also takes CPU tensors.  docs/design/lm_asgd.md
 
 The models are 10-20 small tensors: the stock optimizer costs ~2 ms of dispatcher time per step at the headline
 shape, ten times the forward + backward it follows.  Here one kernel walks every tensor (pointers travel in the
@@ -10,7 +13,9 @@ SURVEY.md section 8f ("next" row).  HIP tensors only; anything else raises (no C
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import math
 
 import torch
 
@@ -226,3 +231,242 @@ def clip_sgd_step(parameters, lr, max_norm):
                                                   scratch.data_ptr(), stream))
     _bump_versions(live)
     return norm
+
+
+# ---- NT-ASGD (Merity, Keskar, Socher, "Regularizing and Optimizing LSTM Language Models"; docs/design/lm_asgd.md) ----
+#   c   = 1 if max_norm <= 0 else min(1, max_norm / (|g|_2 + 1e-6))      |g|_2 over every gradient of the step (clip_sgd_step's)
+#   g'  = c g                         written back into the gradient when c < 1
+#   p'  = p - lr (g' + wd p)
+#   n   = k - 1 - t0                  k: this applied step (1-based, counted on the device), t0: the count at start_averaging()
+#   ax' = ax while averaging is off | p' (a copy) when n <= 1 | ax + (p' - ax) (1 / n) when n >= 2
+# torch.optim.ASGD(lambd=0, t0=t0, weight_decay=wd) behind clip_grad_norm_, its fp32 mu included.  A norm that is not finite skips
+# the step on the device: p, g, ax and the step count keep their bits and the returned norm says so.
+def _check_asgd_hyper(lr, weight_decay, max_norm):
+    for name, v in (("lr", lr), ("weight_decay", weight_decay), ("max_norm", max_norm)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"vmlmf_amd.optim.ASGD: {name} must be a finite number >= 0 (max_norm 0: no clipping), got {v!r}")
+
+
+def new_asgd_state(device):
+    """vmlmf_asgd_step's state block (include/vmlmf_hip.h) of a fresh optimizer: no step applied, averaging off."""
+    words = [0] * _lib.ASGD_WORDS
+    words[_lib.ASGD_T0] = _lib.ASGD_T0_OFF
+    return torch.tensor(words, dtype=torch.int32, device=device)
+
+
+def _check_asgd_lists(params, grads, ax, state, offsets):
+    if not 1 <= len(params) <= _lib.MAX_TENSORS:
+        raise ValueError(f"vmlmf_amd.optim.asgd_step: 1 .. {_lib.MAX_TENSORS} tensors per call (the norm spans all of them), got {len(params)}")
+    if len(params) != len(grads) or len(params) != len(offsets) or any(p.numel() != g.numel() for p, g in zip(params, grads)):
+        raise ValueError("vmlmf_amd.optim.asgd_step: one gradient of its parameter's size and one offset per parameter")
+    if ax.dtype != torch.float32 or ax.dim() != 1 or not ax.is_contiguous():
+        raise RuntimeError("vmlmf_amd.optim.asgd_step: ax is one flat dense float32 buffer")
+    if state.dtype != torch.int32 or state.dim() != 1 or state.numel() < _lib.ASGD_WORDS or not state.is_contiguous():
+        raise RuntimeError(f"vmlmf_amd.optim.asgd_step: the state block is {_lib.ASGD_WORDS} dense int32 words")
+    for o, p in zip(offsets, params):            # the kernel addresses ax through the offsets unchecked
+        if o < 0 or o + p.numel() > ax.numel():
+            raise ValueError(f"vmlmf_amd.optim.asgd_step: offset {o} + {p.numel()} elements lies outside a buffer of {ax.numel()}")
+
+
+@torch.no_grad()
+def asgd_step(params, grads, ax, state, offsets, *, lr, weight_decay=0.0, max_norm=0.0, norm=None):
+    """The rule above on params[i] and grads[i] (both written in place), the flat buffer ax (tensor i at offsets[i]) and the state
+    block (new_asgd_state): vmlmf_asgd_step's three launches, no host read, so it captures.  Returns |g|_2 before clipping as a
+    0-d device tensor (`norm` where given: a captured step writes the same one at every replay)."""
+    params, grads, offsets = list(params), list(grads), list(offsets)
+    _check_asgd_hyper(lr, weight_decay, max_norm)
+    _check_asgd_lists(params, grads, ax, state, offsets)
+    for p, g in zip(params, grads):
+        _check(p, g)
+        if not g.is_contiguous():
+            raise RuntimeError("vmlmf_amd.optim.asgd_step scales the gradients in place: they must be contiguous")
+    dev = params[0].device
+    if not (ax.is_cuda and state.is_cuda):
+        raise RuntimeError("vmlmf_amd.optim.asgd_step: ax and the state block live on the parameters' HIP device (CPU: asgd_step_stock)")
+    if norm is None:
+        norm = torch.empty((), device=dev, dtype=torch.float32)
+    tl = _tensor_lists(list(zip(params, grads)), offsets)[0]
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().vmlmf_asgd_step(ctypes.byref(tl), ax.data_ptr(), state.data_ptr(), float(lr), float(weight_decay),
+                                              float(max_norm), norm.data_ptr(), _Scratch.get(dev).data_ptr(), _lib.raw_stream(dev)))
+    _bump_versions(params)
+    return norm
+
+
+@torch.no_grad()
+def asgd_step_stock(params, grads, ax, state, offsets, *, lr, weight_decay=0.0, max_norm=0.0, norm=None):
+    """asgd_step in stock ops, on whatever device the tensors live on: what CPU tensors take and the benchmark's baseline.  Every
+    decision - the non-finite guard, the clip, off / copy / average - is a select on the device, so this form reads no value back
+    either (unlike the kernel it rewrites unchanged values with their own bits)."""
+    params, grads, offsets = list(params), list(grads), list(offsets)
+    _check_asgd_hyper(lr, weight_decay, max_norm)
+    _check_asgd_lists(params, grads, ax, state, offsets)
+    total = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in grads]))
+    ok = torch.isfinite(total)
+    c = torch.clamp(max_norm / (total + 1e-6), max=1.0) if max_norm > 0 else torch.ones_like(total)
+    k, t0 = state[_lib.ASGD_STEP] + 1, state[_lib.ASGD_T0]
+    n = k - 1 - t0
+    on, average = t0 >= 0, (t0 >= 0) & (n >= 2)
+    mu = torch.where(average, 1.0 / n.clamp(min=1).to(torch.float32), torch.ones_like(total))
+    for p, g, o in zip(params, grads, offsets):
+        a = ax[o:o + p.numel()].view_as(p)
+        gc = g.view_as(p) * c
+        pn = p - lr * (gc + weight_decay * p)
+        an = torch.where(average, a + (pn - a) * mu, pn)
+        g.copy_(torch.where(ok, gc, g.view_as(p)).view_as(g))       # (c == 1: the same bits)
+        a.copy_(torch.where(ok & on, an, a))
+        p.copy_(torch.where(ok, pn, p))
+    # the block's words as device tensors throughout (a Python number assigned into a device tensor is a host copy: not capturable)
+    scalars = torch.stack([c, mu]).to(torch.float32).view(torch.int32)
+    new, skipped = list(state.unbind()), list(state.unbind())
+    new[_lib.ASGD_STEP], new[_lib.ASGD_COEF], new[_lib.ASGD_MU] = k, scalars[0], scalars[1]
+    new[_lib.ASGD_GO] = torch.ones_like(k)
+    new[_lib.ASGD_MODE] = on.to(torch.int32) + average.to(torch.int32)         # ASGD_MODE_OFF / _COPY / _AVERAGE = 0 / 1 / 2
+    skipped[_lib.ASGD_GO] = torch.zeros_like(k)
+    state.copy_(torch.where(ok, torch.stack(new), torch.stack(skipped)))
+    if norm is None:
+        return total
+    norm.copy_(total)
+    return norm
+
+
+class ASGD(torch.optim.Optimizer):
+    """NT-ASGD for a language model (the rule above): SGD with gradient clipping and L2 weight decay that, once the validation metric
+    has stopped improving, also keeps the average of the iterates - the parameters that are evaluated and saved.
+
+        opt = vmlmf_amd.optim.ASGD(model.parameters(), lr=30.0, weight_decay=1.2e-6, max_norm=0.25, nonmono=5)
+        ... loss.backward(); opt.step() ...                      # one fused step: clip, decay, SGD, average (three launches)
+        with opt.averaged():                                     # the parameters hold the average in here (before averaging
+            val = validate(model)                                # has started: evaluate the plain model instead)
+        opt.observe(val)                                         # the non-monotone trigger; start_averaging() switches by hand
+
+    One parameter group; the gradient norm spans every tensor.  lr, weight_decay and max_norm are read from param_groups[0] at every
+    step.  ValueError, before any device work, for a negative or non-finite lr, weight_decay or max_norm, nonmono < 1, more than
+    _lib.MAX_TENSORS tensors, parameters that are not dense float32 on one device, or more than one group.  ax and the state block are
+    created here and never reallocated, and the step reads nothing back: a captured step goes on working across start_averaging()
+    and load_state_dict(), which write those device buffers (lr, weight_decay and max_norm are launch arguments: a captured step
+    keeps the values it was captured with).
+    HIP parameters take the fused launches, CPU parameters the stock ops (`stock = True` forces those on a HIP device)."""
+
+    def __init__(self, params, lr, weight_decay=0.0, max_norm=0.0, nonmono=5):
+        _check_asgd_hyper(lr, weight_decay, max_norm)
+        if isinstance(nonmono, bool) or not isinstance(nonmono, int) or nonmono < 1:
+            raise ValueError(f"vmlmf_amd.optim.ASGD: nonmono must be an integer >= 1, got {nonmono!r}")
+        params = list(params)
+        if any(not isinstance(p, torch.Tensor) for p in params):
+            raise ValueError("vmlmf_amd.optim.ASGD takes one group of parameter tensors (the norm spans all of them)")
+        if not 1 <= len(params) <= _lib.MAX_TENSORS:
+            raise ValueError(f"vmlmf_amd.optim.ASGD: 1 .. {_lib.MAX_TENSORS} parameter tensors (the gradient norm spans all of them), "
+                             f"got {len(params)}")
+        dev = params[0].device
+        if any(p.device != dev or p.dtype != torch.float32 or p.is_sparse or not p.is_contiguous() for p in params):
+            raise ValueError("vmlmf_amd.optim.ASGD: dense float32 parameters on one device")
+        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, max_norm=max_norm))
+        self.nonmono, self.history, self.averaging = nonmono, [], False
+        self.stock = dev.type != "cuda"
+        # every tensor's slice of ax starts on a 16-byte boundary: the update's wide accesses apply to all of them
+        self._params, self._offsets, total = params, [], 0
+        for p in params:
+            self._offsets.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        self.ax = torch.zeros(total, device=dev)
+        self._words = new_asgd_state(dev)
+        self.last_norm = torch.zeros((), device=dev)
+        if not self.stock:
+            _Scratch.get(dev)            # (allocated now, not inside somebody's graph capture)
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("vmlmf_amd.optim.ASGD has one parameter group: the norm, ax and the step count span all its tensors")
+        super().add_param_group(param_group)
+
+    def ax_views(self):
+        """The average of each parameter: views of the flat buffer, in the parameters' order and shapes."""
+        return [self.ax[o:o + p.numel()].view_as(p) for o, p in zip(self._offsets, self._params)]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        group = self.param_groups[0]
+        lr, wd, max_norm = group["lr"], group["weight_decay"], group["max_norm"]
+        _check_asgd_hyper(lr, wd, max_norm)
+        live = [i for i, p in enumerate(self._params) if p.grad is not None]       # parameters without a gradient are skipped
+        if not live:
+            return loss
+        params, grads = [self._params[i] for i in live], [self._params[i].grad for i in live]
+        for p, g in zip(params, grads):
+            if g.dtype != torch.float32 or g.device != p.device or g.is_sparse or not g.is_contiguous():
+                raise RuntimeError("vmlmf_amd.optim.ASGD scales the gradients in place: contiguous dense float32 on the parameters' device")
+        fn = asgd_step_stock if self.stock else asgd_step
+        fn(params, grads, self.ax, self._words, [self._offsets[i] for i in live], lr=lr, weight_decay=wd, max_norm=max_norm,
+           norm=self.last_norm)       # (asgd_step bumps the versions behind its raw-pointer writes; the stock ops bump their own)
+        return loss
+
+    def clip_step(self, parameters, lr, max_norm):
+        """LmDataParallel's update_fn: clip_sgd_step's signature.  Sets the two values and steps (`parameters` are the optimizer's own);
+        returns the norm."""
+        self.param_groups[0]["lr"], self.param_groups[0]["max_norm"] = lr, max_norm
+        self.step()
+        return self.last_norm
+
+    @torch.no_grad()
+    def start_averaging(self):
+        """From the next step on ax follows the parameters: t0 <- the device's step word (device to device, nothing is read back - a
+        captured step goes on working), ax <- the parameters."""
+        self._words[_lib.ASGD_T0:_lib.ASGD_T0 + 1].copy_(self._words[_lib.ASGD_STEP:_lib.ASGD_STEP + 1])
+        for a, p in zip(self.ax_views(), self._params):
+            a.copy_(p)
+        self.averaging = True
+
+    def observe(self, metric):
+        """The non-monotone trigger as AWD-LSTM writes it: call with each validation metric (lower is better).  Returns whether
+        averaging is on."""
+        if not self.averaging and len(self.history) > self.nonmono and metric > min(self.history[:-self.nonmono]):
+            self.start_averaging()
+        self.history.append(float(metric))
+        return self.averaging
+
+    @torch.no_grad()
+    def _exchange(self):
+        for a, p in zip(self.ax_views(), self._params):
+            held = p.detach().clone()
+            p.copy_(a)
+            a.copy_(held)
+        _bump_versions(self._params)
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Inside, the parameters hold ax and ax holds the parameters (an exchange: no third copy is kept); on the way out they are
+        exchanged back, bit for bit, whatever is raised.  Versions are bumped both ways.  RuntimeError before start_averaging()."""
+        if not self.averaging:
+            raise RuntimeError("vmlmf_amd.optim.ASGD.averaged: averaging has not started (start_averaging(), or observe())")
+        self._exchange()
+        try:
+            yield self
+        finally:
+            self._exchange()
+
+    def state_dict(self):
+        """ax per parameter, the step count, t0 (-1: off), the trigger's history and flag, the group's values (one host read)."""
+        words = self._words.tolist()
+        return {"ax": [a.clone() for a in self.ax_views()], "step": words[_lib.ASGD_STEP], "t0": words[_lib.ASGD_T0],
+                "history": list(self.history), "averaging": self.averaging, "nonmono": self.nonmono,
+                "param_groups": [{k: v for k, v in self.param_groups[0].items() if k != "params"}]}
+
+    @torch.no_grad()
+    def load_state_dict(self, d):
+        """Copies INTO the existing buffers (a captured graph sees the loaded state).  ValueError unless d is another ASGD's
+        state_dict() for parameters of the same shapes."""
+        if len(d["ax"]) != len(self._params) or any(tuple(t.shape) != tuple(p.shape) for t, p in zip(d["ax"], self._params)):
+            raise ValueError("vmlmf_amd.optim.ASGD.load_state_dict: 'ax' does not match the parameters' shapes")
+        for dst, src in zip(self.ax_views(), d["ax"]):
+            dst.copy_(src)
+        words = self._words.tolist()
+        words[_lib.ASGD_STEP], words[_lib.ASGD_T0] = int(d["step"]), int(d["t0"])
+        self._words.copy_(torch.tensor(words, dtype=torch.int32))
+        self.history, self.averaging, self.nonmono = [float(v) for v in d["history"]], bool(d["averaging"]), int(d["nonmono"])
+        for k, v in d["param_groups"][0].items():
+            self.param_groups[0][k] = v
