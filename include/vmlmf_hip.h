@@ -466,6 +466,33 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t *tokens, con
                                  size_t scratch_bytes, float p, const int64_t *state, int site, void *stream);
 int vmlmf_embed_backward(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, void *scratch,
                          size_t scratch_bytes, void *stream);
+/* Activation regularisation of the LM's top layer (AR / TAR of Merity, Keskar, Socher 2018: `alpha * dropped_h.pow(2).mean() +
+ * beta * (raw_h[1:] - raw_h[:-1]).pow(2).mean()`; docs/design/lm_actreg.md) with that site's dropout in the same pass.  (ABI 13
+ * still: new symbols only.)  raw (T, B, H) fp32, time-major; f the factors of (state, site, p) - vmlmf_dropout_factors(d, ...), d ==
+ * NULL: identity columns -, all ones at p == 0; yd = raw f; position (t, b) is valid, m[t,b] = 1, iff t < lengths[b] (lengths (B)
+ * int64 on the device, NULL: every position):
+ *   N_ar = H #{m[t,b]}   N_tar = H #{t + 1 < T, m[t,b] m[t+1,b]}      (formed on the device)
+ *   AR   = sum m yd^2 / max(N_ar, 1)       TAR = sum m[t] m[t+1] (raw[t+1] - raw[t])^2 / max(N_tar, 1)
+ *   stats[0] = ar stats[1] + tar stats[2]   stats[1] = batch_scale AR   stats[2] = batch_scale TAR   (a term of weight 0: not formed, 0)
+ *   stats[3] = 2 ar batch_scale / max(N_ar, 1)   stats[4] = 2 tar batch_scale / max(N_tar, 1)   stats[5], [6] = N_ar, N_tar as floats
+ * vmlmf_actreg_forward   ONE launch: reads raw once (and one row more per block of 4 time steps), writes yd (p > 0; at p == 0 yd is
+ *                        not written and may be NULL: it IS raw) and the VMLMF_ACTREG_STATS floats of `stats`.  The sums are taken
+ *                        in a fixed order - per thread, per workgroup, then by the workgroup that finishes last -, no float atomics:
+ *                        the same bits from run to run.  scratch: vmlmf_actreg_scratch_floats(T, B, H) floats; ticket: one zeroed
+ *                        int64 device word that every launch leaves zero (launches sharing it: one stream).
+ * vmlmf_actreg_backward  ONE launch: with g the gradient of yd and s = *dpenalty (NULL: 1) the gradient of stats[0],
+ *                          draw[t] = f (g + m[t] s stats[3] yd) + s stats[4] (m[t-1] m[t] (raw[t] - raw[t-1]) - m[t] m[t+1] (raw[t+1] - raw[t]))
+ *                        the factors regenerated; ar / tar only say which terms are on (as in the forward).  draw may not alias g.
+ * VMLMF_E_BADARG for T, B, H < 1, a null pointer, a negative or non-finite ar, tar or batch_scale, p outside [0, 1), a descriptor of
+ * another H; VMLMF_E_UNSUPPORTED for 2^32 positions and more. */
+#define VMLMF_ACTREG_STATS 8
+size_t vmlmf_actreg_scratch_floats(int T, int B, int H);
+int vmlmf_actreg_forward(int T, int B, int H, const float *raw, float *yd, const int64_t *lengths, float ar, float tar,
+                         float batch_scale, float p, const int64_t *state, int site, const vmlmf_desc *d, float *stats,
+                         float *scratch, int64_t *ticket, void *stream);
+int vmlmf_actreg_backward(int T, int B, int H, const float *raw, const float *g, float *draw, const int64_t *lengths, float ar,
+                          float tar, float p, const int64_t *state, int site, const vmlmf_desc *d, const float *stats,
+                          const float *dpenalty, void *stream);
 
 /* ---- decoding the LM: one launch per token (Model.generate in vmlmf_amd/lm.py; csrc/vmlmf_sample.hip) ----
  * vmlmf_lm_sample  the vocabulary projection of the top layer's output h (B, H) - scores[b][v] = bias[v] + sum_k h[b][k] weight[v][k],

@@ -27,6 +27,7 @@ DT_F32, DT_BF16 = 0, 1
 DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 E_BADARG, E_SHAPE, E_UNSUPPORTED, E_WORKSPACE, E_COMM, E_PROTOCOL = -1, -2, -3, -4, -5, -6
 SUM, AVG = 0, 1
+ACTREG_STATS = 8           # VMLMF_ACTREG_STATS: penalty, B AR, B TAR, the two gradient coefficients, N_ar, N_tar, 0
 SITE_SAMPLE = 0x53414D50   # VMLMF_SITE_SAMPLE: the token sampler's Philox site (vmlmf_lm_sample); dropout sites are 0 .. layers
 COMM_ID_BYTES = 128
 P2P_HANDLE_BYTES = 64
@@ -154,6 +155,11 @@ SYMBOLS = {
     "vmlmf_dropout_factors": (_i, [ctypes.POINTER(Desc), ctypes.c_int64, _i, ctypes.c_float, _vp, _i, _vp, _vp]),
     "vmlmf_embed_dropout_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_embed_dropout_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_actreg_scratch_floats": (_sz, [_i, _i, _i]),
+    "vmlmf_actreg_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i,
+                                  ctypes.POINTER(Desc), _vp, _vp, _vp, _vp]),
+    "vmlmf_actreg_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i,
+                                   ctypes.POINTER(Desc), _vp, _vp, _vp]),
     "vmlmf_lm_sample_workspace_bytes": (_sz, [_i, _i]),
     "vmlmf_lm_sample": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vmlmf_lm_choose": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -305,6 +305,25 @@ int launch_embed_bwd(int R, int H, int V, const long long* tokens, const float* 
 int launch_drop_advance(unsigned long long* state, unsigned long long* snap, hipStream_t s);
 int launch_drop_rows(int mode, long long R, int H, int V, const DropArgs& d, const DropCols& cm, const float* x, const long long* tokens, float* y,
                      hipStream_t s);
+// activation regularisation of the LM's top layer with that site's dropout in the same pass (vmlmf_dropout.hip; the contract:
+// include/vmlmf_hip.h, vmlmf_actreg_forward): one launch per direction
+struct ActRegArgs {
+  int T, B, H;
+  const float* raw;                       // (T, B, H)
+  const long long* lengths;               // (B) or NULL: every position valid
+  float ar, tar, batch_scale;             // a weight of 0: the term is neither read for nor formed
+  DropArgs d;                             // d.state == NULL: no dropout (p == 0); d.yd: the forward's dropped copy
+  DropCols cm;
+  float* stats;                           // VMLMF_ACTREG_STATS floats: forward writes, backward reads [3], [4]
+  unsigned long long* part;               // forward: a workgroup's two sums as one 8-byte word, actreg_workgroups(T, B, H) of them
+  unsigned long long* ticket;             // forward: zero between launches
+  const float* g;                         // backward: gradient of yd
+  const float* dpenalty;                  // backward: gradient of stats[0] or NULL (= 1)
+  float* draw;                            // backward: gradient of raw
+};
+long long actreg_workgroups(int T, int B, int H);
+int launch_actreg_fwd(const ActRegArgs& a, hipStream_t s);
+int launch_actreg_bwd(const ActRegArgs& a, hipStream_t s);
 // one decoded token of the LM: head + greedy / Gumbel-max choice + log-probability (+ the next input row), vmlmf_sample.hip
 struct LmSampleArgs {
   const float *h, *w, *bias, *embed;      // (B, H), (V, H), (V) or NULL, (V, H) or NULL

@@ -180,6 +180,55 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, con
   return hip_tail(rc);
 }
 
+// ---- activation regularisation of the LM's top layer (vmlmf_dropout.hip; docs/design/lm_actreg.md) ----
+size_t vmlmf_actreg_scratch_floats(int T, int B, int H) { return (T < 1 || B < 1 || H < 1) ? 0 : 2 * (size_t)actreg_workgroups(T, B, H); }
+
+// the arguments both directions share; the site's dropout is off (no state read) at p == 0
+static int actreg_args(int T, int B, int H, const float* raw, const int64_t* lengths, float ar, float tar, float p, const int64_t* state,
+                       int site, const vmlmf_desc* d, float* yd, ActRegArgs* a) {
+  memset(a, 0, sizeof(*a));
+  if (T < 1 || B < 1 || H < 1) return fail(VMLMF_E_BADARG, "actreg: T, B, H must be >= 1");
+  if (!(ar >= 0.f && ar < INFINITY && tar >= 0.f && tar < INFINITY)) return fail(VMLMF_E_BADARG, "actreg: ar and tar must be finite and >= 0");
+  if ((long long)T * B >= (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "actreg: 2^32 positions and more");
+  int rc = drop_args(p, p > 0.f ? state : nullptr, site, yd, &a->d);
+  if (rc != 0) return rc;
+  if (raw == nullptr || (p > 0.f && state == nullptr)) return fail(VMLMF_E_BADARG, "actreg: null pointer");
+  a->cm.Hg = H, a->cm.gstride = 0;
+  if (d != nullptr) {
+    VGeo g;
+    RbGeo q;
+    if ((rc = make_geo(d, &g, &q)) != 0) return rc;
+    if (g.H != H) return fail(VMLMF_E_BADARG, "actreg: H is not the layer's hidden size");
+    if (g.rb) a->cm.Hg = g.Hg, a->cm.gstride = 64 * g.W;
+  }
+  a->T = T, a->B = B, a->H = H, a->raw = raw, a->lengths = (const long long*)lengths, a->ar = ar, a->tar = tar;
+  return 0;
+}
+
+int vmlmf_actreg_forward(int T, int B, int H, const float* raw, float* yd, const int64_t* lengths, float ar, float tar, float batch_scale,
+                         float p, const int64_t* state, int site, const vmlmf_desc* d, float* stats, float* scratch, int64_t* ticket,
+                         void* stream) {
+  ActRegArgs a;
+  const int rc = actreg_args(T, B, H, raw, lengths, ar, tar, p, state, site, d, yd, &a);
+  if (rc != 0) return rc;
+  if (!(batch_scale >= 0.f && batch_scale < INFINITY)) return fail(VMLMF_E_BADARG, "actreg: batch_scale must be finite and >= 0");
+  if (!stats || !scratch || !ticket || (p > 0.f && !yd)) return fail(VMLMF_E_BADARG, "actreg: null pointer");
+  a.batch_scale = batch_scale, a.stats = stats;
+  a.part = reinterpret_cast<unsigned long long*>(scratch), a.ticket = reinterpret_cast<unsigned long long*>(ticket);
+  return hip_tail(launch_actreg_fwd(a, (hipStream_t)stream));
+}
+
+int vmlmf_actreg_backward(int T, int B, int H, const float* raw, const float* g, float* draw, const int64_t* lengths, float ar, float tar,
+                          float p, const int64_t* state, int site, const vmlmf_desc* d, const float* stats, const float* dpenalty,
+                          void* stream) {
+  ActRegArgs a;
+  const int rc = actreg_args(T, B, H, raw, lengths, ar, tar, p, state, site, d, nullptr, &a);
+  if (rc != 0) return rc;
+  if (!g || !draw || !stats || g == draw) return fail(VMLMF_E_BADARG, "actreg: null pointer, or draw aliases g");
+  a.stats = const_cast<float*>(stats), a.g = g, a.dpenalty = dpenalty, a.draw = draw;
+  return hip_tail(launch_actreg_bwd(a, (hipStream_t)stream));
+}
+
 // ---- decoding the LM (vmlmf_sample.hip) ----
 size_t vmlmf_lm_sample_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_workspace_bytes(B, V); }
 size_t vmlmf_lm_sample_filtered_workspace_bytes(int B, int V) { return (B < 1 || V < 1) ? 0 : lm_sample_filtered_workspace_bytes(B, V); }

@@ -1496,6 +1496,132 @@ def dropout_factors(rows, H, p, snap, site, layer_desc=None):
     return out
 
 
+# ---- activation regularisation of the LM's top layer (C ABI vmlmf_actreg_*; csrc/vmlmf_dropout.hip; docs/design/lm_actreg.md) ----
+# AR and TAR of AWD-LSTM (Merity, Keskar, Socher, "Regularizing and Optimizing LSTM Language Models"): with raw (T, B, H) the top
+# layer's output, f that site's dropout factors, yd = raw f and m[t,b] = (t < lengths[b]),
+#   AR = sum m yd^2 / max(N_ar, 1)   TAR = sum m[t] m[t+1] (raw[t+1] - raw[t])^2 / max(N_tar, 1)   penalty = B (ar AR + tar TAR)
+# N_ar = H #valid positions, N_tar = H #valid pairs of neighbouring steps.
+def check_actreg(ar, tar):
+    """ValueError for an ar or tar that is negative, not finite, a bool or no number."""
+    import math
+    for name, v in (("ar", ar), ("tar", tar)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"vmlmf_amd: {name} must be finite and >= 0, got {v!r}")
+
+
+def activation_regularizer_stock(raw, *, ar, tar, factors=None, lengths=None, batch_scale=None):
+    """activation_regularizer's rule in stock ops under autograd, the dropout factors of the site given as a tensor (None: all ones) -
+    the path of CPU tensors, of types other than fp32 and of Model.stock_dropout, the baseline tools/bench_actreg.py measures the
+    kernels against and the GPU tests' second opinion.  Returns (yd, penalty, (ar_part, tar_part)) as activation_regularizer does.
+    (torch's mean over no element is NaN; here a term without a valid element is 0: T == 1, or lengths that leave no pair.)"""
+    check_actreg(ar, tar)
+    T, B, H = raw.shape
+    check_lengths(lengths, B, "activation_regularizer_stock")
+    scale = float(B if batch_scale is None else batch_scale)
+    yd = raw if factors is None else raw * factors
+    zero = torch.zeros((), device=raw.device, dtype=raw.dtype)
+    live, n_ar, n_tar = None, float(max(T * B * H, 1)), float(max((T - 1) * B * H, 1))
+    if lengths is not None:
+        n = lengths.to(raw.device).clamp(0, T)
+        live = (torch.arange(T, device=raw.device)[:, None] < n[None, :])[:, :, None]
+        n_ar = (n.sum() * H).clamp(min=1).to(raw.dtype)
+        n_tar = ((n - 1).clamp(min=0).sum() * H).clamp(min=1).to(raw.dtype)
+    ar_part = tar_part = zero
+    if ar > 0:
+        sq = yd * yd
+        ar_part = scale * ((sq if live is None else torch.where(live, sq, zero)).sum() / n_ar)
+    if tar > 0 and T > 1:
+        d = raw[1:] - raw[:-1]
+        sq = d * d
+        tar_part = scale * ((sq if live is None else torch.where(live[1:] & live[:-1], sq, zero)).sum() / n_tar)
+    return yd, ar * ar_part + tar * tar_part, (ar_part.detach(), tar_part.detach())
+
+
+class ActRegFn(torch.autograd.Function):
+    """(yd, penalty, ar_part, tar_part) of activation_regularizer: vmlmf_actreg_forward, and vmlmf_actreg_backward for the gradient of
+    raw from those of yd and the penalty - one launch each, the factors regenerated, nothing kept but raw and eight floats."""
+
+    @staticmethod
+    def forward(ctx, raw, lengths, snap, ar, tar, p, site, layer_desc, batch_scale):
+        _require_hip(raw, "raw")
+        raw = raw.contiguous()
+        T, B, H = raw.shape
+        dev, lib = raw.device, _lib.lib()
+        yd = torch.empty_like(raw) if p > 0 else None
+        stats = torch.empty(_lib.ACTREG_STATS, device=dev, dtype=torch.float32)
+        scratch = _workspace(dev, 4 * lib.vmlmf_actreg_scratch_floats(T, B, H), "actreg")
+        ticket = _stream_ticket(dev, "actreg")
+        desc = None if layer_desc is None else ctypes.byref(layer_desc)
+        with _lib.on_device(dev):
+            _lib.check(lib.vmlmf_actreg_forward(T, B, H, _ptr(raw), _ptr(yd), _ptr(lengths), ar, tar, batch_scale, p, _ptr(snap), site, desc,
+                                                stats.data_ptr(), scratch.data_ptr(), ticket.data_ptr(), _lib.raw_stream(dev)))
+        ctx.save_for_backward(raw, stats, *(t for t in (lengths, snap) if t is not None))
+        ctx.has_lengths, ctx.args, ctx.layer_desc = lengths is not None, (ar, tar, p, site), layer_desc
+        parts = (stats[1], stats[2])
+        ctx.mark_non_differentiable(*parts)
+        return (raw.view_as(raw) if yd is None else yd, stats[0], *parts)      # (p == 0: yd IS raw, nothing was written)
+
+    @staticmethod
+    def backward(ctx, g, dpenalty, *_):
+        raw, stats, *rest = ctx.saved_tensors
+        lengths = rest.pop(0) if ctx.has_lengths else None
+        snap = rest.pop(0) if rest else None
+        ar, tar, p, site = ctx.args
+        T, B, H = raw.shape
+        g = g.contiguous()
+        draw = torch.empty_like(raw)
+        scaled = None if _is_unit(dpenalty) else dpenalty.to(torch.float32).contiguous()
+        desc = None if ctx.layer_desc is None else ctypes.byref(ctx.layer_desc)
+        with _lib.on_device(raw.device):
+            _lib.check(_lib.lib().vmlmf_actreg_backward(T, B, H, _ptr(raw), _ptr(g), _ptr(draw), _ptr(lengths), ar, tar, p, _ptr(snap), site, desc,
+                                                        stats.data_ptr(), _ptr(scaled), _lib.raw_stream(raw.device)))
+        return draw, None, None, None, None, None, None, None, None
+
+
+def activation_regularizer(raw, *, ar, tar, p=0.0, snap=None, site=0, lengths=None, layer_desc=None, batch_scale=None):
+    """AWD-LSTM's activation regularisation (AR, weight `ar`: its --alpha) and temporal activation regularisation (TAR, weight `tar`:
+    its --beta) of a recurrent layer's output raw (T, B, H), with the dropout behind that layer applied in the same pass.  With f the
+    factors of (snap, site, p) - 0 or 1 / (1 - p); all ones at p == 0 -, yd = raw f, and m[t,b] = 1 iff t < lengths[b] (lengths (B)
+    integers, Model.score's contract; None: every position):
+        AR = sum m yd^2 / max(N_ar, 1),  N_ar = H #{m[t,b]}          TAR = sum m[t] m[t+1] (raw[t+1] - raw[t])^2 / max(N_tar, 1),
+        N_tar = H #{t + 1 < T: m[t,b] m[t+1,b]}                      penalty = batch_scale (ar AR + tar TAR)
+    AR is taken on the dropped copy, TAR on the raw one, as AWD-LSTM's main.py takes them; batch_scale (default B) is the factor
+    Model.loss carries over the mean NLL.  At T == 1, or when the lengths leave no pair, TAR is 0 (torch's mean over no element would
+    be NaN).  Returns (yd, penalty, (ar_part, tar_part)): yd for the head - every position's, masked ones included; at p == 0 it is
+    raw itself -, the differentiable penalty, and batch_scale AR and batch_scale TAR, detached and not multiplied by their weights; a
+    term whose weight is 0 is not formed and reported as 0.
+    The factors are the ones dropout(raw, p, snap, site) applies - with layer_desc, the descriptor of a layer whose own launches
+    apply its dropout (vmlmf_dropout_fused), the ones that layer would have applied (dropout_factors(..., layer_desc)).
+    fp32 on a HIP device: ONE launch forward and ONE backward (vmlmf_actreg_forward / _backward): raw is read once per direction,
+    the sums are reduced in a fixed order (the same bits from run to run), the counts are formed on the device from lengths, no
+    value is read back - a step with it captures; an upstream gradient of the penalty other than unit_gradient()'s scales its share
+    inside the backward launch.  CPU tensors and other types take activation_regularizer_stock (with p > 0 on the CPU the factors
+    come from torch's generator: snap and site are not looked at).  ValueError, before any device work, for an ar or tar that is
+    negative, not finite or a bool, p outside [0, 1), p > 0 without a snapshot on a HIP device, a raw that is not (T, B, H) and
+    lengths that are not (B) integers."""
+    check_actreg(ar, tar)
+    if not (isinstance(raw, torch.Tensor) and raw.dim() == 3 and raw.numel() > 0 and raw.is_floating_point()):
+        raise ValueError("vmlmf_amd: activation_regularizer takes activations raw of shape (T, B, H)")
+    T, B, H = raw.shape
+    check_lengths(lengths, B, "activation_regularizer")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"vmlmf_amd: p must lie in [0, 1), got {p!r}")
+    if p > 0 and raw.is_cuda and not (isinstance(snap, torch.Tensor) and snap.is_cuda and snap.dtype == torch.int64 and snap.numel() == 2):
+        raise ValueError("vmlmf_amd: p > 0 takes the snapshot of dropout_advance()")
+    scale = float(B if batch_scale is None else batch_scale)
+    if raw.is_cuda and raw.dtype == torch.float32:
+        n = None if lengths is None else lengths.to(device=raw.device, dtype=torch.int64).contiguous()
+        yd, penalty, ar_part, tar_part = ActRegFn.apply(raw, n, snap if p > 0 else None, float(ar), float(tar), p, int(site), layer_desc, scale)
+        return yd, penalty, (ar_part, tar_part)
+    factors = None
+    if p > 0 and raw.is_cuda:
+        factors = dropout_factors(T * B, H, p, snap, site, layer_desc).view(T, B, H).to(raw.dtype)
+    elif p > 0:
+        factors = torch.nn.functional.dropout(torch.ones_like(raw), p, True)
+    return activation_regularizer_stock(raw, ar=ar, tar=tar, factors=factors, lengths=lengths, batch_scale=scale)
+
+
 class EmbedDropFn(torch.autograd.Function):
     """dropout(w[tokens]) of vmlmf_lm.py:434-435 as one gather launch; backward: EmbedFn's scatter-add with the factors regenerated
     on the fly."""

@@ -283,7 +283,7 @@ class Model(nn.Module):
         return scores, states
 
     def loss(self, x, y, states, *, lengths=None, label_smoothing=0.0, z_loss=0.0, unlikelihood=0.0, negatives=None, normalize="rows",
-             return_parts=False):
+             return_parts=False, ar=0.0, tar=0.0):
         """nll_loss(self(x, states)[0], y) of the training loop (lm_test.py:200-202) without ever handing out the scores: the
         projection's output is overwritten by its own gradient inside the loss (functional.lm_head_loss), which is what the two
         backward GEMMs read.  Returns (loss, states); same values as the two-call form.  With every keyword at its default this is
@@ -302,9 +302,27 @@ class Model(nn.Module):
           formed on the device ("tokens" without lengths is "rows").
         return_parts=True: loss is (loss, nll, smooth, z, unlikelihood), the parts detached, scaled like the loss and not by their
           weights - nll is what perplexity is computed from whatever regulariser is on.
+        ar, tar >= 0: AWD-LSTM's activation regularisation and temporal activation regularisation of the top layer's output (its
+          --alpha and --beta; Merity, Keskar, Socher; docs/design/lm_actreg.md).  With raw (T, B, H) that output, yd its dropped
+          copy (the one the head reads) and m[t,b] = (t < lengths[b]),
+            loss += B (ar AR + tar TAR),  AR = sum m yd^2 / max(H #valid positions, 1),
+                                          TAR = sum m[t] m[t+1] (raw[t+1] - raw[t])^2 / max(H #valid pairs, 1)
+          - B times AWD-LSTM's terms, as this loss is B times the mean NLL, under both normalize settings; TAR is 0 at T == 1 or
+          without a valid pair (torch's mean over no element would be NaN).  With one of them on the top layer runs without its
+          own dropout and functional.activation_regularizer applies that site's dropout itself, with the factors the layer would
+          have drawn - one launch forward, one backward; the head then runs as above on yd, so with the same dropout_state the nll
+          part has the bits of the plain call.  A stack the library does not run with its top layer's dropout off takes the
+          per-layer loop.  return_parts is then (loss, nll, smooth, z, unlikelihood, ar, tar): the two new parts are B AR and
+          B TAR, detached, not multiplied by their weights, zero (and not formed) where the weight is.  With both at 0 the call
+          is what it is without them, launch for launch.
         ValueError, before any device work, for eps outside [0, 1), a negative or non-finite zeta or alpha, another normalize,
-        lengths that are not (B) integers, and negatives of the wrong type, shape or K.  No value is read back from the device."""
-        from .functional import lm_head_loss
+        lengths that are not (B) integers, negatives of the wrong type, shape or K, and an ar or tar that is negative, not finite
+        or a bool.  No value is read back from the device."""
+        from .functional import check_actreg, lm_head_loss
+        check_actreg(ar, tar)
+        if ar > 0 or tar > 0:
+            return self._regularized_loss(x, y, states, lengths, label_smoothing, z_loss, unlikelihood, negatives, normalize, return_parts,
+                                          ar, tar)
         if (lengths is None and negatives is None and not return_parts and normalize == "rows"
                 and label_smoothing == 0.0 and z_loss == 0.0 and unlikelihood == 0.0
                 and not any(isinstance(v, bool) for v in (label_smoothing, z_loss, unlikelihood))):
@@ -372,29 +390,81 @@ class Model(nn.Module):
         loss = lm_head_distill_loss(h, self.fc.w, self.fc.b, y, teacher, alpha=alpha, temperature=temperature, return_parts=return_parts)
         return (loss, states, teacher_states) if module else (loss, states)
 
+    def _regularized_loss(self, x, y, states, lengths, label_smoothing, z_loss, unlikelihood, negatives, normalize, return_parts, ar, tar):
+        """loss() with ar or tar on: the top layer's raw output, functional.activation_regularizer with that site's dropout, the head
+        on the dropped copy."""
+        from .functional import (activation_regularizer, activation_regularizer_stock, check_lengths, check_objective, context_negatives,
+                                 lm_head_loss, lm_head_objective_loss, objective_negatives)
+        check_objective(label_smoothing, z_loss, unlikelihood, normalize)
+        check_lengths(lengths, x.size(1), "Model.loss")
+        if unlikelihood > 0:
+            negatives = objective_negatives(context_negatives(x) if negatives is None else negatives, x.numel())
+        raw, states, site = self._features(x, states, raw_top=True)
+        B = x.size(1)
+        if site is None or len(site) == 4:       # no dropout at that site / the package's, inside the regulariser's launches
+            p, snap, index, desc = site or (0.0, None, 0, None)
+            h, penalty, parts = activation_regularizer(raw, ar=ar, tar=tar, p=p, snap=snap, site=index, lengths=lengths, layer_desc=desc,
+                                                       batch_scale=B)
+        else:                                    # nn.Dropout's factors (CPU tensors, stock_dropout): the rule in stock ops
+            factors = torch.nn.functional.dropout(torch.ones_like(raw), site[0], True)
+            h, penalty, parts = activation_regularizer_stock(raw, ar=ar, tar=tar, factors=factors, lengths=lengths, batch_scale=B)
+        plain = (lengths is None and negatives is None and not return_parts and normalize == "rows" and label_smoothing == 0.0
+                 and z_loss == 0.0 and unlikelihood == 0.0)
+        if plain:
+            return lm_head_loss(h, self.fc.w, self.fc.b, y) + penalty, states
+        head = lm_head_objective_loss(h, self.fc.w, self.fc.b, y, lengths=lengths, label_smoothing=label_smoothing, z_loss=z_loss,
+                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts)
+        if not return_parts:
+            return head + penalty, states
+        return (head[0] + penalty, *head[1:], *parts), states
+
     def features(self, x, states):
         """Everything of forward() in front of the vocabulary projection (vmlmf_lm.py:434-439): (T, B, H) activations, states.
         Training with p > 0 on a HIP device: the three dropouts run without mask tensors (functional.dropout_*: Philox factors
         regenerated in the backward) - the embedding's inside its gather, a VMLMF layer's inside the layer's launches; with
         self.stock_dropout = True they are nn.Dropout's launches as in the reference."""
+        return self._features(x, states)[:2]
+
+    def _top_layer_desc(self, T, B):
+        """The descriptor of the top layer where its own launches would apply its dropout (vmlmf_dropout_fused: the column map of
+        its factors is then the kernels'), else None (identity columns)."""
+        rnn = self.rnns[-1]
+        if not isinstance(rnn, (MyVMLSTM, MyVMLSTMGroup)):
+            return None
+        import ctypes
+        ur = list(rnn.u_ranks) if isinstance(rnn.u_ranks, (list, tuple)) else [rnn.u_ranks]
+        desc = _lib.make_desc(rnn.variant, B, T, rnn.input_size, rnn.hidden_size, rnn.w_rank, ur, g=getattr(rnn, "g", 1), time_major=True,
+                              training=True)
+        return desc if _lib.lib().vmlmf_dropout_fused(ctypes.byref(desc)) == 1 else None
+
+    def _features(self, x, states, raw_top=False):
+        """features(), written once.  raw_top=True (loss() under ar / tar): the top layer runs without the dropout behind it and a
+        third element says what the caller applies in its place: None (eval mode, p == 0), (p, snapshot, site, layer descriptor or
+        None) for functional.activation_regularizer, or (p,) where the dropouts are nn.Dropout's."""
         p = self.dropout.p
+        last = len(self.rnns) - 1
         if self.training and p > 0 and x.is_cuda and not getattr(self, "stock_dropout", False):
             from .functional import dropout, dropout_advance, embedding_dropout
             snap = dropout_advance(self.dropout_state())
+            T, B = x.shape
             x = embedding_dropout(self.embed.w, x, p, snap, 0)
-            stacked = self._stack(x, states, drops=[(p, snap, i + 1) for i in range(len(self.rnns))])
+            site = (p, snap, last + 1, self._top_layer_desc(T, B)) if raw_top else None
+            drops = [None if (raw_top and i == last) else (p, snap, i + 1) for i in range(len(self.rnns))]
+            stacked = self._stack(x, states, drops=drops)
             if stacked is not None:       # every layer in one launch per direction, the dropouts behind them inside it
                 x, new_states = stacked
                 for i, st in enumerate(new_states):
                     states[i] = st
-                return x, states
+                return x, states, site
             for i, rnn in enumerate(self.rnns):
                 if isinstance(rnn, (MyVMLSTM, MyVMLSTMGroup)):
-                    x, states[i] = rnn(x, states[i], drop=(p, snap, i + 1))
+                    x, states[i] = rnn(x, states[i], drop=drops[i])
                 else:
                     x, states[i] = rnn(x, states[i])
-                    x = dropout(x, p, snap, i + 1)
-            return x, states
+                    if drops[i] is not None:
+                        x = dropout(x, p, snap, i + 1)
+            return x, states, site
+        site = (p,) if (raw_top and self.training and p > 0) else None
         x = self.embed(x)
         x = self.dropout(x)
         stacked = self._stack(x, states)
@@ -402,12 +472,14 @@ class Model(nn.Module):
             x, new_states = stacked
             for i, st in enumerate(new_states):
                 states[i] = st
-            x = self.dropout(x)
+            if not raw_top:
+                x = self.dropout(x)
         else:
             for i, rnn in enumerate(self.rnns):
                 x, states[i] = rnn(x, states[i])
-                x = self.dropout(x)
-        return x, states
+                if not (raw_top and i == last):
+                    x = self.dropout(x)
+        return x, states, site
 
     def dropout_state(self, seed=None):
         """{seed, offset} of this model's dropout generator on its device (created on first use; seed=None draws it from torch's CPU
