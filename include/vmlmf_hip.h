@@ -466,6 +466,30 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t *tokens, con
                                  size_t scratch_bytes, float p, const int64_t *state, int site, void *stream);
 int vmlmf_embed_backward(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, void *scratch,
                          size_t scratch_bytes, void *stream);
+/* The table that is embedding AND vocabulary projection (weight tying: Press & Wolf; Inan et al.; AWD-LSTM's --tied), and
+ * AWD-LSTM's embedding (word-level) dropout, --dropoute (docs/design/lm_tied.md).  (ABI 13 still: new symbols only.)
+ *   f[r][n]  the element factor the entries above draw: counter (r, n >> 2, site, offset low word); all ones at p == 0, and then no
+ *            generator call is made.
+ *   fw[v]    the word factor, one per vocabulary row: word 0 of the call with counter (v, 0, VMLMF_SITE_WORD, offset low word) under
+ *            the same key; 0 iff word < round(word_p 2^32), else 1 / (1 - word_p).  At word_p == 0 neither a call nor a
+ *            multiplication is made.  state (two int64, a vmlmf_dropout_advance snapshot) may be NULL when p == word_p == 0.
+ * vmlmf_embed_dropout_forward_ex  out[r][n] = (weight[tokens[r]][n] * fw[tokens[r]]) * f[r][n]: two single-rounded multiplications
+ *            in that order; a dropped word's row is written as zeros without reading the table.
+ * vmlmf_embed_backward_ex  with s[v] the sum of dy[p] f[p] over the positions p with tokens[p] == v in ascending order (the sum of
+ *            the entries above, to the bit) and c[v] = fw[v] s[v] (one rounded multiplication, none at word_p == 0):
+ *              accumulate == 0: dweight[v] = c[v]; rows no token selects and rows of a dropped word are written as zeros - the call
+ *                               fills all of dweight (at word_p == 0: the bits of vmlmf_embed_backward / _embed_dropout_backward)
+ *              accumulate == 1: dweight[v] = dweight[v] + c[v] (one rounded addition) on the rows that are selected and whose word is
+ *                               kept; every other row is NEITHER READ NOR WRITTEN - the tied table's gradient is the head's dW with
+ *                               at most R rows touched.
+ *            scratch: vmlmf_embed_backward_scratch_bytes(R, V).  H <= 1024.  No float atomics; two runs give the same bits.
+ * Accesses choose 16, 8 or 4 bytes per address: any 4-byte aligned dy, weight, out and dweight are taken.
+ */
+#define VMLMF_SITE_WORD 0x574F5244 /* "WORD": the word factors' Philox site, apart from 0 .. layers and VMLMF_SITE_SAMPLE */
+int vmlmf_embed_dropout_forward_ex(int R, int H, int V, const int64_t *tokens, const float *weight, float *out, float p, float word_p,
+                                   const int64_t *state, int site, void *stream);
+int vmlmf_embed_backward_ex(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, int accumulate, void *scratch,
+                            size_t scratch_bytes, float p, float word_p, const int64_t *state, int site, void *stream);
 /* Activation regularisation of the LM's top layer (AR / TAR of Merity, Keskar, Socher 2018: `alpha * dropped_h.pow(2).mean() +
  * beta * (raw_h[1:] - raw_h[:-1]).pow(2).mean()`; docs/design/lm_actreg.md) with that site's dropout in the same pass.  (ABI 13
  * still: new symbols only.)  raw (T, B, H) fp32, time-major; f the factors of (state, site, p) - vmlmf_dropout_factors(d, ...), d ==

@@ -155,6 +155,8 @@ SYMBOLS = {
     "vmlmf_dropout_factors": (_i, [ctypes.POINTER(Desc), ctypes.c_int64, _i, ctypes.c_float, _vp, _i, _vp, _vp]),
     "vmlmf_embed_dropout_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_embed_dropout_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_embed_dropout_forward_ex": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_embed_backward_ex": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_actreg_scratch_floats": (_sz, [_i, _i, _i]),
     "vmlmf_actreg_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i,
                                   ctypes.POINTER(Desc), _vp, _vp, _vp, _vp]),

@@ -55,6 +55,53 @@ __device__ __forceinline__ void drop_factors(const DropKey& k, const unsigned th
   for (int i = 0; i < 4; ++i) f[i] = w[i] < thresh ? 0.f : scale;
 }
 
+// four neighbouring columns of a row: one 16-byte access where the address allows it, two 8-byte ones where it is 8 bytes off (H =
+// 650: every second position), by element for a row's tail or an odd width; columns behind the row read as zero
+__device__ __forceinline__ void load_quad(const float* __restrict__ p, const int valid, float (&v)[4]) {
+  const uintptr_t at = reinterpret_cast<uintptr_t>(p);
+  if (valid == 4 && (at & 15) == 0) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+  } else if (valid == 4 && (at & 7) == 0) {
+    const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
+    v[0] = lo.x, v[1] = lo.y, v[2] = hi.x, v[3] = hi.y;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = e < valid ? p[e] : 0.f;
+  }
+}
+__device__ __forceinline__ void store_quad(float* __restrict__ p, const int valid, const float (&v)[4]) {
+  const uintptr_t at = reinterpret_cast<uintptr_t>(p);
+  if (valid == 4 && (at & 15) == 0) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else if (valid == 4 && (at & 7) == 0) {
+    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    *reinterpret_cast<float2*>(p + 2) = make_float2(v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < valid) p[e] = v[e];
+  }
+}
+
+// Word (embedding-row) dropout of the tied / AWD-LSTM table (docs/design/lm_tied.md): ONE factor per vocabulary row v, shared by
+// every position that holds the word - word 0 of the call with counter (v, 0, DROP_SITE_WORD, offset low word) under the forward's
+// key; 0 iff word < thresh, else scale.  Kept out of line: its callers hold a generator call of their own already, and the library
+// is held to a size.
+constexpr unsigned DROP_SITE_WORD = 0x574F5244u;   // "WORD" (include/vmlmf_hip.h: VMLMF_SITE_WORD)
+static __device__ __noinline__ float word_factor(const unsigned long long* state, const unsigned thresh, const float scale, const unsigned v) {
+  const unsigned long long seed = state[0], off = state[1];
+  unsigned w[4];
+  philox4x32_10(v, 0u, DROP_SITE_WORD, (unsigned)off, (unsigned)seed, (unsigned)(seed >> 32) + (unsigned)(off >> 32), w);
+  return w[0] < thresh ? 0.f : scale;
+}
+// what the _ex embedding entries take beside the element dropout's DropArgs (d.state is also the word factors' state)
+struct WordDrop {
+  unsigned thresh;   // the word is dropped iff its generator word < thresh
+  float scale;       // 1 / (1 - word_p)
+  int drop, word;    // element dropout on (p > 0) / word dropout on (word_p > 0): uniform branches of one kernel
+};
+
 // host side of DropArgs: p in [0, 1)
 inline unsigned drop_thresh(float p) {
   const double t = (double)p * 4294967296.0 + 0.5;

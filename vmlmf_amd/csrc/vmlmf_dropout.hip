@@ -67,6 +67,40 @@ __global__ void __launch_bounds__(256) drop_rows_kernel(long long R, int H, int 
   }
 }
 
+// The gather under word dropout (vmlmf_embed_dropout_forward_ex; docs/design/lm_tied.md): out[r] = (w[tok_r] * fw[tok_r]) * f[r] -
+// AWD-LSTM's masked table, then the input dropout: two single-rounded multiplications in that order, each skipped where its
+// probability is 0 (uniform branches of the one instantiation).  A thread owns four columns of a position as above; a dropped
+// word's quad is written as zeros without reading the table.  Accesses choose their width per address.
+__global__ void __launch_bounds__(256) embed_fwd_ex_kernel(int R, int H, int V, DropArgs d, WordDrop wd, const float* __restrict__ w,
+                                                           const long long* __restrict__ tokens, float* __restrict__ y) {
+  const int quads = (H + 3) >> 2;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)R * quads) return;
+  const int r = (int)(i / quads);
+  const int n0 = (int)(i - (long long)r * quads) * 4;
+  const int valid = H - n0 < 4 ? H - n0 : 4;
+  long long t = tokens[r];
+  t = t < 0 ? 0 : (t >= V ? V - 1 : t);   // (as drop_rows_kernel: a valid row for a token the stock gather faults on)
+  float* dst = y + (size_t)r * H + n0;
+  float x[4] = {0.f, 0.f, 0.f, 0.f};
+  float fw = 1.f;
+  if (wd.word) fw = word_factor(d.state, wd.thresh, wd.scale, (unsigned)t);
+  if (fw != 0.f) {
+    load_quad(w + (size_t)t * H + n0, valid, x);
+    if (wd.word) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = __fmul_rn(x[e], fw);
+    }
+    if (wd.drop) {
+      float f[4];
+      drop_factors(drop_key(d), d.thresh, d.scale, (unsigned)r, (unsigned)(n0 >> 2), f);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[e] = __fmul_rn(x[e], f[e]);
+    }
+  }
+  store_quad(dst, valid, x);
+}
+
 // ---- activation regularisation of the top layer (AR / TAR; include/vmlmf_hip.h: vmlmf_actreg_forward; docs/design/lm_actreg.md) ----
 // A thread owns four neighbouring columns of one batch row and walks AR_TC time steps with them: grid (ceil(B quads / 256), ceil(T /
 // AR_TC)).  It loads its AR_TC rows and the halo a difference over time needs (forward: the row behind the block; backward: the rows on
@@ -78,34 +112,6 @@ __global__ void __launch_bounds__(256) drop_rows_kernel(long long R, int H, int 
 // in the order docs/design/lm_actreg.md counts; tests/actreg_cases.py restates both kernels in numpy's float32.
 constexpr int AR_TC = 4;
 
-// four neighbouring columns of a row: one 16-byte access where the address allows it, two 8-byte ones where it is 8 bytes off (H =
-// 650: every second position), by element for a row's tail or an odd width; columns behind the row read as zero
-__device__ __forceinline__ void load_quad(const float* __restrict__ p, const int valid, float (&v)[4]) {
-  const uintptr_t at = reinterpret_cast<uintptr_t>(p);
-  if (valid == 4 && (at & 15) == 0) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else if (valid == 4 && (at & 7) == 0) {
-    const float2 lo = *reinterpret_cast<const float2*>(p), hi = *reinterpret_cast<const float2*>(p + 2);
-    v[0] = lo.x, v[1] = lo.y, v[2] = hi.x, v[3] = hi.y;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = e < valid ? p[e] : 0.f;
-  }
-}
-__device__ __forceinline__ void store_quad(float* __restrict__ p, const int valid, const float (&v)[4]) {
-  const uintptr_t at = reinterpret_cast<uintptr_t>(p);
-  if (valid == 4 && (at & 15) == 0) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else if (valid == 4 && (at & 7) == 0) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    *reinterpret_cast<float2*>(p + 2) = make_float2(v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (e < valid) p[e] = v[e];
-  }
-}
 // the factor of one column on a layer's map (group layers: a call per column; kept out of line, the library is held to a size)
 __device__ __noinline__ float mapped_factor(const DropKey k, const unsigned thresh, const float scale, const DropCols cm, const unsigned r, const int n) {
   const int col = (n / cm.Hg) * cm.gstride + n % cm.Hg;
@@ -339,5 +345,13 @@ int launch_drop_rows(int mode, long long R, int H, int V, const DropArgs& d, con
   if (mode == 0) hipLaunchKernelGGL(drop_rows_kernel<0>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
   else if (mode == 1) hipLaunchKernelGGL(drop_rows_kernel<1>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
   else hipLaunchKernelGGL(drop_rows_kernel<2>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
+  return (int)hipGetLastError();
+}
+
+int launch_embed_fwd_ex(int R, int H, int V, const DropArgs& d, const WordDrop& wd, const float* w, const long long* tokens, float* y,
+                        hipStream_t s) {
+  const long long n = (long long)R * ((H + 3) / 4);
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(embed_fwd_ex_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, R, H, V, d, wd, w, tokens, y);
   return (int)hipGetLastError();
 }

@@ -123,7 +123,110 @@ __global__ __launch_bounds__(256) void embed_bwd_drop_kernel(int R, int H, int V
   }
 }
 
+// The gradient of a table that is ALSO the vocabulary projection, and of a table under word dropout (vmlmf_embed_backward_ex;
+// docs/design/lm_tied.md).  The same bit-row walk, a lane owning four neighbouring columns per round as above; ONE instantiation -
+// element dropout, word dropout and accumulate are uniform branches (the library is held to a size).  With s the position-ordered
+// sum of dy[p] f[p] (the expression of the kernels above, so their bits) the row's contribution is c = fw s (__fmul_rn; not formed
+// without word dropout), and
+//   accumulate == 0: dW[v] = c; rows no token hit and rows of a dropped word are written as zeros
+//   accumulate == 1: dW[v] = dW[v] + c (__fadd_rn) on rows that are hit and whose word is kept - every other row is neither read nor
+//                    written: the head's dW stays where it is, and a step touches at most R of the V rows
+// dW is read and written through the one pointer, by the lane that owns the quad.  Accesses choose 16 / 8 / 4 bytes per address
+// (load_quad / store_quad): H = 650 puts every second row 8 bytes off, and a view may start anywhere.
+__global__ __launch_bounds__(256) void embed_bwd_ex_kernel(int R, int H, int V, int words, const unsigned* __restrict__ bits,
+                                                           const float* __restrict__ dy, float* dW, DropArgs d, WordDrop wd, int accumulate) {
+  const int lane = threadIdx.x & 63;
+  const int v = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (v >= V) return;
+  float* out = dW + (size_t)v * H;
+  float fw = 1.f;
+  if (wd.word) {
+    fw = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(word_factor(d.state, wd.thresh, wd.scale, (unsigned)v))));
+    if (fw == 0.f) {   // a dropped word: no position's gradient reaches its row
+      if (accumulate) return;
+      const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int col = 4 * lane; col < H; col += 256) store_quad(out + col, H - col < 4 ? H - col : 4, zero);
+      return;
+    }
+  }
+  DropKey key = {0u, 0u, 0u, 0u};
+  if (wd.drop) key = drop_key(d);
+  const unsigned* brow = bits + (size_t)v * words;
+  bool hit = false;
+  float acc[4][4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[c][e] = 0.f;
+  for (int w0 = 0; w0 < words; w0 += 64) {
+    const int wi = w0 + lane;
+    const unsigned mine = wi < words ? brow[wi] : 0u;
+    unsigned long long any = __ballot(mine != 0u);
+    hit = hit || any != 0ull;
+    while (any != 0ull) {
+      const int src = __ffsll((long long)any) - 1;
+      any &= any - 1ull;
+      unsigned word = (unsigned)__shfl((int)mine, src, 64);
+      while (word != 0u) {
+        const int bit = __ffs((int)word) - 1;
+        word &= word - 1u;
+        const int p = (w0 + src) * 32 + bit;
+        const float* row = dy + (size_t)p * H;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int col = 4 * lane + 256 * c;
+          if (col < H) {
+            float g[4];
+            load_quad(row + col, H - col < 4 ? H - col : 4, g);
+            if (wd.drop) {
+              float f[4];
+              drop_factors(key, d.thresh, d.scale, (unsigned)p, (unsigned)(col >> 2), f);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[c][e] += g[e] * f[e];
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[c][e] += g[e];
+            }
+          }
+        }
+      }
+    }
+  }
+  if (accumulate && !hit) return;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int col = 4 * lane + 256 * c;
+    if (col >= H) continue;
+    const int valid = H - col < 4 ? H - col : 4;
+    if (wd.word) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[c][e] = __fmul_rn(fw, acc[c][e]);
+    }
+    if (accumulate) {
+      float base[4];
+      load_quad(out + col, valid, base);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[c][e] = __fadd_rn(base[e], acc[c][e]);
+    }
+    store_quad(out + col, valid, acc[c]);
+  }
+}
+
 }  // namespace
+
+int launch_embed_bwd_ex(int R, int H, int V, const long long* tokens, const float* dy, float* dW, int accumulate, void* scratch,
+                        size_t scratch_bytes, const DropArgs& d, const WordDrop& wd, hipStream_t s) {
+  if (H > 1024) return -3;
+  const int words = (R + 31) / 32;
+  const size_t need = embed_bwd_scratch_bytes(R, V);
+  if (scratch == nullptr || scratch_bytes < need) return -4;
+  hipError_t e = hipMemsetAsync(scratch, 0, need, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(embed_mark_kernel, dim3((R + 255) / 256), dim3(256), 0, s, R, V, words, tokens, (unsigned*)scratch);
+  hipLaunchKernelGGL(embed_bwd_ex_kernel, dim3((V + 3) / 4), dim3(256), 0, s, R, H, V, words, (const unsigned*)scratch, dy, dW, d, wd,
+                     accumulate != 0);
+  return (int)hipGetLastError();
+}
 
 size_t embed_bwd_scratch_bytes(int R, int V) { return (size_t)V * (size_t)((R + 31) / 32) * sizeof(unsigned); }
 

@@ -300,6 +300,12 @@ size_t embed_bwd_scratch_bytes(int R, int V);
 int launch_transpose(int rows, int cols, const float* src, float* dst, hipStream_t s);   // dst (cols x rows) = src^T
 int launch_embed_bwd(int R, int H, int V, const long long* tokens, const float* dy, float* dW, void* scratch, size_t scratch_bytes,
                      hipStream_t s, const DropArgs* drop = nullptr);
+// the table gradient that accumulates into a given dW and takes word dropout (vmlmf_embed.hip), and the gather under word dropout
+// (vmlmf_dropout.hip): include/vmlmf_hip.h, vmlmf_embed_backward_ex; d.state may be NULL when wd.drop == wd.word == 0
+int launch_embed_bwd_ex(int R, int H, int V, const long long* tokens, const float* dy, float* dW, int accumulate, void* scratch,
+                        size_t scratch_bytes, const DropArgs& d, const WordDrop& wd, hipStream_t s);
+int launch_embed_fwd_ex(int R, int H, int V, const DropArgs& d, const WordDrop& wd, const float* w, const long long* tokens, float* y,
+                        hipStream_t s);
 // dropout launches (vmlmf_dropout.hip): snapshot + advance of the generator state; mode 0: y = x * factor, 1: y = factor, 2: y =
 // w[tokens] * factor over R positions of H columns
 int launch_drop_advance(unsigned long long* state, unsigned long long* snap, hipStream_t s);

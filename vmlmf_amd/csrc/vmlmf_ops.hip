@@ -180,6 +180,40 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, con
   return hip_tail(rc);
 }
 
+// ---- the table that is embedding and vocabulary projection at once, and word dropout (docs/design/lm_tied.md) ----
+// both probabilities checked, the element dropout's arguments and the word dropout's; the state is needed iff one of them is on
+static int embed_ex_args(float p, float word_p, const int64_t* state, int site, DropArgs* d, WordDrop* wd) {
+  int rc = drop_args(p, state, site, nullptr, d);
+  if (rc != 0) return rc;
+  if (!(word_p >= 0.f && word_p < 1.f)) return fail(VMLMF_E_BADARG, "embed: word_p must be in [0, 1)");
+  wd->thresh = drop_thresh(word_p), wd->scale = 1.f / (1.f - word_p), wd->drop = p > 0.f, wd->word = word_p > 0.f;
+  if ((wd->drop || wd->word) && !state) return fail(VMLMF_E_BADARG, "embed: dropout without a generator state");
+  return 0;
+}
+
+int vmlmf_embed_dropout_forward_ex(int R, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, float word_p,
+                                   const int64_t* state, int site, void* stream) {
+  if (R < 0 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R >= 0, H >= 1, V >= 1");
+  DropArgs d;
+  WordDrop wd;
+  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd)) return rc;
+  if (!tokens || !weight || !out) return fail(VMLMF_E_BADARG, "embed: null pointer");
+  return hip_tail(launch_embed_fwd_ex(R, H, V, d, wd, weight, (const long long*)tokens, out, (hipStream_t)stream));
+}
+
+int vmlmf_embed_backward_ex(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, int accumulate, void* scratch,
+                            size_t scratch_bytes, float p, float word_p, const int64_t* state, int site, void* stream) {
+  if (R < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R, H, V must be >= 1");
+  if (!tokens || !dy || !dweight) return fail(VMLMF_E_BADARG, "embed: null pointer");
+  DropArgs d;
+  WordDrop wd;
+  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd)) return rc;
+  const int rc = launch_embed_bwd_ex(R, H, V, (const long long*)tokens, dy, dweight, accumulate, scratch, scratch_bytes, d, wd, (hipStream_t)stream);
+  if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "embed_backward_ex: embedding width > 1024");
+  if (rc == -4) return fail(VMLMF_E_WORKSPACE, "embed_backward_ex: scratch smaller than vmlmf_embed_backward_scratch_bytes()");
+  return hip_tail(rc);
+}
+
 // ---- activation regularisation of the LM's top layer (vmlmf_dropout.hip; docs/design/lm_actreg.md) ----
 size_t vmlmf_actreg_scratch_floats(int T, int B, int H) { return (T < 1 || B < 1 || H < 1) ? 0 : 2 * (size_t)actreg_workgroups(T, B, H); }
 

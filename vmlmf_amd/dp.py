@@ -472,8 +472,10 @@ class BucketedGradAllReduce:
 def lm_buckets(model):
     """Buckets of the LM network (vmlmf_lm.py:366-440) in the order its backward pass completes them: the vocabulary
     projection first (its gradients exist before the recurrent layers' backward starts), then the recurrent layers from
-    the top one down, the embedding table last (its gradient needs layer 0's dx)."""
-    out = [list(model.fc.parameters())]
+    the top one down, the embedding table last (its gradient needs layer 0's dx).  A tied table (Model.tie_weights) is named once,
+    in that last bucket: its gradient is complete only behind the embedding's backward."""
+    table = {id(p) for p in model.embed.parameters()}
+    out = [[p for p in model.fc.parameters() if id(p) not in table]]
     out += [list(r.parameters()) for r in reversed(list(model.rnns))]
     out.append(list(model.embed.parameters()))
     seen = {id(p) for b in out for p in b}

@@ -191,8 +191,10 @@ class DynamicEval:
         model = self.model
         for p in self.params:
             p.grad = None
-        h, states = model.features(x, [(hh.detach(), cc.detach()) for hh, cc in states])
-        loss, rows = lm_head_loss(h, model.fc.w, model.fc.b, y, return_rows=True)
+        states = [(hh.detach(), cc.detach()) for hh, cc in states]
+        tied = model._tied_gradient(x) if hasattr(model, "_tied_gradient") else None     # a tied table: one gradient, no table-wide add
+        h, states = model.features(x, states) if tied is None else model._features(x, states, grad_from=tied)[:2]
+        loss, rows = lm_head_loss(h, model.fc.w, model.fc.b, y, return_rows=True, grad_to=tied)
         loss.backward(unit_gradient(loss.device))
         return rows, model.detach(states)
 

@@ -1049,18 +1049,54 @@ def _head_loss_forward(ctx, h, w, b, y, stats_floats, launch):
     return stats
 
 
+class TiedGradient:
+    """The holder of ONE (V, H) gradient of a table that is both the embedding and the vocabulary projection (Model.tie_weights;
+    docs/design/lm_tied.md): it carries the head's dW from the head's backward to the embedding's backward of the SAME call, which
+    adds its rows into that tensor in place (vmlmf_embed_backward_ex, accumulate=1) and returns it as the table's one gradient.
+    The head takes the table detached, so autograd has no edge - and forms no table-wide sum - of its own.  Make a fresh holder
+    per loss call and hand it to both ends (lm_head_loss(..., grad_to=) and embedding(..., grad_from=))."""
+    __slots__ = ("dw",)
+
+    def __init__(self):
+        self.dw = None
+
+    def put(self, dw):
+        self.dw = dw
+
+    def take(self):
+        dw, self.dw = self.dw, None
+        return dw
+
+
+def tied_gradient(weight, tokens):
+    """A fresh TiedGradient where both ends of a tied table take it - the table requires grad under autograd, the package's
+    embedding backward covers it (_embed_covered) and the fused head loss covers its width - else None: autograd's own accumulation
+    of the two gradients, which is always correct."""
+    V = weight.shape[0]
+    if (torch.is_grad_enabled() and weight.requires_grad and _embed_covered(weight, tokens) and tokens.numel() > 0
+            and V % 4 == 0 and V <= 12288):
+        return TiedGradient()
+    return None
+
+
 def _head_loss_backward(ctx, dloss):
-    """(dh, dw, db) of the LM head's training losses: the two GEMMs read the scores' gradient where the forward left it."""
+    """(dh, dw, db) of the LM head's training losses: the two GEMMs read the scores' gradient where the forward left it.  A head that
+    was handed a TiedGradient (ctx.tied; its weight came in detached) forms dw all the same, puts it into the holder and returns
+    None for the weight: the embedding's backward of this call finishes it."""
     h2, w, dz = ctx.saved_tensors[:3]
     dbias = ctx.saved_tensors[3] if ctx.has_b else None
+    tied = getattr(ctx, "tied", None)
     scaled = not _is_unit(dloss)
     dh = _run_form(ctx.forms["dh"], dz, w) if ctx.needs_input_grad[0] else None
-    dw = _run_form(ctx.forms["dw"], dz, h2) if ctx.needs_input_grad[1] else None
+    dw = _run_form(ctx.forms["dw"], dz, h2) if (ctx.needs_input_grad[1] or tied is not None) else None
     db = dbias if (ctx.has_b and ctx.needs_input_grad[2]) else None
     if scaled:                                   # d(loss) is not the package's constant one: the stored gradient is for 1
         dh = None if dh is None else dh.mul_(dloss)
         dw = None if dw is None else dw.mul_(dloss)
         db = None if db is None else db * dloss
+    if tied is not None:
+        tied.put(dw)
+        dw = None
     return (None if dh is None else dh.view(ctx.hshape)), dw, db
 
 
@@ -1074,7 +1110,8 @@ class LmHeadLossFn(torch.autograd.Function):
     """loss = nll_loss(Linear(h), y) (vmlmf_lm.py:355-358 + lm_test.py:140-153) for training; see the block comment above."""
 
     @staticmethod
-    def forward(ctx, h, w, b, y, rows=False):
+    def forward(ctx, h, w, b, y, rows=False, tied=None):
+        ctx.tied = tied
         stats = _head_loss_forward(ctx, h, w, b, y, lambda R: 1 + R, _nll_launch)            # loss | rowloss
         if not rows:
             return stats[0]
@@ -1084,18 +1121,23 @@ class LmHeadLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, *_):
-        return (*_head_loss_backward(ctx, dloss), None, None)
+        return (*_head_loss_backward(ctx, dloss), None, None, None)
 
 
-def lm_head_loss(h, weight, bias, y, return_rows=False):
+def lm_head_loss(h, weight, bias, y, return_rows=False, grad_to=None):
     """Training form of nll_loss(Linear(h), y): h (T, B, H), weight (V, H), bias (V), y (T, B) int64 -> scalar loss whose
     backward reads the scores' gradient where the forward left it.  Call loss.backward(vmlmf_amd.unit_gradient(device)) to spare
     the three scalings a foreign d(loss) tensor costs.  Vocabulary widths the in-register loss does not cover (not a multiple
     of four, beyond 12288) and CPU tensors take projection + nll_loss.
     return_rows=True: (loss, rows) - rows (T B) fp32 is what each position is charged, logsumexp(z_r) - z_r[y_r], unscaled and not
-    differentiable: the row output the loss launch writes anyway (the stock path forms it in stock ops)."""
+    differentiable: the row output the loss launch writes anyway (the stock path forms it in stock ops).
+    grad_to: a TiedGradient (tied_gradient()) when `weight` is also the embedding table of the same call - the fused path then takes
+    the weight detached and leaves its dW in the holder for embedding(..., grad_from=) (the other paths leave the holder empty and
+    autograd adds the two gradients up)."""
     V = weight.shape[0]
     if h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288:
+        if grad_to is not None:
+            return LmHeadLossFn.apply(h, weight.detach(), bias, y, bool(return_rows), grad_to)
         return LmHeadLossFn.apply(h, weight, bias, y, True) if return_rows else LmHeadLossFn.apply(h, weight, bias, y)
     scores = torch.addmm(bias, h.reshape(-1, h.shape[-1]), weight.t())
     if not return_rows:
@@ -1165,7 +1207,8 @@ class LmHeadDistillFn(torch.autograd.Function):
     loss launch is vmlmf_distill_forward_grad.  hard and soft are reported, not differentiable."""
 
     @staticmethod
-    def forward(ctx, h, w, b, y, dense, tok, tsc, alpha, tau):
+    def forward(ctx, h, w, b, y, dense, tok, tsc, alpha, tau, tied=None):
+        ctx.tied = tied
         kd = _lib.Distill(alpha=alpha, temperature=tau, teacher=None if dense is None else dense.data_ptr(),
                           top_tokens=None if tok is None else tok.data_ptr(), top_scores=None if tsc is None else tsc.data_ptr(),
                           top=0 if tok is None else tok.shape[1])
@@ -1182,10 +1225,10 @@ class LmHeadDistillFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, dhard, dsoft):
-        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None)
+        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None, None)
 
 
-def lm_head_distill_loss(h, weight, bias, y, teacher, *, alpha=0.5, temperature=2.0, return_parts=False):
+def lm_head_distill_loss(h, weight, bias, y, teacher, *, alpha=0.5, temperature=2.0, return_parts=False, grad_to=None):
     """lm_head_loss with a soft-target term (knowledge distillation): h (T, B, H), weight (V, H), bias (V) or None, y (T, B) int64.
     With z = Linear(h), tau = temperature, Q = softmax(z / tau) and the teacher's distribution P, per row
         hard = logsumexp(z) - z[y]        soft = tau^2 KL(P || Q)        loss = scale sum ((1 - alpha) hard + alpha soft)
@@ -1207,14 +1250,17 @@ def lm_head_distill_loss(h, weight, bias, y, teacher, *, alpha=0.5, temperature=
     alpha, tau = float(alpha), float(temperature)
     fused = h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288
     if fused and alpha == 0.0:
-        loss = LmHeadLossFn.apply(h, weight, bias, y)
+        loss = LmHeadLossFn.apply(h, weight, bias, y) if grad_to is None else LmHeadLossFn.apply(h, weight.detach(), bias, y, False, grad_to)
         return (loss, loss.detach(), torch.zeros_like(loss)) if return_parts else loss
     if fused:
         given = [t.detach().contiguous() for t in (dense, tok, tsc) if t is not None]
         if any(t.device != h.device for t in given):
             raise ValueError(f"vmlmf_amd: the teacher's tensors must be on the student's device {h.device}")
         dense, tok, tsc = (given[0], None, None) if dense is not None else (None, given[0], given[1])
-        loss, hard, soft = LmHeadDistillFn.apply(h, weight, bias, y, dense, tok, tsc, alpha, tau)
+        if grad_to is not None:                  # a tied table (lm_head_loss's grad_to)
+            loss, hard, soft = LmHeadDistillFn.apply(h, weight.detach(), bias, y, dense, tok, tsc, alpha, tau, grad_to)
+        else:
+            loss, hard, soft = LmHeadDistillFn.apply(h, weight, bias, y, dense, tok, tsc, alpha, tau)
     else:
         h2 = h.reshape(-1, h.shape[-1])
         scores = torch.mm(h2, weight.t()) if bias is None else torch.addmm(bias, h2, weight.t())
@@ -1332,7 +1378,8 @@ class LmHeadObjectiveFn(torch.autograd.Function):
     lm_head_loss's, the loss launch is vmlmf_objective_forward_grad.  The parts are reported, not differentiable."""
 
     @staticmethod
-    def forward(ctx, h, w, b, y, negatives, scale_dev, eps, zeta, alpha):
+    def forward(ctx, h, w, b, y, negatives, scale_dev, eps, zeta, alpha, tied=None):
+        ctx.tied = tied
         obj = _lib.Objective(label_smoothing=eps, z_loss=zeta, unlikelihood=alpha, negatives=None if negatives is None else negatives.data_ptr(),
                              k=0 if negatives is None else negatives.shape[1], scale_dev=None if scale_dev is None else scale_dev.data_ptr())
 
@@ -1348,11 +1395,11 @@ class LmHeadObjectiveFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss, *dparts):
-        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None)
+        return (*_head_loss_backward(ctx, dloss), None, None, None, None, None, None, None)
 
 
 def lm_head_objective_loss(h, weight, bias, y, *, lengths=None, label_smoothing=0.0, z_loss=0.0, unlikelihood=0.0, negatives=None,
-                           normalize="rows", return_parts=False):
+                           normalize="rows", return_parts=False, grad_to=None):
     """lm_head_loss with a padding mask, label smoothing, z-loss and token-level unlikelihood: h (T, B, H), weight (V, H), bias (V)
     or None, y (T, B) int64.  With z = Linear(h), p = softmax(z), eps = label_smoothing, zeta = z_loss, alpha = unlikelihood, per row
         nll = lse - z[y]    sm = lse - mean z    zl = lse^2    ul = sum over c in C of -log(max(1 - p_c, 1e-5))
@@ -1380,15 +1427,18 @@ def lm_head_objective_loss(h, weight, bias, y, *, lengths=None, label_smoothing=
     neg = objective_negatives(negatives, R) if alpha > 0 else None
     fused = h.is_cuda and h.dtype == torch.float32 and y.dtype == torch.int64 and V % 4 == 0 and V <= 12288
     if lengths is None and eps == 0.0 and zeta == 0.0 and alpha == 0.0 and not return_parts:
-        return lm_head_loss(h, weight, bias, y)
+        return lm_head_loss(h, weight, bias, y, grad_to=grad_to)
     if fused:
         if neg is not None and neg.device != h.device:
             raise ValueError(f"vmlmf_amd: negatives must be on the scores' device {h.device}")
         scale_dev = None
         if normalize == "tokens" and lengths is not None:
             scale_dev = float(R) / _valid_count(lengths.to(h.device), y.shape[0], torch.float32)
-        out = LmHeadObjectiveFn.apply(h, weight, bias, _mask_targets(y, lengths), None if neg is None else neg.contiguous(), scale_dev,
-                                      eps, zeta, alpha)
+        args = (_mask_targets(y, lengths), None if neg is None else neg.contiguous(), scale_dev, eps, zeta, alpha)
+        if grad_to is not None:                  # a tied table (lm_head_loss's grad_to)
+            out = LmHeadObjectiveFn.apply(h, weight.detach(), bias, *args, grad_to)
+        else:
+            out = LmHeadObjectiveFn.apply(h, weight, bias, *args)
     else:
         h2 = h.reshape(-1, h.shape[-1])
         scores = torch.mm(h2, weight.t()) if bias is None else torch.addmm(bias, h2, weight.t())
@@ -1659,18 +1709,115 @@ def _embed_covered(weight, tokens):
             and weight.is_contiguous() and weight.shape[0] * ((tokens.numel() + 31) // 32) * 4 <= (64 << 20))
 
 
-def embedding_dropout(weight, tokens, p, snap, site=0):
+def check_word_dropout(word_p, who="embed_dropout"):
+    """ValueError for a word-dropout probability that is a bool, not a number or outside [0, 1)."""
+    if isinstance(word_p, bool) or not isinstance(word_p, (int, float)) or not 0.0 <= word_p < 1.0:
+        raise ValueError(f"vmlmf_amd: {who} must be a number in [0, 1), got {word_p!r}")
+
+
+class EmbedExFn(torch.autograd.Function):
+    """(w[tokens] * fw[tokens]) * f - the gather under AWD-LSTM's word dropout (fw: one factor per vocabulary row) and the element
+    dropout (f) - and / or the embedding end of a tied table (docs/design/lm_tied.md): vmlmf_embed_dropout_forward_ex and
+    vmlmf_embed_backward_ex, one launch sequence per direction.  With a TiedGradient that the head's backward filled the backward
+    adds its rows INTO the head's dW (accumulate=1: rows no token hit are neither read nor written) and returns that tensor as
+    the table's one gradient; with an empty holder, or none, it returns its own (accumulate=0).
+    The order is safe: this function's output feeds the layers, which feed the head, so within a backward pass autograd runs the
+    head's backward - which fills the holder - before this one.  This is the one place that relies on it."""
+
+    @staticmethod
+    def forward(ctx, w, tokens, p, word_p, snap, site, holder):
+        V, H = w.shape
+        tok = tokens.reshape(-1).contiguous()
+        if p > 0.0 or word_p > 0.0:
+            out = torch.empty(tuple(tokens.shape) + (H,), device=w.device, dtype=torch.float32)
+            with _lib.on_device(w.device):
+                _lib.check(_lib.lib().vmlmf_embed_dropout_forward_ex(tok.numel(), H, V, _ptr(tok), _ptr(w), _ptr(out), float(p), float(word_p),
+                                                                     snap.data_ptr(), int(site), _lib.raw_stream(w.device)))
+            ctx.save_for_backward(tok, snap)
+        else:
+            out = torch.nn.functional.embedding(tokens, w)
+            ctx.save_for_backward(tok)
+        ctx.wshape, ctx.p, ctx.word_p, ctx.site, ctx.holder = w.shape, float(p), float(word_p), int(site), holder
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        tok = ctx.saved_tensors[0]
+        snap = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
+        V, H = ctx.wshape
+        dy2 = dy.reshape(-1, H).contiguous()
+        R = dy2.shape[0]
+        dw = ctx.holder.take() if ctx.holder is not None else None     # the head's dW of this backward pass, or nothing
+        accumulate = dw is not None
+        if not accumulate:
+            dw = torch.empty((V, H), device=dy.device, dtype=torch.float32)
+        lib = _lib.lib()
+        nbytes = lib.vmlmf_embed_backward_scratch_bytes(R, V)
+        scratch = _workspace(dy.device, nbytes, "embed")
+        with _lib.on_device(dy.device):
+            _lib.check(lib.vmlmf_embed_backward_ex(R, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), int(accumulate), scratch.data_ptr(), nbytes, ctx.p,
+                                                   ctx.word_p, None if snap is None else snap.data_ptr(), ctx.site,
+                                                   _lib.raw_stream(dy.device)))
+        return dw, None, None, None, None, None, None
+
+
+def _embed_ex(weight, tokens, p, word_p, snap, site, grad_from):
+    if not _embed_covered(weight, tokens):
+        raise RuntimeError("vmlmf_amd: word dropout and a tied table's gradient take a contiguous fp32 table on a HIP device, up to 1024 "
+                           "wide and 64 MB of position bits, and int64 tokens (embedding_dropout_stock is the form in stock ops)")
+    if (p > 0.0 or word_p > 0.0) and snap is None:
+        raise ValueError("vmlmf_amd: dropout takes a snapshot of the generator (dropout_advance())")
+    return EmbedExFn.apply(weight, tokens, float(p), float(word_p), snap, site, grad_from)
+
+
+def embedding_dropout(weight, tokens, p, snap, site=0, *, word_p=0.0, grad_from=None):
     """dropout(weight[tokens]) - the first two lines of Model.forward (vmlmf_lm.py:434-435) - as one launch per direction on HIP fp32
-    tables up to 1024 wide; embedding() followed by dropout() otherwise."""
-    if p <= 0.0:
-        return embedding(weight, tokens)
-    if _embed_covered(weight, tokens):
-        return EmbedDropFn.apply(weight, tokens, p, snap, site)
-    return dropout(embedding(weight, tokens), p, snap, site)
+    tables up to 1024 wide; embedding() followed by dropout() otherwise.
+    word_p in [0, 1): AWD-LSTM's embedding dropout (--dropoute) in the same launches - whole WORDS are dropped, one factor per
+    vocabulary row (0, or 1 / (1 - word_p)) shared by every position that holds the word, applied before the element dropout:
+    (weight[tokens] * fw[tokens]) * f; word_dropout_factors() shows fw.  grad_from: a TiedGradient when `weight` is also the
+    head's weight of the same call (EmbedExFn).  With both at their defaults the call is what it was without them."""
+    check_word_dropout(word_p, "word_p")
+    if word_p == 0.0 and grad_from is None:
+        if p <= 0.0:
+            return embedding(weight, tokens)
+        if _embed_covered(weight, tokens):
+            return EmbedDropFn.apply(weight, tokens, p, snap, site)
+        return dropout(embedding(weight, tokens), p, snap, site)
+    return _embed_ex(weight, tokens, max(float(p), 0.0), word_p, snap, site, grad_from)
 
 
-def embedding(weight, tokens):
-    """weight[tokens] with the package's backward on HIP fp32 tables up to 1024 wide and 64 MB of position bits; the stock op otherwise."""
+def embedding_dropout_stock(weight, tokens, p, word_p, training=True):
+    """The same rule in stock ops under autograd, literally AWD-LSTM's embedded_dropout followed by the input dropout - for CPU
+    tensors and Model.stock_dropout: F.dropout(F.embedding(tokens, weight * F.dropout(ones(V, 1), word_p)), p), masks from torch's
+    generator."""
+    F = torch.nn.functional
+    check_word_dropout(word_p, "word_p")
+    if training and word_p > 0.0:
+        weight = weight * F.dropout(torch.ones((weight.shape[0], 1), device=weight.device, dtype=weight.dtype), word_p, True)
+    return F.dropout(F.embedding(tokens, weight), p, training)
+
+
+def word_dropout_factors(V, word_p, snap):
+    """The (V) fp32 word factors fw (0 or 1 / (1 - word_p)) that embedding_dropout(..., word_p=) applies under the snapshot `snap`:
+    formed by the gather itself on a (V, 4) table of ones.  For tests, and for users who want to see the mask."""
+    check_word_dropout(word_p, "word_p")
+    if not (isinstance(snap, torch.Tensor) and snap.is_cuda and snap.dtype == torch.int64 and snap.numel() == 2):
+        raise RuntimeError("vmlmf_amd: the snapshot is two int64 words on a HIP device (dropout_advance())")
+    ones = torch.ones((int(V), 4), device=snap.device, dtype=torch.float32)
+    out = torch.empty_like(ones)
+    tok = torch.arange(int(V), device=snap.device, dtype=torch.int64)
+    with _lib.on_device(snap.device):
+        _lib.check(_lib.lib().vmlmf_embed_dropout_forward_ex(int(V), 4, int(V), _ptr(tok), _ptr(ones), _ptr(out), 0.0, float(word_p),
+                                                             snap.data_ptr(), 0, _lib.raw_stream(snap.device)))
+    return out[:, 0].contiguous()
+
+
+def embedding(weight, tokens, grad_from=None):
+    """weight[tokens] with the package's backward on HIP fp32 tables up to 1024 wide and 64 MB of position bits; the stock op otherwise.
+    grad_from: a TiedGradient when `weight` is also the head's weight of the same call (EmbedExFn)."""
+    if grad_from is not None:
+        return _embed_ex(weight, tokens, 0.0, 0.0, None, 0, grad_from)
     if _embed_covered(weight, tokens):
         return EmbedFn.apply(weight, tokens)
     return weight[tokens]

@@ -218,10 +218,13 @@ class Model(nn.Module):
     "vm_group" silently builds torch.nn.LSTM layers.  Build MyVMLSTMGroup layers directly for the group variant."""
 
     def __init__(self, vocab_size, hidden_size, layer_num, dropout, winit, w_rank=None, u_ranks=None,
-                 lstm_type="pytorch", dense_layer=None):
+                 lstm_type="pytorch", dense_layer=None, tie_weights=False, embed_dropout=0.0):
         """dense_layer: overrides the class built for lstm_type="custom" (default: LSTM above, the reference's dense baseline
-        layer in stock ops); any class with the signature (input_size, hidden_size) and forward(x, states)."""
+        layer in stock ops); any class with the signature (input_size, hidden_size) and forward(x, states).
+        tie_weights, embed_dropout: NOT part of the reference's interface - AWD-LSTM's --tied (tie_weights()) and --dropoute (the
+        embed_dropout attribute); docs/design/lm_tied.md."""
         super().__init__()
+        self.embed_dropout = embed_dropout
         self.vocab_size = vocab_size
         self.hidden_size = hidden_size
         self.layer_num = layer_num
@@ -242,13 +245,65 @@ class Model(nn.Module):
         self.fc = Linear(hidden_size, vocab_size)
         self.dropout = nn.Dropout(p=dropout)
         self.reset_parameters()
+        if tie_weights:
+            self.tie_weights()
 
     def reset_parameters(self):
-        for param in self.parameters():
+        for param in self.parameters():          # (a tied table is met once: parameters() names a shared tensor once)
             nn.init.uniform_(param, -self.winit, self.winit)
 
+    # ---- one table as embedding and vocabulary projection (weight tying); word-level embedding dropout: docs/design/lm_tied.md ----
+    @property
+    def tied(self):
+        """True while fc.w IS embed.w (tie_weights())."""
+        return self.fc.w is self.embed.w
+
+    def tie_weights(self):
+        """Weight tying (Press & Wolf; Inan et al.; AWD-LSTM's --tied): fc.w becomes the very Parameter embed.w is - embed.w's values
+        are kept, as AWD-LSTM's `decoder.weight = encoder.weight` keeps them; Embed(V, H) and Linear(H, V) have the same (V, H) shape
+        here.  parameters() then names the table once (one tensor and V H elements fewer: half of the PTB network, of every optimizer
+        step and of the data-parallel gradient traffic); state_dict() keeps both keys, torch's behaviour, and the tie survives
+        load_state_dict, .to() and copy.deepcopy.  loss(), distill_loss() and DynamicEval form the table's ONE gradient without a
+        table-wide add: the embedding's backward adds its rows into the head's dW in place (functional.TiedGradient); forward()'s
+        scores and every other use are correct through autograd's own accumulation.  Optimizers built before the call still
+        hold the old fc.w: build them after it.  Returns self."""
+        self.fc.w = self.embed.w
+        return self
+
+    def untie_weights(self):
+        """fc.w gets a Parameter of its own again, a clone of the table.  Returns self."""
+        if self.tied:
+            w = self.embed.w
+            self.fc.w = nn.Parameter(w.detach().clone(), requires_grad=w.requires_grad)
+        return self
+
+    @property
+    def embed_dropout(self):
+        """AWD-LSTM's embedding dropout (--dropoute), a probability in [0, 1): in training mode whole WORDS are dropped from the
+        table for a forward pass - one factor per vocabulary row, 0 or 1 / (1 - embed_dropout), shared by every position that holds
+        the word - in front of the element dropout of `dropout`.  On a HIP device inside the gather's and the table gradient's own
+        launches (functional.embedding_dropout(word_p=)); on CPU tensors and under stock_dropout in stock ops
+        (functional.embedding_dropout_stock).  ValueError for a bool or a value outside [0, 1)."""
+        return getattr(self, "_embed_dropout", 0.0)
+
+    @embed_dropout.setter
+    def embed_dropout(self, value):
+        from .functional import check_word_dropout
+        check_word_dropout(value, "Model.embed_dropout")
+        self._embed_dropout = float(value)
+
+    def _tied_gradient(self, x):
+        """A fresh functional.TiedGradient for one loss call on tokens x where the table is tied and both ends take it, else None."""
+        if not self.tied:
+            return None
+        if self.training and self.embed_dropout > 0 and getattr(self, "stock_dropout", False):
+            return None                          # the word dropout in stock ops: autograd adds the two gradients up
+        from .functional import tied_gradient
+        return tied_gradient(self.embed.w, x)
+
     @classmethod
-    def with_group_layers(cls, vocab_size, hidden_size, layer_num, dropout, winit, w_rank, u_ranks, g=2):
+    def with_group_layers(cls, vocab_size, hidden_size, layer_num, dropout, winit, w_rank, u_ranks, g=2, tie_weights=False,
+                          embed_dropout=0.0):
         """The network of BASELINE configs[4] - Model with MyVMLSTMGroup layers - which the reference's constructor cannot build
         (lstm_type "vmgroup" reduces the rank list to its last element and MyVMLSTMGroup then fails, vmlmf_lm.py:387-392; "vm_group",
         the CLI's spelling, builds nn.LSTM).  NOT part of the reference's interface: the constructor above keeps the reference's
@@ -259,6 +314,9 @@ class Model(nn.Module):
                                     for _ in range(layer_num)])
         model.lstm_type = "vmgroup"
         model.reset_parameters()
+        model.embed_dropout = embed_dropout
+        if tie_weights:
+            model.tie_weights()
         return model
 
     def state_init(self, batch_size):
@@ -326,16 +384,19 @@ class Model(nn.Module):
         if (lengths is None and negatives is None and not return_parts and normalize == "rows"
                 and label_smoothing == 0.0 and z_loss == 0.0 and unlikelihood == 0.0
                 and not any(isinstance(v, bool) for v in (label_smoothing, z_loss, unlikelihood))):
-            h, states = self.features(x, states)
-            return lm_head_loss(h, self.fc.w, self.fc.b, y), states
+            tied = self._tied_gradient(x)
+            h, states = self.features(x, states) if tied is None else self._features(x, states, grad_from=tied)[:2]
+            return lm_head_loss(h, self.fc.w, self.fc.b, y, grad_to=tied), states
         from .functional import check_lengths, check_objective, context_negatives, lm_head_objective_loss, objective_negatives
         check_objective(label_smoothing, z_loss, unlikelihood, normalize)
         check_lengths(lengths, x.size(1), "Model.loss")
         if unlikelihood > 0:
             negatives = objective_negatives(context_negatives(x) if negatives is None else negatives, x.numel())
-        h, states = self.features(x, states)
+        tied = self._tied_gradient(x)
+        h, states = self.features(x, states) if tied is None else self._features(x, states, grad_from=tied)[:2]
         loss = lm_head_objective_loss(h, self.fc.w, self.fc.b, y, lengths=lengths, label_smoothing=label_smoothing, z_loss=z_loss,
-                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts)
+                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts,
+                                      grad_to=tied)
         return loss, states
 
     def distill_loss(self, x, y, states, teacher, *, alpha=0.5, temperature=2.0, teacher_states=None, top=0, return_parts=False):
@@ -386,8 +447,10 @@ class Model(nn.Module):
         else:
             from .functional import distill_teacher
             distill_teacher(teacher, x.numel(), self.vocab_size, self.fc.w.dtype)
-        h, states = self.features(x, states)
-        loss = lm_head_distill_loss(h, self.fc.w, self.fc.b, y, teacher, alpha=alpha, temperature=temperature, return_parts=return_parts)
+        tied = self._tied_gradient(x)
+        h, states = self.features(x, states) if tied is None else self._features(x, states, grad_from=tied)[:2]
+        loss = lm_head_distill_loss(h, self.fc.w, self.fc.b, y, teacher, alpha=alpha, temperature=temperature, return_parts=return_parts,
+                                    grad_to=tied)
         return (loss, states, teacher_states) if module else (loss, states)
 
     def _regularized_loss(self, x, y, states, lengths, label_smoothing, z_loss, unlikelihood, negatives, normalize, return_parts, ar, tar):
@@ -399,7 +462,8 @@ class Model(nn.Module):
         check_lengths(lengths, x.size(1), "Model.loss")
         if unlikelihood > 0:
             negatives = objective_negatives(context_negatives(x) if negatives is None else negatives, x.numel())
-        raw, states, site = self._features(x, states, raw_top=True)
+        tied = self._tied_gradient(x)
+        raw, states, site = self._features(x, states, raw_top=True, grad_from=tied)
         B = x.size(1)
         if site is None or len(site) == 4:       # no dropout at that site / the package's, inside the regulariser's launches
             p, snap, index, desc = site or (0.0, None, 0, None)
@@ -411,9 +475,10 @@ class Model(nn.Module):
         plain = (lengths is None and negatives is None and not return_parts and normalize == "rows" and label_smoothing == 0.0
                  and z_loss == 0.0 and unlikelihood == 0.0)
         if plain:
-            return lm_head_loss(h, self.fc.w, self.fc.b, y) + penalty, states
+            return lm_head_loss(h, self.fc.w, self.fc.b, y, grad_to=tied) + penalty, states
         head = lm_head_objective_loss(h, self.fc.w, self.fc.b, y, lengths=lengths, label_smoothing=label_smoothing, z_loss=z_loss,
-                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts)
+                                      unlikelihood=unlikelihood, negatives=negatives, normalize=normalize, return_parts=return_parts,
+                                      grad_to=tied)
         if not return_parts:
             return head + penalty, states
         return (head[0] + penalty, *head[1:], *parts), states
@@ -422,7 +487,8 @@ class Model(nn.Module):
         """Everything of forward() in front of the vocabulary projection (vmlmf_lm.py:434-439): (T, B, H) activations, states.
         Training with p > 0 on a HIP device: the three dropouts run without mask tensors (functional.dropout_*: Philox factors
         regenerated in the backward) - the embedding's inside its gather, a VMLMF layer's inside the layer's launches; with
-        self.stock_dropout = True they are nn.Dropout's launches as in the reference."""
+        self.stock_dropout = True they are nn.Dropout's launches as in the reference.  embed_dropout > 0 adds the word dropout of
+        the table to the same gather (training mode only)."""
         return self._features(x, states)[:2]
 
     def _top_layer_desc(self, T, B):
@@ -437,20 +503,21 @@ class Model(nn.Module):
                               training=True)
         return desc if _lib.lib().vmlmf_dropout_fused(ctypes.byref(desc)) == 1 else None
 
-    def _features(self, x, states, raw_top=False):
+    def _features(self, x, states, raw_top=False, grad_from=None):
         """features(), written once.  raw_top=True (loss() under ar / tar): the top layer runs without the dropout behind it and a
         third element says what the caller applies in its place: None (eval mode, p == 0), (p, snapshot, site, layer descriptor or
         None) for functional.activation_regularizer, or (p,) where the dropouts are nn.Dropout's."""
         p = self.dropout.p
         last = len(self.rnns) - 1
-        if self.training and p > 0 and x.is_cuda and not getattr(self, "stock_dropout", False):
+        word_p = self.embed_dropout if self.training else 0.0
+        if self.training and (p > 0 or word_p > 0) and x.is_cuda and not getattr(self, "stock_dropout", False):
             from .functional import dropout, dropout_advance, embedding_dropout
             snap = dropout_advance(self.dropout_state())
             T, B = x.shape
-            x = embedding_dropout(self.embed.w, x, p, snap, 0)
-            site = (p, snap, last + 1, self._top_layer_desc(T, B)) if raw_top else None
-            drops = [None if (raw_top and i == last) else (p, snap, i + 1) for i in range(len(self.rnns))]
-            stacked = self._stack(x, states, drops=drops)
+            x = embedding_dropout(self.embed.w, x, p, snap, 0, word_p=word_p, grad_from=grad_from)
+            site = (p, snap, last + 1, self._top_layer_desc(T, B)) if (raw_top and p > 0) else None
+            drops = [None if (raw_top and i == last) or not p > 0 else (p, snap, i + 1) for i in range(len(self.rnns))]
+            stacked = self._stack(x, states, drops=drops if p > 0 else None)
             if stacked is not None:       # every layer in one launch per direction, the dropouts behind them inside it
                 x, new_states = stacked
                 for i, st in enumerate(new_states):
@@ -465,8 +532,15 @@ class Model(nn.Module):
                         x = dropout(x, p, snap, i + 1)
             return x, states, site
         site = (p,) if (raw_top and self.training and p > 0) else None
-        x = self.embed(x)
-        x = self.dropout(x)
+        if word_p > 0:                           # CPU tensors, stock_dropout: AWD-LSTM's embedded_dropout in stock ops
+            from .functional import embedding_dropout_stock
+            x = embedding_dropout_stock(self.embed.w, x, p, word_p)
+        elif grad_from is not None:
+            from .functional import embedding
+            x = self.dropout(embedding(self.embed.w, x, grad_from=grad_from))
+        else:
+            x = self.embed(x)
+            x = self.dropout(x)
         stacked = self._stack(x, states)
         if stacked is not None:
             x, new_states = stacked
