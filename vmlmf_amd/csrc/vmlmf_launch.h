@@ -68,6 +68,7 @@ struct AtbArgs {
 // ntg workgroups per worker index; prog = one progress word per batch row (zero between launches)
 constexpr int WR_PROG_STRIDE = 32;   // unsigned words between two rows' progress words: one 128-byte line each (written through
                                      // every other step by 64+ workgroups: words sharing a line serialise at the memory side)
+constexpr int WR_LAG_DEFAULT = 3;    // WRide::lag unless tuned (VMLMF_WRIDE_LAG): the storers' loops exist with its counted waits as immediates
 // codes a kernel leaves in the host-visible status word when one of its bounded waits gives up (the results are NaN then); the
 // next C-ABI call on the device returns VMLMF_E_PROTOCOL (vmlmf_api.hip: take_status)
 constexpr unsigned VMLMF_ST_WRIDE = 1, VMLMF_ST_CLUSTER = 2, VMLMF_ST_WF_FWD = 3, VMLMF_ST_WF_BWD = 4, VMLMF_ST_P2P = 5;

@@ -25,8 +25,14 @@
 constexpr int R3_MAXS = 3;   // waves of hidden units (thread slots / 64) these kernels cover
 
 
-// sum of the (up to four) wave partials of this lane's rank, in wave order
-__device__ __forceinline__ float r3_total(float4 p) { return (p.x + p.y) + (p.z + p.w); }
+// sum of the (up to four) wave partials of this lane's rank, in wave order: three plain adds.  (The first sum is made opaque:
+// left alone, the compiler packs the two inner sums into one v_pk_add_f32 and pays three v_mov_b32 to line the pairs up - five
+// instructions on the dependent chain, right behind the partials' read, instead of three.)
+__device__ __forceinline__ float r3_total(float4 p) {
+  float lo = p.x + p.y;
+  asm("" : "+v"(lo));
+  return lo + (p.z + p.w);
+}
 
 // 16 rotations with four accumulators (two dependent chains of eight measured 6.4 ticks a step, independent ones 5.1)
 __device__ __forceinline__ float fmac_ror_x16_4(float src, const float* w) {
@@ -310,23 +316,35 @@ static int rec3_fwd_launch_kh(const VGeo& g, const FwdArgs& a, const XwArgs& xw,
 // ====================================================================================================================
 // backward
 // ====================================================================================================================
+// The tape ring of rec3_bwd_kernel is R3_NB = 8 slots deep: a power of two, so that the slot of step t is t & 7 (two's complement:
+// also for the steps below zero the loader and the last fetch name) and the compute waves' step loop, unrolled over the ring's
+// period, names every slot and both out-stage buffers by a constant.  (BWD_NB = 6 cost every wave a division by six per step.)
+// fixed: the riding launches, which own their CU (84 KB asked for), lay the ring and the out-stage out for R3_NTS = 192 thread
+// slots whatever NT is - every LDS address of the step loop is then a per-thread base plus an immediate offset.
+constexpr int R3_NB = 8;
+constexpr int R3_NTS = 64 * R3_MAXS;
 // (+ DR_SCR_FLOATS per thread slot: the compute waves' slots for the direct mode's per-lane rotations, vmlmf_direct.inc)
-__host__ __device__ inline size_t rec3_bwd_lds_floats(int NT) {
-  return 128 + (size_t)BWD_NB * NT * 6 + (size_t)2 * NT * 4 + 256 + 4 + (size_t)DR_SCR_FLOATS * NT;
+__host__ __device__ inline size_t rec3_bwd_lds_floats(int NT, bool fixed = false) {
+  const size_t nts = fixed ? R3_NTS : NT;
+  return 128 + (size_t)R3_NB * nts * 6 + (size_t)2 * nts * 4 + 256 + 4 + (size_t)DR_SCR_FLOATS * NT;
 }
 
 // z[0] + sum_k (z[k] received through row_ror:k), 15 v_add_f32_dpp on three accumulators.  With register k of lane l holding
 // the lane's contribution to the rank k rotation steps away, lane i of every 16-lane row ends with rank i summed over the row.
 // (s_nop 1: the registers were written by VALU instructions right in front - two wait states before a DPP read.)
 #define VG_ADD1(acc, src, k) "v_add_f32_dpp %" #acc ", %" #src ", %" #acc " row_ror:" #k " row_mask:0xf bank_mask:0xf\n\t"
+// (The second and third accumulator start as 0 + their first term, the zero read from a register of its own: the same sums as
+//  into zeroed accumulators, without a v_mov_b32 per accumulator and step.)
+#define VG_ADD0(acc, src, k) "v_add_f32_dpp %" #acc ", %" #src ", %18 row_ror:" #k " row_mask:0xf bank_mask:0xf\n\t"
 __device__ __forceinline__ float add_ror_x16(const float (&z)[16]) {
-  float a0 = z[0], a1 = 0.f, a2 = 0.f;
-  asm("s_nop 1\n\t" VG_ADD1(1, 3, 1) VG_ADD1(2, 4, 2) VG_ADD1(0, 5, 3) VG_ADD1(1, 6, 4) VG_ADD1(2, 7, 5) VG_ADD1(0, 8, 6) VG_ADD1(1, 9, 7)
+  float a0 = z[0], a1, a2;
+  const float zero = 0.f;
+  asm("s_nop 1\n\t" VG_ADD0(1, 3, 1) VG_ADD0(2, 4, 2) VG_ADD1(0, 5, 3) VG_ADD1(1, 6, 4) VG_ADD1(2, 7, 5) VG_ADD1(0, 8, 6) VG_ADD1(1, 9, 7)
       VG_ADD1(2, 10, 8) VG_ADD1(0, 11, 9) VG_ADD1(1, 12, 10) VG_ADD1(2, 13, 11) VG_ADD1(0, 14, 12) VG_ADD1(1, 15, 13) VG_ADD1(2, 16, 14)
       VG_ADD1(0, 17, 15)
-      : "+v"(a0), "+v"(a1), "+v"(a2)
+      : "+v"(a0), "=&v"(a1), "=&v"(a2)
       : "v"(z[1]), "v"(z[2]), "v"(z[3]), "v"(z[4]), "v"(z[5]), "v"(z[6]), "v"(z[7]), "v"(z[8]), "v"(z[9]), "v"(z[10]), "v"(z[11]),
-        "v"(z[12]), "v"(z[13]), "v"(z[14]), "v"(z[15]));
+        "v"(z[12]), "v"(z[13]), "v"(z[14]), "v"(z[15]), "v"(zero));
   return (a0 + a1) + a2;
 }
 
@@ -346,13 +364,14 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
   const size_t sstride = (size_t)g.Bp * NT;
   const int row = blockIdx.x;
 
+  const int NTS = RIDE > 0 ? R3_NTS : NT;          // thread slots a ring slot / an out-stage buffer is laid out for (rec3_bwd_lds_floats)
   extern __shared__ float4 smem4[];
   float* part = reinterpret_cast<float*>(smem4);   // [2][16 ranks][4 waves]
-  float* tg = part + 128;                          // [BWD_NB][NT][4]  gates of the step
-  float* tcp = tg + BWD_NB * NT * 4;               // [BWD_NB][NT]     c_{t-1}
-  float* tdy = tcp + BWD_NB * NT;                  // [BWD_NB][NT]     dy_t
-  float* outs = tdy + BWD_NB * NT;                 // [2][NT][4]       dpre
-  float* spare = outs + 2 * NT * 4;                // 256 floats: target of the dummy DMAs
+  float* tg = part + 128;                          // [R3_NB][NTS][4]  gates of the step
+  float* tcp = tg + R3_NB * NTS * 4;               // [R3_NB][NTS]     c_{t-1}
+  float* tdy = tcp + R3_NB * NTS;                  // [R3_NB][NTS]     dy_t
+  float* outs = tdy + R3_NB * NTS;                 // [2][NTS][4]      dpre
+  float* spare = outs + 2 * NTS * 4;               // 256 floats: target of the dummy DMAs
   float* drscr = spare + 256 + 4;                  // [NT][DR_SCR_FLOATS]: direct mode, compute waves' prologue only
   if (tid < 128) part[tid] = 0.f;
 
@@ -362,11 +381,11 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
     constexpr int NDMA = 3 * MAXS;
     constexpr int DEPTH = 2;
     constexpr int DIST = DEPTH + 2;
-    static_assert(DIST < BWD_NB && 2 * NDMA <= 63, "tape ring");
+    static_assert(DIST < R3_NB && (R3_NB & (R3_NB - 1)) == 0 && 2 * NDMA <= 63, "tape ring");
     if (wave == NW) {
       auto issue = [&](int ttarget) {   // tape of step ttarget (clamped at 0) -> ring slot
         const int tc = ttarget > 0 ? ttarget : 0;
-        const int ring = ((ttarget % BWD_NB) + BWD_NB) % BWD_NB;
+        const int ring = ttarget & (R3_NB - 1);
 #pragma unroll
         for (int i = 0; i < MAXS; ++i) {
           const bool real = i < NW;
@@ -374,7 +393,7 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
           const size_t e = (size_t)tc * sstride + (size_t)row * NT + slot;
           int n;
           if (!vg_slot_unit(g, slot, n)) n = 0;   // pad slots must not index past the row
-          const size_t lo = (size_t)ring * NT + 64 * (real ? i : 0);
+          const size_t lo = (size_t)ring * NTS + 64 * (real ? i : 0);
           dma16(a.gates + e * 4, real ? tg + lo * 4 : spare);
           dma4(a.cs + e, real ? tcp + lo : spare);                      // slice tc = c_{tc-1}
           dma4(has_dy ? a.dy + ((size_t)tc * g.syT + (size_t)row * g.syB + n) : a.cs + e, real ? tdy + lo : spare);
@@ -392,7 +411,7 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
     const unsigned qdst = (unsigned)(row * KH + (lane < KH ? lane : 0)) * 4u;
     constexpr bool SAFE_ST = false;   // (vmlmf_device.h, hazard 2: set for the instantiations tools/check_asm_hazards.py flags)
     auto drain = [&](int ts) {   // dpre of step ts -> HBM (every slot is written), dQ[ts]
-      const float* src = outs + (size_t)(ts & 1) * NT * 4;
+      const float* src = outs + (size_t)(ts & 1) * NTS * 4;
       float* dt = a.dpre + (size_t)ts * sstride * 4;
       float4 d4[MAXS];
 #pragma unroll
@@ -414,18 +433,33 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
     const int nd = NW + 1;
     const int lag = a.wr.lag;
     const int nwait = nd * lag;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // opening barrier
-    for (int t = T - 1; t >= 0; --t) {   // segment t: step t+1 is complete
-      if (t + 1 < T) {
-        drain(t + 1);
-        if constexpr (RIDE > 0) {
-          wait_vm_dyn(nwait);
-          const int done = T - (t + 1 + lag);   // steps T-1 .. t+1+lag are in memory
-          if (lane == 0 && (t & 1) == 0)
-            st1_sv_sys<SAFE_ST>(a.wr.prog, 4u * (unsigned)(row * WR_PROG_STRIDE), (unsigned)(done > 0 ? done : 0));
+    // The counted wait of a segment takes its count as an immediate, and the count is fixed for the launch: the loop exists once
+    // with the count of the default lag at three waves of units (WR_LAG_DEFAULT segments of nd = 4 stores; NWAIT >= 0) and once
+    // with the run-time count behind wait_vm_dyn's branch tree, which every other launch takes (NWAIT < 0).
+    auto segments = [&](auto nwait_c) {
+      constexpr int NWAIT = decltype(nwait_c)::value;
+      for (int t = T - 1; t >= 0; --t) {   // segment t: step t+1 is complete
+        if (t + 1 < T) {
+          drain(t + 1);
+          if constexpr (RIDE > 0) {
+            if constexpr (NWAIT >= 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
+            else wait_vm_dyn(nwait);
+            const int done = T - (t + 1 + lag);   // steps T-1 .. t+1+lag are in memory
+            if (lane == 0 && (t & 1) == 0)
+              st1_sv_sys<SAFE_ST>(a.wr.prog, 4u * (unsigned)(row * WR_PROG_STRIDE), (unsigned)(done > 0 ? done : 0));
+          }
         }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // barrier(t)
       }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // barrier(t)
+    };
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // opening barrier
+    if constexpr (RIDE == 1 && KH == 16) {   // (the headline instantiation: the library's size)
+      switch (nwait) {
+        case 4 * WR_LAG_DEFAULT: segments(std::integral_constant<int, 4 * WR_LAG_DEFAULT>{}); break;   // three waves of units
+        default: segments(std::integral_constant<int, -1>{}); break;
+      }
+    } else {
+      segments(std::integral_constant<int, -1>{});
     }
     drain(0);
     if constexpr (RIDE > 0) {
@@ -511,9 +545,8 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
 
   float4 g4n;
   float cprvn, dyvn;
-  auto fetch_tape = [&](int tt) {
-    const int ringn = ((tt % BWD_NB) + BWD_NB) % BWD_NB;
-    const size_t lo = (size_t)ringn * NT + tid;
+  auto fetch_tape = [&](const int ringn) __attribute__((always_inline)) {   // ringn: the ring slot, step & (R3_NB - 1)
+    const size_t lo = (size_t)ringn * NTS + tid;
     g4n = ld4(tg + lo * 4);
     cprvn = tcp[lo];
     dyvn = tdy[lo];
@@ -525,14 +558,16 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
     fdy = (valid && has_dy) ? dyvn : 0.f;
     ccur = cprvn;   // c of the step before
   };
-  fetch_tape(T - 1);
+  fetch_tape((T - 1) & (R3_NB - 1));
   prepare();
-  for (int t = T - 1; t >= 0; --t) {
-    const int buf = t & 1;
+  // One time step t.  It names the step by what it addresses: ringp = ring slot of step t-1's tape, buf = t & 1.  Called with
+  // constants (the unrolled loop below), every LDS access of the step is a loop-invariant per-thread base plus an immediate offset
+  // and nothing of the step is index arithmetic.
+  auto step = [&](const int ringp, const int buf) __attribute__((always_inline)) {
     // tape of step t-1: landed at the barrier before this segment (the loader's counted wait); consumed by prepare() below
-    fetch_tape(t - 1);   // (t = 0: a valid, unused ring slot)
+    fetch_tape(ringp);   // (t = 0: a valid, unused ring slot)
     const float4 dp = cell_bwd_step(fac, fdy + dhrec, dcs);
-    st4(outs + (size_t)buf * NT * 4 + (size_t)tid * 4, dp);
+    st4(outs + (size_t)buf * NTS * 4 + (size_t)tid * 4, dp);
     const float ehterm = cell_ehterm_fma(dp, eh[0], eh[1], eh[2], eh[3]);   // (explicit fused multiply-adds: see there)
     // ---- rank-space reduce of dpre: fold the four gates per lane, then rotate-and-add across the row
     f32x2 z2[8];
@@ -550,12 +585,34 @@ __global__ void __launch_bounds__(320) rec3_bwd_kernel(VGeo g, BwdArgs a) {
     const float s = rowsum4(add_ror_x16(z));
     if (lane < 16) part[buf * 64 + lane * 4 + wave] = s;
     // ---- in the shadow of that write and of the barrier: the dh-independent factors of step t-1
+    // (behind the barrier instead, in the shadow of the partials' read: no faster - tools/experiments/step_loops_prepare_behind_barrier.patch)
     prepare();
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // barrier(t)
     const float4 p = ld4(part + buf * 64 + (lane & 15) * 4);
     float tot = r3_total(p);
     dpp_fence(tot);
     dhrec = ehterm + fmac_ror_x16_4(tot, ue);
+  };
+  // Steps T-1 .. 0: first the (T mod 8) steps down to a ring boundary, slot and buffer taken from t; then whole periods of the
+  // ring, t = 8 k + 7 .. 8 k, every slot and buffer a constant.  (No loop-carried register copies at a period's end either.)
+  // RIDE == 0 shares its CU with other rows' workgroups and keeps every step in the first loop: eight slots' worth of hoisted
+  // addresses took it from 132 to 148 VGPRs, past the 136 its occupancy rests on (tools/kernel_budget.py).
+  // (Nor the other riding instantiations: eight copies of the step in each would take the library past the size it is held to.)
+  constexpr bool PERIODS = RIDE == 1 && KH == 16;
+  int t = T - 1;
+  for (; PERIODS ? (t & (R3_NB - 1)) != R3_NB - 1 : t >= 0; --t) step((t - 1) & (R3_NB - 1), t & 1);
+  if constexpr (PERIODS) {
+    for (; t >= 0; t -= R3_NB) {
+      step(6, 1);
+      step(5, 0);
+      step(4, 1);
+      step(3, 0);
+      step(2, 1);
+      step(1, 0);
+      step(0, 1);
+      step(7, 0);
+    }
+    static_assert(R3_NB == 8, "the unrolled period above");
   }
 
   if (valid) {
@@ -570,7 +627,7 @@ __host__ inline bool rec3_bwd_ok(const VGeo& g) {
 
 template <int KH>
 static int rec3_bwd_launch_kh(const VGeo& g, const BwdArgs& a, hipStream_t s) {
-  const size_t lds = sizeof(float) * rec3_bwd_lds_floats(g.NT);
+  const size_t lds = sizeof(float) * rec3_bwd_lds_floats(g.NT, a.wr.K > 0);
   if (a.wr.K > 0) {
     const int n1 = (vg_nb1(g) + 31) / 32, n2 = (g.G * g.KH + 31) / 32;
     if (n1 > 2 || n2 > 2) return -3;

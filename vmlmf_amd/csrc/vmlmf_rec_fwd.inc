@@ -23,6 +23,24 @@
 #include "vmlmf_direct.inc"
 
 constexpr int FWD_NB = 6;   // depth of the gx ring in LDS
+// The instantiations with the x-projection wave (XW: one row, at most 192 thread slots, one workgroup per CU by their registers)
+// have a ring of FWD_XNB = 8 slots - a power of two: the slot of step t is t & 7, no division by six per wave and step - and lay
+// the ring and the out-stage out for FWD_XNTS thread slots whatever NT is: the compute waves' step loop, unrolled over the ring's
+// period, then addresses LDS by a per-thread base plus an immediate offset.
+constexpr int FWD_XNB = 8;
+constexpr int FWD_XNTS = 192;
+
+// Rank-major partials: the instantiations of rec_fwd_kernel with one row, at most 256 thread slots (so at most four compute waves),
+// one 16-rank pass and at most four waves per consumer keep the wave partials of the rank reduce as [buffer][rank][wave], one float4
+// per rank, as rec3_fwd_kernel and rec3_bwd_kernel do: lane i of a 16-lane row reads rank i's four partials with its one
+// ds_read_b128 and adds them with plain adds - no DPP butterfly over the waves.  Columns of waves that do not exist stay zero.
+template <int KH, int R, bool FLAT, int MAXT, int CNT>
+constexpr bool fwd_rank_major() { return !FLAT && R == 1 && MAXT == 256 && (KH == 8 || KH == 16) && CNT <= 4; }
+// floats of the partials' double buffer in LDS
+template <int KH, int R, bool FLAT, int MAXT, int CNT>
+__host__ __device__ constexpr size_t fwd_part_floats(int NW) {
+  return fwd_rank_major<KH, R, FLAT, MAXT, CNT>() ? (size_t)128 : (size_t)2 * R * NW * ((KH + 15) / 16 * 16);
+}
 
 
 // ---------------------------------------------------------------------------------------------------
@@ -206,7 +224,7 @@ __host__ __device__ inline size_t xwave_lds_floats() { return (size_t)XW_NB * 64
 // masks as well gave the gain back: 0.1550)
 template <int IM, int IE = IM>
 __device__ __attribute__((noinline)) void xwave_role(const __attribute__((address_space(4))) char* ka, float* gxs,
-                                                     float* xlds, int row, int ring_nb) {
+                                                     float* xlds, int row) {
   VGeo g;
   XwArgs xa;
   copy_from_kernarg(&g, ka);
@@ -299,7 +317,7 @@ __device__ __attribute__((noinline)) void xwave_role(const __attribute__((addres
       for (int m = 0; m < IM; ++m) q = fmaf(sx[m], uxc[m], q);
     }
     if (g.foldx == 0 && lane < KX) qxs[(t & 1) * 32 + lane] = q;
-    lds_f* dst = gxl + (size_t)(t % ring_nb) * NT * 4;
+    lds_f* dst = gxl + (size_t)(t & (FWD_XNB - 1)) * FWD_XNTS * 4;
 #pragma unroll
     for (int i = 0; i < XW_SLOTS; ++i) {
       if (real[i]) {   // wave-uniform
@@ -343,13 +361,17 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
   const size_t sstride = (size_t)g.Bp * NT;   // slots per time slice of the slot-padded buffers
 
   extern __shared__ float4 smem4[];
-  float* part = reinterpret_cast<float*>(smem4);           // [2][R][NW][KQ]
-  float* gxs = part + 2 * R * NW * KQ;                     // [FWD_NB][R][NT][4]
+  constexpr bool RM = fwd_rank_major<KH, R, FLAT, MAXT, CNT>();
+  float* part = reinterpret_cast<float*>(smem4);           // [2][R][NW][KQ]; RM: [2][16 ranks][4 waves]
+  static_assert(!XW || (R == 1 && MAXT == 256 && !FLAT), "the x-projection wave's instantiations");
+  constexpr int NB = XW ? FWD_XNB : FWD_NB;                // depth of the gx ring
+  const int NTS = XW ? FWD_XNTS : NT;                      // thread slots a ring slot / an out-stage buffer is laid out for
+  float* gxs = part + fwd_part_floats<KH, R, FLAT, MAXT, CNT>(NW);   // [NB][R][NTS][4]
   // out-stage, structure of arrays: [2][ R x NT x (i f o n) | R x NT x (c h) | R x NT x 2 spare ].  As one 32-byte record per
   // thread the 16-byte and 8-byte accesses hit every bank 2 and 4 times (rocprofv3: 42 % of the kernel's LDS cycles were
   // bank conflicts, profiles/r02_pmc_util.json); contiguous 16- and 8-byte elements are conflict-free
-  float* outs = gxs + FWD_NB * R * NT * 4;
-  float* zero4 = outs + 2 * R * NT * 8 + 256;              // 4 zero floats (after the spare kilobyte)
+  float* outs = gxs + NB * R * NTS * 4;
+  float* zero4 = outs + 2 * R * NTS * 8 + 256;             // 4 zero floats (after the spare kilobyte)
   if (tid < 4) zero4[tid] = 0.f;
 
   if (mover) {
@@ -365,8 +387,8 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
     constexpr int NDMA = R * MAXS;
     constexpr int DEPTH = (2 * NDMA <= 63) ? 2 : 1;      // segments of DMAs allowed in flight
     constexpr int DIST = DEPTH + 2;                      // issue distance in steps
-    static_assert(DIST < FWD_NB, "gx ring too shallow");
-    float* spare = outs + 2 * R * NT * 8;   // 256 floats
+    static_assert(DIST < NB && (!XW || (NB & (NB - 1)) == 0), "gx ring too shallow");
+    float* spare = outs + 2 * R * NTS * 8;   // 256 floats
     int row[R];
     bool rok[R];
 #pragma unroll
@@ -380,20 +402,20 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
             (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
         float* xlds = zero4 + 4;
         switch ((g.I + 3) / 4) {
-          case 1: xwave_role<4>(ka, gxs, xlds, row[0], FWD_NB); break;
-          case 2: xwave_role<8>(ka, gxs, xlds, row[0], FWD_NB); break;
+          case 1: xwave_role<4>(ka, gxs, xlds, row[0]); break;
+          case 2: xwave_role<8>(ka, gxs, xlds, row[0]); break;
           case 3:
-            if (g.I == 9) xwave_role<12, 9>(ka, gxs, xlds, row[0], FWD_NB);   // UCI-HAR: nine real columns of the twelve
-            else if (g.I == 10) xwave_role<12, 10>(ka, gxs, xlds, row[0], FWD_NB);
-            else xwave_role<12>(ka, gxs, xlds, row[0], FWD_NB);
+            if (g.I == 9) xwave_role<12, 9>(ka, gxs, xlds, row[0]);   // UCI-HAR: nine real columns of the twelve
+            else if (g.I == 10) xwave_role<12, 10>(ka, gxs, xlds, row[0]);
+            else xwave_role<12>(ka, gxs, xlds, row[0]);
             break;
-          default: xwave_role<16>(ka, gxs, xlds, row[0], FWD_NB); break;
+          default: xwave_role<16>(ka, gxs, xlds, row[0]); break;
         }
         return;
       }
       auto issue = [&](int ttarget) {
         const int tc = ttarget < T ? ttarget : T - 1;
-        float* dst = gxs + (size_t)(ttarget % FWD_NB) * R * NT * 4;
+        float* dst = gxs + (size_t)(ttarget % NB) * R * NTS * 4;
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -401,7 +423,7 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
             const bool real = i < NW;
             const int i0 = real ? i : 0;
             dma16(a.gx + ((size_t)tc * sstride + (size_t)row[r] * NT + lane + 64 * i0) * 4,
-                  real ? dst + ((size_t)r * NT + 64 * i0) * 4 : spare);
+                  real ? dst + ((size_t)r * NTS + 64 * i0) * 4 : spare);
           }
       };
       for (int s0 = 0; s0 < DIST; ++s0) issue(s0);           // targets 0 .. DIST-1
@@ -449,7 +471,7 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
       const int s = (g.G == 2 && rr >= g.off1) ? 1 : 0;
       const int w0 = ((j + s) % g.G) * W;
       qv[q] = in && train && (blockIdx.x * R + r) < B;
-      qsrc[q] = (unsigned)((r * NW + w0) * KQ + rr);
+      qsrc[q] = RM ? (unsigned)(rr * 4 + w0) : (unsigned)((r * NW + w0) * KQ + rr);
       qdst[q] = (unsigned)((blockIdx.x * R + r) * GK + jr);
     }
     // One segment of the storer: out-stage of step td -> y / tape (td < 0: nothing yet), Q[tq] and, with the
@@ -465,8 +487,8 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
       // back to normal before the stores: 0.1566 -> 0.1554 ms per step same-box ((git c7e095c) tools/sessions/r03yc.sh)
       __builtin_amdgcn_s_setprio(3);
       const int tdc = td < 0 ? 0 : td, tqc = tq < 0 ? 0 : tq;
-      const float* src = outs + (size_t)(tdc & 1) * R * NT * 8;
-      const float* qsrc_ = part + (size_t)(tqc & 1) * R * NW * KQ;
+      const float* src = outs + (size_t)(tdc & 1) * R * NTS * 8;
+      const float* qsrc_ = part + (RM ? (size_t)(tqc & 1) * 64 : (size_t)(tqc & 1) * R * NW * KQ);
       float4 g4[R][MAXS];
       float2 ch[R][MAXS];
       float v[QE][MAXS];
@@ -476,13 +498,13 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
 #pragma unroll
         for (int i = 0; i < MAXS; ++i) {
           const int slot = lane + 64 * (i < NW ? i : 0);
-          g4[r][i] = ld4(src + ((size_t)r * NT + slot) * 4);
-          ch[r][i] = *reinterpret_cast<const float2*>(src + (size_t)R * NT * 4 + ((size_t)r * NT + slot) * 2);
+          g4[r][i] = ld4(src + ((size_t)r * NTS + slot) * 4);
+          ch[r][i] = *reinterpret_cast<const float2*>(src + (size_t)R * NTS * 4 + ((size_t)r * NTS + slot) * 2);
         }
 #pragma unroll
       for (int q = 0; q < QE; ++q)
 #pragma unroll
-        for (int w = 0; w < MAXS; ++w) v[q][w] = qsrc_[qsrc[q] + (w < W ? w : 0) * KQ];
+        for (int w = 0; w < MAXS; ++w) v[q][w] = qsrc_[qsrc[q] + (w < W ? w : 0) * (RM ? 1 : KQ)];
       if constexpr (XW) qxv = qxs[(tqc & 1) * 32 + (lane & 31)];
       __builtin_amdgcn_s_setprio(0);
       if (td >= 0) {
@@ -638,6 +660,17 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
     const int q0 = FLATQ ? (lane >> 5) : grp;   // which rank-space vector this lane helps to sum
     rdoff = (w < CNT && cc < NC) ? ((((q0 + s) % g.G) * W + w) * KQ + 4 * cc) : -1;
   }
+  // RM: lane i of a row sums rank i.  With two groups (then CNT <= 2) the rank may come from the second group's waves, columns
+  // W .. 2 W - 1 (the choice per 4-rank chunk, as above); with one group the columns past NW are zero, once and for all.
+  static_assert(!RM || FASTQ16, "rank-major partials replace the 16-lane butterfly");
+  bool rmsel = false;
+  if constexpr (RM) {
+    const int li = lane & 15;
+    const int s = (g.G == 2 && 4 * (li >> 2) >= g.off1) ? 1 : 0;
+    rmsel = ((grp + s) % g.G) != 0;
+    if (wave == 0 && lane < 16)
+      for (int w = NW; w < 4; ++w) part[lane * 4 + w] = 0.f, part[64 + lane * 4 + w] = 0.f;
+  }
 
   float h[R], c[R];
 #pragma unroll
@@ -650,8 +683,8 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
     if (train) a.cs[(size_t)row * NT + tid] = c[r];  // tape slice 0 = c_{-1}
   }
 
-  for (int t = 0; t < T; ++t) {
-    const int buf = t & 1;
+  // One time step t, named by what it addresses: ring = the gx ring slot of step t, buf = t & 1.
+  auto step = [&](const int ring, const int buf) __attribute__((always_inline)) {
     // ---- 1. rank-space reduce of h_{t-1}
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -662,20 +695,39 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
         float a0 = 0.f, a1 = 0.f;
         fmac_ror_x16(a0, a1, hv, &ur[p * 16]);
         const float s = rowsum4(a0 + a1);
-        if (lane < 16) part[((buf * R + r) * NW + wave) * KQ + p * 16 + lane] = s;
+        if constexpr (RM) {
+          if (lane < 16) part[buf * 64 + lane * 4 + wave] = s;
+        } else {
+          if (lane < 16) part[((buf * R + r) * NW + wave) * KQ + p * 16 + lane] = s;
+        }
       }
     }
     // ---- 2. barrier(t): partials of step t, gx ring slot t and the previous out-stage are published
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     // ---- 3. expand + gates
-    const float* gxt = gxs + (size_t)(t % FWD_NB) * R * NT * 4;
-    float* ot = outs + (size_t)buf * R * NT * 8;
+    const float* gxt = gxs + (size_t)ring * R * NTS * 4;
+    float* ot = outs + (size_t)buf * R * NTS * 8;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const float* src = part + (size_t)(buf * R + r) * NW * KQ;
-      const float4 gx4 = ld4(gxt + ((size_t)r * NT + tid) * 4);
+      const float4 gx4 = ld4(gxt + ((size_t)r * NTS + tid) * 4);
       float4 q[NC], q2[FLAT ? NC : 1];
-      if constexpr (FASTQ) {
+      if constexpr (RM) {
+        // the sum in the order the butterfly had: (w0 + w2) + (w1 + w3), absent waves zero (class_sum16<4>: first the lane eight
+        // places on, then the one four places on - the lanes of waves 2 and then 1 / 3 under either direction of the rotation)
+        const float4 v = ld4(part + buf * 64 + (lane & 15) * 4);
+        float tot;
+        if constexpr (CNT >= 3) {
+          tot = (v.x + v.z) + (v.y + v.w);
+        } else {
+          const float a0 = CNT == 1 ? (rmsel ? v.y : v.x) : (rmsel ? v.z : v.x);
+          const float a1 = CNT == 1 ? 0.f : (rmsel ? v.w : v.y);
+          tot = (a0 + 0.f) + (a1 + 0.f);
+        }
+#pragma unroll
+        for (int cc = 0; cc < NC; ++cc)
+          q[cc] = make_float4(bcast_lane(tot, 4 * cc), bcast_lane(tot, 4 * cc + 1), bcast_lane(tot, 4 * cc + 2), bcast_lane(tot, 4 * cc + 3));
+      } else if constexpr (FASTQ) {
         const float4 v = ld4(rdoff >= 0 ? src + rdoff : zero4);
         float sx = class_sum16<NCP>(v.x), sy = class_sum16<NCP>(v.y);
         float sz = class_sum16<NCP>(v.z), sw = class_sum16<NCP>(v.w);
@@ -726,10 +778,30 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
       const f32x2 pre01 = p01a + p01b, pre23 = p23a + p23b;
       const CellFwd cell = cell_fwd(pre01.x, pre01.y, pre23.x, pre23.y, c[r]);
       c[r] = cell.c, h[r] = cell.h;
-      st4(ot + ((size_t)r * NT + tid) * 4, cell.gates);
-      *reinterpret_cast<float2*>(ot + (size_t)R * NT * 4 + ((size_t)r * NT + tid) * 2) = make_float2(c[r], h[r]);
+      st4(ot + ((size_t)r * NTS + tid) * 4, cell.gates);
+      *reinterpret_cast<float2*>(ot + (size_t)R * NTS * 4 + ((size_t)r * NTS + tid) * 2) = make_float2(c[r], h[r]);
+    }
+  };
+  // The headline's instantiation: whole periods of the ring first, t = 8 k .. 8 k + 7 with every slot and buffer a constant (every
+  // LDS address of the step a loop-invariant per-thread base plus an immediate, no index arithmetic, no loop-carried register
+  // copies), then the T mod 8 steps that remain; every other instantiation takes slot and buffer from t.
+  // (Unrolled in the headline's instantiation alone - ranks up to 16, three waves: eight copies of the step in every XW
+  //  instantiation would take the library past the size it is held to.)
+  int t = 0;
+  if constexpr (XW && KH == 16 && CNT == 3) {
+    static_assert(FWD_XNB == 8, "the unrolled period below");
+    for (; t + FWD_XNB <= T; t += FWD_XNB) {
+      step(0, 0);
+      step(1, 1);
+      step(2, 0);
+      step(3, 1);
+      step(4, 0);
+      step(5, 1);
+      step(6, 0);
+      step(7, 1);
     }
   }
+  for (; t < T; ++t) step(XW ? (t & (FWD_XNB - 1)) : t % FWD_NB, t & 1);
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // barrier(T): last out-stage published
 
 #pragma unroll
@@ -744,7 +816,7 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
     {   // classifier on the final hidden state (one scalar load and out without one; a flag in FwdArgs instead cost the
         // recurrent loop 5 us: one more live scalar)
       typedef __attribute__((address_space(3))) float lds_f;
-      const float* chp = outs + (size_t)((T - 1) & 1) * R * NT * 8 + (size_t)R * NT * 4;
+      const float* chp = outs + (size_t)((T - 1) & 1) * R * NTS * 8 + (size_t)R * NTS * 4;
       head_epilogue((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr(), (const lds_f*)chp,
                     (int)blockIdx.x, wave, (lds_f*)part);   // (the partials' slots: nothing reads them after barrier(T))
       ce_epilogue((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr(), (int)blockIdx.x, wave, (lds_f*)part);
@@ -754,18 +826,24 @@ __global__ void __launch_bounds__(VG_REC_BOUNDS) rec_fwd_kernel(VGeo g, FwdArgs 
 
 template <int KH, int R, bool FLAT, int MAXT, int CNT>
 static int fwd_launch_one(const VGeo& g, const FwdArgs& a, const XwArgs& xw, hipStream_t s) {
-  constexpr int KQ = (KH + 15) / 16 * 16;
   if (a.xwave != 0) {
     if constexpr (R == 1 && MAXT == 256 && !FLAT) {
-      const size_t ldsx = sizeof(float) * ((size_t)2 * g.NW * KQ + (size_t)FWD_NB * g.NT * 4 + (size_t)2 * g.NT * 8 + 256 + 4 +
-                                           xwave_lds_floats() + ((a.xwave & 2) != 0 ? (size_t)(4 * g.I + 4) * g.NT : 0));
-      hipLaunchKernelGGL((rec_fwd_kernel<KH, R, FLAT, MAXT, CNT, true>), dim3(g.nwg), dim3(g.NT + 128), ldsx, s, g, a, xw);
+      // (ring and out-stage laid out for FWD_XNTS thread slots: the kernel's NB / NTS)
+      const size_t ldsx = sizeof(float) * (fwd_part_floats<KH, R, FLAT, MAXT, CNT>(g.NW) + (size_t)FWD_XNB * FWD_XNTS * 4 + (size_t)2 * FWD_XNTS * 8 +
+                                           256 + 4 + xwave_lds_floats() + ((a.xwave & 2) != 0 ? (size_t)(4 * g.I + 4) * g.NT : 0));
+      auto kernx = rec_fwd_kernel<KH, R, FLAT, MAXT, CNT, true>;
+      if (g.NT > FWD_XNTS) return -3;
+      if (ldsx > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx);
+        if (e != hipSuccess) return (int)e;
+      }
+      hipLaunchKernelGGL(kernx, dim3(g.nwg), dim3(g.NT + 128), ldsx, s, g, a, xw);
       return (int)hipGetLastError();
     } else {
       return -3;
     }
   }
-  const size_t lds = sizeof(float) * ((size_t)2 * R * g.NW * KQ + (size_t)FWD_NB * R * g.NT * 4 + (size_t)2 * R * g.NT * 8 + 256 + 4);
+  const size_t lds = sizeof(float) * (fwd_part_floats<KH, R, FLAT, MAXT, CNT>(g.NW) + (size_t)FWD_NB * R * g.NT * 4 + (size_t)2 * R * g.NT * 8 + 256 + 4);
   auto kern = rec_fwd_kernel<KH, R, FLAT, MAXT, CNT>;
   if (lds > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),

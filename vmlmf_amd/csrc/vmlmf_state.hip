@@ -58,7 +58,7 @@ const Switch g_switches[] = {
     {"VMLMF_WRIDE", nullptr, 1, ENV_ON, &g_wride},
     {"VMLMF_WRIDE_K", nullptr, 32, ENV_POS, &g_wride_k},
     {"VMLMF_WRIDE_MAXB", nullptr, 64, ENV_POS, &g_wride_maxb},
-    {"VMLMF_WRIDE_LAG", nullptr, 3, ENV_POS, &g_wride_lag},
+    {"VMLMF_WRIDE_LAG", nullptr, WR_LAG_DEFAULT, ENV_POS, &g_wride_lag},
     {"VMLMF_WRIDE_RC", nullptr, 32, ENV_POS, &g_wride_rc},
     // row-block MFMA kernels (vmlmf_rb.hip).  rb_min_batch 0 = never: measured the one-row-per-CU kernels win
     // at every batch up to 2048 - sixteen rows' tape traffic through ONE CU's memory pipe costs more than the MFMAs save
