@@ -238,7 +238,15 @@ typedef struct vmlmf_ce {
  * multiplies it by the same factors, regenerated from (state, site) - no mask tensor, no launch.  The factors are a pure function of
  * (state[0] = seed, state[1] = offset, site, position t*B + b, column): Philox4x32-10, csrc/vmlmf_dropout.h; vmlmf_dropout_factors()
  * returns them as a tensor (tests: the oracle multiplies by it).  Only layers for which vmlmf_dropout_fused() is 1; others:
- * VMLMF_E_UNSUPPORTED, use vmlmf_dropout_apply behind the layer. */
+ * VMLMF_E_UNSUPPORTED, use vmlmf_dropout_apply behind the layer.
+ * Locked (variational) dropout (Gal & Ghahramani; AWD-LSTM's LockedDropout; docs/design/lm_locked.md; ABI 13 still: a flag bit and
+ * new symbols only): a site with VMLMF_SITE_LOCKED set draws ONE mask per forward pass, shared by every time step - the counter's
+ * position word is the batch row b where the per-element scheme has t*B + b.  The site word enters the Philox counter AS PASSED,
+ * flag included, so the locked stream of a site is apart from its per-element stream.  Entries that know B take the flag
+ * (vmlmf_dropout.site of vmlmf_seq_forward_ex / _backward_ex and of vmlmf_stack_layer.drop, vmlmf_actreg_forward / _backward);
+ * entries that see R flat rows refuse it with VMLMF_E_BADARG, nothing launched - their forms with an explicit B are
+ * vmlmf_dropout_apply_locked, vmlmf_dropout_factors_locked, vmlmf_embed_dropout_forward_lk and vmlmf_embed_backward_lk. */
+#define VMLMF_SITE_LOCKED ((int32_t)(-2147483647 - 1)) /* bit 31: clear in every other legal site (0 .. layers, _SITE_WORD, _SITE_SAMPLE) */
 typedef struct vmlmf_dropout {
   float p;                   /* drop probability, [0, 1)                                                                     */
   int32_t site;              /* which dropout of the network (a different stream of factors per site)                       */
@@ -464,6 +472,12 @@ int vmlmf_embed_dropout_forward(int R, int H, int V, const int64_t *tokens, cons
                                 const int64_t *state, int site, void *stream);
 int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, void *scratch,
                                  size_t scratch_bytes, float p, const int64_t *state, int site, void *stream);
+/* The same over R = T*B time-major rows under a LOCKED mask (VMLMF_SITE_LOCKED above): row r takes the factors of batch row r % B.
+ * The flag is set in the site word whether or not the caller set it.  B < 1 or R % B != 0: VMLMF_E_BADARG.  A thread of the apply /
+ * factors launch keeps its (batch row, four columns) for four time steps and draws once. */
+int vmlmf_dropout_apply_locked(int64_t R, int B, int H, const float *x, float *y, float p, const int64_t *state, int site, void *stream);
+int vmlmf_dropout_factors_locked(const vmlmf_desc *d, int64_t R, int B, int H, float p, const int64_t *state, int site, float *factors,
+                                 void *stream);
 int vmlmf_embed_backward(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, void *scratch,
                          size_t scratch_bytes, void *stream);
 /* The table that is embedding AND vocabulary projection (weight tying: Press & Wolf; Inan et al.; AWD-LSTM's --tied), and
@@ -490,6 +504,12 @@ int vmlmf_embed_dropout_forward_ex(int R, int H, int V, const int64_t *tokens, c
                                    const int64_t *state, int site, void *stream);
 int vmlmf_embed_backward_ex(int R, int H, int V, const int64_t *tokens, const float *dy, float *dweight, int accumulate, void *scratch,
                             size_t scratch_bytes, float p, float word_p, const int64_t *state, int site, void *stream);
+/* The _ex contract with the element factors LOCKED over the R = T*B time-major positions: f[r][n] is drawn with counter (r % B, n >> 2,
+ * site | VMLMF_SITE_LOCKED, offset low word); the word factors are as above.  B < 1 or R % B != 0: VMLMF_E_BADARG. */
+int vmlmf_embed_dropout_forward_lk(int R, int B, int H, int V, const int64_t *tokens, const float *weight, float *out, float p,
+                                   float word_p, const int64_t *state, int site, void *stream);
+int vmlmf_embed_backward_lk(int R, int B, int H, int V, const int64_t *tokens, const float *dy, float *dweight, int accumulate,
+                            void *scratch, size_t scratch_bytes, float p, float word_p, const int64_t *state, int site, void *stream);
 /* Activation regularisation of the LM's top layer (AR / TAR of Merity, Keskar, Socher 2018: `alpha * dropped_h.pow(2).mean() +
  * beta * (raw_h[1:] - raw_h[:-1]).pow(2).mean()`; docs/design/lm_actreg.md) with that site's dropout in the same pass.  (ABI 13
  * still: new symbols only.)  raw (T, B, H) fp32, time-major; f the factors of (state, site, p) - vmlmf_dropout_factors(d, ...), d ==

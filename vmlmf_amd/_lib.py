@@ -28,6 +28,7 @@ DTYPES = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 E_BADARG, E_SHAPE, E_UNSUPPORTED, E_WORKSPACE, E_COMM, E_PROTOCOL = -1, -2, -3, -4, -5, -6
 SUM, AVG = 0, 1
 ACTREG_STATS = 8           # VMLMF_ACTREG_STATS: penalty, B AR, B TAR, the two gradient coefficients, N_ar, N_tar, 0
+SITE_LOCKED = -(1 << 31)   # VMLMF_SITE_LOCKED: bit 31 of a site word (as the int32 the C ABI takes) - locked (variational) factors
 SITE_SAMPLE = 0x53414D50   # VMLMF_SITE_SAMPLE: the token sampler's Philox site (vmlmf_lm_sample); dropout sites are 0 .. layers
 COMM_ID_BYTES = 128
 P2P_HANDLE_BYTES = 64
@@ -153,10 +154,14 @@ SYMBOLS = {
     "vmlmf_dropout_advance": (_i, [_vp, _vp, _vp]),
     "vmlmf_dropout_apply": (_i, [ctypes.c_int64, _i, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_dropout_factors": (_i, [ctypes.POINTER(Desc), ctypes.c_int64, _i, ctypes.c_float, _vp, _i, _vp, _vp]),
+    "vmlmf_dropout_apply_locked": (_i, [ctypes.c_int64, _i, _i, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_dropout_factors_locked": (_i, [ctypes.POINTER(Desc), ctypes.c_int64, _i, _i, ctypes.c_float, _vp, _i, _vp, _vp]),
     "vmlmf_embed_dropout_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_embed_dropout_backward": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_embed_dropout_forward_ex": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_embed_backward_ex": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_embed_dropout_forward_lk": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
+    "vmlmf_embed_backward_lk": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, ctypes.c_float, ctypes.c_float, _vp, _i, _vp]),
     "vmlmf_actreg_scratch_floats": (_sz, [_i, _i, _i]),
     "vmlmf_actreg_forward": (_i, [_i, _i, _i, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _i,
                                   ctypes.POINTER(Desc), _vp, _vp, _vp, _vp]),

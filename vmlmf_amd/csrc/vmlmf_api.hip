@@ -377,10 +377,10 @@ int backward_tail(const VGeo& g, const LayerPlan& pl, const Layout& L, const vml
   return run(SL_FINISH, s, "finish", [&] { return launch_finish(g, to_refp(p), ws + L.b_cgrad, og, hb, s, health_word(s)); });
 }
 
-int site_drop(const vmlmf_dropout* dr, bool forward, DropArgs* out) {
+int site_drop(const vmlmf_dropout* dr, bool forward, int B, DropArgs* out) {
   memset(out, 0, sizeof(*out));
   if (dr == nullptr) return 0;
-  const int rc = drop_args(dr->p, dr->state, dr->site, forward ? dr->y_dropped : nullptr, out);
+  const int rc = drop_args(dr->p, dr->state, dr->site, forward ? dr->y_dropped : nullptr, out, B);
   if (rc != 0) return rc;
   if (dr->state == nullptr || (forward && dr->y_dropped == nullptr)) return fail(VMLMF_E_BADARG, "dropout: null state / y_dropped");
   return 0;
@@ -557,7 +557,7 @@ static int head_and_ce_after(const VGeo& g, const vmlmf_head* head, const vmlmf_
 
 // vmlmf_dropout of a call -> kernel arguments (vmlmf_dropout.h); rc != 0: bad arguments / a layer whose kernels do not take it
 static int make_drop(const vmlmf_dropout* dr, const VGeo& g, bool forward, DropArgs* out) {
-  const int rc = site_drop(dr, forward, out);
+  const int rc = site_drop(dr, forward, g.B, out);
   if (rc != 0 || dr == nullptr || drop_fused(g)) return rc;
   return fail(VMLMF_E_UNSUPPORTED, "dropout inside the layer's launches: row-block layers in the time-major layout (vmlmf_dropout_fused)");
 }

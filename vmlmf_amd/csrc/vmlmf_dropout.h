@@ -7,6 +7,9 @@
 //   counter = (position, column >> 2, site, offset low word), key = (seed low word, seed high word + offset high word)
 //   element (position, column) is DROPPED iff word[column & 3] < thresh, thresh = round(p 2^32); kept values are scaled by 1/(1-p)
 //   position = t B + b (the row of the flattened (T, B) grid), site = 0 for the embedding's output, l + 1 for layer l's
+//              locked (variational) dropout, DropArgs::period == B > 0: position = b for every time step - ONE mask per forward
+//              pass, shared by every t (docs/design/lm_locked.md); drop_position below is the one place that says so.  Its site
+//              word carries VMLMF_SITE_LOCKED, so a site's locked stream is not its per-element stream
 //   column   = the hidden unit, or - inside the row-block kernels - the unit's thread slot (vmlmf_geo.h: group g's units start at
 //              slot 64 W g, a multiple of four, so the four units a lane owns are one call; DropCols below is that map)
 // (seed, offset) live in device memory: a captured graph replays with fresh masks because vmlmf_dropout_advance - a node of the
@@ -20,7 +23,7 @@ struct DropArgs {
   float* yd;                         // forward of a layer: the dropped copy of y (same layout)
   unsigned thresh;                   // dropped iff word < thresh
   float scale;                       // 1 / (1 - p)
-  int site, pad;
+  int site, period;                  // period: 0 per-element factors, B > 0 locked ones (drop_position)
 };
 // hidden unit -> column of the counter: (n / Hg) * gstride + n % Hg; identity: Hg = H, gstride = 0
 struct DropCols {
@@ -54,6 +57,17 @@ __device__ __forceinline__ void drop_factors(const DropKey& k, const unsigned th
 #pragma unroll
   for (int i = 0; i < 4; ++i) f[i] = w[i] < thresh ? 0.f : scale;
 }
+
+// The counter's position word, for every caller of drop_factors: the row t B + b of the flattened (T, B) grid per element (period ==
+// 0: the bits of every release before `period` existed), the batch row b alone under a locked mask (period == B).  The recurrent
+// kernels know (t, b); the flat-row kernels know r = t B + b.
+// A kernel that walks time steps forms t's stride once, in front of its loop (B, or 0 under a locked mask), so a step's position
+// costs what it cost before there was a period.
+__device__ __forceinline__ int drop_tstride(const int period, const int B) { return period != 0 ? 0 : B; }
+__device__ __forceinline__ unsigned drop_position(const int tstride, const int t, const int b) {
+  return (unsigned)t * (unsigned)tstride + (unsigned)b;   // (unsigned: the host admits T B up to 2^32 positions)
+}
+__device__ __forceinline__ unsigned drop_position(const int period, const unsigned r) { return period != 0 ? r % (unsigned)period : r; }
 
 // four neighbouring columns of a row: one 16-byte access where the address allows it, two 8-byte ones where it is 8 bytes off (H =
 // 650: every second position), by element for a row's tail or an odd width; columns behind the row read as zero

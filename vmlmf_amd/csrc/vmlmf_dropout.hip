@@ -17,16 +17,35 @@ __global__ void drop_advance_kernel(unsigned long long* state, unsigned long lon
   state[1] = off + 1ull;
 }
 
-// one thread per four columns of a position; MODE 0: y = x * factor, MODE 1: y = factor, MODE 2: y = w[tokens[position]] * factor
-template <int MODE>
-__global__ void __launch_bounds__(256) drop_rows_kernel(long long R, int H, int V, DropArgs d, DropCols cm, const float* __restrict__ x,
-                                                        const long long* __restrict__ tokens, float* __restrict__ y) {
-  const int quads = (H + 3) >> 2;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= R * quads) return;
-  const long long r = i / quads;
-  const int n0 = (int)(i - r * quads) * 4;
-  const DropKey k = drop_key(d);
+// the factor of one column on a layer's map (group layers: a call per column; kept out of line, the library is held to a size)
+__device__ __noinline__ float mapped_factor(const DropKey k, const unsigned thresh, const float scale, const DropCols cm, const unsigned r, const int n) {
+  const int col = (n / cm.Hg) * cm.gstride + n % cm.Hg;
+  float w[4];
+  drop_factors(k, thresh, scale, r, (unsigned)(col >> 2), w);
+  return w[col & 3];
+}
+// the factors of columns n0 .. n0 + 3 at position r: one call on the identity map, a call per column on a layer's map
+__device__ __forceinline__ void quad_factors(const DropKey& k, const DropArgs& d, const DropCols& cm, const unsigned r, const int n0, const int H,
+                                             float (&f)[4]) {
+  if (cm.gstride == 0 || cm.Hg >= H) {
+    drop_factors(k, d.thresh, d.scale, r, (unsigned)(n0 >> 2), f);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) f[e] = mapped_factor(k, d.thresh, d.scale, cm, r, n0 + e < H ? n0 + e : H - 1);
+}
+
+// One thread per four columns of a position; mode 0: y = x * factor, mode 1: y = factor, mode 2: y = w[tokens[position]] * factor
+// (a uniform branch of one kernel: the library is held to a size).
+// Under a locked mask (d.period == B; docs/design/lm_locked.md) a thread keeps its (batch row, four columns) for DR_TC time steps
+// and draws once: the factors do not depend on t.  Per element (d.period == 0) the walk is one position long.
+constexpr int DR_TC = 4;
+__host__ __device__ inline long long drop_rows_threads(long long R, int quads, int period) {
+  return period != 0 ? (long long)period * ((R / period + DR_TC - 1) / DR_TC) * quads : R * quads;
+}
+// one position's four columns: y = x * f / f / w[token] * f
+__device__ __forceinline__ void drop_row(const int MODE, const long long r, const int n0, const int H, const int V, const float (&f)[4],
+                                         const float* __restrict__ x, const long long* __restrict__ tokens, float* __restrict__ y) {
   const float* src = x;
   if (MODE == 2) {
     long long t = tokens[r];
@@ -36,35 +55,40 @@ __global__ void __launch_bounds__(256) drop_rows_kernel(long long R, int H, int 
     src = x + (size_t)r * H;
   }
   float* dst = y + (size_t)r * H;
-  const bool ident = cm.gstride == 0 || cm.Hg >= H;
-  if (ident) {   // one call for the thread's four columns; 16-byte accesses where the rows allow them
-    float f[4];
-    drop_factors(k, d.thresh, d.scale, (unsigned)r, (unsigned)(n0 >> 2), f);
-    if ((H & 3) == 0) {
-      float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
-      if (MODE != 1) v = *reinterpret_cast<const float4*>(src + n0);
-      *reinterpret_cast<float4*>(dst + n0) = make_float4(v.x * f[0], v.y * f[1], v.z * f[2], v.w * f[3]);
-    } else {   // (H = 650 of the PTB network: rows start 8 bytes off)
-      float v[4];
+  if ((H & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {   // 16-byte accesses where the rows allow them
+    float4 v = make_float4(1.f, 1.f, 1.f, 1.f);
+    if (MODE != 1) v = *reinterpret_cast<const float4*>(src + n0);
+    *reinterpret_cast<float4*>(dst + n0) = make_float4(v.x * f[0], v.y * f[1], v.z * f[2], v.w * f[3]);
+  } else {   // (H = 650 of the PTB network: rows start 8 bytes off)
+    float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (MODE != 1 && n0 + e < H) ? src[n0 + e] : 1.f;
+    for (int e = 0; e < 4; ++e) v[e] = (MODE != 1 && n0 + e < H) ? src[n0 + e] : 1.f;
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n0 + e < H) dst[n0 + e] = v[e] * f[e];
-    }
+    for (int e = 0; e < 4; ++e)
+      if (n0 + e < H) dst[n0 + e] = v[e] * f[e];
+  }
+}
+__global__ void __launch_bounds__(256) drop_rows_kernel(const int MODE, long long R, int H, int V, DropArgs d, DropCols cm, const float* __restrict__ x,
+                                                        const long long* __restrict__ tokens, float* __restrict__ y) {
+  const int quads = (H + 3) >> 2;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  float f[4];   // (a layer's map - what a row-block layer's kernels apply, as a tensor -: a call per column)
+  if (d.period == 0) {   // per element: the thread's one position, straight through (the path every release had)
+    if (i >= R * quads) return;
+    const long long r = i / quads;
+    const int n0 = (int)(i - r * quads) * 4;
+    quad_factors(drop_key(d), d, cm, drop_position(0, (unsigned)r), n0, H, f);
+    drop_row(MODE, r, n0, H, V, f, x, tokens, y);
     return;
   }
-  // mapped columns (the factors a row-block layer's kernels apply, as a tensor): a call per element
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int n = n0 + e;
-    if (n >= H) break;
-    const int col = (n / cm.Hg) * cm.gstride + n % cm.Hg;
-    float f[4];
-    drop_factors(k, d.thresh, d.scale, (unsigned)r, (unsigned)(col >> 2), f);
-    const float fe = f[col & 3];
-    dst[n] = MODE == 1 ? fe : src[n] * fe;
-  }
+  if (i >= drop_rows_threads(R, quads, d.period)) return;
+  long long r = i / quads;   // = chunk B + b (below 2^32: the host refuses more positions): the chunk's first position of row b
+  const int n0 = (int)(i - r * quads) * 4;
+  r += (long long)((unsigned)r / (unsigned)d.period) * (DR_TC - 1) * d.period;
+  long long rend = r + (long long)DR_TC * d.period;
+  if (rend > R) rend = R;
+  quad_factors(drop_key(d), d, cm, drop_position(d.period, (unsigned)r), n0, H, f);
+  for (; r < rend; r += d.period) drop_row(MODE, r, n0, H, V, f, x, tokens, y);
 }
 
 // The gather under word dropout (vmlmf_embed_dropout_forward_ex; docs/design/lm_tied.md): out[r] = (w[tok_r] * fw[tok_r]) * f[r] -
@@ -93,7 +117,7 @@ __global__ void __launch_bounds__(256) embed_fwd_ex_kernel(int R, int H, int V, 
     }
     if (wd.drop) {
       float f[4];
-      drop_factors(drop_key(d), d.thresh, d.scale, (unsigned)r, (unsigned)(n0 >> 2), f);
+      drop_factors(drop_key(d), d.thresh, d.scale, drop_position(d.period, (unsigned)r), (unsigned)(n0 >> 2), f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) x[e] = __fmul_rn(x[e], f[e]);
     }
@@ -112,23 +136,6 @@ __global__ void __launch_bounds__(256) embed_fwd_ex_kernel(int R, int H, int V, 
 // in the order docs/design/lm_actreg.md counts; tests/actreg_cases.py restates both kernels in numpy's float32.
 constexpr int AR_TC = 4;
 
-// the factor of one column on a layer's map (group layers: a call per column; kept out of line, the library is held to a size)
-__device__ __noinline__ float mapped_factor(const DropKey k, const unsigned thresh, const float scale, const DropCols cm, const unsigned r, const int n) {
-  const int col = (n / cm.Hg) * cm.gstride + n % cm.Hg;
-  float w[4];
-  drop_factors(k, thresh, scale, r, (unsigned)(col >> 2), w);
-  return w[col & 3];
-}
-// the factors of columns n0 .. n0 + 3 at position r: one call on the identity map, a call per column on a layer's map
-__device__ __forceinline__ void quad_factors(const DropKey& k, const DropArgs& d, const DropCols& cm, const unsigned r, const int n0, const int H,
-                                             float (&f)[4]) {
-  if (cm.gstride == 0 || cm.Hg >= H) {
-    drop_factors(k, d.thresh, d.scale, r, (unsigned)(n0 >> 2), f);
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f[e] = mapped_factor(k, d.thresh, d.scale, cm, r, n0 + e < H ? n0 + e : H - 1);
-}
 // the workgroup's sums of a and b, left in thread 0: a wave's shuffle tree (lane l takes lane l + 32, + 16, ... + 1), then the four
 // waves in order - the same order every time
 __device__ __forceinline__ void block_sum2(float& a, float& b, float (*red)[2]) {
@@ -180,6 +187,7 @@ __global__ void __launch_bounds__(256) actreg_fwd_kernel(const ActRegArgs a) {
     }
     DropKey k = {0u, 0u, 0u, 0u};
     if (DROP) k = drop_key(a.d);
+    float f[4];   // under a locked mask (a.d.period == B) drawn at the walk's first step (t0 < T always) and kept: one call per thread
 #pragma unroll
     for (int j = 0; j < AR_TC; ++j) {
       const int t = t0 + j;
@@ -188,8 +196,7 @@ __global__ void __launch_bounds__(256) actreg_fwd_kernel(const ActRegArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = v[j][e];
         if (DROP) {
-          float f[4];
-          quad_factors(k, a.d, a.cm, (unsigned)((long long)t * a.B + b), n0, a.H, f);
+          if (j == 0 || a.d.period == 0) quad_factors(k, a.d, a.cm, drop_position(drop_tstride(a.d.period, a.B), t, b), n0, a.H, f);
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[e] = __fmul_rn(v[j][e], f[e]);
           store_quad(a.d.yd + ((size_t)t * a.B + b) * a.H + n0, valid, y);
@@ -287,12 +294,12 @@ __global__ void __launch_bounds__(256) actreg_bwd_kernel(const ActRegArgs a) {
   }
   DropKey k = {0u, 0u, 0u, 0u};
   if (DROP) k = drop_key(a.d);
+  float f[4] = {1.f, 1.f, 1.f, 1.f};   // (locked: the first step's call serves the walk, as in the forward)
 #pragma unroll
   for (int j = 0; j < AR_TC; ++j) {
     const int t = t0 + j;
     if (t >= a.T) continue;
-    float f[4] = {1.f, 1.f, 1.f, 1.f};
-    if (DROP) quad_factors(k, a.d, a.cm, (unsigned)((long long)t * a.B + b), n0, a.H, f);
+    if (DROP && (j == 0 || a.d.period == 0)) quad_factors(k, a.d, a.cm, drop_position(drop_tstride(a.d.period, a.B), t, b), n0, a.H, f);
     const bool live = t < len, prev = live && t >= 1, next = t + 1 < len;
     float out[4];
 #pragma unroll
@@ -339,12 +346,10 @@ int launch_drop_advance(unsigned long long* state, unsigned long long* snap, hip
 
 int launch_drop_rows(int mode, long long R, int H, int V, const DropArgs& d, const DropCols& cm, const float* x, const long long* tokens, float* y,
                      hipStream_t s) {
-  const long long n = R * ((H + 3) / 4);
+  const long long n = drop_rows_threads(R, (H + 3) / 4, d.period);
   if (n <= 0) return 0;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  if (mode == 0) hipLaunchKernelGGL(drop_rows_kernel<0>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
-  else if (mode == 1) hipLaunchKernelGGL(drop_rows_kernel<1>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
-  else hipLaunchKernelGGL(drop_rows_kernel<2>, grid, block, 0, s, R, H, V, d, cm, x, tokens, y);
+  hipLaunchKernelGGL(drop_rows_kernel, grid, block, 0, s, mode, R, H, V, d, cm, x, tokens, y);
   return (int)hipGetLastError();
 }
 

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void embed_bwd_drop_kernel(int R, int H, int V
           const int col = 4 * lane + 256 * c;
           if (col < H) {
             float f[4];
-            drop_factors(key, d.thresh, d.scale, (unsigned)p, (unsigned)(col >> 2), f);
+            drop_factors(key, d.thresh, d.scale, drop_position(d.period, (unsigned)p), (unsigned)(col >> 2), f);
             float4 g;
             if (vec) g = *reinterpret_cast<const float4*>(row + col);
             else g = make_float4(row[col], col + 1 < H ? row[col + 1] : 0.f, col + 2 < H ? row[col + 2] : 0.f, col + 3 < H ? row[col + 3] : 0.f);
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void embed_bwd_ex_kernel(int R, int H, int V, 
             load_quad(row + col, H - col < 4 ? H - col : 4, g);
             if (wd.drop) {
               float f[4];
-              drop_factors(key, d.thresh, d.scale, (unsigned)p, (unsigned)(col >> 2), f);
+              drop_factors(key, d.thresh, d.scale, drop_position(d.period, (unsigned)p), (unsigned)(col >> 2), f);
 #pragma unroll
               for (int e = 0; e < 4; ++e) acc[c][e] += g[e] * f[e];
             } else {

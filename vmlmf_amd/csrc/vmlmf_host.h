@@ -122,15 +122,21 @@ int check_grads(const VGeo& g, const vmlmf_grads* gr);
 int check_head(const VGeo& g, const vmlmf_head* hd, bool fwd);
 
 // ---- dropout (vmlmf_dropout.h).  One builder of the kernel arguments of a site: yd is the dropped copy a forward writes (else NULL)
-inline int drop_args(float p, const void* state, int site, float* yd, DropArgs* out) {
+// B: the batch rows of an entry that knows them - a site with VMLMF_SITE_LOCKED then draws locked factors (period = B); 0: a flat
+// entry, which refuses the flag (it would draw per-element factors under a site word that promises locked ones)
+inline int drop_args(float p, const void* state, int site, float* yd, DropArgs* out, int B = 0) {
   memset(out, 0, sizeof(*out));
   if (!(p >= 0.f && p < 1.f)) return fail(VMLMF_E_BADARG, "dropout: p must be in [0, 1)");
+  if ((site & VMLMF_SITE_LOCKED) != 0) {
+    if (B < 1) return fail(VMLMF_E_BADARG, "dropout: VMLMF_SITE_LOCKED takes an entry that knows B (the _locked / _lk forms)");
+    out->period = B;
+  }
   out->state = reinterpret_cast<const unsigned long long*>(state), out->yd = yd;
   out->thresh = drop_thresh(p), out->scale = 1.f / (1.f - p), out->site = site;
   return 0;
 }
 // ... of a layer call's or a stack layer's vmlmf_dropout (NULL: none, all-zero arguments)
-int site_drop(const vmlmf_dropout* dr, bool forward, DropArgs* out);
+int site_drop(const vmlmf_dropout* dr, bool forward, int B, DropArgs* out);
 // the layers whose own launches apply it (vmlmf_dropout_fused): row-block layers in the time-major layout
 inline bool drop_fused(const VGeo& g) { return g.rb && g.syT == (long long)g.B * g.H; }
 

@@ -131,11 +131,18 @@ int vmlmf_dropout_advance(int64_t* state, int64_t* snapshot, void* stream) {
   return hip_tail(launch_drop_advance(reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(snapshot), (hipStream_t)stream));
 }
 
+// B: 0 for the flat entries; the _locked forms' batch rows (R = T B positions, time-major), the flag set here
+static int locked_site(int64_t R, int B, int* site) {
+  if (B < 1 || R % B != 0) return fail(VMLMF_E_BADARG, "dropout: a locked mask takes B >= 1 and R = T B rows");
+  *site |= VMLMF_SITE_LOCKED;
+  return 0;
+}
+
 static int drop_rows(int mode, int64_t R, int H, int V, float p, const int64_t* state, int site, const DropCols& cm, const float* x,
-                     const int64_t* tokens, float* y, void* stream) {
+                     const int64_t* tokens, float* y, void* stream, int B = 0) {
   if (R < 0 || H < 1) return fail(VMLMF_E_BADARG, "dropout: R >= 0, H >= 1");
   DropArgs d;
-  const int rc = drop_args(p, state, site, nullptr, &d);
+  const int rc = drop_args(p, state, site, nullptr, &d, B);
   if (rc != 0) return rc;
   if (!state || !y || (mode != 1 && !x) || (mode == 2 && !tokens)) return fail(VMLMF_E_BADARG, "dropout: null pointer");
   if (R >= (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "dropout: 2^32 positions and more");
@@ -147,7 +154,13 @@ int vmlmf_dropout_apply(int64_t R, int H, const float* x, float* y, float p, con
   return drop_rows(0, R, H, 0, p, state, site, cm, x, nullptr, y, stream);
 }
 
-int vmlmf_dropout_factors(const vmlmf_desc* d, int64_t R, int H, float p, const int64_t* state, int site, float* factors, void* stream) {
+int vmlmf_dropout_apply_locked(int64_t R, int B, int H, const float* x, float* y, float p, const int64_t* state, int site, void* stream) {
+  if (int rc = locked_site(R, B, &site)) return rc;
+  const DropCols cm = {H, 0};
+  return drop_rows(0, R, H, 0, p, state, site, cm, x, nullptr, y, stream, B);
+}
+
+static int drop_factors_entry(const vmlmf_desc* d, int64_t R, int B, int H, float p, const int64_t* state, int site, float* factors, void* stream) {
   DropCols cm = {H, 0};
   if (d != nullptr) {
     VGeo g;
@@ -157,7 +170,17 @@ int vmlmf_dropout_factors(const vmlmf_desc* d, int64_t R, int H, float p, const 
     if (g.H != H) return fail(VMLMF_E_BADARG, "dropout_factors: H is not the layer's hidden size");
     if (g.rb) cm.Hg = g.Hg, cm.gstride = 64 * g.W;
   }
-  return drop_rows(1, R, H, 0, p, state, site, cm, nullptr, nullptr, factors, stream);
+  return drop_rows(1, R, H, 0, p, state, site, cm, nullptr, nullptr, factors, stream, B);
+}
+
+int vmlmf_dropout_factors(const vmlmf_desc* d, int64_t R, int H, float p, const int64_t* state, int site, float* factors, void* stream) {
+  return drop_factors_entry(d, R, 0, H, p, state, site, factors, stream);
+}
+
+int vmlmf_dropout_factors_locked(const vmlmf_desc* d, int64_t R, int B, int H, float p, const int64_t* state, int site, float* factors,
+                                 void* stream) {
+  if (int rc = locked_site(R, B, &site)) return rc;
+  return drop_factors_entry(d, R, B, H, p, state, site, factors, stream);
 }
 
 int vmlmf_embed_dropout_forward(int R, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, const int64_t* state,
@@ -182,8 +205,8 @@ int vmlmf_embed_dropout_backward(int R, int H, int V, const int64_t* tokens, con
 
 // ---- the table that is embedding and vocabulary projection at once, and word dropout (docs/design/lm_tied.md) ----
 // both probabilities checked, the element dropout's arguments and the word dropout's; the state is needed iff one of them is on
-static int embed_ex_args(float p, float word_p, const int64_t* state, int site, DropArgs* d, WordDrop* wd) {
-  int rc = drop_args(p, state, site, nullptr, d);
+static int embed_ex_args(float p, float word_p, const int64_t* state, int site, DropArgs* d, WordDrop* wd, int B = 0) {
+  int rc = drop_args(p, state, site, nullptr, d, B);
   if (rc != 0) return rc;
   if (!(word_p >= 0.f && word_p < 1.f)) return fail(VMLMF_E_BADARG, "embed: word_p must be in [0, 1)");
   wd->thresh = drop_thresh(word_p), wd->scale = 1.f / (1.f - word_p), wd->drop = p > 0.f, wd->word = word_p > 0.f;
@@ -191,27 +214,50 @@ static int embed_ex_args(float p, float word_p, const int64_t* state, int site, 
   return 0;
 }
 
-int vmlmf_embed_dropout_forward_ex(int R, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, float word_p,
-                                   const int64_t* state, int site, void* stream) {
+// the _ex entries (B == 0) and their _lk forms (B >= 1, the flag set), written once
+static int embed_forward_entry(int R, int B, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, float word_p,
+                               const int64_t* state, int site, void* stream) {
   if (R < 0 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R >= 0, H >= 1, V >= 1");
   DropArgs d;
   WordDrop wd;
-  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd)) return rc;
+  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd, B)) return rc;
   if (!tokens || !weight || !out) return fail(VMLMF_E_BADARG, "embed: null pointer");
   return hip_tail(launch_embed_fwd_ex(R, H, V, d, wd, weight, (const long long*)tokens, out, (hipStream_t)stream));
 }
 
-int vmlmf_embed_backward_ex(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, int accumulate, void* scratch,
-                            size_t scratch_bytes, float p, float word_p, const int64_t* state, int site, void* stream) {
+int vmlmf_embed_dropout_forward_ex(int R, int H, int V, const int64_t* tokens, const float* weight, float* out, float p, float word_p,
+                                   const int64_t* state, int site, void* stream) {
+  return embed_forward_entry(R, 0, H, V, tokens, weight, out, p, word_p, state, site, stream);
+}
+
+int vmlmf_embed_dropout_forward_lk(int R, int B, int H, int V, const int64_t* tokens, const float* weight, float* out, float p,
+                                   float word_p, const int64_t* state, int site, void* stream) {
+  if (int rc = locked_site(R, B, &site)) return rc;
+  return embed_forward_entry(R, B, H, V, tokens, weight, out, p, word_p, state, site, stream);
+}
+
+static int embed_backward_entry(int R, int B, int H, int V, const int64_t* tokens, const float* dy, float* dweight, int accumulate,
+                                void* scratch, size_t scratch_bytes, float p, float word_p, const int64_t* state, int site, void* stream) {
   if (R < 1 || H < 1 || V < 1) return fail(VMLMF_E_BADARG, "embed: R, H, V must be >= 1");
   if (!tokens || !dy || !dweight) return fail(VMLMF_E_BADARG, "embed: null pointer");
   DropArgs d;
   WordDrop wd;
-  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd)) return rc;
+  if (int rc = embed_ex_args(p, word_p, state, site, &d, &wd, B)) return rc;
   const int rc = launch_embed_bwd_ex(R, H, V, (const long long*)tokens, dy, dweight, accumulate, scratch, scratch_bytes, d, wd, (hipStream_t)stream);
   if (rc == -3) return fail(VMLMF_E_UNSUPPORTED, "embed_backward_ex: embedding width > 1024");
   if (rc == -4) return fail(VMLMF_E_WORKSPACE, "embed_backward_ex: scratch smaller than vmlmf_embed_backward_scratch_bytes()");
   return hip_tail(rc);
+}
+
+int vmlmf_embed_backward_ex(int R, int H, int V, const int64_t* tokens, const float* dy, float* dweight, int accumulate, void* scratch,
+                            size_t scratch_bytes, float p, float word_p, const int64_t* state, int site, void* stream) {
+  return embed_backward_entry(R, 0, H, V, tokens, dy, dweight, accumulate, scratch, scratch_bytes, p, word_p, state, site, stream);
+}
+
+int vmlmf_embed_backward_lk(int R, int B, int H, int V, const int64_t* tokens, const float* dy, float* dweight, int accumulate,
+                            void* scratch, size_t scratch_bytes, float p, float word_p, const int64_t* state, int site, void* stream) {
+  if (int rc = locked_site(R, B, &site)) return rc;
+  return embed_backward_entry(R, B, H, V, tokens, dy, dweight, accumulate, scratch, scratch_bytes, p, word_p, state, site, stream);
 }
 
 // ---- activation regularisation of the LM's top layer (vmlmf_dropout.hip; docs/design/lm_actreg.md) ----
@@ -224,7 +270,7 @@ static int actreg_args(int T, int B, int H, const float* raw, const int64_t* len
   if (T < 1 || B < 1 || H < 1) return fail(VMLMF_E_BADARG, "actreg: T, B, H must be >= 1");
   if (!(ar >= 0.f && ar < INFINITY && tar >= 0.f && tar < INFINITY)) return fail(VMLMF_E_BADARG, "actreg: ar and tar must be finite and >= 0");
   if ((long long)T * B >= (1ll << 32)) return fail(VMLMF_E_UNSUPPORTED, "actreg: 2^32 positions and more");
-  int rc = drop_args(p, p > 0.f ? state : nullptr, site, yd, &a->d);
+  int rc = drop_args(p, p > 0.f ? state : nullptr, site, yd, &a->d, B);
   if (rc != 0) return rc;
   if (raw == nullptr || (p > 0.f && state == nullptr)) return fail(VMLMF_E_BADARG, "actreg: null pointer");
   a->cm.Hg = H, a->cm.gstride = 0;

@@ -355,6 +355,7 @@ __global__ void __launch_bounds__(256) rb_fwd_kernel(VGeo g, RbGeo q, RbFwdArgs 
   const bool dropping = a.drop.state != nullptr;
   DropKey dkey = {0u, 0u, 0u, 0u};
   if (dropping) dkey = drop_key(a.drop);
+  const int dts = drop_tstride(a.drop.period, B);
   auto store_tile = [&](const int ts, const int tl, const f32x4v& ig, const f32x4v& fg, const f32x4v& og, const f32x4v& ng) {
     if (tl < nt && rok) {
       const size_t so = (size_t)ts * sstride + (size_t)row * NT + sbt[tl] + 4 * kq;
@@ -370,7 +371,7 @@ __global__ void __launch_bounds__(256) rb_fwd_kernel(VGeo g, RbGeo q, RbFwdArgs 
         if (uval[tl][reg]) yt[reg] = h[tl][reg];
       if (dropping) {   // the copy the next layer / the projection reads (vmlmf_lm.py:438-439), the lane's four units in one call
         float f[4];
-        drop_factors(dkey, a.drop.thresh, a.drop.scale, (unsigned)(ts * B + row), (unsigned)(sbt[tl] >> 2) + kq, f);
+        drop_factors(dkey, a.drop.thresh, a.drop.scale, drop_position(dts, ts, row), (unsigned)(sbt[tl] >> 2) + kq, f);
         float* yd = a.drop.yd + yo;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg)
@@ -583,6 +584,7 @@ __global__ void __launch_bounds__(256) rb_bwd_kernel(VGeo g, RbGeo q, RbBwdArgs 
   const bool dropping = a.drop.state != nullptr && has_dy;   // dy is the gradient of the DROPPED copy of y
   DropKey dkey = {0u, 0u, 0u, 0u};
   if (dropping) dkey = drop_key(a.drop);
+  const int dts = drop_tstride(a.drop.period, B);
   auto fetch_tape = [&](int t) {
     const int tc = t > 0 ? t : 0;
 #pragma unroll
@@ -599,7 +601,7 @@ __global__ void __launch_bounds__(256) rb_bwd_kernel(VGeo g, RbGeo q, RbBwdArgs 
       // here made the compiler wait for the loads above in front of the branch - with dropout off too (rb_bwd_kernel 240 -> 262 us)
       if (dropping) {
         float f[4];
-        drop_factors(dkey, a.drop.thresh, a.drop.scale, (unsigned)(tc * B + rowc), (unsigned)(sbt[tl] >> 2) + kq, f);
+        drop_factors(dkey, a.drop.thresh, a.drop.scale, drop_position(dts, tc, rowc), (unsigned)(sbt[tl] >> 2) + kq, f);
         dfn[tl] = f32x4v{f[0], f[1], f[2], f[3]};
       }
     }

@@ -176,6 +176,7 @@ __global__ void __launch_bounds__(256) rbx_fwd_kernel(VGeo g, RbGeo q, RbxFwdArg
   const bool dropping = a.drop.state != nullptr;
   DropKey dkey = {0u, 0u, 0u, 0u};
   if (dropping) dkey = drop_key(a.drop);
+  const int dts = drop_tstride(a.drop.period, B);
   // the tape of a step (activated gates, c_t, h_t = y[t] and its dropped copy), from the registers that hold them until the next
   // step's gates overwrite them: issued inside the NEXT step's exchange (rb_fwd_kernel: DEFER)
   f32x4v pg[4];
@@ -200,7 +201,7 @@ __global__ void __launch_bounds__(256) rbx_fwd_kernel(VGeo g, RbGeo q, RbxFwdArg
       }
       if (dropping) {   // the copy the layer above / the projection reads (vmlmf_lm.py:438-439), the lane's four units in one call
         float f[4];
-        drop_factors(dkey, a.drop.thresh, a.drop.scale, (unsigned)(ts * B + row), (unsigned)(sbt >> 2) + kq, f);
+        drop_factors(dkey, a.drop.thresh, a.drop.scale, drop_position(dts, ts, row), (unsigned)(sbt >> 2) + kq, f);
         float* yd = a.drop.yd + yo;
         if (pub) {
 #pragma unroll
@@ -424,6 +425,7 @@ __global__ void __launch_bounds__(256) rbx_bwd_kernel(VGeo g, RbGeo q, RbxBwdArg
   const bool dropping = a.drop.state != nullptr && has_dy;   // dy is the gradient of the DROPPED copy of y
   DropKey dkey = {0u, 0u, 0u, 0u};
   if (dropping) dkey = drop_key(a.drop);
+  const int dts = drop_tstride(a.drop.period, B);
   unsigned seen = 0;
   bool dead = false;
   auto fetch_tape = [&](int t) {
@@ -462,7 +464,7 @@ __global__ void __launch_bounds__(256) rbx_bwd_kernel(VGeo g, RbGeo q, RbxBwdArg
       }
       if (dropping) {
         float f[4];
-        drop_factors(dkey, a.drop.thresh, a.drop.scale, (unsigned)(t * B + rowc), (unsigned)(sbt >> 2) + kq, f);
+        drop_factors(dkey, a.drop.thresh, a.drop.scale, drop_position(dts, t, rowc), (unsigned)(sbt >> 2) + kq, f);
         dfn = f32x4v{f[0], f[1], f[2], f[3]};
       }
     }

@@ -218,7 +218,7 @@ static int rbx_stack_forward(const StackPlan& S, const vmlmf_stack_layer* ly, co
     float* pack = training ? rs + Lr.r_pack : wl + Lr.f_pack;
     rps[l] = to_refp(ly[l].params), packs[l] = pack, imgs[l] = pack + S.P[l].RB, fflags[l] = reinterpret_cast<unsigned*>(wl + Lr.f_flag);
     RbxLayerF& w = a.l[l];
-    if ((rc = site_drop(ly[l].drop, true, &w.drop)) != 0) return rc;
+    if ((rc = site_drop(ly[l].drop, true, S.g[0].B, &w.drop)) != 0) return rc;
     w.x = stack_input(ly, l, x);
     w.EH = pack + S.P[l].EH, w.EXT = pack + S.P[l].EXT, w.BBT = pack + S.P[l].BBT, w.img = pack + S.P[l].RB;
     w.h0 = ly[l].h0, w.c0 = ly[l].c0, w.y = ly[l].y, w.hT = ly[l].hT, w.cT = ly[l].cT;
@@ -255,7 +255,7 @@ static int rbx_stack_backward(const StackPlan& S, const vmlmf_stack_layer* ly, c
     const float* pack = rs + Lr.r_pack;
     float* wl = ws + S.ws_layer[l];
     RbxLayerB& w = a.l[L - 1 - l];   // launch position 0 is the top layer: the producer comes first in the grid
-    if ((rc = site_drop(ly[l].drop, false, &w.drop)) != 0) return rc;
+    if ((rc = site_drop(ly[l].drop, false, S.g[0].B, &w.drop)) != 0) return rc;
     w.gates = rs + Lr.r_gates, w.cs = rs + Lr.r_cs, w.EH = pack + S.P[l].EH, w.EXT = pack + S.P[l].EXT, w.img = pack + S.P[l].RB;
     w.dy = l == L - 1 ? dy : ws + S.ws_dx[l + 1];
     w.dhT = ly[l].dhT, w.dcT = ly[l].dcT, w.dh0 = ly[l].dh0, w.dc0 = ly[l].dc0;
@@ -361,7 +361,7 @@ int vmlmf_stack_forward(int L, const vmlmf_stack_layer* ly, const float* x, cons
     rps[l] = to_refp(ly[l].params), packs[l] = pack;
     WfFwdLayer& w = a.l[l];
     w.x = stack_input(ly, l, x);
-    if ((rc = site_drop(ly[l].drop, true, &a.drop[l])) != 0) return rc;
+    if ((rc = site_drop(ly[l].drop, true, S.g[0].B, &a.drop[l])) != 0) return rc;
     w.sxT = g.sxT, w.sxB = g.sxB, w.I = g.I;
     w.syT = g.syT, w.syB = g.syB, w.H = g.H, w.Hg = g.Hg;
     const bool mixed = g.KH != g.KX;   // both sides at the wider padded rank: re-laid images in the WF region
@@ -417,7 +417,7 @@ int vmlmf_stack_backward(int L, const vmlmf_stack_layer* ly, const float* x, con
       const float* pack = rs + Lr.r_pack;
       float* wl = ws + S.ws_layer[l];
       WfBwdLayer& w = a.l[L - 1 - l];   // launch position 0 is the top layer
-      if ((rc = site_drop(ly[l].drop, false, &a.drop[L - 1 - l])) != 0) return rc;
+      if ((rc = site_drop(ly[l].drop, false, S.g[0].B, &a.drop[L - 1 - l])) != 0) return rc;
       if (ly[l].drop != nullptr && S.g[0].G != 1) return fail(VMLMF_E_UNSUPPORTED, "stack: dropout inside the wavefront launches for one-group layers");
       w.gates = rs + Lr.r_gates, w.cs = rs + Lr.r_cs;
       w.dy = l == L - 1 ? dy : ws + S.ws_dx[l + 1];

@@ -65,6 +65,14 @@ __device__ __forceinline__ DropArgs wf_drop_karg(size_t off_in_args) {
   wf_copy_kernarg(&d, ka + off);
   return d;
 }
+// ... and its `period` alone, as one dword load of its own in front of the rest: read with the other seven words it made the
+// struct one eight-register tuple, and wf_bwd_kernel<24,4,1,256,false> answered with 470 more v_readlane_b32 (docs/design/lm_locked.md)
+__device__ __forceinline__ int wf_drop_period_karg(size_t off_in_args) {
+  size_t off = ((sizeof(VGeo) + 7) & ~(size_t)7) + off_in_args + offsetof(DropArgs, period);
+  asm volatile("" : "+s"(off));
+  const wkarg_c* ka = (const wkarg_c*)__builtin_amdgcn_kernarg_segment_ptr();
+  return *(const wkarg_i*)(ka + off);
+}
 __device__ __forceinline__ const void* wf_ptr_karg(size_t off_in_args) {   // one pointer of the argument block (not laundered: two registers)
   const __attribute__((address_space(4))) char* ka = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
   return *(const void* const __attribute__((address_space(4)))*)(ka + ((sizeof(VGeo) + 7) & ~(size_t)7) + off_in_args);
@@ -331,10 +339,11 @@ __global__ void __launch_bounds__(2 * MAXT + 128) wf_fwd_kernel(VGeo g, WfFwdArg
     if constexpr (G == 1) dropping = wf_ptr_karg(droff + offsetof(DropArgs, state)) != nullptr;
     auto factors = [&](int j) {
       if (dropping && j >= 0 && j < T && 4 * lane < NT) {
+        const unsigned position = drop_position(drop_tstride(wf_drop_period_karg(droff), B), j, row);
         const DropArgs dr = wf_drop_karg(droff);
         const DropKey dkey = drop_key(dr);
         float f[4];
-        drop_factors(dkey, dr.thresh, dr.scale, (unsigned)(j * B + row), (unsigned)lane, f);
+        drop_factors(dkey, dr.thresh, dr.scale, position, (unsigned)lane, f);
         st4(fring + (size_t)(j & 1) * NT + 4 * lane, make_float4(f[0], f[1], f[2], f[3]));
       }
     };
@@ -697,10 +706,11 @@ __global__ void __launch_bounds__(2 * MAXT + 128) wf_bwd_kernel(VGeo g, WfBwdArg
       const int tc = ttarget > 0 ? ttarget : 0;
       const int ring = ((ttarget % WF_BNB) + WF_BNB) % WF_BNB;
       if (dropping && 4 * lane < NT) {
+        const unsigned position = drop_position(drop_tstride(wf_drop_period_karg(droff), B), tc, row);
         const DropArgs dr = wf_drop_karg(droff);
         const DropKey dkey = drop_key(dr);
         float f[4];
-        drop_factors(dkey, dr.thresh, dr.scale, (unsigned)(tc * B + row), (unsigned)lane, f);
+        drop_factors(dkey, dr.thresh, dr.scale, position, (unsigned)lane, f);
         st4(tfac + (size_t)ring * NT + 4 * lane, make_float4(f[0], f[1], f[2], f[3]));
       }
       if (prog < (unsigned)(T - tc)) {   // dy[tc] exists once the layer above has published T - tc rows

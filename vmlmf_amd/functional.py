@@ -314,7 +314,7 @@ class VmlmfSeqFn(torch.autograd.Function):
         yd = dr = None
         if drop is not None:
             yd = torch.empty_like(y)
-            dr = _lib.Dropout(float(drop[0]), int(drop[2]), drop[1].data_ptr(), yd.data_ptr())
+            dr = _lib.Dropout(float(drop[0]), site_word(drop), drop[1].data_ptr(), yd.data_ptr())
             ex.drop = ctypes.pointer(dr)
         with _lib.on_device(dev):
             _lib.check(_lib.lib().vmlmf_seq_forward_ex(
@@ -325,7 +325,7 @@ class VmlmfSeqFn(torch.autograd.Function):
             ctx.has_h0, ctx.has_c0 = h0 is not None, c0 is not None
             ctx.has_head, ctx.has_head_b = hw is not None, hb is not None
             ctx.has_ce = dz_unit is not None
-            ctx.drop = None if drop is None else (float(drop[0]), int(drop[2]))
+            ctx.drop = None if drop is None else (float(drop[0]), site_word(drop))
             ctx.save_for_backward(x, y, reserve, *params, *([h0c] if h0 is not None else []),
                                   *([c0c] if c0 is not None else []), *([hw] if hw is not None else []),
                                   *([dz_unit] if dz_unit is not None else []), *([drop[1]] if drop is not None else []))
@@ -395,7 +395,8 @@ def vmlmf_sequence(variant, x, h0, c0, params, w_rank, u_ranks, g=1, time_major=
     default arguments, train.py:58-65) comes back as a fifth element, formed inside the same forward launch.
     drop: (p, snapshot, site) - nn.Dropout(p) behind the layer (vmlmf_lm.py:438-439) without a mask tensor: the returned y is the
     dropped activation; inside the layer's own launches where the library takes it (vmlmf_dropout_fused: the row-block kernels,
-    time-major), one launch of the package's otherwise (dropout()).  Not together with a head.
+    time-major), one launch of the package's otherwise (dropout()).  Not together with a head.  (p, snapshot, site, True): the
+    LOCKED form of that dropout - one (B, H) mask for every time step (docs/design/lm_locked.md) - in the same launches.
     """
     cfg = _layer_cfg(variant, g, w_rank, u_ranks, time_major, dtype)
     hw, hb = (None, None) if head is None else head
@@ -417,8 +418,27 @@ def vmlmf_sequence(variant, x, h0, c0, params, w_rank, u_ranks, g=1, time_major=
     else:
         out = ops.sequence(x, h0, c0, list(params), variant, g, cfg[2], list(cfg[3]), cfg[4], cfg[5], packed, hw, hb)
     if drop is not None:                    # ... and as one launch of the package's behind the layer otherwise
-        return dropout(out[0], drop[0], drop[1], drop[2]), out[1], out[2]
+        if drop_locked(drop) and not cfg[4]:                            # (a locked mask is laid over time-major rows)
+            return dropout(out[0].transpose(0, 1), drop[0], drop[1], drop[2], locked=True).transpose(0, 1), out[1], out[2]
+        return dropout(out[0], drop[0], drop[1], drop[2], locked=drop_locked(drop)), out[1], out[2]
     return out[:3 if head is None else 4 if target is None else 5]
+
+
+def locked_site(site):
+    """`site` with VMLMF_SITE_LOCKED (bit 31) set: the locked (variational) dropout of that site - one (B, H) mask shared by every
+    time step (docs/design/lm_locked.md) - for activation_regularizer(site=), the one place of this module that takes the flag in
+    the site itself as the C ABI does; dropout(), embedding_dropout() and the layers' drop tuples say `locked`."""
+    return int(site) | (1 << 31)
+
+
+def drop_locked(drop):
+    """Is a layer's drop tuple - (p, snapshot, site) or (p, snapshot, site, locked) - the locked form?"""
+    return len(drop) > 3 and bool(drop[3])
+
+
+def site_word(drop):
+    """The site of a drop tuple as the C ABI's vmlmf_dropout.site takes it: VMLMF_SITE_LOCKED (bit 31) set for the locked form."""
+    return int(drop[2]) + (_lib.SITE_LOCKED if drop_locked(drop) else 0)
 
 
 # ---- stacked layers: one wavefront launch per direction (C ABI 7: vmlmf_stack_*) ----------------------------------------
@@ -506,7 +526,7 @@ class VmlmfStackFn(torch.autograd.Function):
             ly.desc, ly.params = descs[l], ctypes.pointer(ps)
             if drops is not None and drops[l] is not None:
                 yds[l] = torch.empty_like(ys[l])
-                dr = _lib.Dropout(float(drops[l][0]), int(drops[l][2]), drops[l][1].data_ptr(), yds[l].data_ptr())
+                dr = _lib.Dropout(float(drops[l][0]), site_word(drops[l]), drops[l][1].data_ptr(), yds[l].data_ptr())
                 keep.append(dr)
                 ly.drop = ctypes.pointer(dr)
             ly.y, ly.hT, ly.cT = ys[l].data_ptr(), hc[l][0].data_ptr(), hc[l][1].data_ptr()
@@ -522,7 +542,7 @@ class VmlmfStackFn(torch.autograd.Function):
             ctx.cfg, ctx.L, ctx.nper, ctx.plan = cfg, L, nper, plan
             ctx.has_head, ctx.has_head_b = hw is not None, hb is not None
             ctx.has_h0, ctx.has_c0 = h0c is not None, c0c is not None
-            ctx.drops = None if drops is None else [None if d is None else (float(d[0]), int(d[2])) for d in drops]
+            ctx.drops = None if drops is None else [None if d is None else (float(d[0]), site_word(d)) for d in drops]
             dsaved = [] if drops is None else [t for l in range(L) if drops[l] is not None for t in (yds[l], drops[l][1])]
             ctx.save_for_backward(x, *ys, *reserves, *params, *([hw] if hw is not None else []),
                                   *([h0c] if h0c is not None else []), *([c0c] if c0c is not None else []), *dsaved)
@@ -1503,46 +1523,70 @@ class DropoutFn(torch.autograd.Function):
     regenerated in the backward (no mask is kept)."""
 
     @staticmethod
-    def forward(ctx, x, p, snap, site):
+    def forward(ctx, x, p, snap, site, locked_batch=0):
         _require_hip(x, "input")
         x = x.contiguous()
         y = torch.empty_like(x)
-        H = x.shape[-1]
-        with _lib.on_device(x.device):
-            _lib.check(_lib.lib().vmlmf_dropout_apply(x.numel() // H, H, _ptr(x), _ptr(y), float(p), snap.data_ptr(), int(site),
-                                                      _lib.raw_stream(x.device)))
         ctx.save_for_backward(snap)
-        ctx.p, ctx.site = float(p), int(site)
+        ctx.p, ctx.site, ctx.locked_batch = float(p), int(site), int(locked_batch)
+        DropoutFn.launch(ctx, snap, x, y)
         return y
 
     @staticmethod
+    def launch(ctx, snap, x, y):
+        """y = x * factor: the forward, and on the upstream gradient the backward; locked_batch = B > 0: x is (T, B, H) and the
+        factors are those of the batch row (vmlmf_dropout_apply_locked)."""
+        H = x.shape[-1]
+        lib, stream = _lib.lib(), _lib.raw_stream(x.device)
+        with _lib.on_device(x.device):
+            if ctx.locked_batch:
+                _lib.check(lib.vmlmf_dropout_apply_locked(x.numel() // H, ctx.locked_batch, H, _ptr(x), _ptr(y), ctx.p, snap.data_ptr(),
+                                                          ctx.site, stream))
+            else:
+                _lib.check(lib.vmlmf_dropout_apply(x.numel() // H, H, _ptr(x), _ptr(y), ctx.p, snap.data_ptr(), ctx.site, stream))
+
+    @staticmethod
     def backward(ctx, dy):
-        (snap,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        H = dy.shape[-1]
-        with _lib.on_device(dy.device):
-            _lib.check(_lib.lib().vmlmf_dropout_apply(dy.numel() // H, H, _ptr(dy), _ptr(dx), ctx.p, snap.data_ptr(), ctx.site,
-                                                      _lib.raw_stream(dy.device)))
-        return dx, None, None, None
+        DropoutFn.launch(ctx, ctx.saved_tensors[0], dy, dx)
+        return dx, None, None, None, None
 
 
-def dropout(x, p, snap, site):
-    """nn.Dropout(p)(x) in training mode with the package's generator: x (..., H) float32 on a HIP device."""
+def locked_dropout_stock(x, p, training=True):
+    """AWD-LSTM's LockedDropout in stock ops: one (1, B, H) mask of x (T, B, H), drawn from torch's generator, for every time step -
+    the form of CPU tensors and of Model.stock_dropout."""
+    if not training or p <= 0.0:
+        return x
+    return x * (x.new_empty(1, x.shape[1], x.shape[2]).bernoulli_(1 - p) / (1 - p))
+
+
+def dropout(x, p, snap, site, locked=False):
+    """nn.Dropout(p)(x) in training mode with the package's generator: x (..., H) float32 on a HIP device.  locked=True: locked
+    (variational) dropout of x (T, B, H) - ONE (B, H) mask for every time step (AWD-LSTM's LockedDropout; the factors of
+    dropout_factors(..., locked_batch=B)), in the same single launch per direction."""
+    if locked and x.dim() != 3:
+        raise ValueError("vmlmf_amd.dropout: a locked mask takes activations of shape (T, B, H)")
     if p <= 0.0:
         return x
     if x.dtype != torch.float32:
         raise RuntimeError("vmlmf_amd.dropout: float32 activations")
-    return DropoutFn.apply(x, p, snap, site)
+    return DropoutFn.apply(x, p, snap, site, x.shape[1] if locked else 0)
 
 
-def dropout_factors(rows, H, p, snap, site, layer_desc=None):
+def dropout_factors(rows, H, p, snap, site, layer_desc=None, locked_batch=None):
     """The (rows, H) factors (0 or 1/(1-p)) the kernels apply for (snapshot, site) - for a layer whose launches apply them
-    themselves pass its descriptor (vmlmf_dropout_factors).  The parity tests multiply a CPU restatement by this tensor."""
+    themselves pass its descriptor (vmlmf_dropout_factors).  The parity tests multiply a CPU restatement by this tensor.
+    locked_batch=B: the locked factors of rows = T B time-major positions (vmlmf_dropout_factors_locked): row r has batch row r % B's."""
     out = torch.empty((rows, H), device=snap.device, dtype=torch.float32)
+    desc = None if layer_desc is None else ctypes.byref(layer_desc)
     with _lib.on_device(snap.device):
-        _lib.check(_lib.lib().vmlmf_dropout_factors(None if layer_desc is None else ctypes.byref(layer_desc), rows, H, float(p),
-                                                     snap.data_ptr(), int(site), out.data_ptr(), _lib.raw_stream(snap.device)))
+        if locked_batch is None:
+            _lib.check(_lib.lib().vmlmf_dropout_factors(desc, rows, H, float(p), snap.data_ptr(), int(site), out.data_ptr(),
+                                                         _lib.raw_stream(snap.device)))
+        else:
+            _lib.check(_lib.lib().vmlmf_dropout_factors_locked(desc, rows, int(locked_batch), H, float(p), snap.data_ptr(), int(site),
+                                                                out.data_ptr(), _lib.raw_stream(snap.device)))
     return out
 
 
@@ -1648,12 +1692,16 @@ def activation_regularizer(raw, *, ar, tar, p=0.0, snap=None, site=0, lengths=No
     inside the backward launch.  CPU tensors and other types take activation_regularizer_stock (with p > 0 on the CPU the factors
     come from torch's generator: snap and site are not looked at).  ValueError, before any device work, for an ar or tar that is
     negative, not finite or a bool, p outside [0, 1), p > 0 without a snapshot on a HIP device, a raw that is not (T, B, H) and
-    lengths that are not (B) integers."""
+    lengths that are not (B) integers.
+    site=locked_site(i): the site's dropout is the LOCKED one (dropout(..., locked=True): one (B, H) mask for every step) - the
+    flag rides in the site word as it does in the C ABI, whose entries that know B take it; a thread of either launch then draws
+    once for its four time steps."""
     check_actreg(ar, tar)
     if not (isinstance(raw, torch.Tensor) and raw.dim() == 3 and raw.numel() > 0 and raw.is_floating_point()):
         raise ValueError("vmlmf_amd: activation_regularizer takes activations raw of shape (T, B, H)")
     T, B, H = raw.shape
     check_lengths(lengths, B, "activation_regularizer")
+    locked, site = bool(int(site) & (1 << 31)), int(site) & 0x7FFFFFFF
     p = float(p)
     if not 0.0 <= p < 1.0:
         raise ValueError(f"vmlmf_amd: p must lie in [0, 1), got {p!r}")
@@ -1662,11 +1710,14 @@ def activation_regularizer(raw, *, ar, tar, p=0.0, snap=None, site=0, lengths=No
     scale = float(B if batch_scale is None else batch_scale)
     if raw.is_cuda and raw.dtype == torch.float32:
         n = None if lengths is None else lengths.to(device=raw.device, dtype=torch.int64).contiguous()
-        yd, penalty, ar_part, tar_part = ActRegFn.apply(raw, n, snap if p > 0 else None, float(ar), float(tar), p, int(site), layer_desc, scale)
+        word = int(site) + (_lib.SITE_LOCKED if locked else 0)      # (these entries know B: the flag asks for the locked factors)
+        yd, penalty, ar_part, tar_part = ActRegFn.apply(raw, n, snap if p > 0 else None, float(ar), float(tar), p, word, layer_desc, scale)
         return yd, penalty, (ar_part, tar_part)
     factors = None
     if p > 0 and raw.is_cuda:
-        factors = dropout_factors(T * B, H, p, snap, site, layer_desc).view(T, B, H).to(raw.dtype)
+        factors = dropout_factors(T * B, H, p, snap, site, layer_desc, B if locked else None).view(T, B, H).to(raw.dtype)
+    elif p > 0 and locked:
+        factors = locked_dropout_stock(torch.ones_like(raw[:1]), p)
     elif p > 0:
         factors = torch.nn.functional.dropout(torch.ones_like(raw), p, True)
     return activation_regularizer_stock(raw, ar=ar, tar=tar, factors=factors, lengths=lengths, batch_scale=scale)
@@ -1725,19 +1776,25 @@ class EmbedExFn(torch.autograd.Function):
     head's backward - which fills the holder - before this one.  This is the one place that relies on it."""
 
     @staticmethod
-    def forward(ctx, w, tokens, p, word_p, snap, site, holder):
+    def forward(ctx, w, tokens, p, word_p, snap, site, holder, locked_batch=0):
         V, H = w.shape
         tok = tokens.reshape(-1).contiguous()
         if p > 0.0 or word_p > 0.0:
             out = torch.empty(tuple(tokens.shape) + (H,), device=w.device, dtype=torch.float32)
+            lib, stream = _lib.lib(), _lib.raw_stream(w.device)
             with _lib.on_device(w.device):
-                _lib.check(_lib.lib().vmlmf_embed_dropout_forward_ex(tok.numel(), H, V, _ptr(tok), _ptr(w), _ptr(out), float(p), float(word_p),
-                                                                     snap.data_ptr(), int(site), _lib.raw_stream(w.device)))
+                if locked_batch:       # tokens (T, B): the element factors of a position are its batch row's (the _lk entries)
+                    _lib.check(lib.vmlmf_embed_dropout_forward_lk(tok.numel(), int(locked_batch), H, V, _ptr(tok), _ptr(w), _ptr(out), float(p),
+                                                                  float(word_p), snap.data_ptr(), int(site), stream))
+                else:
+                    _lib.check(lib.vmlmf_embed_dropout_forward_ex(tok.numel(), H, V, _ptr(tok), _ptr(w), _ptr(out), float(p), float(word_p),
+                                                                  snap.data_ptr(), int(site), stream))
             ctx.save_for_backward(tok, snap)
         else:
             out = torch.nn.functional.embedding(tokens, w)
             ctx.save_for_backward(tok)
         ctx.wshape, ctx.p, ctx.word_p, ctx.site, ctx.holder = w.shape, float(p), float(word_p), int(site), holder
+        ctx.locked_batch = int(locked_batch) if p > 0.0 else 0
         return out
 
     @staticmethod
@@ -1754,30 +1811,43 @@ class EmbedExFn(torch.autograd.Function):
         lib = _lib.lib()
         nbytes = lib.vmlmf_embed_backward_scratch_bytes(R, V)
         scratch = _workspace(dy.device, nbytes, "embed")
+        state, stream = None if snap is None else snap.data_ptr(), _lib.raw_stream(dy.device)
         with _lib.on_device(dy.device):
-            _lib.check(lib.vmlmf_embed_backward_ex(R, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), int(accumulate), scratch.data_ptr(), nbytes, ctx.p,
-                                                   ctx.word_p, None if snap is None else snap.data_ptr(), ctx.site,
-                                                   _lib.raw_stream(dy.device)))
-        return dw, None, None, None, None, None, None
+            if ctx.locked_batch:
+                _lib.check(lib.vmlmf_embed_backward_lk(R, ctx.locked_batch, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), int(accumulate),
+                                                       scratch.data_ptr(), nbytes, ctx.p, ctx.word_p, state, ctx.site, stream))
+            else:
+                _lib.check(lib.vmlmf_embed_backward_ex(R, H, V, _ptr(tok), _ptr(dy2), _ptr(dw), int(accumulate), scratch.data_ptr(), nbytes, ctx.p,
+                                                       ctx.word_p, state, ctx.site, stream))
+        return dw, None, None, None, None, None, None, None
 
 
-def _embed_ex(weight, tokens, p, word_p, snap, site, grad_from):
+def _embed_ex(weight, tokens, p, word_p, snap, site, grad_from, locked_batch=0):
     if not _embed_covered(weight, tokens):
         raise RuntimeError("vmlmf_amd: word dropout and a tied table's gradient take a contiguous fp32 table on a HIP device, up to 1024 "
                            "wide and 64 MB of position bits, and int64 tokens (embedding_dropout_stock is the form in stock ops)")
     if (p > 0.0 or word_p > 0.0) and snap is None:
         raise ValueError("vmlmf_amd: dropout takes a snapshot of the generator (dropout_advance())")
-    return EmbedExFn.apply(weight, tokens, float(p), float(word_p), snap, site, grad_from)
+    return EmbedExFn.apply(weight, tokens, float(p), float(word_p), snap, site, grad_from, locked_batch)
 
 
-def embedding_dropout(weight, tokens, p, snap, site=0, *, word_p=0.0, grad_from=None):
+def embedding_dropout(weight, tokens, p, snap, site=0, *, word_p=0.0, grad_from=None, locked=False):
     """dropout(weight[tokens]) - the first two lines of Model.forward (vmlmf_lm.py:434-435) - as one launch per direction on HIP fp32
     tables up to 1024 wide; embedding() followed by dropout() otherwise.
     word_p in [0, 1): AWD-LSTM's embedding dropout (--dropoute) in the same launches - whole WORDS are dropped, one factor per
     vocabulary row (0, or 1 / (1 - word_p)) shared by every position that holds the word, applied before the element dropout:
     (weight[tokens] * fw[tokens]) * f; word_dropout_factors() shows fw.  grad_from: a TiedGradient when `weight` is also the
-    head's weight of the same call (EmbedExFn).  With both at their defaults the call is what it was without them."""
+    head's weight of the same call (EmbedExFn).  With both at their defaults the call is what it was without them.
+    locked=True: tokens are (T, B) and the element dropout is the locked one - a position's factors are its batch row's, the same
+    at every time step (dropout(..., locked=True)) - in the same launches; it composes with word_p and grad_from."""
     check_word_dropout(word_p, "word_p")
+    if locked:
+        if tokens.dim() != 2:
+            raise ValueError("vmlmf_amd.embedding_dropout: a locked mask takes tokens of shape (T, B)")
+        if p > 0.0 and word_p == 0.0 and grad_from is None and not _embed_covered(weight, tokens):
+            return dropout(embedding(weight, tokens), p, snap, site, locked=True)
+        if p > 0.0:
+            return _embed_ex(weight, tokens, float(p), word_p, snap, site, grad_from, tokens.shape[1])
     if word_p == 0.0 and grad_from is None:
         if p <= 0.0:
             return embedding(weight, tokens)

@@ -58,7 +58,8 @@ class MyVMLSTM(nn.Module):
         return hn, cn
 
     def forward(self, x, states, drop=None):
-        """drop = (p, snapshot, site): the returned y went through Model's dropout (vmlmf_lm.py:438-439) - inside this layer's own
+        """drop = (p, snapshot, site), or (p, snapshot, site, True) for the locked form (one (B, H) mask for every time step:
+        docs/design/lm_locked.md): the returned y went through Model's dropout (vmlmf_lm.py:438-439) - inside this layer's own
         launches where the library covers it (functional.vmlmf_sequence)."""
         h, c = states
         y, hT, cT = self._run(x, h, c, drop)
@@ -107,7 +108,8 @@ class MyVMLSTMGroup(nn.Module):
         return hn, cn
 
     def forward(self, x, states, drop=None):
-        """drop = (p, snapshot, site): the returned y went through Model's dropout (vmlmf_lm.py:438-439) - inside this layer's own
+        """drop = (p, snapshot, site), or (p, snapshot, site, True) for the locked form (one (B, H) mask for every time step:
+        docs/design/lm_locked.md): the returned y went through Model's dropout (vmlmf_lm.py:438-439) - inside this layer's own
         launches where the library covers it (functional.vmlmf_sequence)."""
         h, c = states
         y, hT, cT = self._run(x, h, c, drop)
@@ -185,7 +187,8 @@ def stack_layers(rnns, x, states, drops=None):
     (MyVMLSTM layers, no dropout between the layers), or - layers of the PTB size, MyVMLSTM or MyVMLSTMGroup, at batch sizes whose
     clusters are co-resident for all layers (up to 128 rows for two layers: what a GPU of an 8-GPU node holds of configs[4]) - the
     clustered form (csrc/vmlmf_rbx.hip), which also applies the dropout behind every layer inside its launches (drops: one
-    (p, snapshot, site) per layer; the returned activations are then the top layer's dropped copy).
+    (p, snapshot, site) per layer - (p, snapshot, site, True): the locked form; None: no dropout behind that layer -; the returned
+    activations are then the top layer's dropped copy).
     Returns (y, [(hT, cT) per layer]), or None when the stack is not covered: the caller loops over the layers."""
     rnns = list(rnns)
     if not x.is_cuda or len(rnns) < 2:
@@ -218,13 +221,18 @@ class Model(nn.Module):
     "vm_group" silently builds torch.nn.LSTM layers.  Build MyVMLSTMGroup layers directly for the group variant."""
 
     def __init__(self, vocab_size, hidden_size, layer_num, dropout, winit, w_rank=None, u_ranks=None,
-                 lstm_type="pytorch", dense_layer=None, tie_weights=False, embed_dropout=0.0):
+                 lstm_type="pytorch", dense_layer=None, tie_weights=False, embed_dropout=0.0, locked_dropout=False, input_dropout=None,
+                 hidden_dropout=None, output_dropout=None):
         """dense_layer: overrides the class built for lstm_type="custom" (default: LSTM above, the reference's dense baseline
         layer in stock ops); any class with the signature (input_size, hidden_size) and forward(x, states).
         tie_weights, embed_dropout: NOT part of the reference's interface - AWD-LSTM's --tied (tie_weights()) and --dropoute (the
-        embed_dropout attribute); docs/design/lm_tied.md."""
+        embed_dropout attribute); docs/design/lm_tied.md.
+        locked_dropout, input_dropout, hidden_dropout, output_dropout: neither - AWD-LSTM's LockedDropout and its --dropouti,
+        --dropouth and --dropout (the attributes of these names); docs/design/lm_locked.md."""
         super().__init__()
         self.embed_dropout = embed_dropout
+        self.locked_dropout = locked_dropout
+        self.input_dropout, self.hidden_dropout, self.output_dropout = input_dropout, hidden_dropout, output_dropout
         self.vocab_size = vocab_size
         self.hidden_size = hidden_size
         self.layer_num = layer_num
@@ -292,6 +300,58 @@ class Model(nn.Module):
         check_word_dropout(value, "Model.embed_dropout")
         self._embed_dropout = float(value)
 
+    # ---- locked (variational) dropout and a rate per site: docs/design/lm_locked.md ----
+    @property
+    def locked_dropout(self):
+        """True: the three activation dropouts (behind the embedding, between the layers, behind the top layer) are AWD-LSTM's
+        LockedDropout - ONE (B, H) mask per site and forward pass, shared by every time step - where nn.Dropout draws a factor for
+        every (t, b, n).  On a HIP device inside the launches that apply the per-element dropout (no mask tensor, no added launch);
+        on CPU tensors and under stock_dropout the rule in stock ops (functional.locked_dropout_stock).  ValueError unless a bool."""
+        return getattr(self, "_locked_dropout", False)
+
+    @locked_dropout.setter
+    def locked_dropout(self, value):
+        if not isinstance(value, bool):
+            raise ValueError(f"vmlmf_amd: Model.locked_dropout must be a bool, got {value!r}")
+        self._locked_dropout = value
+
+    def _site_rate(name, doc):
+        def get(self):
+            return getattr(self, "_" + name, None)
+
+        def put(self, value):
+            if value is not None:
+                from .functional import check_word_dropout
+                check_word_dropout(value, "Model." + name)
+                value = float(value)
+            setattr(self, "_" + name, value)
+        return property(get, put, doc=doc + "  A probability in [0, 1), or None: follow `dropout.p`.  ValueError for a bool or a "
+                        "value outside [0, 1).")
+
+    input_dropout = _site_rate("input_dropout", "The rate of dropout site 0, behind the embedding (AWD-LSTM's --dropouti).")
+    hidden_dropout = _site_rate("hidden_dropout", "The rate of sites 1 .. L - 1, between the layers (AWD-LSTM's --dropouth).")
+    output_dropout = _site_rate("output_dropout", "The rate of site L, behind the top layer (AWD-LSTM's --dropout).")
+    del _site_rate
+
+    def site_rates(self):
+        """The drop probability of every site 0 .. L in the current mode (all zero in eval mode): input_dropout, hidden_dropout for
+        each site between two layers, output_dropout; None among them reads `dropout.p`."""
+        L, p = len(self.rnns), float(self.dropout.p)
+        if not self.training:
+            return [0.0] * (L + 1)
+        pick = lambda v: p if v is None else v
+        return [pick(self.input_dropout)] + [pick(self.hidden_dropout)] * (L - 1) + [pick(self.output_dropout)]
+
+    def _site_dropout(self, x, p):
+        """One site's dropout in stock ops (CPU tensors, stock_dropout): nn.Dropout - self.dropout itself at its own rate, so a
+        model built without the new arguments runs the ops it ran - or AWD-LSTM's LockedDropout."""
+        if self.locked_dropout:
+            from .functional import locked_dropout_stock
+            return locked_dropout_stock(x, p, self.training)
+        if p == self.dropout.p or not self.training:
+            return self.dropout(x)
+        return torch.nn.functional.dropout(x, p, self.training)
+
     def _tied_gradient(self, x):
         """A fresh functional.TiedGradient for one loss call on tokens x where the table is tied and both ends take it, else None."""
         if not self.tied:
@@ -303,13 +363,15 @@ class Model(nn.Module):
 
     @classmethod
     def with_group_layers(cls, vocab_size, hidden_size, layer_num, dropout, winit, w_rank, u_ranks, g=2, tie_weights=False,
-                          embed_dropout=0.0):
+                          embed_dropout=0.0, locked_dropout=False, input_dropout=None, hidden_dropout=None, output_dropout=None):
         """The network of BASELINE configs[4] - Model with MyVMLSTMGroup layers - which the reference's constructor cannot build
         (lstm_type "vmgroup" reduces the rank list to its last element and MyVMLSTMGroup then fails, vmlmf_lm.py:387-392; "vm_group",
         the CLI's spelling, builds nn.LSTM).  NOT part of the reference's interface: the constructor above keeps the reference's
         behaviour, this puts the group layers in by hand (as a maintainer has to) and initialises every parameter as
         Model.reset_parameters does.  u_ranks: one rank per group rotation, e.g. [32, 32]."""
-        model = cls(vocab_size, hidden_size, layer_num, dropout, winit, w_rank=w_rank, u_ranks=[list(u_ranks)[-1]], lstm_type="vmlmf")
+        model = cls(vocab_size, hidden_size, layer_num, dropout, winit, w_rank=w_rank, u_ranks=[list(u_ranks)[-1]], lstm_type="vmlmf",
+                    locked_dropout=locked_dropout, input_dropout=input_dropout, hidden_dropout=hidden_dropout,
+                    output_dropout=output_dropout)
         model.rnns = nn.ModuleList([MyVMLSTMGroup(hidden_size, hidden_size, w_rank=w_rank, u_ranks=list(u_ranks), g=g)
                                     for _ in range(layer_num)])
         model.lstm_type = "vmgroup"
@@ -331,7 +393,7 @@ class Model(nn.Module):
 
     def _stack(self, x, states, drops=None):
         """stack_layers() on this model's layers, unless dropout is active and not handed in (`drops`)."""
-        if (self.training and self.dropout.p > 0) and drops is None:
+        if max(self.site_rates()) > 0 and drops is None:
             return None
         return stack_layers(self.rnns, x, states, drops)
 
@@ -457,7 +519,7 @@ class Model(nn.Module):
         """loss() with ar or tar on: the top layer's raw output, functional.activation_regularizer with that site's dropout, the head
         on the dropped copy."""
         from .functional import (activation_regularizer, activation_regularizer_stock, check_lengths, check_objective, context_negatives,
-                                 lm_head_loss, lm_head_objective_loss, objective_negatives)
+                                 lm_head_loss, lm_head_objective_loss, locked_site, objective_negatives)
         check_objective(label_smoothing, z_loss, unlikelihood, normalize)
         check_lengths(lengths, x.size(1), "Model.loss")
         if unlikelihood > 0:
@@ -465,12 +527,14 @@ class Model(nn.Module):
         tied = self._tied_gradient(x)
         raw, states, site = self._features(x, states, raw_top=True, grad_from=tied)
         B = x.size(1)
-        if site is None or len(site) == 4:       # no dropout at that site / the package's, inside the regulariser's launches
-            p, snap, index, desc = site or (0.0, None, 0, None)
+        if site is None or len(site) >= 4:       # no dropout at that site / the package's, inside the regulariser's launches
+            p, snap, index, desc = (site or (0.0, None, 0, None))[:4]
+            if site is not None and len(site) > 4:       # locked_dropout: the flag rides in the site, as in the C ABI
+                index = locked_site(index)
             h, penalty, parts = activation_regularizer(raw, ar=ar, tar=tar, p=p, snap=snap, site=index, lengths=lengths, layer_desc=desc,
                                                        batch_scale=B)
-        else:                                    # nn.Dropout's factors (CPU tensors, stock_dropout): the rule in stock ops
-            factors = torch.nn.functional.dropout(torch.ones_like(raw), site[0], True)
+        else:                                    # nn.Dropout's / LockedDropout's factors (CPU tensors, stock_dropout): the rule in stock ops
+            factors = self._site_dropout(torch.ones_like(raw[:1] if self.locked_dropout else raw), site[0])
             h, penalty, parts = activation_regularizer_stock(raw, ar=ar, tar=tar, factors=factors, lengths=lengths, batch_scale=B)
         plain = (lengths is None and negatives is None and not return_parts and normalize == "rows" and label_smoothing == 0.0
                  and z_loss == 0.0 and unlikelihood == 0.0)
@@ -506,18 +570,23 @@ class Model(nn.Module):
     def _features(self, x, states, raw_top=False, grad_from=None):
         """features(), written once.  raw_top=True (loss() under ar / tar): the top layer runs without the dropout behind it and a
         third element says what the caller applies in its place: None (eval mode, p == 0), (p, snapshot, site, layer descriptor or
-        None) for functional.activation_regularizer, or (p,) where the dropouts are nn.Dropout's."""
-        p = self.dropout.p
+        None) for functional.activation_regularizer - with a fifth element, True, under locked_dropout -, or (p,) where the
+        dropouts are stock ops'.  Site i's rate is site_rates()[i]; a site whose rate is 0 is skipped."""
+        rates = self.site_rates()
+        locked = self.locked_dropout
         last = len(self.rnns) - 1
         word_p = self.embed_dropout if self.training else 0.0
-        if self.training and (p > 0 or word_p > 0) and x.is_cuda and not getattr(self, "stock_dropout", False):
+        if (max(rates) > 0 or word_p > 0) and x.is_cuda and not getattr(self, "stock_dropout", False):
             from .functional import dropout, dropout_advance, embedding_dropout
             snap = dropout_advance(self.dropout_state())
             T, B = x.shape
-            x = embedding_dropout(self.embed.w, x, p, snap, 0, word_p=word_p, grad_from=grad_from)
-            site = (p, snap, last + 1, self._top_layer_desc(T, B)) if (raw_top and p > 0) else None
-            drops = [None if (raw_top and i == last) or not p > 0 else (p, snap, i + 1) for i in range(len(self.rnns))]
-            stacked = self._stack(x, states, drops=drops if p > 0 else None)
+            form = (True,) if locked else ()     # (three-tuples are the per-element form, as before there was another)
+            x = embedding_dropout(self.embed.w, x, rates[0], snap, 0, word_p=word_p, grad_from=grad_from, locked=locked)
+            top = rates[last + 1]
+            site = (top, snap, last + 1, self._top_layer_desc(T, B)) + form if (raw_top and top > 0) else None
+            drops = [None if (raw_top and i == last) or not rates[i + 1] > 0 else (rates[i + 1], snap, i + 1) + form
+                     for i in range(len(self.rnns))]
+            stacked = self._stack(x, states, drops=drops)     # (all None: a stack that needs no dropout - it still runs stacked)
             if stacked is not None:       # every layer in one launch per direction, the dropouts behind them inside it
                 x, new_states = stacked
                 for i, st in enumerate(new_states):
@@ -529,30 +598,31 @@ class Model(nn.Module):
                 else:
                     x, states[i] = rnn(x, states[i])
                     if drops[i] is not None:
-                        x = dropout(x, p, snap, i + 1)
+                        x = dropout(x, rates[i + 1], snap, i + 1, locked=locked)
             return x, states, site
-        site = (p,) if (raw_top and self.training and p > 0) else None
+        site = (rates[last + 1],) if (raw_top and rates[last + 1] > 0) else None
         if word_p > 0:                           # CPU tensors, stock_dropout: AWD-LSTM's embedded_dropout in stock ops
             from .functional import embedding_dropout_stock
-            x = embedding_dropout_stock(self.embed.w, x, p, word_p)
+            x = self._site_dropout(embedding_dropout_stock(self.embed.w, x, 0.0, word_p), rates[0]) if locked else \
+                embedding_dropout_stock(self.embed.w, x, rates[0], word_p)
         elif grad_from is not None:
             from .functional import embedding
-            x = self.dropout(embedding(self.embed.w, x, grad_from=grad_from))
+            x = self._site_dropout(embedding(self.embed.w, x, grad_from=grad_from), rates[0])
         else:
             x = self.embed(x)
-            x = self.dropout(x)
+            x = self._site_dropout(x, rates[0])
         stacked = self._stack(x, states)
         if stacked is not None:
             x, new_states = stacked
             for i, st in enumerate(new_states):
                 states[i] = st
             if not raw_top:
-                x = self.dropout(x)
+                x = self._site_dropout(x, rates[last + 1])
         else:
             for i, rnn in enumerate(self.rnns):
                 x, states[i] = rnn(x, states[i])
                 if not (raw_top and i == last):
-                    x = self.dropout(x)
+                    x = self._site_dropout(x, rates[i + 1])
         return x, states, site
 
     def dropout_state(self, seed=None):
